@@ -10,8 +10,14 @@ one all-gather of q (Ne doubles) per update, made INSIDE the library on its own 
 the once-per-run A build is sharded by tiles and summed over RCCL, every rank keeps only its rows of the projected inverse
 -> "strong" scaling.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload headline|headline_slab|big|il_onelayer|il_twolayer|dilute|cond2] [--no-configs] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload headline|headline_slab|big|il_onelayer|il_twolayer|dilute|cond2] [--dump-outputs DIR]
+    python bench.py --full [--no-configs] [--no-cpu-baseline] [--no-profile] ...
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run does what `value` needs and nothing else: setup, SETTLE_UPDATES + W untimed updates, the K timed updates, the outputs
+of the last one (--dump-outputs), the JSON line.  --full adds what the run measured besides: the host-buffer hook pass, the
+per-kernel pass (`kernels_ms`), HIP events inside the timed region (`roofline`), the composite roofline, the CPU baseline and the
+other BASELINE configs (`configs`, headline workload only).
 """
 import argparse
 import json
@@ -26,6 +32,11 @@ import numpy as np  # noqa: E402
 
 FP64_PEAK_TFLOPS = 78.6   # MI355X FP64 vector = matrix peak (AMD spec); 77.8 measured with tools/microbench/mfma_f64_bench.hip
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md
+# untimed updates ahead of the W warm-up updates of a plain run: the chip needs ~65 launches after the setup phase before its clock
+# governor has settled; without them a 20-step timed region starts cold and reads ~5 % slow.  --full gets
+# them from its auxiliary passes instead.
+SETTLE_UPDATES = 200
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 def make_workload(name):
@@ -238,14 +249,25 @@ def main():
                          "(BASELINE configs[2] runs il_twolayer with it)")
     ap.add_argument("--classic", action="store_true",
                     help="the full (planar, kz) contraction (sk_gemm) instead of the z-window form -- round 4's kernels, for comparison")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides `value` too: host-buffer hook pass, per-kernel pass, roofline, CPU baseline, "
+                         "the other BASELINE configs (the --no-* switches below trim this)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=1)
-    ap.add_argument("--no-profile", action="store_true", help="do not time individual kernels with HIP events")
+    ap.add_argument("--no-profile", action="store_true", help="--full without timing individual kernels with HIP events")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the `configs` block (the other BASELINE configs, measured after the headline's timed region)")
+                    help="--full without the `configs` block (the other BASELINE configs, measured after the headline's timed region)")
     ap.add_argument("--pppm", type=int, nargs=3, metavar=("NX", "NY", "NZ"), default=None,
                     help="k-space b through the PPPM mesh (`pppm` keyword, BASELINE configs[3]) with this mesh, order 5")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned to its caller (the charge array q of every "
+                         "atom, float64) as DIR/q.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        # a plain run: only what `value` needs
+        args.no_cpu_baseline = args.no_profile = args.no_configs = True
 
     import torch
     import torch.distributed as dist
@@ -354,7 +376,7 @@ def main():
     #     Twice: out of pageable host arrays (staged, blocking copy), and with the arrays page-locked in place
     #     (conp_fix_pin_host_arrays -- what the LAMMPS glue does between re-neighbourings): the second is the reported figure.
     host_ms = host_ms_pageable = None
-    if world == 1:
+    if world == 1 and args.full:
         nh = max(10, args.steps // 4)
 
         def host_pass():
@@ -386,6 +408,9 @@ def main():
         dt_prof = time.perf_counter() - t0
         prof = fx.profile_read()
         fx.profile(0)
+    settle = 0 if args.full else SETTLE_UPDATES
+    for _ in range(settle):
+        step()
 
     for _ in range(args.warmup):
         step()
@@ -410,6 +435,13 @@ def main():
         dt = float(tt.item())
     ms_per_step = dt / args.steps * 1e3
     value = args.steps / dt
+    if args.dump_outputs and rank == 0:
+        # what the last timed update handed back: conp_fix_pre_force_device writes the charges into the caller's q array in place
+        q_out = d_q.detach().cpu().numpy().astype(np.float64)
+        if q_out.nbytes > DUMP_LIMIT_BYTES:
+            raise SystemExit(f"--dump-outputs: q is {q_out.nbytes} bytes, more than {DUMP_LIMIT_BYTES}")
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "q.npy"), q_out)
 
     if rank == 0:
         K, nl = info.kcount, info.n_elyte_charged
@@ -487,7 +519,12 @@ def main():
                               note="achieved / frac: the bytes this formulation reads (symmetric storage: 4 Ne^2 + the diagonal "
                                    "tiles) over the HIP-event time of the launch(es); survey_*: SURVEY 8d's algorithmic 8 Ne^2 "
                                    "over the same time")
-        composite = composite_roofline(info, ms_per_step, world, pppm=tuple(args.pppm) if args.pppm else None)
+        if args.full:
+            order = ("setup; host-buffer hook pass; %d updates with events around every kernel (kernels_ms); "
+                     "%d warm-up + %d timed updates (value; events around every 4th launch of the dominant kernel only)"
+                     % (n_prof if not args.no_profile else 0, args.warmup, args.steps))
+        else:
+            order = "setup; %d settling + %d warm-up updates; %d timed updates (value)" % (settle, args.warmup, args.steps)
         out = dict(metric="charge-solve updates/sec + ns/day, 4096-atom electrode / 32k electrolyte", value=value,
                    unit="updates/s", n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=ms_per_step,
                    higher_is_better=True, scaling="strong", vs_baseline=None, dtype="f64", data="synthetic",
@@ -501,15 +538,15 @@ def main():
                                parallelism=f"S(k): electrolyte atoms sharded (all k, all rows) + all-reduce(b); solve: electrode rows sharded + all-gather(q); x{world}" + (", RCCL inside libconp_hip" if lib_collectives else "")),
                    collectives=collectives,
                    ns_per_day_solver_limited=value * 2.0 * 86400 * 1e-6,   # Nevery=1, dt = 2 fs (tests/il_onelayer/input:87)
-                   ms_per_step_host_buffers_pcie=host_ms, ms_per_step_host_buffers_pcie_pageable=host_ms_pageable,
-                   host_buffers_ghost_images=bool(world == 1),
                    setup_s=dict(total=t_a1 - t_setup0, a_build_inverse_setq=t_a1 - t_a0),
-                   kernels_ms={k: round(v[0], 5) for k, v in prof.items()},
-                   ms_per_step_profiled_pass=dt_prof / n_prof * 1e3,
-                   order_of_passes=("setup; host-buffer hook pass; %d updates with events around every kernel (kernels_ms); "
-                                   "%d warm-up + %d timed updates (value; events around every 4th launch of the dominant kernel only)"
-                                   % (n_prof if not args.no_profile else 0, args.warmup, args.steps)),
-                   roofline=roofline, roofline_hbm_member=hbm_member, composite_roofline=composite)
+                   order_of_passes=order)
+        if args.full:
+            composite = composite_roofline(info, ms_per_step, world, pppm=tuple(args.pppm) if args.pppm else None)
+            out.update(ms_per_step_host_buffers_pcie=host_ms, ms_per_step_host_buffers_pcie_pageable=host_ms_pageable,
+                       host_buffers_ghost_images=bool(world == 1),
+                       kernels_ms={k: round(v[0], 5) for k, v in prof.items()},
+                       ms_per_step_profiled_pass=dt_prof / n_prof * 1e3,
+                       roofline=roofline, roofline_hbm_member=hbm_member, composite_roofline=composite)
         if not args.no_cpu_baseline and world == 1:
             S = fx.matrix()
             base = cpu_baseline(s, at, alist, blist, S, args.cpu_threads)
