@@ -21,7 +21,6 @@ class ConpError(RuntimeError):
 
 
 def library_path():
-    # CONP_LIB: a diagnostic build of the same ABI (tools/sk_stamp.py loads the s_memtime-stamped one); never set in tests / bench
     return os.environ.get("CONP_LIB") or os.path.join(HERE, "libconp_hip.so")
 
 
@@ -104,10 +103,8 @@ SYMBOLS = [
 
 # test hooks of the ABI (include/conp_hip.h, CONP_PATH_*): alternative code paths the parity tests compare the default ones with
 PATH_PARTIAL_TILES, PATH_A_GENERAL, PATH_INV_PIVOTED, PATH_CG_TWO_LAUNCH, PATH_GEMV_ROWS = 1, 2, 4, 8, 16
-PATH_PHASE_LAUNCH, PATH_PPPM_SPREAD_LAUNCH, PATH_ROWS_HOST, PATH_TIME_SPLIT, PATH_HC_NO_WAIT = 32, 64, 128, 256, 512
-PATH_HC_FUSED = 1024
-PATH_CG_PERSIST = 2048
-PATH_SK_CLASSIC = 4096
+PATH_PHASE_LAUNCH, PATH_PPPM_SPREAD_LAUNCH, PATH_ROWS_HOST, PATH_TIME_SPLIT = 32, 64, 128, 256
+PATH_SK_CLASSIC = 4096      # (512, 1024, 2048: retired test paths, ignored by the library)
 
 
 class test_paths:

@@ -339,27 +339,13 @@ struct conp_fix {
   double *d_b = nullptr, *d_eleallq = nullptr;   // bound (external) or own buffers
   bool b_bound = false, q_bound = false;         // conp_fix_bind_device_buffers gave us the host's vectors
   int n_slab_part = 0;
-  const bool no_fuse = diag_switch("CONP_NO_FUSE") != nullptr;   // experiment switch: separate sk_reduce / b_hc launches
-  const bool shard_by_cost = diag_switch("CONP_SHARD_COST_AXIS") != nullptr;   // comparison switch: rank shards = shares of the cost axis (round 2)
   const bool sk_partials = path_on(CONP_PATH_PARTIAL_TILES);   // comparison switch: partial tiles + reducing launch, no projection in sk_gemm
-  const char *hc_presum_env = diag_switch("CONP_HC_PRESUM");      // comparison switch: 1 / 0 = always / never add the pieces in a launch of their own
   // The host-buffer hooks report Ktime / Ctime (fix_conp.cpp:553-568).  By default they run the SAME kernels as the device hooks
   // (bitwise-equal charges): the pair sums share a launch with the k-space phases, so Ctime stays 0 and Ktime holds all of b_cal.
   // CONP_TIME_SPLIT=1 launches the two halves separately (last-ulp different dot order) so that each gets its own figure.
   const bool time_split = path_on(CONP_PATH_TIME_SPLIT);
-  // the dot workgroups' bounded wait for the class table (b_zc_fused_kernel); CONP_PATH_HC_NO_WAIT: zero -- every dot workgroup adds
-  // the pieces itself, the path a wait that runs out takes (tested against the hand-off: the same bits)
-  const unsigned hc_spin_limit = path_on(CONP_PATH_HC_NO_WAIT) ? 0u : (1u << 16);
-  // Measured and NOT the default (round 5, tools/ab_libs.sh on one box, profiles/r05_tail_handoff_ab.txt): the pieces' sums, the pair
-  // sums and the dot as ONE launch with the fence-free hand-off -- reduce_project 24.7-25.3 us against 19.0-19.1 for hc_sum_kernel +
-  // b_zc_final_kernel (headline), 26.5-27.0 against 20.0-20.4 (slab geometry).  What a kernel boundary does in ~2 us (make 18 KB
-  // visible to 256 workgroups on eight XCDs) costs the hand-off a write-through, a ticket, a poll and 256 x 18 KB of sc1 reads from
-  // the memory side; the pair rows, which filled the idle CUs beside hc_sum's handful of workgroups, sit on every dot workgroup's
-  // own path instead.  Kept as a test path (bit-identical b, tests/test_gpu_decks.py).
-  const bool hc_fused = path_on(CONP_PATH_HC_FUSED);
   const bool gemv_rows = path_on(CONP_PATH_GEMV_ROWS);      // test path: the row-by-row product at every size
   const bool no_phase_fuse = path_on(CONP_PATH_PHASE_LAUNCH);      // comparison switch: always the stand-alone phase launch
-  const bool no_ride = diag_switch("CONP_NO_RIDE") != nullptr;      // comparison switch: the real-space pair sums in a launch of their own (b_real_combine)
   int table_c0 = 0, table_c1 = 0;  // chunk range (16 atoms each) whose phase tables this rank's sk_gemm reads
   int hslots = 0;                  // entries of the owned row tiles' segment lists (d_hslot_idx)
   bool g_current = true;           // d_G holds the last update's structure factors (false after a projecting update: conp_fix_get_sfac re-forms it)
@@ -399,17 +385,13 @@ struct conp_fix {
   // The wait at the end of a host-buffer update: the runtime's blocking synchronisation wakes the thread tens of microseconds after
   // the stream drained; polling the stream for the first two milliseconds (an update takes 0.03 - 20 ms) returns within a few.
   // Longer waits (setup, large systems) fall back to the blocking call: no core is burnt for them.
-  const bool sync_block = diag_switch("CONP_SYNC_BLOCK") != nullptr;      // comparison switch: always the blocking call
-  const bool results_by_copy = diag_switch("CONP_RESULTS_COPY") != nullptr;      // comparison switch: charges / scalars back by hipMemcpyAsync
   void sync() {
-    if (!sync_block) {
-      const double t0 = now_s();
-      for (;;) {
-        const hipError_t e = hipStreamQuery(stream);
-        if (e == hipSuccess) return;
-        if (e != hipErrorNotReady) HIP_TRY(e);
-        if (now_s() - t0 > 2e-3) break;
-      }
+    const double t0 = now_s();
+    for (;;) {
+      const hipError_t e = hipStreamQuery(stream);
+      if (e == hipSuccess) return;
+      if (e != hipErrorNotReady) HIP_TRY(e);
+      if (now_s() - t0 > 2e-3) break;
     }
     HIP_TRY(hipStreamSynchronize(stream));
   }
@@ -525,81 +507,27 @@ struct conp_fix {
                     plan.kxmax, plan.kymax, d_p_ikx.p, d_p_iky.p, d_p_sgn.p, d_nb_act.p, d_wfull.p};
     d_G.reserve((size_t)plan.R_pad * plan.C_pad); d_Gw.reserve((size_t)plan.R_pad * plan.C_pad);
     d_G.zero(stream); d_Gw.zero(stream);
-    // k-shard.  The structure-factor work is laid out on ONE axis -- tile after tile (col tile major), chunk after chunk, the axis
-    // build_items cuts into workgroup shares -- and rank r takes the r-th N-th of it by cost.  A tile that straddles a rank
-    // boundary is shared: each side multiplies its own chunk range, reduces and projects its partial G (the projection is linear
-    // in G), and the all-reduce of b adds the pieces.  Every rank gets the same work whatever the number of tiles (the first
-    // version dealt whole row tiles, heaviest first: 8 unequal tiles on 8 ranks left the heaviest rank 18 % above the mean, and
-    // more ranks than tiles idle).  Boundaries are fractions of a tile here; build_items turns them into chunk numbers -- both
-    // neighbours evaluate the same expression, so their ranges meet exactly.  CONP_SHARD_TILES=1: whole tiles (comparison).
+    // k-shard (round 3): rank r takes the r-th N-th of the ATOMS of every tile (the axis the XCD-aware shares cut inside a rank, one
+    // level up).  Every rank has every tile with the same chunk count: equal work by construction, whatever the tiles' costs, and a
+    // rank needs the phase tables of ITS atoms only -- the phase kernel, replicated until then (12 us of an 89-us update on 8
+    // emulated ranks), shrinks with the share.  Each rank projects its partial structure factors for all rows; the all-reduce of b
+    // adds them.  The shares are fractions of a tile here; build_items turns them into chunk numbers -- neighbouring ranks evaluate
+    // the same expression, so their ranges meet exactly.  (Round 2 cut one cost axis over all tiles; round 1 dealt whole row tiles,
+    // heaviest first: 8 unequal tiles on 8 ranks left the heaviest rank 18 % above the mean.)
     {
-      struct GT { int rt, ct; double c; };
-      std::vector<GT> all;
-      for (int ct = 0; ct < plan.n_col_tiles; ++ct)
-        for (int rt = 0; rt < plan.n_row_tiles; ++rt) {
-          if (plan.nba(rt, ct) <= 0) continue;
-          const unsigned nbf = plan.nfa16(rt, ct);
-          double sum = 0.0;
-          for (int f = 0; f < 4; ++f) sum += (double)((nbf >> (8 * f)) & 255u);
-          all.push_back(GT{rt, ct, 0.125 * sum + SK_C0});     // nbf counts 8-kz column fragments: two per kz block
-        }
-      std::vector<double> flo(all.size(), 0.0), fhi(all.size(), 0.0);
-#ifdef CONP_DIAG
-      const bool whole_tiles = getenv("CONP_SHARD_TILES") && env.nranks > 1;     // diagnostic library only
-#else
-      const bool whole_tiles = false;
-#endif
-      if (whole_tiles) {
-        // whole row tiles, heaviest first to the least loaded rank (every rank computes the same map)
-        std::vector<std::pair<double, int>> order;
-        std::vector<double> rtc(plan.n_row_tiles, 0.0);
-        for (const auto &g : all) rtc[g.rt] += g.c;
-        for (int rt = 0; rt < plan.n_row_tiles; ++rt) order.push_back({-rtc[rt], rt});
-        std::stable_sort(order.begin(), order.end());
-        std::vector<double> load(env.nranks, 0.0);
-        std::vector<int> owner(plan.n_row_tiles, 0);
-        for (auto &e : order) {
-          int best = 0;
-          for (int r = 1; r < env.nranks; ++r) if (load[r] < load[best]) best = r;
-          owner[e.second] = best;
-          load[best] += -e.first;
-        }
-        for (size_t t = 0; t < all.size(); ++t) if (owner[all[t].rt] == env.rank) fhi[t] = 1.0;
-      } else if (!shard_by_cost) {
-        // Round 3: rank r takes the r-th N-th of the ATOMS of every tile (the axis the XCD-aware shares cut inside a rank, one level
-        // up).  Every rank has every tile with the same chunk count: equal work by construction, whatever the tiles' costs, and a
-        // rank needs the phase tables of ITS atoms only -- the phase kernel, replicated until now (12 us of an 89-us update on 8
-        // emulated ranks), shrinks with the share.  Each rank projects its partial structure factors for all rows; the
-        // all-reduce of b adds them, as it did for tiles that straddled a rank boundary.
-        for (size_t t = 0; t < all.size(); ++t) {
-          flo[t] = (double)env.rank / (double)env.nranks;
-          fhi[t] = (double)(env.rank + 1) / (double)env.nranks;
-        }
-      } else {
-        double W = 0.0;
-        for (const auto &g : all) W += g.c;
-        const double lo = W * (double)env.rank / (double)env.nranks, hi = W * (double)(env.rank + 1) / (double)env.nranks;
-        double S = 0.0;
-        for (size_t t = 0; t < all.size(); ++t) {
-          const double c = all[t].c;
-          flo[t] = std::min(1.0, std::max(0.0, (lo - S) / c));
-          fhi[t] = env.rank + 1 == env.nranks && t + 1 == all.size() ? 1.0 : std::min(1.0, std::max(0.0, (hi - S) / c));
-          S += c;
-        }
-      }
+      const double flo = (double)env.rank / (double)env.nranks, fhi = (double)(env.rank + 1) / (double)env.nranks;
       std::vector<int> mine(plan.n_row_tiles, 0);
       tiles_h.clear(); tile_flo.clear(); tile_fhi.clear();
       ct_ptr_h.assign(plan.n_col_tiles + 1, 0);
-      for (size_t t = 0; t < all.size(); ++t) {
-        if (fhi[t] > flo[t]) {
-          const int rt = all[t].rt, ct = all[t].ct;
+      for (int ct = 0; ct < plan.n_col_tiles; ++ct) {
+        for (int rt = 0; rt < plan.n_row_tiles; ++rt) {
+          if (plan.nba(rt, ct) <= 0) continue;
           tiles_h.push_back(SkTile{rt, ct, plan.nba(rt, ct), 0, 0, plan.nfa16(rt, ct)});
-          tile_flo.push_back(flo[t]); tile_fhi.push_back(fhi[t]);
+          tile_flo.push_back(flo); tile_fhi.push_back(fhi);
           mine[rt] = 1;
         }
-        ct_ptr_h[all[t].ct + 1] = (int)tiles_h.size();
+        ct_ptr_h[ct + 1] = (int)tiles_h.size();
       }
-      for (int ct = 0; ct < plan.n_col_tiles; ++ct) ct_ptr_h[ct + 1] = std::max(ct_ptr_h[ct + 1], ct_ptr_h[ct]);
       own_rt_h.clear();
       for (int rt = 0; rt < plan.n_row_tiles; ++rt) if (mine[rt]) own_rt_h.push_back(rt);
       d_rt_mine.upload(mine, stream);
@@ -1143,7 +1071,7 @@ struct conp_fix {
   // sk_gemm's output per segment: the projected piece (planar electrodes) or the partial tile.  The partial tiles of a projecting
   // handle are allocated when somebody asks for the structure factors (conp_fix_get_sfac).
   bool sk_projects() const {
-    return nzc > 0 && nzc <= sk_hc_max_classes() && !args.pppm && !sk_partials && !no_fuse;
+    return nzc > 0 && nzc <= sk_hc_max_classes() && !args.pppm && !sk_partials;
   }
   void reserve_partials(bool tiles_too = false) {
     const size_t ns = std::max<size_t>(1, (size_t)n_slots);
@@ -1208,8 +1136,8 @@ struct conp_fix {
   // tile after tile, chunk after chunk, with cost (mean nba of the 4 row fragments + SK_C0) per chunk of 16 atoms (MFMA work ~ nba, operand
   // generation + barrier ~ SK_C0), and cut into num_cus equal shares.  A share is a list of segments (tile, chunk
   // range); every segment writes one partial tile, sk_reduce adds a tile's segments in order.
-  // The two constants are a least-squares fit of per-segment lengths measured on the headline box (tools/sk_stamp.py ->
-  // tools/sk_fit.py; round 3's kernel:  us = 0.483 * chunks * (mean kz blocks + 1.37) + 2.8 per segment): a segment's start (first
+  // The two constants are a least-squares fit of per-segment lengths measured on the headline box (in-kernel stamps,
+  // round 3's kernel:  us = 0.483 * chunks * (mean kz blocks + 1.37) + 2.8 per segment): a segment's start (first
   // panel with nothing to overlap it) and its partial-tile write cost as much as 5.74 units of chunk cost.  The fit leaves 1 % rms
   // per segment; what remains between workgroups (max / median 1.05 on the box measured) is the speed of the XCD a workgroup
   // lands on (+-3 %, different XCDs on different boxes) -- nothing a static plan can see, and an adaptive one would give up the
@@ -1217,9 +1145,7 @@ struct conp_fix {
   // per-segment term) left the heavy tiles' workgroups and those whose share straddles a tile boundary 3 % behind the rest.
   // (Tried on top: a linear ramp of the shares so that early finishers' partial-tile stores overlap the others' last chunks --
   //  no effect at +-8 / 16 / 24 units, 244.1 - 244.5 us.  What is left is a +-2 % spread between XCDs.)
-  static double diag_number(const char *v, double dflt) { return v ? atof(v) : dflt; }      // (diag_switch folds to null in the product)
-  double SK_C0 = diag_number(diag_switch("CONP_SK_C0"), 1.37);
-  double SK_CSEG = diag_number(diag_switch("CONP_SK_CSEG"), 5.74);
+  static constexpr double SK_C0 = 1.37;
   // what the schedule was cut for: the same padded atom count, plan and output form give the same schedule -- a re-neighbour that
   // changes none of them (the usual one) keeps the work list that is on the device
   struct ItemsKey { int nl_pad = -1; long plan_gen = -1; bool proj = false; int nzc = -1; int nranks = 0; bool operator==(const ItemsKey &o) const {
@@ -1250,13 +1176,13 @@ struct conp_fix {
     // paid a tile's full per-chunk cost), and 80 instead of 64 MFMAs per wave and chunk where the sphere is full.  A band that
     // straddles two row tiles of the plan writes one output slot per tile (zero rows where the other band writes): everything
     // behind sk_gemm still sees row tiles.  Only the projecting mode takes bands of five (its slots are 8-KB pieces; partial tiles
-    // would double sk_reduce's reads); CONP_SK_BANDS4: comparison switch, bands = row tiles everywhere.
+    // would double sk_reduce's reads).
     struct Band { int g0, rf, ct; unsigned long long nbf; int clo, chi; };
     std::vector<Band> bands;
     {
       std::map<std::pair<int, int>, size_t> tile_at;
       for (size_t i = 0; i < ntiles; ++i) tile_at[{tiles_h[i].rt, tiles_h[i].ct}] = i;
-      const bool five = sk_projects() && uniform && ntiles > 0 && diag_switch("CONP_SK_BANDS4") == nullptr;
+      const bool five = sk_projects() && uniform && ntiles > 0;
       for (int ct = 0; ct < plan.n_col_tiles; ++ct) {
         const int nfr = 4 * plan.n_row_tiles;
         std::vector<int> nfa(nfr + 8, 0);
@@ -1300,7 +1226,7 @@ struct conp_fix {
     const size_t nt = bands.size();
     // a segment that ends in the projecting epilogue costs about twice one that stores its partial tile (stamped build: 15 units;
     // A/B on one rank: 5.74 / 9 / 12 equal within noise, 15 worse; on emulated ranks with 16 chunks per workgroup 12-14 is 7 % faster)
-    if (!diag_switch("CONP_SK_CSEG")) SK_CSEG = sk_projects() ? 12.0 : 5.74;
+    const double SK_CSEG = sk_projects() ? 12.0 : 5.74;
     // one workgroup per CU, except for small problems: sk_reduce walks a tile's splits serially (~1 us per split), so a tile
     // is cut into more than 16 segments only when a segment still holds >= 8 chunks (measured on the decks: il_onelayer
     // 57 -> 52 us per update with 32 instead of 256 workgroups)
@@ -1385,7 +1311,7 @@ struct conp_fix {
     //  tools/rank_emulation.py, N = 4: 80.9 vs 74.6 us, N = 8: 48.3 vs 41.2)
     const int span = nt ? chi[0] - clo[0] : 0;
     const bool long_shares = (size_t)span * nt >= (size_t)32 * nwg;
-    const bool xcd_aware = uniform && long_shares && nwg >= 64 && nwg % 8 == 0 && span >= 64 && diag_switch("CONP_SK_FLAT") == nullptr;
+    const bool xcd_aware = uniform && long_shares && nwg >= 64 && nwg % 8 == 0 && span >= 64;
     if (xcd_aware) {
       std::vector<int> lo(nt), hi(nt);
       for (int x = 0; x < 8; ++x) {
@@ -1463,8 +1389,8 @@ struct conp_fix {
     d_witems.upload(wl, stream);
     d_tiles.upload(tiles_h, stream);
     // projecting mode: a segment leaves ONE band-local piece (slot = its index; a band's segments are contiguous).  hc_sum_kernel
-    // adds a band's pieces and maps its rows to the plan's; when every band IS a row tile of the plan (rf = 4, aligned: the decks,
-    // CONP_SK_BANDS4) the dot kernel may add a row tile's few pieces itself, from the per-row-tile lists below
+    // adds a band's pieces and maps its rows to the plan's; when every band IS a row tile of the plan (rf = 4, aligned: the decks)
+    // the dot kernel may add a row tile's few pieces itself, from the per-row-tile lists below
     bands_aligned = true;
     for (const Band &bd : bands) if (bd.rf != 4 || (bd.g0 & 3)) bands_aligned = false;
     {
@@ -1557,8 +1483,7 @@ struct conp_fix {
         if (it == cls.end()) { it = cls.emplace(z[i], (int)cls.size()).first; rep.push_back(i); }
         zclass[i] = it->second;
       }
-      const bool off = diag_switch("CONP_NO_ZCLASS") != nullptr;
-      nzc = (!off && cls.size() <= 64 && 4 * cls.size() <= (size_t)ne) ? (int)cls.size() : 0;   // worthwhile only if it compresses
+      nzc = (cls.size() <= 64 && 4 * cls.size() <= (size_t)ne) ? (int)cls.size() : 0;   // worthwhile only if it compresses
       // b_zc_dot keeps Hc for 32 rows of every row tile and every class in LDS
       if ((size_t)plan.n_row_tiles * 32 * (size_t)nzc * sizeof(double) > 96 * 1024) nzc = 0;
       if (nzc > 0) {
@@ -1993,9 +1918,6 @@ struct conp_fix {
   // read-back: scalars, flag, net charge and the residual history come over in ONE copy into the page-locked staging buffer.
   int cg_batch = 8;
   const bool cg_unfused = path_on(CONP_PATH_CG_TWO_LAUNCH);      // comparison switch: two launches per iteration (round 1)
-  bool cg_persist_off = false;
-  long cg_solves = 0;
-  DevBuf<unsigned> d_cg_tk;            // two grid-barrier words of the one-launch solve, alternating between solves
   void cg() {
     const int ne = idx.elenum_all;
     const int nctl = 16 + args.maxiter + 1;                  // scal[0..12], pad, hist[0..maxiter] at offset 16
@@ -2007,34 +1929,8 @@ struct conp_fix {
     double *ctl = pinned((size_t)ne_pad + 8 + nctl) + ne_pad + 8;
     int done = 0, iter = 1, batch = std::max(2, std::min(16, cg_batch));
     prof.begin("cg", stream);
-    // round 5, measured and NOT the default (CONP_PATH_CG_PERSIST selects it; profiles/r05_cg_persist_ab.txt): the whole solve as ONE
-    // persistent launch -- the matrix stays in the XCDs' L2s between iterations, which a kernel boundary invalidates (cg_step_kernel
-    // fetches 8 n^2 bytes from the memory side at every launch) -- with one fence-free grid barrier per iteration.  il_twolayer: 92-94 us
-    // per solve against 76-78 with a launch per iteration: the barrier (write-through of the products, ticket, poll, sc1 read-back of the
-    // product vector by every workgroup) costs ~2.5 us more than a kernel boundary plus the re-read of 22 MB from the Infinity Cache.
-    bool persisted = false;
-    if (!two_launch && !cg_persist_off && cg_persist_fits(ne) && !results_by_copy && path_on(CONP_PATH_CG_PERSIST)) {
-      if (d_cg_tk.n == 0) { d_cg_tk.reserve(2); d_cg_tk.zero(stream); }
-      unsigned *tk = d_cg_tk.p + (cg_solves & 1), *tkn = d_cg_tk.p + ((cg_solves + 1) & 1);
-      if (launch_cg_persist(stream, num_cus, ne, d_A.p, d_b, d_eleallq, d_cg_ap.p, d_cg_scal.p, args.tolerance, args.maxiter, hist_dev, ctl,
-                            tk, tkn, 1u << 20)) {
-        ++cg_solves;
-        if (spec_dq) scatter_device(spec_dq, spec_pot, false);      // update_direct: the charge write rides behind the solve
-        sync();
-        if (ctl[8] < 0.0) {
-          // a workgroup's wait at the grid barrier ran out (the workgroups were not all resident: another kernel on the device?):
-          // this handle takes a launch per iteration from now on; the solve is repeated (b is untouched, q is reset by the start)
-          cg_persist_off = true;
-          mesgf("conp/hip: the one-launch CG solve timed out at its grid barrier; falling back to one launch per iteration\n");
-        } else {
-          persisted = true;
-          done = ctl[8] != 0.0;
-          if (spec_dq && done) spec_done = true;
-        }
-      }
-    }
-    if (persisted) {
-    } else if (two_launch) {
+    // (the whole solve as ONE persistent launch with a grid barrier per iteration was measured slower: DESIGN-LOG.md 13.4)
+    if (two_launch) {
       launch_cg_init(stream, ne, d_A.p, d_b, d_eleallq, d_cg_res.p, d_cg_p.p, d_cg_scal.p);
       while (iter < args.maxiter && !done) {
         const int batch_end = std::min(args.maxiter, iter + batch);
@@ -2051,14 +1947,13 @@ struct conp_fix {
       // iteration's update alone before the read-back; same arithmetic, same bits as the two-launch form
       auto step = [&](int it, int mode) {
         launch_cg_step(stream, ne, d_A.p, d_b, d_eleallq, d_cg_res.p, d_cg_p.p, d_cg_ap.p, d_cg_scal.p, args.tolerance,
-                       d_cg_done.p, it, hist_dev, mode, results_by_copy ? nullptr : ctl, 16 + it + 1);
+                       d_cg_done.p, it, hist_dev, mode, ctl, 16 + it + 1);
       };
       step(1, 1);                                            // iter = the iteration whose matvec is in flight
       while (true) {
         const int last = std::min(args.maxiter - 1, iter + batch - 1);
         for (; iter < last; ++iter) step(iter + 1, 2);
         step(iter, 4);                                        // (stores the control block into `ctl` itself)
-        if (results_by_copy) HIP_TRY(hipMemcpyAsync(ctl, d_cg_scal.p, (size_t)(16 + iter + 1) * sizeof(double), hipMemcpyDeviceToHost, stream));
         if (spec_dq) scatter_device(spec_dq, spec_pot, false);      // update_direct: speculative charge write
         sync();
         done = ctl[8] != 0.0;
@@ -2155,8 +2050,8 @@ struct conp_fix {
       // `pppm` keyword: the k-space b comes from the mesh (pppm_conp.cpp:269-316); the mesh is not sharded -- rank 0 owns it
       prof.begin("pppm_b", stream);
       // one rank: the real-space pair sums ride in the spread launch and the stencil gather completes the rows of b (slab term,
-      // pair sums): no b_real_combine launch behind the mesh (round 4; CONP_NO_RIDE / CONP_NO_FUSE / CONP_TIME_SPLIT: as before)
-      const bool pp_fin = env.nranks == 1 && !nccl && !decomposed && !no_fuse && !no_ride && !(timed && time_split);
+      // pair sums): no b_real_combine launch behind the mesh (round 4; CONP_TIME_SPLIT: as before)
+      const bool pp_fin = env.nranks == 1 && !nccl && !decomposed && !(timed && time_split);
       BRowArgs pairs = make_brow(ne, ne_pad, rr0, rr1, d_b_rowptr.p, d_b_ele.p, d_b_oth.p, dx, dq, d_type.p, real_params(), 0,
                                  nullptr, 0, nullptr, nullptr, 0, 0.0, nullptr, nullptr);
       fin = make_brow(ne, ne_pad, rr0, rr1, d_b_rowptr.p, d_b_ele.p, d_b_oth.p, dx, dq, d_type.p, real_params(), 1, d_bk.p, slab,
@@ -2177,9 +2072,9 @@ struct conp_fix {
       // host-buffer hooks were asked to time the two halves of b_cal separately (CONP_TIME_SPLIT; Ktime / Ctime, fix_conp.cpp:553-568)
       BRowArgs pairs = make_brow(ne, ne_pad, rr0, rr1, d_b_rowptr.p, d_b_ele.p, d_b_oth.p, dx, dq, d_type.p, real_params(), 0,
                                  nullptr, 0, nullptr, nullptr, 0, 0.0, nullptr, nullptr);
-      ride = !no_fuse && !(timed && time_split) && !no_ride;
+      ride = !(timed && time_split);
       // small systems on one rank: no phase launch at all -- every sk_gemm segment computes the phase tables of its own atoms in
-      // front of its chunk loop, the pair sums ride in spare workgroups of that launch (SkFuse; CONP_NO_PHASE_FUSE: comparison switch).
+      // front of its chunk loop, the pair sums ride in spare workgroups of that launch (SkFuse; CONP_PATH_PHASE_LAUNCH: test path).
       // A workgroup of this launch owns its CU (registers): the pair workgroups run on the CUs sk_gemm leaves free, in at most two
       // rounds of ~5 us -- shorter than the ~13 us the sk_gemm workgroups take
       const int nwg_sk = (int)seg_ptr_h.size() - 1;
@@ -2204,11 +2099,9 @@ struct conp_fix {
         // pair sums ride THERE, not in the phase launch: that launch sits at the ~5 us floor of any small kernel with a handful of
         // workgroups, the pair rows fill the rest of the chip beside it (17.7 -> 19.2 us for hc_sum + dot), while in the phase
         // kernel they compete with 37 MB of table writes (15.1 -> 10.7 us without them): 0.2791 / 0.2796 -> 0.2763 / 0.2757 ms per
-        // update at the headline size, 0.7261 / 0.7268 -> 0.7228 / 0.7244 in the slab geometry (one box, tools/ab_env.sh).
-        // CONP_RIDE_PHASE: comparison switch, the phase launch as before.
-        ride_hc = ride && diag_switch("CONP_RIDE_PHASE") == nullptr && sk_projects() && n_frags > 0 && nzc > 0 &&
-                  zc_final_fits((int)own_rt_h.size(), nzc) &&
-                  (zn_use() || !bands_aligned || (hc_presum_env ? atoi(hc_presum_env) != 0 : hslots > 32 * (int)own_rt_h.size()));
+        // update at the headline size, 0.7261 / 0.7268 -> 0.7228 / 0.7244 in the slab geometry (one box).
+        ride_hc = ride && sk_projects() && n_frags > 0 && nzc > 0 && zc_final_fits((int)own_rt_h.size(), nzc) &&
+                  (zn_use() || !bands_aligned || hslots > 32 * (int)own_rt_h.size());
         prof.begin("elyte_phase", stream);
         ZnWindow zw{};
         const bool zn_now = zn_use() || zn_gen_use();
@@ -2237,7 +2130,7 @@ struct conp_fix {
         prof.begin("reduce_project", stream);
         launch_project_zclass_pieces(stream, dplan, ne_pad, (int)own_rt_h.size(), d_own_rt.p, nzc, d_zn_pieces.p, d_hslot_ptr.p, d_hslot_idx.p,
                                      true, d_zn_frag_ptr.p, d_zn_frag_ents.p, zn_nfrag, d_Rp.p, d_Xe.p, d_Ye.p, d_own_pv.p, d_zclass.p, d_Hc.p,
-                                     d_bk.p, use_fin ? &fin : nullptr, ride_hc ? &pairs_keep : nullptr, d_breal.p, nullptr, 1u << 16,
+                                     d_bk.p, use_fin ? &fin : nullptr, ride_hc ? &pairs_keep : nullptr, d_breal.p,
                                      zn_nrg > 32 /*a piece per range: 32 threads per element*/);
         prof.end(stream);
       } else if (zn_gen_use() && !fuse_phase) {
@@ -2259,21 +2152,19 @@ struct conp_fix {
       reserve_partials();
       prof.begin("sk_gemm", stream);
       launch_sk_gemm(stream, dplan, d_witems.p, witems_maxseg, nwg_sk, nl_pad, d_Xt.p, d_Yt.p, d_Zt.p, d_qc.p,
-                     proj ? d_Hpart.p : d_Gpart.p, proj ? d_skproj.p : nullptr, fuse_phase ? d_skfuse.p : nullptr, ne,
-                     reinterpret_cast<unsigned *>(d_scalars.p + 8));
+                     proj ? d_Hpart.p : d_Gpart.p, proj ? d_skproj.p : nullptr, fuse_phase ? d_skfuse.p : nullptr, ne);
       prof.end(stream);
       g_current = !proj;
       if (proj) {
         // planar electrodes: the segments left their projected pieces (128 x nzc each); the dot kernel adds them per row tile
         // (a launch of its own first when there are many: every block of the dot kernel would re-add them all)
-        const bool presum = !bands_aligned || (hc_presum_env ? atoi(hc_presum_env) != 0 : hslots > 32 * (int)own_rt_h.size());
+        const bool presum = !bands_aligned || hslots > 32 * (int)own_rt_h.size();
         prof.begin("reduce_project", stream);
         launch_project_zclass_pieces(stream, dplan, ne_pad, (int)own_rt_h.size(), d_own_rt.p, nzc, d_Hpart.p, d_hslot_ptr.p, d_hslot_idx.p,
                                      presum, d_frag_ptr.p, d_frag_ents.p, n_frags, d_Rp.p, d_Xe.p, d_Ye.p, d_own_pv.p, d_zclass.p, d_Hc.p, d_bk.p,
-                                     use_fin ? &fin : nullptr, ride_hc ? &pairs_keep : nullptr, d_breal.p,
-                                     (hc_fused && !(timed && time_split)) ? reinterpret_cast<unsigned *>(d_scalars.p + 8) : nullptr, hc_spin_limit);
+                                     use_fin ? &fin : nullptr, ride_hc ? &pairs_keep : nullptr, d_breal.p);
         prof.end(stream);
-      } else if (nzc > 0 && plan.n_col_tiles == 1 && !no_fuse) {
+      } else if (nzc > 0 && plan.n_col_tiles == 1) {
         // planar electrodes, one column tile: partial-tile sum + Hc product fused, then the per-atom dot (+ row assembly)
         prof.begin("reduce_project", stream);
         launch_reduce_project_zclass(stream, dplan, d_tiles.p, (int)tiles_h.size(), max_nsplit, d_Gpart.p, d_G.p, ne_pad,
@@ -2400,10 +2291,6 @@ struct conp_fix {
       sync();
       rc.sum(h, ne);
       HIP_TRY(hipMemcpyAsync(d_b, h, ne * sizeof(double), hipMemcpyHostToDevice, stream));
-#ifdef CONP_DIAG
-    } else if (getenv("CONP_RANK_EMULATION")) {
-      // diagnostic library only (tools/rank_emulation.py): one rank's compute time measured on a box that has no partner ranks
-#endif
     } else throw ConpError(CONP_ERR_STATE, "an update on several ranks needs conp_fix_comm_init_rccl or conp_fix_set_comm (or do the "
                                            "two collectives yourself between conp_fix_b_cal_device / _solve_device / _scatter_device)");
     prof.end(stream);
@@ -2430,7 +2317,7 @@ struct conp_fix {
 
   // plain `fix conp` on one rank with the inverse solver: GEMV and charge write in one launch (gemv_finish_kernel)
   bool can_fuse_solve() const {
-    return !no_fuse && args.minimizer == CONP_SOLVER_INV && !args.conq && !args.cond && env.nranks == 1 && !nccl && !s_sharded &&
+    return args.minimizer == CONP_SOLVER_INV && !args.conq && !args.cond && env.nranks == 1 && !nccl && !s_sharded &&
            runstage >= 3;
   }
   // The projected inverse as a symmetric matrix (conp_kernels.hip "GEMV ... as a SYMMETRIC matrix"): from 2048 electrode atoms up
@@ -2538,19 +2425,14 @@ struct conp_fix {
     }
     double t0 = time_host ? now_s() : 0.0;
     double *qe = pinned((size_t)ne_pad + 8);
-    if (results_by_copy) {
-      HIP_TRY(hipMemcpyAsync(qe, d_qele.p, ne * sizeof(double), hipMemcpyDeviceToHost, stream));
-      finish_scalar(potdiff);               // one synchronisation for the charges and the scalars
-    } else {
-      // charges and scalars stored into the page-locked staging area by ONE kernel (which also forms the fix scalar's group-1 sum):
-      // no copy-engine transfer at the end of the update
-      double *h = qe + ne_pad;
-      launch_results_out(stream, ne, d_elecheck.p, d_eleallq, d_scalars.p, left_stale, d_qele.p, qe, h);
-      left_stale = false;
-      sync();
-      scalar_output = (args.conq || args.cond) ? h[3] : potdiff * totsetq + h[1];
-      slabcorr = h[2];
-    }
+    // charges and scalars stored into the page-locked staging area by ONE kernel (which also forms the fix scalar's group-1 sum):
+    // no copy-engine transfer at the end of the update
+    double *h = qe + ne_pad;
+    launch_results_out(stream, ne, d_elecheck.p, d_eleallq, d_scalars.p, left_stale, d_qele.p, qe, h);
+    left_stale = false;
+    sync();
+    scalar_output = (args.conq || args.cond) ? h[3] : potdiff * totsetq + h[1];
+    slabcorr = h[2];
     collect_b_times();
     if (time_host) { const double t1 = now_s(); th[3] += t1 - t0; t0 = t1; }
     // owned and ghost electrode atoms :1153-1158, through the (atom, row) list of the last post_neighbor (the atom arrays keep
@@ -2648,14 +2530,13 @@ struct conp_fix {
     // CG on one rank: the charge write is enqueued behind every batch of iterations BEFORE the host reads the convergence flag
     // (cg()): the device does not idle through the read-back and a launch from cold; a batch that did not converge just wrote
     // intermediate charges, which the next batch's write replaces
-    const bool spec = args.minimizer == CONP_SOLVER_CG && env.nranks <= 1 && !nccl && !args.conq && !args.cond && !cg_no_spec;
+    const bool spec = args.minimizer == CONP_SOLVER_CG && env.nranks <= 1 && !nccl && !args.conq && !args.cond;
     if (spec) { spec_dq = dq; spec_pot = potdiff; spec_done = false; }
     solve_device();
     spec_dq = nullptr;
     allgather_q();
     if (!(spec && spec_done)) scatter_device(dq, potdiff);
   }
-  const bool cg_no_spec = diag_switch("CONP_CG_NO_SPEC") != nullptr;      // comparison switch: charge write after the read-back
   double *spec_dq = nullptr;
   double spec_pot = 0.0;
   bool spec_done = false;

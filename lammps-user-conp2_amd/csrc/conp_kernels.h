@@ -7,19 +7,12 @@
 namespace conp {
 
 // Alternative code paths.  (i) What the parity tests compare the default paths with is selected through the C ABI
-// (conp_debug_set_paths, include/conp_hip.h: a process-wide bit mask, CONP_PATH_*) -- path_on().  (ii) Switches of decided
-// experiments ("measured, not kept", DESIGN-LOG.md) and those that change the PHYSICS of a run (sk_gemm ablation, rank emulation,
-// whole-tile sharding) exist in the diagnostic library only (-DCONP_DIAG, `make diag`): diag_switch() reads the environment
-// there and folds to a null constant -- name and all -- in the product.  (iii) The product reads from the environment only
-// operational knobs: CONP_GUARD, CONP_GRAPH, CONP_PANEL_SINGLE / _MAXG / _SPIN, CONP_HOST_THREADS, CONP_TIME_HOST / _REN.
+// (conp_debug_set_paths, include/conp_hip.h: a process-wide bit mask, CONP_PATH_*) -- path_on().  (ii) The library reads from the
+// environment only operational knobs: CONP_GUARD, CONP_GRAPH, CONP_PANEL_SINGLE / _MAXG / _SPIN, CONP_HOST_THREADS,
+// CONP_TIME_HOST / _REN.  Decided experiments ("measured, not kept") are recorded in DESIGN-LOG.md, not kept as switches.
 bool path_on(unsigned bit);
 int debug_sk_workgroups();
 const char *env_knob(const char *name);      // operational knob: getenv + one line on stderr the first time a set knob is read
-#ifdef CONP_DIAG
-#define diag_switch(name) ::conp::env_knob(name)
-#else
-#define diag_switch(name) (static_cast<const char *>(nullptr))
-#endif
 
 struct DevPlan {              // device copy of KPlan geometry
   int np, nz, n_row_tiles, n_col_tiles, R_pad, C_pad, kxmax, kymax;
@@ -149,7 +142,7 @@ bool zc_final_fits(int n_own, int nzc);
 void launch_sk_gemm(hipStream_t s, const DevPlan &pl, const SkWItem *witems /*[nwg][maxseg]*/, int maxseg, int nwg, int nl_pad,
                     const double2 *Xt, const double2 *Yt, const double2 *Zs, const double *qc, double *part, const SkProj *proj = nullptr,
                     const SkFuse *fuse = nullptr /*small systems: phase tables and pair sums inside this launch (DEVICE copy of the block)*/,
-                    int fuse_rows = 0 /*its rows.ne*/, unsigned *ticket = nullptr /*zeroed by workgroup 0: b_zc_fused_kernel's hand-off word*/);
+                    int fuse_rows = 0 /*its rows.ne*/);
 int sk_hc_stride();           // doubles per segment of sk_gemm's projected output
 int sk_hc_max_classes();      // most z classes the projecting mode takes
 void launch_project_zclass_pieces(hipStream_t s, const DevPlan &pl, int ne_pad, int n_own, const int *own_rt, int nzc, const double *Hp,
@@ -159,8 +152,6 @@ void launch_project_zclass_pieces(hipStream_t s, const DevPlan &pl, int ne_pad, 
                                   const double2 *Ye, const int *own_pv, const int *zclass, double *Hc, double *bk_part, const BRowArgs *fin,
                                   const BRowArgs *pairs = nullptr /*with breal_out: the pair sums ride in hc_sum's launch*/,
                                   double *breal_out = nullptr,
-                                  unsigned *ticket = nullptr /*with fin and pairs: ONE launch, the pieces' sums handed over inside it (round 5)*/,
-                                  unsigned spin_limit = 1u << 16,
                                   bool wide = false /*many pieces per fragment: 32 threads per element in the sum*/);
 void launch_sk_reduce(hipStream_t s, const DevPlan &pl, const SkTile *tiles, int ntiles, int max_nsplit, double *part, double *G,
                       double *Gwf);
@@ -253,11 +244,6 @@ void launch_cg_init(hipStream_t s, int n, const double *A, const double *b, doub
 void launch_cg_iter(hipStream_t s, int n, const double *A, double *q, double *res, double *p, double *ap, double *scal,
                     double tolerance, int *done, int iter, double *hist);
 // one launch per CG iteration (update of iteration iter - 1 repeated by every workgroup + its rows of the matvec); see the kernel
-// round 5: the whole CG solve as one persistent launch (n <= 4096); false: not all workgroups can be resident
-bool cg_persist_fits(int n);
-bool launch_cg_persist(hipStream_t s, int num_cus, int n, const double *A, const double *b, double *q, double *ap2, double *scal,
-                       double tolerance, int maxiter, double *hist, double *host_ctl, unsigned *ticket, unsigned *ticket_next,
-                       unsigned spin_limit);
 bool cg_step_fits(int n);
 void launch_cg_step(hipStream_t s, int n, const double *A, const double *b, double *q, double *res2 /*[2][n]*/, double *p2 /*[2][n]*/,
                     double *ap2 /*[2][n]*/, double *scal, double tolerance, int *done, int iter, double *hist, int mode,

@@ -50,23 +50,6 @@ extern "C" void conp_debug_set_sk_workgroups(int n) { g_sk_nwg.store(n > 0 ? n :
 
 __device__ double block_sum_1024(double v, double *red);
 
-// cache-policy experiments (comparison builds only; the product leaves both at 0): non-temporal partial-tile stores / loads,
-// non-temporal phase-table stores
-#ifndef SK_PART_NT
-#define SK_PART_NT 0
-#endif
-#ifndef EP_TABLE_NT
-#define EP_TABLE_NT 0
-#endif
-__device__ __forceinline__ void st_d2(double2 *p, double2 v, bool nt) {
-  if (nt) { __builtin_nontemporal_store(v.x, &p->x); __builtin_nontemporal_store(v.y, &p->y); }
-  else *p = v;
-}
-__device__ __forceinline__ double2 ld_d2(const double2 *p, bool nt) {
-  if (nt) { double2 v; v.x = __builtin_nontemporal_load(&p->x); v.y = __builtin_nontemporal_load(&p->y); return v; }
-  return *p;
-}
-
 // ================================================================================================
 // 1. electrolyte phase tables  (km_ewald.cpp:685-724: libm cos/sin of unitk*x, then the angle-addition
 //    recurrence c_m = c_{m-1} c_1 - s_{m-1} s_1, s_m = s_{m-1} c_1 + c_{m-1} s_1)
@@ -146,7 +129,7 @@ __global__ __launch_bounds__(EP_THREADS) void elyte_phase_kernel(int nb, int nl,
       if (nrow > 1) t[16] = make_double2(sc * c1, sc * s1);
       for (int m = 2; m < nrow; ++m) {
         rot(cm, sm, c1, s1);
-        st_d2(t + (size_t)m * 16, make_double2(sc * cm, sc * sm), EP_TABLE_NT);
+        t[(size_t)m * 16] = make_double2(sc * cm, sc * sm);
       }
     } else if (zw.Bt) {
       // the z-window form (conp_zn.hip): this atom's row of the window matrix, dense over its chunk's columns:
@@ -201,7 +184,7 @@ __global__ __launch_bounds__(EP_THREADS) void elyte_phase_kernel(int nb, int nl,
         for (int q40 = 0; q40 < 4; ++q40) {
 #pragma unroll
           for (int r = 0; r < 8; ++r) {
-            st_d2(t + (size_t)(1 + 32 * ct + 8 * q40 + r) * 16, make_double2(sc8[r], ss8[r]), EP_TABLE_NT);
+            t[(size_t)(1 + 32 * ct + 8 * q40 + r) * 16] = make_double2(sc8[r], ss8[r]);
             if (q40 < 3) rot(sc8[r], ss8[r], c40, s40);
           }
         }
@@ -271,9 +254,6 @@ void launch_elyte_phase(hipStream_t s, int nl, int nl_pad, const int *elyte_idx,
 //    build first, multiply second).  Partial tiles go to part[segment] in fragment-major order (sk_part_off); sk_reduce sums a
 //    tile's segments in a fixed order (deterministic).
 // ================================================================================================
-#ifndef SK_LATE_MODE
-#define SK_LATE_MODE 1
-#endif
 // raise a kernel's dynamic-LDS limit, only when a launch needs more than it was last given: per-update launches must not
 // pay a runtime call each (the decks' updates are bound by host launch cost)
 // The attribute is per device: the cache is indexed by the calling thread's current device (handles on several GPUs in one
@@ -306,50 +286,8 @@ constexpr int SK_NF = 160 + 320;
 constexpr int SK_PANEL = SK_NF * SK_LD;          // doubles per buffer (61,440 bytes)
 constexpr unsigned SK_BUF1 = 65536;              // byte offset of the second buffer: switching buffers is one XOR of a byte address
 constexpr size_t SK_LDS_BYTES = SK_BUF1 + (size_t)SK_PANEL * sizeof(double);
-// Measured and left off (round 5, tools/ab_libs.sh on one box, `make variant_nobar VDEF=-DSK_NOBAR=1`): the chunk loop WITHOUT the
-// workgroup barrier -- sk_gemm 244.6-252.9 us against 234.5-236.6 with the barrier (headline size; parity tests green in both forms).
-// Why it loses (tools/microbench/pipe_share*_bench.hip, profiles/r05_pipe_share.txt): the SIMD's issue arbiter serves the OLDER wave
-// first -- a wave that streams MFMAs keeps its rate (64.0 cycles per MFMA) whatever its younger partner does, and the partner gets what
-// is left (its own MFMAs: 13 % of the pipe; VALU / LDS instructions: one per ~30 cycles instead of ~10).  Waves 0-3 are the older
-// ones: let loose, they run a chunk ahead and take the pipe from the late waves' multiply of the previous chunk, then wait for it in
-// front of their next build -- while both roles build at the same time (nobody multiplies); the barrier is what keeps the two
-// roles' multiply phases apart, back to back.  Also left off: SK_LOAD_AHEAD (the early waves' table loads in front of the barrier
-// instead of behind it): 237.1-237.5 vs 234.5-236.6 us.
-// The form without the barrier: four counters in the gap between the two panel buffers -- built[b] counts the
-// wave-builds written into buffer b, done[b] the wave-multiplies that have finished reading it (both monotonic inside a segment,
-// zeroed at its start).  A wave waits for the panel it needs (8 builds per chunk) or for the buffer it is about to overwrite (8
-// multiplies per chunk), not for the slowest wave of the workgroup: the early and the late waves of a SIMD may drift by up to a
-// chunk against each other.  LDS operations of one wave complete in order, so the ds_add behind a wave's panel writes is its release;
-// the waiting side has the counter's value back (it branches on it) before it requests operands.
-#ifndef SK_NOBAR
-#define SK_NOBAR 0
-#endif
-// SK_LOAD_AHEAD: the early waves request the table rows of chunk c + 2 right behind their build of chunk c + 1 -- in front of the
-// chunk's barrier, where they wait for the late waves anyway -- instead of at the top of the next chunk, between the barrier and
-// their first multiply (the address arithmetic and issue of 6-8 loads: ~150 cycles of every chunk on the workgroup's critical path)
-#ifndef SK_LOAD_AHEAD
-#define SK_LOAD_AHEAD 0
-#endif
-constexpr unsigned SK_CNT = (unsigned)SK_PANEL * sizeof(double);     // byte 61440: built[0], built[1], done[0], done[1]
-static_assert(SK_CNT + 16 <= SK_BUF1, "counters sit in the gap between the panel buffers");
-typedef __attribute__((address_space(3))) char *sk_lds_ptr;
-// (inline assembly on purpose: through a generic pointer the compiler reads the counter with a FLAT load and waits for vmcnt(0) --
-//  every table load in flight -- at each poll; and its atomic optimiser wraps a one-lane add in a wave reduction)
-__device__ __forceinline__ void sk_cnt_signal(char *smem, unsigned idx) {
-  const unsigned a = (unsigned)(unsigned long)(sk_lds_ptr)smem + SK_CNT + 4u * idx;
-  unsigned long long save;
-  asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, 1\n\tds_add_u32 %1, %2\n\ts_mov_b64 exec, %0"
-               : "=&s"(save) : "v"(a), "v"(1u) : "memory");
-}
-__device__ __forceinline__ void sk_cnt_wait(char *smem, unsigned idx, unsigned target) {
-  const unsigned a = (unsigned)(unsigned long)(sk_lds_ptr)smem + SK_CNT + 4u * idx;
-  for (;;) {
-    unsigned v;
-    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(a) : "memory");
-    if ((unsigned)__builtin_amdgcn_readfirstlane((int)v) >= target) break;
-    __builtin_amdgcn_s_sleep(1);
-  }
-}
+// The chunk loop keeps its workgroup barrier: the barrier-free form with LDS counters and the table loads issued ahead of the
+// barrier were measured slower (DESIGN-LOG.md, round 5).
 
 // one step of the angle-addition recurrence without FMA contraction (same arithmetic as elyte_phase_kernel)
 __device__ __forceinline__ double2 zstep(double2 z, double2 st) {
@@ -405,7 +343,6 @@ struct SkCtx {        // per-thread constants of one work item
   const double2 *Xt, *Yt, *Zs;
   const double *qc;
   const SkProj *proj;               // projected output (planar electrodes, sk_project_out) when not null
-  int dbg;
   int nfr;                          // row fragments (16 planar vectors each) the plan has: 4 n_row_tiles (a band's padding lies beyond)
 };
 
@@ -475,82 +412,25 @@ __device__ __forceinline__ void sk_build_panel(const SkCtx &c, const SkRaw &r, d
   }
 }
 
-// MFMA phase of one chunk for a wave that owns NFW column fragments (fi = 4 g + cg, g < NFW) x 4 row fragments f.
+// MFMA phase of one chunk for a wave that owns NFW column fragments (fi = 4 g + cg, g < NFW) x RF row fragments f: all four
+// k-steps unrolled, the sphere cut F0 a template parameter -- no loop, no branch, no scalar bookkeeping between MFMAs.
 // Row-fragment-major.  Fragment registers: the NFW B values of the current k-step, one A value in use and the NEXT A value
 // already on its way (issued before the <= NFW MFMAs of the current row fragment); during the last row fragment of a k-step
 // every B value is re-read for the next k-step right after its last use.  So each LDS read has about NFW MFMAs (64 cycles
 // apiece) between issue and first use, with 2 NFW + 4 fragment registers instead of 2 NFW + 8 -- a wave that multiplies alone
-// (its SIMD partner is building the next panel) no longer stalls on LDS at the top of every k-step (tools/sk_stamp.py: that
-// was ~1900 of the ~7900 cycles of a chunk).  After the last k-step the "next" reads wrap to k-step 0 of the same buffer:
-// six reads nobody uses instead of a branch.
-// Sphere culling: row fragments f >= f0 skip the wave's LAST column fragment (the host orders planar vectors by |k_p|, so the
+// (its SIMD partner is building the next panel) does not stall on LDS at the top of every k-step.
+// The (k-step, lane)-dependent 32-byte group of the swizzle costs one address register per k-step and operand side (8 in all,
+// XORed with the buffer bit once per chunk); fragment / column-group offsets are immediates.
+// Sphere culling: row fragments f >= F0 skip the wave's LAST column fragment (the host orders planar vectors by |k_p|, so the
 // kz cut never grows with f; a fragment whose cut is shorter still than NFW - 1 multiplies a few zero-weight columns: G entries
-// no listed k reads).  One wave-uniform branch per row fragment instead of one per MFMA.
+// no listed k reads).
+// (Measured and left off, DESIGN-LOG.md: the round-2 k-step loop, the operand reads gathered into bursts, and the first operand
+// reads requested ahead of the build or of the table loads.)
 #define SK_LDS_F64(byte_addr) (*reinterpret_cast<const double *>(smem + (byte_addr)))
-template <int RF, int NFW>
-__device__ __forceinline__ void sk_mfma_chunk(const SkCtx &c, const char *smem, unsigned buf, d4 (&acc)[RF][NFW > 0 ? NFW : 1]) {
+template <int RF, int NFW, int F0>
+__device__ __forceinline__ void sk_mfma_chunk_u(const SkCtx &c, const char *smem, unsigned buf, d4 (&acc)[RF][NFW > 0 ? NFW : 1]) {
   if constexpr (NFW > 0) {
     constexpr unsigned FA = 16 * SK_LD * 8, FB = 64 * SK_LD * 8;        // bytes between row fragments / between this wave's column fragments
-    const unsigned ba = c.base_a ^ buf, bb = c.base_b ^ buf;
-    double bf[NFW], a0, a1;
-    unsigned q = c.pq;                                                  // (ks ^ p) << 5 for ks = 0: the 32-byte group of k-step 0
-    // Issue order matters: LDS reads retire in order and the compiler's s_waitcnt at the top of the k-step loop must cover the
-    // loop entry AND the back edge.  A first, then the B fragments one instruction each (a paired ds_read2st64 here would merge
-    // two counter slots), exactly the order the loop body re-reads them in: the waits become lgkmcnt(NFW), (NFW-1), ... -- every
-    // fragment gets ~NFW MFMAs of cover.  (B first / A last made the loop head wait for the read issued JUST before it:
-    // one full LDS round trip per k-step with the matrix pipe idle.)
-    a0 = SK_LDS_F64(ba + q);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int g = 0; g < NFW; ++g) { bf[g] = SK_LDS_F64(bb + q + g * FB); __builtin_amdgcn_sched_barrier(0); }
-#pragma unroll 1
-    for (int ks = 0; ks < SK_J / 4; ++ks) {
-      const unsigned qn = (unsigned)(((ks + 1) & 3) << 5) ^ c.pq;       // the group of the next k-step (wraps after the last)
-      const unsigned an = ba + qn, bn = bb + qn, ac = ba + q;
-#pragma unroll
-      for (int f = 0; f < RF; ++f) {
-        a1 = f < RF - 1 ? SK_LDS_F64(ac + (f + 1) * FA) : SK_LDS_F64(an);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int g = 0; g + 1 < NFW; ++g) {
-          acc[f][g] = MFMA_F64(a0, bf[g], acc[f][g]);
-          if (f == RF - 1) { bf[g] = SK_LDS_F64(bn + g * FB); __builtin_amdgcn_sched_barrier(0); }
-        }
-        if (f < c.f0) acc[f][NFW - 1] = MFMA_F64(a0, bf[NFW - 1], acc[f][NFW - 1]);      // wave-uniform
-        if (f == RF - 1) bf[NFW - 1] = SK_LDS_F64(bn + (NFW - 1) * FB);
-        __builtin_amdgcn_sched_barrier(0);
-        a0 = a1;
-      }
-      q = qn;
-    }
-  }
-}
-
-// Straight-line form of the same phase: all four k-steps unrolled, the sphere cut F0 a template parameter -- no loop, no branch,
-// no scalar bookkeeping between MFMAs.  The (k-step, lane)-dependent 32-byte group of the swizzle costs one address register per
-// k-step and operand side (8 in all, XORed with the buffer bit once per chunk); fragment / column-group offsets are immediates.
-// The first reads of a chunk's MFMA phase -- the A value of row fragment 0 and the wave's NFW B values of k-step 0 -- can be
-// requested apart from the phase itself (SkPre): a LATE wave requests them BEFORE it builds the next panel, so that they queue
-// ahead of the build's fourteen LDS writes (LDS operations of a wave complete in order) and the first MFMAs do not wait for the
-// write drain behind the build.
-template <int NFW>
-struct SkPre { double a0; double bf[NFW > 0 ? NFW : 1]; };
-template <int NFW>
-__device__ __forceinline__ void sk_mfma_prefetch(const SkCtx &c, const char *smem, unsigned buf, SkPre<NFW> &pre) {
-  if constexpr (NFW > 0) {
-    constexpr unsigned FB = 64 * SK_LD * 8;
-    const unsigned q = c.pq;
-    pre.a0 = SK_LDS_F64((c.base_a ^ buf) + q);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int g = 0; g < NFW; ++g) { pre.bf[g] = SK_LDS_F64((c.base_b ^ buf) + q + g * FB); __builtin_amdgcn_sched_barrier(0); }
-  }
-}
-template <int RF, int NFW, int F0>
-__device__ __forceinline__ void sk_mfma_chunk_u(const SkCtx &c, const char *smem, unsigned buf, d4 (&acc)[RF][NFW > 0 ? NFW : 1],
-                                                const SkPre<NFW> *pre = nullptr) {
-  if constexpr (NFW > 0) {
-    constexpr unsigned FA = 16 * SK_LD * 8, FB = 64 * SK_LD * 8;
     unsigned aa[4], ab[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
@@ -559,16 +439,12 @@ __device__ __forceinline__ void sk_mfma_chunk_u(const SkCtx &c, const char *smem
       ab[ks] = (c.base_b ^ buf) + q;
     }
     double bf[NFW], a0, a1;
-    if (pre) {
-      a0 = pre->a0;
+    // Issue order matters: LDS reads retire in order.  A first, then the B fragments one instruction each (a paired ds_read2st64
+    // here would merge two counter slots), exactly the order the k-steps re-read them in: every fragment gets ~NFW MFMAs of cover.
+    a0 = SK_LDS_F64(aa[0]);
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int g = 0; g < NFW; ++g) bf[g] = pre->bf[g];
-    } else {
-      a0 = SK_LDS_F64(aa[0]);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int g = 0; g < NFW; ++g) { bf[g] = SK_LDS_F64(ab[0] + g * FB); __builtin_amdgcn_sched_barrier(0); }
-    }
+    for (int g = 0; g < NFW; ++g) { bf[g] = SK_LDS_F64(ab[0] + g * FB); __builtin_amdgcn_sched_barrier(0); }
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       const int kn = (ks + 1) & 3;
@@ -590,143 +466,6 @@ __device__ __forceinline__ void sk_mfma_chunk_u(const SkCtx &c, const char *smem
     }
   }
 }
-
-// Round 5: the same MFMAs and the same registers (NFW B values, two A values), the operand reads gathered into FEWER interruptions
-// of the MFMA stream.  tools/microbench/sk_reads_bench.hip (profiles/r05_sk_reads.txt): a single wave's stream loses ~6.6 % against
-// constant operand registers, and loses the same when the reads go into registers nobody multiplies -- it is not the waiting, it is
-// every PLACE where a non-MFMA instruction sits between two MFMAs (~10 cycles each, whether one read is issued there or four).  The
-// form above has RF + NFW such places per k-step (an A read in front of every row-fragment group, a B re-read behind every MFMA of
-// the last group); this one has RF: the last group re-reads the wave's B values in two bursts -- half of them and the next k-step's
-// first A value behind its middle MFMA, the rest and the next k-step's second A value behind its last -- and the groups 1 .. RF-2
-// read the A value of the group behind them as before.  Microbenchmark, one wave per SIMD: 0.715 -> 0.737 of peak (constant
-// operands: 0.764).
-template <int RF, int NFW, int F0>
-__device__ __forceinline__ void sk_mfma_chunk_v(const SkCtx &c, const char *smem, unsigned buf, d4 (&acc)[RF][NFW > 0 ? NFW : 1]) {
-  if constexpr (NFW > 0) {
-    constexpr unsigned FA = 16 * SK_LD * 8, FB = 64 * SK_LD * 8;
-    unsigned aa[4], ab[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const unsigned q = (unsigned)(ks << 5) ^ c.pq;
-      aa[ks] = (c.base_a ^ buf) + q;
-      ab[ks] = (c.base_b ^ buf) + q;
-    }
-    double bf[NFW], av[2];                 // av[p]: the A value of the current group, av[p ^ 1]: the next one's (p flips per group)
-    av[0] = SK_LDS_F64(aa[0]);
-    if (RF > 1) av[1] = SK_LDS_F64(aa[0] + FA);
-#pragma unroll
-    for (int g = 0; g < NFW; ++g) bf[g] = SK_LDS_F64(ab[0] + g * FB);
-    __builtin_amdgcn_sched_barrier(0);
-    constexpr int H = (NFW + 1) / 2;        // B values re-read in the first burst of the last group
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const int kn = (ks + 1) & 3;
-#pragma unroll
-      for (int f = 0; f < RF; ++f) {
-        const int p = (ks * RF + f) & 1;    // (compile-time: everything is unrolled)
-        // in front of the groups 1 .. RF-2: the A value of the group behind this one, into the register the previous group freed
-        if (f >= 1 && f + 1 < RF) { av[p ^ 1] = SK_LDS_F64(aa[ks] + (f + 1) * FA); __builtin_amdgcn_sched_barrier(0); }
-        const int nm = f < F0 ? NFW : NFW - 1;              // MFMAs of this group (the sphere cut drops the last column fragment)
-        if (f < RF - 1 || ks == 3) {
-#pragma unroll
-          for (int g = 0; g < NFW; ++g) if (g < nm) acc[f][g] = MFMA_F64(av[p], bf[g], acc[f][g]);
-          __builtin_amdgcn_sched_barrier(0);
-        } else {
-          // the last group of a k-step that has a successor: two bursts
-#pragma unroll
-          for (int g = 0; g < NFW; ++g) if (g < H && g < nm) acc[f][g] = MFMA_F64(av[p], bf[g], acc[f][g]);
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int g = 0; g < H; ++g) bf[g] = SK_LDS_F64(ab[kn] + g * FB);
-          if (RF > 1) av[p ^ 1] = SK_LDS_F64(aa[kn]);       // the next k-step's first A value (this group has no successor in ITS k-step)
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int g = 0; g < NFW; ++g) if (g >= H && g < nm) acc[f][g] = MFMA_F64(av[p], bf[g], acc[f][g]);
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int g = H; g < NFW; ++g) bf[g] = SK_LDS_F64(ab[kn] + g * FB);
-          if (RF > 1) av[p] = SK_LDS_F64(aa[kn] + FA);      // ... and its second, into the register this group is done with
-          else av[p ^ 1] = SK_LDS_F64(aa[kn]);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-    }
-  }
-}
-
-// The product multiplies with the straight-line form; -DSK_MFMA_LOOP=1 (`make loopform`) builds the round-2 loop form for A/B runs.
-#ifndef SK_MFMA_LOOP
-#define SK_MFMA_LOOP 0
-#endif
-#if SK_MFMA_LOOP
-#define SK_MFMA_PHASE(RF, NFW, F0, c, smem, buf, acc) sk_mfma_chunk<RF, NFW>(c, smem, buf, acc)
-#define SK_LATE_PREFETCH 0
-#else
-// Measured in the kernel and left off (tools/ab_libs.sh, one box): sk_gemm 237.1-237.7 us with the burst form against 234.8-235.3 (headline),
-// 676.4-679.8 against 673.9-676.5 (slab geometry) -- what a single wave gains in the microbenchmark its SIMD partner was already filling
-// in the kernel, and the next k-step's first A value has two MFMAs of cover instead of a group's.
-#ifndef SK_BURST_READS
-#define SK_BURST_READS 0
-#endif
-#if SK_BURST_READS
-#define SK_MFMA_PHASE(RF, NFW, F0, c, smem, buf, acc) sk_mfma_chunk_v<RF, NFW, F0>(c, smem, buf, acc)
-#else
-#define SK_MFMA_PHASE(RF, NFW, F0, c, smem, buf, acc) sk_mfma_chunk_u<RF, NFW, F0>(c, smem, buf, acc)
-#endif
-// Measured and left off (round 4, one box, `make variant_pre VDEF=-DSK_LATE_PREFETCH=1`): the late waves' first operand reads requested
-// ahead of their panel build -- sk_gemm 243.5 vs 238.6 us at the headline size, 734 vs 734 us in the slab geometry.  The reads
-// queue ahead of the build's LDS writes as intended, but NFW + 1 more live registers through the build and a wait for them in
-// front of it cost more than the write drain they skip.
-#ifndef SK_LATE_PREFETCH
-#define SK_LATE_PREFETCH 0
-#endif
-// Early waves: first operand reads ahead of the next chunk's table loads.  Measured (tools/ab_libs.sh, one box each): in every body,
-// sk_gemm 235.9 -> 234.2 us at the headline size, 677 us either way in the slab geometry -- but four chunk loops of the bodies that
-// hold all 20 accumulator fragments then spill (tests/test_host_logic.py); restricted to the bodies with headroom: 235.2 vs 235.0 us,
-// and 17.24 vs 17.15 ms at 16384 / 262144.  Left off.
-#ifndef SK_EARLY_PREFETCH
-#define SK_EARLY_PREFETCH 0
-#endif
-// issue priority of the LATE waves (build first, multiply second: they arrive last at every barrier, the early waves wait ~a
-// quarter of a chunk for them): SK_PRIO > 0 raises them above their SIMD partner -- 3 through their build, SK_PRIO through their
-// multiply phase -- the early waves stay at 0
-#ifndef SK_PRIO
-#define SK_PRIO 0
-#endif
-// the same for the EARLY waves (multiply first): 1 = raised through their multiply phase only, 2 = through multiply and build.
-// Measured on one box (tools/ab_libs.sh, sk_gemm us, headline / slab geometry): late waves raised (SK_PRIO 1 / 2) 243.5 / 243.6 vs
-// 237.9 and 709 / 709 vs 680 -- worse; early waves raised through the multiply phase (SK_PRIO_E 1) 238.2 vs 237.6 and 675.7 vs 678.4;
-// through multiply and build (2) 236.5 and 673.4: the product's setting (3, the highest priority, reads the same: 235.5 / 674 either way).
-#ifndef SK_PRIO_E
-#define SK_PRIO_E 2
-#endif
-#endif
-// Ablation switches (phases of the kernel turned off, TIMING ONLY, results are garbage) exist in the diagnostic build
-// -DSK_ABLATE only (`make ablate`, tools/sk_ablate.sh); in the product build the tests below fold to constants.
-#ifdef SK_ABLATE
-#define SK_DBG(c, bit) ((c).dbg & (bit))
-#else
-#define SK_DBG(c, bit) 0
-#endif
-
-// ---- diagnostic build only (-DSK_STAMP, `make stamp`, tools/sk_stamp.py): s_memtime stamps around the phases of a chunk,
-// summed per wave in scalar registers and stored once per segment into a buffer nothing else reads.  In the product build no
-// stamp executes.  Its fences forbid overlaps the real kernel has: read the SHARES, never the length (guide, "In-kernel stamps").
-#ifdef SK_STAMP
-__device__ unsigned long long sk_stamp_buf[1024 * 8 * 8];   // [workgroup][wave][prologue, load issue, mfma, build, barrier, epilogue, chunks, late]
-__device__ unsigned long long sk_clock_buf[1024 * 4];       // [workgroup][s_memtime start, end, s_memrealtime (100 MHz) start, end]
-__device__ unsigned long long sk_seg_buf[4096 * 4];         // [segment][workgroup << 32 | rt, nbf, chunks, s_memrealtime ticks]: cost-model fit
-#define SK_STAMP_T(t)                                                          \
-  do {                                                                         \
-    __builtin_amdgcn_sched_barrier(0);                                         \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");  \
-    __builtin_amdgcn_sched_barrier(0);                                         \
-  } while (0)
-#define SK_STAMP_ADD(sum, a, b) sum += (b) - (a)
-#else
-#define SK_STAMP_T(t) do { } while (0)
-#define SK_STAMP_ADD(sum, a, b) do { } while (0)
-#endif
 
 // Planar electrodes: every electrode atom's z phase is one of a few columns ("z classes", b_hc_kernel), and all the update needs
 // from G is  Hc[r][zc] = sum_t w[r][t] G[r][t] Tzc[t][zc]  -- linear in G, so a segment projects ITS partial tile before it leaves
@@ -857,6 +596,7 @@ __device__ __forceinline__ void sk_project_out(const SkCtx &c, char *smem, d4 (&
 // One segment = (tile, chunk range).  Between two barriers the workgroup multiplies chunk c (panel buffer c&1) and
 // builds chunk c+1 (other buffer).  The two waves of a SIMD (w and w+4) do this in OPPOSITE order -- waves 0-3
 // multiply first, waves 4-7 build first -- so one wave's operand generation overlaps its partner's MFMAs.
+// The early waves run at issue priority 2 through their multiply and build, the late waves at 0 (DESIGN-LOG.md, round 4).
 template <int RF, int NFW, bool late, int F0>
 __device__ __forceinline__ void sk_body(const SkCtx &c, char *smem, double *outA, double *outB, double *outP) {
   // the fifth row fragment's planar vectors (64 + gs, gs < 16) are built by the threads gs < 16: the EARLY waves, which wait at the
@@ -868,118 +608,29 @@ __device__ __forceinline__ void sk_body(const SkCtx &c, char *smem, double *outA
 #pragma unroll
     for (int g = 0; g < (NFW > 0 ? NFW : 1); ++g) acc[f][g] = (d4){0.0, 0.0, 0.0, 0.0};
   SkRaw raw;
-#ifdef SK_STAMP
-  unsigned long long st_a = 0, st_b = 0, s_pro = 0, s_load = 0, s_mfma = 0, s_build = 0, s_bar = 0, s_epi = 0;
-#endif
-  SK_STAMP_T(st_a);
   sk_load_raw<THIRD>(c, c.it.c0, raw);
-#if SK_NOBAR
-  if (threadIdx.x < 4) reinterpret_cast<unsigned *>(smem + SK_CNT)[threadIdx.x] = 0u;
-#endif
   sk_build_panel<RF, THIRD>(c, raw, reinterpret_cast<double *>(smem));
-  if ((late || SK_LOAD_AHEAD) && c.it.c0 + 1 < c.it.c1) sk_load_raw<THIRD>(c, c.it.c0 + 1, raw);
+  if (late && c.it.c0 + 1 < c.it.c1) sk_load_raw<THIRD>(c, c.it.c0 + 1, raw);
   __syncthreads();
-  SK_STAMP_T(st_b); SK_STAMP_ADD(s_pro, st_a, st_b);
   unsigned buf = 0;                                    // byte offset of the panel being multiplied: 0 or SK_BUF1
   for (int ch = c.it.c0; ch < c.it.c1; ++ch, buf ^= SK_BUF1) {
     double *nxt = reinterpret_cast<double *>(smem + (buf ^ SK_BUF1));
     const bool more = ch + 1 < c.it.c1;
-#if SK_NOBAR
-    // chunk i of the segment lives in buffer i & 1.  Its panel is complete when built[i & 1] has reached 8 ((i + 1) >> 1) (chunk 0
-    // was built in front of the segment's barrier); buffer (i + 1) & 1 may be overwritten with chunk i + 1 when done[(i + 1) & 1]
-    // has reached 8 ((i + 1) >> 1): all eight waves have multiplied chunk i - 1
-    const unsigned bi = buf ? 1u : 0u;
-    const unsigned tgt = 8u * (unsigned)((ch - c.it.c0 + 1) >> 1);
-#define SK_WAIT_PANEL() sk_cnt_wait(smem, bi, tgt)
-#define SK_DONE_PANEL() sk_cnt_signal(smem, 2u + bi)
-#define SK_WAIT_FREE() sk_cnt_wait(smem, 2u + (bi ^ 1u), tgt)
-#define SK_BUILT_NEXT() sk_cnt_signal(smem, bi ^ 1u)
-#else
-#define SK_WAIT_PANEL() do { } while (0)
-#define SK_DONE_PANEL() do { } while (0)
-#define SK_WAIT_FREE() do { } while (0)
-#define SK_BUILT_NEXT() do { } while (0)
-#endif
     if (!late) {
-      SK_STAMP_T(st_a);
-#if SK_PRIO_E
-      __builtin_amdgcn_s_setprio(SK_PRIO_E);
-#endif
-      // the phase's first operand reads go out BEFORE the next chunk's table loads are issued: the loads' address arithmetic and
-      // issue (6-8 instructions per thread) then run in the shadow of the LDS round trip instead of in front of it.  Not in the
-      // bodies that hold all 20 accumulator fragments: NFW + 1 more live registers there mean spills inside the chunk loop
-      constexpr bool EPRE = SK_EARLY_PREFETCH && !SK_MFMA_LOOP && RF * NFW < 20;
-      SkPre<NFW> pre;
-      if constexpr (EPRE) { if (!(SK_DBG(c, 2))) sk_mfma_prefetch<NFW>(c, smem, buf, pre); }
-      if (!SK_LOAD_AHEAD && more && !(SK_DBG(c, 4))) sk_load_raw<THIRD>(c, ch + 1, raw);
-      SK_STAMP_T(st_b); SK_STAMP_ADD(s_load, st_a, st_b);
-      SK_WAIT_PANEL();
-      if constexpr (EPRE) { if (!(SK_DBG(c, 2))) sk_mfma_chunk_u<RF, NFW, F0>(c, smem, buf, acc, &pre); }
-      else { if (!(SK_DBG(c, 2))) SK_MFMA_PHASE(RF, NFW, F0, c, smem, buf, acc); }
-      SK_DONE_PANEL();
-      SK_STAMP_T(st_a); SK_STAMP_ADD(s_mfma, st_b, st_a);
-#if SK_PRIO_E == 1
-      __builtin_amdgcn_s_setprio(0);            // (variant 1: the early waves' build at the base priority; 2 / 3: raised throughout)
-#endif
-      if (more) {
-        SK_WAIT_FREE();
-        if (!(SK_DBG(c, 1))) sk_build_panel<RF, THIRD>(c, raw, nxt);
-        SK_BUILT_NEXT();
-      }
-      if (SK_LOAD_AHEAD && ch + 2 < c.it.c1 && !(SK_DBG(c, 4))) sk_load_raw<THIRD>(c, ch + 2, raw);
-      SK_STAMP_T(st_b); SK_STAMP_ADD(s_build, st_a, st_b);
+      __builtin_amdgcn_s_setprio(2);
+      if (more) sk_load_raw<THIRD>(c, ch + 1, raw);
+      sk_mfma_chunk_u<RF, NFW, F0>(c, smem, buf, acc);
+      if (more) sk_build_panel<RF, THIRD>(c, raw, nxt);
     } else {
-#if SK_LATE_MODE == 1
-      // full stagger: build first, multiply second
-      SK_STAMP_T(st_a);
-#if SK_PRIO
-      __builtin_amdgcn_s_setprio(3);
-#endif
-#if SK_LATE_PREFETCH
-      // (the phase's first operand reads go out ahead of the build's LDS writes: sk_mfma_prefetch)
-      SkPre<NFW> pre;
-      if (!(SK_DBG(c, 2))) sk_mfma_prefetch<NFW>(c, smem, buf, pre);
-#endif
-      if (more) {
-        SK_WAIT_FREE();
-        if (!(SK_DBG(c, 1))) sk_build_panel<RF, THIRD>(c, raw, nxt);
-        SK_BUILT_NEXT();
-      }
-      SK_STAMP_T(st_b); SK_STAMP_ADD(s_build, st_a, st_b);
-      if (ch + 2 < c.it.c1 && !(SK_DBG(c, 4))) sk_load_raw<THIRD>(c, ch + 2, raw);
-      SK_STAMP_T(st_a); SK_STAMP_ADD(s_load, st_b, st_a);
-#if SK_PRIO
-      __builtin_amdgcn_s_setprio(SK_PRIO);
-#endif
-      SK_WAIT_PANEL();
-#if SK_LATE_PREFETCH
-      if (!(SK_DBG(c, 2))) sk_mfma_chunk_u<RF, NFW, F0>(c, smem, buf, acc, &pre);
-#else
-      if (!(SK_DBG(c, 2))) SK_MFMA_PHASE(RF, NFW, F0, c, smem, buf, acc);
-#endif
-      SK_DONE_PANEL();
-      SK_STAMP_T(st_b); SK_STAMP_ADD(s_mfma, st_a, st_b);
-#else
-#error "only the full stagger (SK_LATE_MODE 1) is kept: half stagger measured 264 vs 260 us (DESIGN.md)"
-#endif
+      if (more) sk_build_panel<RF, THIRD>(c, raw, nxt);
+      if (ch + 2 < c.it.c1) sk_load_raw<THIRD>(c, ch + 2, raw);
+      sk_mfma_chunk_u<RF, NFW, F0>(c, smem, buf, acc);
     }
-#if !SK_NOBAR
     __syncthreads();
-#endif
-    SK_STAMP_T(st_a); SK_STAMP_ADD(s_bar, st_b, st_a);
-#undef SK_WAIT_PANEL
-#undef SK_DONE_PANEL
-#undef SK_WAIT_FREE
-#undef SK_BUILT_NEXT
   }
-#if SK_NOBAR
-  __syncthreads();          // the epilogue re-uses the panels' memory: every wave has multiplied its last chunk
-#endif
   // ---- partial tile out (only the active fragments), fragment-major: sk_part_off().  Two 16-byte stores per fragment, each
   //      wave-instruction one contiguous KB (the row-major layout took four 8-byte stores per fragment, each four 128-byte pieces:
   //      the store tail of a segment is issue-bound)
-  if (SK_DBG(c, 16)) return;
-  SK_STAMP_T(st_a);
   if (c.proj) {
     sk_project_out<RF, NFW>(c, smem, acc, outP);
   } else {
@@ -997,19 +648,11 @@ __device__ __forceinline__ void sk_body(const SkCtx &c, char *smem, double *outA
       double2 *o = reinterpret_cast<double2 *>(ob + lane_off) + (((g & 3) * 20) << 7);
 #pragma unroll
       for (int gg = 0; gg < NFW; ++gg) {
-        st_d2(o + ((4 * gg) << 7), make_double2(acc[f][gg][0], acc[f][gg][1]), SK_PART_NT);
-        st_d2(o + ((4 * gg) << 7) + 64, make_double2(acc[f][gg][2], acc[f][gg][3]), SK_PART_NT);
+        o[(4 * gg) << 7] = make_double2(acc[f][gg][0], acc[f][gg][1]);
+        o[((4 * gg) << 7) + 64] = make_double2(acc[f][gg][2], acc[f][gg][3]);
       }
     }
   }
-#ifdef SK_STAMP
-  SK_STAMP_T(st_b); SK_STAMP_ADD(s_epi, st_a, st_b);
-  if ((threadIdx.x & 63) == 0 && blockIdx.x < 1024) {
-    unsigned long long *o = sk_stamp_buf + ((size_t)blockIdx.x * 8 + (threadIdx.x >> 6)) * 8;
-    o[0] += s_pro; o[1] += s_load; o[2] += s_mfma; o[3] += s_build; o[4] += s_bar; o[5] += s_epi;
-    o[6] += (unsigned long long)(c.it.c1 - c.it.c0); o[7] = late ? 1 : 0;
-  }
-#endif
 }
 
 
@@ -1125,13 +768,11 @@ template <bool FUSE>
 __global__ __launch_bounds__(512, 2) void sk_gemm_kernel(DevPlan pl, const SkWItem *__restrict__ witems, int maxseg, int nl_pad,
                                                          const double2 *__restrict__ Xt, const double2 *__restrict__ Yt,
                                                          const double2 *__restrict__ Zs, const double *__restrict__ qc,
-                                                         double *__restrict__ part, const SkProj *__restrict__ proj, int dbg,
-                                                         const SkFuse *__restrict__ fzp /*device copy, or null*/, int nwg_sk,
-                                                         unsigned *__restrict__ ticket /*b_zc_fused_kernel's hand-off word, zeroed here; or null*/) {
+                                                         double *__restrict__ part, const SkProj *__restrict__ proj,
+                                                         const SkFuse *__restrict__ fzp /*device copy, or null*/, int nwg_sk) {
   extern __shared__ __attribute__((aligned(16))) char smem[];   // panel buffer 0 at byte 0, buffer 1 at byte SK_BUF1
   const int t = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-  if (ticket && blockIdx.x == 0 && t == 0) *ticket = 0u;
   if (FUSE && (int)blockIdx.x >= nwg_sk) {
     // spare workgroups of a small system's launch: the real-space pair sums of the electrode rows, one wavefront per row
     const BRowArgs ra = fzp->rows;
@@ -1143,16 +784,12 @@ __global__ __launch_bounds__(512, 2) void sk_gemm_kernel(DevPlan pl, const SkWIt
     return;
   }
   SkCtx c;
-  c.dbg = dbg;
   c.nl_pad = nl_pad; c.nz = pl.nz;
   c.rh = wave & 1; c.cg = wave >> 1; c.wave = wave;
   c.Xt = Xt; c.Yt = Yt; c.Zs = Zs; c.qc = qc;
   c.proj = proj;
   c.nrx16 = (unsigned)(pl.kxmax + 2) * 16; c.nry16 = (unsigned)(pl.kymax + 1) * 16; c.nrz16 = (unsigned)(1 + pl.n_col_tiles * 32) * 16;
-  const bool late = wave >= 4 && !(SK_DBG(c, 8));
-#ifdef SK_STAMP
-  unsigned long long ck0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
+  const bool late = wave >= 4;
   const SkWItem *wi = witems + (size_t)blockIdx.x * maxseg;
   SkWItem cur = wi[0];
   const int nseg = cur.nseg;
@@ -1227,9 +864,6 @@ __global__ __launch_bounds__(512, 2) void sk_gemm_kernel(DevPlan pl, const SkWIt
       outA = part + (size_t)cur.sga * (128 * 320);
       if (cur.sgb >= 0) outB = part + (size_t)cur.sgb * (128 * 320);
     }
-#ifdef SK_STAMP
-    const unsigned long long sg_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
     // one body per (row fragments of the band, column fragments of this wave, stagger role, sphere cut): the MFMA phase is
     // straight-line code.  f0 = rf (no culling) is always correct -- culled fragments only hold G entries that no listed k reads --
     // and serves as the default.  RF = 4 bands take up to 5 column fragments per wave, RF = 5 bands up to 4 (20 accumulator
@@ -1272,40 +906,8 @@ __global__ __launch_bounds__(512, 2) void sk_gemm_kernel(DevPlan pl, const SkWIt
 #undef SK_BODY_NFW
 #undef SK_BODY_F0_4
 #undef SK_BODY_F0_5
-#ifdef SK_STAMP
-    if (t == 0 && sg < 4096) {
-      unsigned long long *o = sk_seg_buf + (size_t)sg * 4;
-      unsigned xcc;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcc));      // which XCD this workgroup landed on
-      o[0] = ((unsigned long long)blockIdx.x << 32) | ((xcc & 15u) << 16) | (unsigned)c.it.g0; o[1] = c.it.nbf; o[2] = (unsigned long long)(unsigned)(c.it.c1 - c.it.c0) | ((unsigned long long)c.it.rf << 32);
-      o[3] = __builtin_amdgcn_s_memrealtime() - sg_t0;
-    }
-#endif
   }
-#ifdef SK_STAMP
-  if (t == 0 && blockIdx.x < 1024) {
-    unsigned long long *o = sk_clock_buf + (size_t)blockIdx.x * 4;
-    o[0] = ck0; o[1] = __builtin_amdgcn_s_memtime(); o[2] = rt0; o[3] = __builtin_amdgcn_s_memrealtime();
-  }
-#endif
 }
-
-#ifdef SK_STAMP
-extern "C" int conp_debug_sk_clock(unsigned long long *out /*[1024*4]*/) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(sk_clock_buf), sizeof(unsigned long long) * 1024 * 4) == hipSuccess ? 0 : -1;
-}
-extern "C" int conp_debug_sk_segs(unsigned long long *out /*[4096*4]*/) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(sk_seg_buf), sizeof(unsigned long long) * 4096 * 4) == hipSuccess ? 0 : -1;
-}
-extern "C" int conp_debug_sk_stamps(unsigned long long *out /*[1024*8*8]*/, int reset) {
-  if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(sk_stamp_buf), sizeof(unsigned long long) * 1024 * 8 * 8) != hipSuccess) return -1;
-  if (reset) {
-    static unsigned long long zeros[1024 * 8 * 8];
-    if (hipMemcpyToSymbol(HIP_SYMBOL(sk_stamp_buf), zeros, sizeof(zeros)) != hipSuccess) return -1;
-  }
-  return 0;
-}
-#endif
 
 int sk_hc_stride() { return SK_HC * SK_HC_ROWS; }
 int sk_hc_max_classes() { return SK_HC_MAX; }
@@ -1314,7 +916,7 @@ int sk_hc_max_classes() { return SK_HC_MAX; }
 // classes; proj = device copy of the parameter block) the segments' projected pieces [segment][sk_hc_stride()]
 void launch_sk_gemm(hipStream_t s, const DevPlan &pl, const SkWItem *witems, int maxseg, int nwg, int nl_pad,
                     const double2 *Xt, const double2 *Yt, const double2 *Zs, const double *qc, double *part, const SkProj *proj,
-                    const SkFuse *fuse, int fuse_rows, unsigned *ticket) {
+                    const SkFuse *fuse, int fuse_rows) {
   if (nwg <= 0) return;
   // fuse: DEVICE copy of the parameter block (conp_fix.cpp uploads it when its content changes); fuse_rows: its rows.ne
   const int extra = fuse ? (fuse_rows + 7) / 8 : 0;
@@ -1322,17 +924,12 @@ void launch_sk_gemm(hipStream_t s, const DevPlan &pl, const SkWItem *witems, int
   static DynLdsCache granted{}, granted_f{};
   if (fuse) ensure_dyn_lds(sk_gemm_kernel<true>, lds, granted_f);
   else ensure_dyn_lds(sk_gemm_kernel<false>, lds, granted);
-#ifdef SK_ABLATE
-  static const int dbg = getenv("CONP_SK_DBG") ? atoi(getenv("CONP_SK_DBG")) : 0;   // diagnostic build only
-#else
-  const int dbg = 0;
-#endif
   if (fuse)
     hipLaunchKernelGGL(sk_gemm_kernel<true>, dim3(nwg + extra), dim3(512), lds, s, pl, witems, maxseg, nl_pad, Xt, Yt, Zs, qc, part, proj,
-                       dbg, fuse, nwg, ticket);
+                       fuse, nwg);
   else
-    hipLaunchKernelGGL(sk_gemm_kernel<false>, dim3(nwg), dim3(512), lds, s, pl, witems, maxseg, nl_pad, Xt, Yt, Zs, qc, part, proj, dbg,
-                       fuse, nwg, ticket);
+    hipLaunchKernelGGL(sk_gemm_kernel<false>, dim3(nwg), dim3(512), lds, s, pl, witems, maxseg, nl_pad, Xt, Yt, Zs, qc, part, proj,
+                       fuse, nwg);
 }
 
 // G = sum over a tile's splits (fixed order).  Gwf = w * G in MFMA-fragment-major order for b_project:
@@ -1370,7 +967,7 @@ __device__ __forceinline__ double2 part_sum2(const double *__restrict__ src, siz
   for (; sp + 16 <= count; sp += 16) {
     double2 v[16];
 #pragma unroll
-    for (int u = 0; u < 16; ++u) v[u] = ld_d2(reinterpret_cast<const double2 *>(src + (size_t)(sp + u) * step), SK_PART_NT);
+    for (int u = 0; u < 16; ++u) v[u] = *reinterpret_cast<const double2 *>(src + (size_t)(sp + u) * step);
 #pragma unroll
     for (int u = 0; u < 8; ++u) { a8[u] += v[u].x; b8[u] += v[u].y; }
 #pragma unroll
@@ -1379,12 +976,12 @@ __device__ __forceinline__ double2 part_sum2(const double *__restrict__ src, siz
   for (; sp + 8 <= count; sp += 8) {
     double2 v[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = ld_d2(reinterpret_cast<const double2 *>(src + (size_t)(sp + u) * step), SK_PART_NT);
+    for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const double2 *>(src + (size_t)(sp + u) * step);
 #pragma unroll
     for (int u = 0; u < 8; ++u) { a8[u] += v[u].x; b8[u] += v[u].y; }
   }
   for (int u = 0; sp < count; ++sp, ++u) {
-    const double2 v = ld_d2(reinterpret_cast<const double2 *>(src + (size_t)sp * step), SK_PART_NT);
+    const double2 v = *reinterpret_cast<const double2 *>(src + (size_t)sp * step);
     a8[u] += v.x; b8[u] += v.y;
   }
   return make_double2(((a8[0] + a8[1]) + (a8[2] + a8[3])) + ((a8[4] + a8[5]) + (a8[6] + a8[7])),
@@ -1403,7 +1000,7 @@ constexpr int SKR_GROUP = 16;
 constexpr int SKR_T = 640;                         // threads per block
 // two levels (one more launch) once the most-split tile has more than this many partials: measured break-even on the headline
 // box -- 40 partials (one GPU) 4 us faster in one level, 57 (two ranks) equal, 113 (four ranks) 12 us faster in two
-static int skr_two_level_from() { static const int v = diag_switch("CONP_SKR_TWO") ? atoi(diag_switch("CONP_SKR_TWO")) : 4 * SKR_GROUP; return v; }
+constexpr int SKR_TWO_LEVEL_FROM = 4 * SKR_GROUP;
 template <int SKR_SL>
 __global__ __launch_bounds__(SKR_T) void sk_reduce_kernel(int C_pad, const SkTile *__restrict__ tiles,
                                                         double *__restrict__ part, const double *__restrict__ wfull,
@@ -1462,7 +1059,7 @@ static int skr_slices(int ntiles) { return ntiles * 32 >= 200 ? 4 : 8; }
 template <int SL>
 static void launch_sk_reduce_sl(hipStream_t s, const DevPlan &pl, const SkTile *tiles, int ntiles, int max_nsplit, double *part, double *G,
                                 double *Gwf) {
-  if (max_nsplit > skr_two_level_from()) {
+  if (max_nsplit > SKR_TWO_LEVEL_FROM) {
     const int ngroups = (max_nsplit + SKR_GROUP - 1) / SKR_GROUP;
     hipLaunchKernelGGL(sk_reduce_kernel<SL>, dim3(ntiles * 8 * SL, ngroups), dim3(SKR_T), 0, s, pl.C_pad, tiles, part, pl.wfull, G, Gwf, 1);
     hipLaunchKernelGGL(sk_reduce_kernel<SL>, dim3(ntiles * 8 * SL), dim3(SKR_T), 0, s, pl.C_pad, tiles, part, pl.wfull, G, Gwf, 2);
@@ -1935,203 +1532,8 @@ __global__ __launch_bounds__(256) void hc_sum_wide_kernel(const int *__restrict_
   if (live && (threadIdx.x & (8 * NO - 1)) == 0) Hc4[(size_t)cls * R_pad + (size_t)(g >> 2) * 128 + 64 * half + 16 * (g & 3) + i] = acc;
 }
 
-// ---- round 5: hc_sum_kernel and b_zc_final_kernel as ONE launch (headline and slab plans: many pieces per row fragment) ----------
-// The dot kernel needs the whole class table H of the rank, the pieces' sums are a few workgroups' work: they used to be two launches
-// with the real-space pair rows riding in the first.  Here the first P workgroups add the pieces (hc_sum_kernel's arithmetic: eight
-// lanes per element, groups of eight by a butterfly, groups in list order) and PUBLISH the table -- write-through stores (agent-scope
-// relaxed atomics = sc1), the storing waves' vmcnt(0), the workgroup barrier, ONE relaxed agent-scope ticket add per workgroup: the
-// fence-free hand-off of the inverse's panel (conp_inverse.hip; a device-scope fence writes back and invalidates an XCD's whole L2:
-// the hand-offs of rounds 2-4 that lost were built on those, or put the waiting on sk_gemm's critical path).  The dot workgroups do
-// everything that does not need H first -- request their first eight tiles' phases, and form the pair sums of their 16 electrode
-// rows, one wavefront per row (the rows that rode along in hc_sum's launch) -- then ONE thread polls the ticket, and H comes out of
-// memory by sc1 loads.  Co-residency: the grid is P + ne_pad / 16 workgroups of 1024 threads (273 at the headline size, two fit a
-// CU), producers first in dispatch order; a dot workgroup whose wait runs out (bounded spin) adds the pieces it needs ITSELF --
-// the same bits, frag_sum_serial -- so a co-scheduled kernel can slow this one down but not hang it.
-// The ticket word is zeroed by sk_gemm's launch (workgroup 0), which is always in front of this one on the stream.
-__device__ __forceinline__ double frag_sum_serial(const int *__restrict__ frag_ptr, const int2 *__restrict__ ents,
-                                                  const double *__restrict__ Hp, int g, int cls, int half, int i) {
-  const int s0 = frag_ptr[g], s1 = frag_ptr[g + 1];
-  double acc = 0.0;
-  const int ng = (s1 - s0) / 8 + 1;
-  for (int gb = 0; gb < ng; ++gb) {
-    double v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int sidx = s0 + 8 * gb + u;
-      v[u] = 0.0;
-      if (sidx < s1) {
-        const int2 en = ents[sidx];
-        v[u] = Hp[(size_t)en.x + (size_t)(cls * 32 * en.y + half * 16 * en.y + i)];
-      }
-    }
-    acc += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-  }
-  return acc;
-}
-struct HcFused {
-  const int *frag_ptr; const int2 *ents; const double *Hp; double *Hc; unsigned *ticket;
-  int nfrag, P; unsigned spin_limit;
-};
-__global__ __launch_bounds__(1024) void b_zc_fused_kernel(HcFused hf, int n_own, const int *__restrict__ own_rt, int R_pad, int ne_pad,
-                                                          int nzc, const double2 *__restrict__ Xe, const double2 *__restrict__ Ye,
-                                                          const int *__restrict__ own_pv, const int *__restrict__ zclass, BRowArgs ra,
-                                                          BRowArgs pairs) {
-#pragma clang fp contract(off)
-  extern __shared__ __attribute__((aligned(16))) char zf_smem[];
-  const int tid = threadIdx.x;
-  if ((int)blockIdx.x < hf.P) {
-    // ---- producer: 128 elements of the class table per workgroup, eight lanes each
-    const int u = tid & 7, e = (int)blockIdx.x * 128 + (tid >> 3);
-    const int per = 32 * nzc;
-    const bool live = e < hf.nfrag * per;
-    const int g = live ? e / per : 0, rem = live ? e - g * per : 0;
-    const int cls = rem >> 5, half = (rem >> 4) & 1, i = rem & 15;
-    const int s0 = hf.frag_ptr[g], s1 = live ? hf.frag_ptr[g + 1] : s0;
-    double acc = 0.0;
-    const int ng = (s1 - s0) / 8 + 1;                  // (uniform over the wave: its eight elements belong to one fragment)
-    for (int gb = 0; gb < ng; gb += HCS_MAXG) {
-      double v[HCS_MAXG];
-#pragma unroll
-      for (int k = 0; k < HCS_MAXG; ++k) {
-        const int sidx = s0 + 8 * (gb + k) + u;
-        v[k] = 0.0;
-        if (sidx < s1) {
-          const int2 en = hf.ents[sidx];
-          v[k] = hf.Hp[(size_t)en.x + (size_t)(cls * 32 * en.y + half * 16 * en.y + i)];
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < HCS_MAXG; ++k) {
-        if (gb + k >= ng) break;
-        double t = v[k];
-        t += __shfl_xor(t, 1, 64);
-        t += __shfl_xor(t, 2, 64);
-        t += __shfl_xor(t, 4, 64);
-        acc += t;
-      }
-    }
-    if (live && u == 0)
-      __hip_atomic_store(hf.Hc + (size_t)cls * R_pad + (size_t)(g >> 2) * 128 + 64 * half + 16 * (g & 3) + i, acc, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) __hip_atomic_fetch_add(hf.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return;
-  }
-  // ---- dot workgroup: b_zc_final_kernel with the pair sums and the wait in it
-  double *H = reinterpret_cast<double *>(zf_smem);          // [n_own * 128][nzc]
-  __shared__ double red[64][17];
-  __shared__ double prl[16];
-  __shared__ int s_ready;
-  const int blk = (int)blockIdx.x - hf.P;
-  const int a = tid & 15, w = tid >> 4;
-  const int i = blk * 16 + a;
-  const int zc = zclass[i];
-  const double sc = (ra.slab && tid < 64) ? b_slab_scalar(ra, tid) : 0.0;
-  double fin_z = 0.0;
-  if (w == 0 && i < ra.ne && ra.slab) fin_z = ra.ele_z[i];
-  double2 xe0[8], ye0[8];
-  int sg0[8];
-#pragma unroll
-  for (int u = 0; u < 8; ++u) {
-    const bool ok = u < n_own;
-    const int pk = own_pv[(ok ? u : 0) * 64 + w];
-    sg0[u] = (pk >> 24) & 1;
-    xe0[u] = ok ? Xe[(size_t)(pk & 4095) * ne_pad + i] : make_double2(0.0, 0.0);
-    ye0[u] = Ye[(size_t)((pk >> 12) & 4095) * ne_pad + i];
-  }
-  {
-    // the real-space pair sum of electrode row 16 blk + wave, by this wavefront
-    const int row = blk * 16 + (tid >> 6);
-    const double v = row < pairs.ne ? b_row_pairs(pairs, row, tid & 63) : 0.0;
-    if ((tid & 63) == 0) prl[tid >> 6] = v;
-  }
-  if (tid == 0) {
-    unsigned spins = 0;
-    int ok = 1;
-    while (__hip_atomic_load(hf.ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)hf.P) {
-      if (++spins > hf.spin_limit) { ok = 0; break; }
-      __builtin_amdgcn_s_sleep(1);
-    }
-    s_ready = ok;
-  }
-  __syncthreads();
-  const int nrow = n_own * 128;
-  if (s_ready) {
-    // class-major table: runs of rows, classes in use only; sc1 loads, up to four per thread in flight (64 KB of table at most)
-    for (int e0 = tid; e0 < nrow * nzc; e0 += 4 * 1024) {
-      double hv[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int e = e0 + 1024 * u;
-        hv[u] = 0.0;
-        if (e < nrow * nzc) {
-          const int cls = e / nrow, rowl = e - cls * nrow;
-          const double *src = hf.Hc + (size_t)cls * R_pad + (size_t)own_rt[rowl >> 7] * 128 + (rowl & 127);
-          asm volatile("global_load_dwordx2 %0, %1, off sc1" : "=v"(hv[u]) : "v"(src) : "memory");
-        }
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int e = e0 + 1024 * u;
-        if (e < nrow * nzc) { const int cls = e / nrow, rowl = e - cls * nrow; H[rowl * nzc + cls] = hv[u]; }
-      }
-    }
-  } else {
-    for (int e = tid; e < nrow * nzc; e += 1024) {      // the wait ran out: the same sums, by this workgroup
-      const int cls = e / nrow, rowl = e - cls * nrow, r = rowl & 127;
-      H[rowl * nzc + cls] = frag_sum_serial(hf.frag_ptr, hf.ents, hf.Hp, 4 * own_rt[rowl >> 7] + ((r & 63) >> 4), cls, r >> 6, r & 15);
-    }
-  }
-  __syncthreads();
-  double sum = 0.0;
-  auto phase = [](double2 X, double2 Y, int neg, double &pa, double &pb) {
-    const double sy = neg ? -Y.y : Y.y;
-    pa = X.x * Y.x - X.y * sy;
-    pb = X.x * sy + X.y * Y.x;
-  };
-#pragma unroll
-  for (int u = 0; u < 8; ++u) {
-    const int kk = u < n_own ? u : 0;
-    double pa, pb;
-    phase(xe0[u], ye0[u], sg0[u], pa, pb);
-    sum += pa * H[(kk * 128 + w) * nzc + zc];
-    sum += pb * H[(kk * 128 + w + 64) * nzc + zc];
-  }
-  for (int k0 = 8; k0 < n_own; k0 += 4) {
-    double2 xe[4], ye[4];
-    int sg[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const bool ok = k0 + u < n_own;
-      const int pk = own_pv[(ok ? k0 + u : k0) * 64 + w];
-      sg[u] = (pk >> 24) & 1;
-      xe[u] = ok ? Xe[(size_t)(pk & 4095) * ne_pad + i] : make_double2(0.0, 0.0);
-      ye[u] = Ye[(size_t)((pk >> 12) & 4095) * ne_pad + i];
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int kk = k0 + u < n_own ? k0 + u : k0;
-      double pa, pb;
-      phase(xe[u], ye[u], sg[u], pa, pb);
-      sum += pa * H[(kk * 128 + w) * nzc + zc];
-      sum += pb * H[(kk * 128 + w + 64) * nzc + zc];
-    }
-  }
-  red[w][a] = sum;
-  __syncthreads();
-  if (w == 0 && i < ra.ne) {
-    double tot = 0.0;
-#pragma unroll
-    for (int k = 0; k < 64; k += 4) tot += (red[k][a] + red[k + 1][a]) + (red[k + 2][a] + red[k + 3][a]);
-    double v = -tot;
-    if (ra.slab) v -= fin_z * sc;
-    v += prl[a];
-    ra.b_out[i] = v;
-    if (ra.slab && i == 0 && ra.slab_out) *ra.slab_out = sc;
-  }
-}
+// (Measured and left off, DESIGN-LOG.md 13.3: hc_sum_kernel, the pair sums and b_zc_final_kernel as ONE launch with an in-launch
+//  hand-off of the class table.)
 
 // (The four row-quarter partials of an atom are added, with the slab and real-space terms, by b_real_combine_kernel.  Letting the
 //  last-arriving quarter block of each atom block do that here -- sc1 hand-off, ticket -- was measured: 32 -> 47 us for the pair
@@ -2224,7 +1626,7 @@ template <int SL>
 static void launch_reduce_hc_sl(hipStream_t s, const DevPlan &pl, const SkTile *tiles, int ntiles, int max_nsplit, double *part, double *G,
                                 const double *Tzc, double *Hc, int nzc16) {
   int level = 0;
-  if (max_nsplit > skr_two_level_from()) {
+  if (max_nsplit > SKR_TWO_LEVEL_FROM) {
     const int ngroups = (max_nsplit + SKR_GROUP - 1) / SKR_GROUP;
     hipLaunchKernelGGL(sk_reduce_kernel<SL>, dim3(ntiles * 8 * SL, ngroups), dim3(SKR_T), 0, s, pl.C_pad, tiles, part, pl.wfull, G, nullptr, 1);
     level = 2;
@@ -2262,20 +1664,9 @@ void launch_project_zclass_pieces(hipStream_t s, const DevPlan &pl, int ne_pad, 
                                   const int *slot_ptr, const int *slot_idx, bool presum, const int *frag_ptr, const int2 *frag_ents, int nfrag,
                                   const double *Rp, const double2 *Xe,
                                   const double2 *Ye, const int *own_pv, const int *zclass, double *Hc, double *bk_part, const BRowArgs *fin,
-                                  const BRowArgs *pairs, double *breal_out, unsigned *ticket, unsigned spin_limit, bool wide) {
+                                  const BRowArgs *pairs, double *breal_out, bool wide) {
   if (n_own <= 0) return;
   if (fin && !presum) { launch_b_zc_final(s, pl, n_own, own_rt, ne_pad, nzc, Xe, Ye, own_pv, Hp, zclass, *fin, 0, slot_ptr, slot_idx); return; }
-  if (nfrag > 0 && fin && pairs && ticket) {
-    // ONE launch (round 5): the pieces' sums published through the fence-free hand-off, the pair sums and the dot behind them
-    HcFused hf{frag_ptr, frag_ents, Hp, Hc, ticket, nfrag, (nfrag * 32 * nzc + 127) / 128, spin_limit};
-    const BRowArgs fa = *fin;
-    const size_t lds = (size_t)n_own * 128 * nzc * sizeof(double);
-    static DynLdsCache granted{};
-    ensure_dyn_lds(b_zc_fused_kernel, lds, granted);
-    hipLaunchKernelGGL(b_zc_fused_kernel, dim3(hf.P + ne_pad / 16), dim3(1024), lds, s, hf, n_own, own_rt, pl.R_pad, ne_pad, nzc, Xe, Ye,
-                       own_pv, zclass, fa, *pairs);
-    return;
-  }
   if (nfrag > 0) {
     // pairs: the real-space pair sums ride in this launch (block rows behind the fragments)
     const BRowArgs ra = pairs ? *pairs : BRowArgs{};
@@ -2328,11 +1719,7 @@ void launch_b_real_combine(hipStream_t s, int ne, int ne_pad, int row0, int row1
 // ~110 MB of other per-update traffic, nominally inside the 256 MiB Infinity Cache): plain loads made the GEMV 1.5 us faster and
 // the phase and reduction kernels 3.5 us slower -- the matrix does not stay resident beside that much written data.
 constexpr size_t GEMV_RESIDENT_BYTES = (size_t)64 << 20;
-static bool gemv_nt(size_t matrix_bytes) {
-  static const char *e = diag_switch("CONP_GEMV_NT");      // comparison switch: 0 / 1 forces the policy
-  if (e) return atoi(e) != 0;
-  return matrix_bytes > GEMV_RESIDENT_BYTES;
-}
+static bool gemv_nt(size_t matrix_bytes) { return matrix_bytes > GEMV_RESIDENT_BYTES; }
 template <bool NT>
 __device__ __forceinline__ double2 nt_load(const double2 *p) {
   if constexpr (!NT) return *p;
@@ -3504,159 +2891,7 @@ __global__ __launch_bounds__(1024) void cg_step_kernel(int n, const double *__re
   if (lane == 0) ap2[(size_t)(iter & 1) * n + row] = s0;
 }
 
-// ---- round 5: the whole solve as ONE launch (n <= 4096: the vectors live in registers, four elements per thread).  MEASURED SLOWER than a
-// launch per iteration (il_twolayer: 92-94 against 76-78 us per solve, profiles/r05_cg_persist_ab.txt): a test path, not the default.
-// A kernel boundary invalidates the XCDs' L2s (the counters say so: cg_step_kernel fetches the whole matrix from the memory side at
-// every launch, FETCH_SIZE = 8 n^2 bytes), so a launch per iteration re-reads a deck-sized matrix that would fit the aggregate L2
-// (22 MB at Ne = 1664) seven times.  Here the workgroups stay: each keeps multiplying ITS rows (plain loads: from its XCD's L2 from
-// the second iteration on), publishes the products by write-through stores, passes ONE grid barrier per iteration -- the fence-free
-// ticket of the inverse's panel -- and reads the whole product vector back by sc1 loads; every workgroup then repeats the vector
-// update for itself (cg_step_kernel's code, reduction trees and element mapping: the same bits in every workgroup and the same bits
-// as the launch-per-iteration forms), with p, r and q never leaving its registers.  All workgroups must be resident (the host asks
-// the occupancy API); a barrier wait that runs out stores -7 in the control block and the host repeats the solve with a launch per
-// iteration.  Two ticket words alternate between solves: this solve zeroes the other one.
-__global__ __launch_bounds__(1024) void cg_persist_kernel(int n, const double *__restrict__ A, const double *__restrict__ b,
-                                                          double *__restrict__ q, double *ap2 /*[2][n]: the products, by iteration parity*/,
-                                                          double *__restrict__ scal, double tolerance, int maxiter, double *__restrict__ hist,
-                                                          int rows_per_block, double *__restrict__ host_ctl, unsigned *ticket,
-                                                          unsigned *ticket_next, unsigned spin_limit) {
-  extern __shared__ __attribute__((aligned(16))) char cg_smem[];
-  double *pl = reinterpret_cast<double *>(cg_smem);          // the direction of the matvec: [n]
-  __shared__ double red[32];
-  __shared__ int s_abort;
-  const bool writer = blockIdx.x == 0;
-  const unsigned G = gridDim.x;
-  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-  if (writer && tid == 0) *ticket_next = 0u;
-  if (tid == 0) s_abort = 0;
-  double kp[4], kr[4], kq[4], kap[4];
-  // ---- start (cg_step_kernel mode 1)
-  double lresnorm, gamma;
-  {
-    double netr = 0, l2 = 0;
-    for (int i = tid; i < n; i += 1024) { const double r = b[i]; netr += r; l2 += r * r; }
-    netr = block_sum_1024(netr, red);
-    l2 = block_sum_1024(l2, red);
-    const double ave = netr / n;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = tid + 1024 * u;
-      const double r = i < n ? b[i] : 0.0;
-      kr[u] = r; kp[u] = i < n ? r - ave : 0.0; kq[u] = 0.0;
-    }
-    const double lres = l2 - netr * ave;
-    lresnorm = lres; gamma = lres;
-    if (writer && tid == 0) { scal[0] = lres; scal[1] = lres; scal[2] = netr; scal[6] = 0.0; scal[7] = 0.0; scal[8] = 0.0; }
-  }
-  const int row = blockIdx.x * rows_per_block + wv;
-  const bool has_row = wv < rows_per_block && row < n;
-  auto finish = [&](int it, double done_flag, double lr, double lg, double netr, double ptap, double alpha, double beta) {
-    // the writer workgroup leaves the solution and the control block (device copy and, when asked, the page-locked host copy)
-    if (!writer) return;
-    double qs = 0.0;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { const int i = tid + 1024 * u; if (i < n) { q[i] = kq[u]; qs += kq[u]; } }
-    qs = block_sum_1024(qs, red);
-    if (tid == 0) {
-      scal[0] = lr; scal[1] = lg; scal[2] = netr; scal[3] = ptap; scal[4] = alpha; scal[5] = beta;
-      scal[6] = (double)it; scal[7] = qs; scal[8] = done_flag;
-    }
-    __syncthreads();
-    if (host_ctl) for (int i = tid; i < 16 + it + 1; i += 1024) host_ctl[i] = i < 16 ? scal[i] : hist[i - 16];
-  };
-  for (int it = 1;; ++it) {
-    // ---- matvec of iteration it with the direction every workgroup holds
-    __syncthreads();                                         // (the previous iteration's readers of pl are done)
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { const int i = tid + 1024 * u; if (i < n) pl[i] = kp[u]; }
-    __syncthreads();
-    double *apw = ap2 + (size_t)(it & 1) * n;
-    if (has_row) {
-      const double s0 = wave_sum(cg_row_dot(n, A + (size_t)row * n, pl, lane));
-      if (lane == 0) __hip_atomic_store(apw + row, s0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {                                          // grid barrier #it
-      __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned target = G * (unsigned)it;
-      unsigned spins = 0;
-      while (__hip_atomic_load(ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-        if (++spins > spin_limit) { s_abort = 1; break; }
-        __builtin_amdgcn_s_sleep(1);
-      }
-    }
-    __syncthreads();
-    if (s_abort) {
-      if (writer && tid == 0) { scal[8] = -7.0; if (host_ctl) host_ctl[8] = -7.0; }
-      return;
-    }
-    // (sc1 loads requested together: as relaxed atomics the compiler waits for each before it issues the next)
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = tid + 1024 * u;
-      kap[u] = 0.0;
-      if (i < n) { const double *src = apw + i; asm volatile("global_load_dwordx2 %0, %1, off sc1" : "=v"(kap[u]) : "v"(src) : "memory"); }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int u = 0; u < 4; ++u) asm volatile("" : "+v"(kap[u]));
-    // ---- the update of iteration it (cg_step_kernel modes 2 / 4, the `keep` branch)
-    double ptap = 0;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) if (tid + 1024 * u < n) ptap += kp[u] * kap[u];
-    ptap = block_sum_1024(ptap, red);
-    const double alpha = lresnorm / ptap;
-    double lg = 0, netr = 0;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = tid + 1024 * u;
-      if (i < n) {
-        kq[u] = kq[u] + alpha * kp[u];
-        const double r = kr[u] - alpha * kap[u];
-        kr[u] = r;
-        lg += r * r; netr += r;
-      }
-    }
-    block_sum2_1024(lg, netr, red);
-    const double ave = netr / n;
-    lg -= netr * ave;
-    const double beta = lg / gamma;
-    double lr = 0;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = tid + 1024 * u;
-      if (i < n) {
-        const double r = kr[u];
-        const double pn = beta * kp[u] + r - ave;
-        kp[u] = pn;
-        lr += r * pn;
-      }
-    }
-    lr = block_sum_1024(lr, red);
-    if (writer && tid == 0) hist[it] = lr;
-    lresnorm = lr; gamma = lg;
-    const bool converged = lr / n < tolerance;               // uniform over the whole grid: every workgroup holds the same lr
-    if (converged || it + 1 >= maxiter) { finish(it, converged ? 1.0 : 0.0, lr, lg, netr, ptap, alpha, beta); return; }
-  }
-}
-bool cg_persist_fits(int n) { return n > 0 && n <= 4096; }
-// returns false when the workgroups cannot all be resident on `num_cus` compute units (the caller takes the launch-per-iteration form)
-bool launch_cg_persist(hipStream_t s, int num_cus, int n, const double *A, const double *b, double *q, double *ap2, double *scal,
-                       double tolerance, int maxiter, double *hist, double *host_ctl, unsigned *ticket, unsigned *ticket_next,
-                       unsigned spin_limit) {
-  const size_t lds = (size_t)n * sizeof(double);
-  static DynLdsCache granted{};
-  ensure_dyn_lds(cg_persist_kernel, lds, granted);
-  const int rpb = 8;
-  const int nwg = (n + rpb - 1) / rpb;
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cg_persist_kernel, 1024, lds) != hipSuccess) { (void)hipGetLastError(); return false; }
-  if (per_cu <= 0 || nwg > per_cu * num_cus) return false;
-  hipLaunchKernelGGL(cg_persist_kernel, dim3(nwg), dim3(1024), lds, s, n, A, b, q, ap2, scal, tolerance, maxiter, hist, rpb, host_ctl, ticket,
-                     ticket_next, spin_limit);
-  return true;
-}
+// (Measured and left off, DESIGN-LOG.md 13.4: the whole solve as ONE persistent launch with a grid barrier per iteration.)
 
 bool cg_step_fits(int n) { return n > 0 && (size_t)n * sizeof(double) <= 128 * 1024; }
 

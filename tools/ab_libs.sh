@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of library builds on ONE box (boxes differ by 1-2 %): bash tools/ab_libs.sh [workload] name1 name2 ...   (name = "product" or
-# the NAME of lammps-user-conp2_amd/conp_amd/libconp_hip_NAME.so, e.g. a `make variant_NAME VDEF=...` build); two rounds each;
+# the NAME of lammps-user-conp2_amd/conp_amd/libconp_hip_NAME.so, e.g. a tools/build_variant.sh build); two rounds each;
 # AB_ARGS: more bench.py flags, e.g. AB_ARGS='--solver cg'
 set -o pipefail
 W=headline; case "$1" in headline|big|headline_slab|headline_rough|il_onelayer|il_twolayer|dilute|cond2) W=$1; shift;; esac
