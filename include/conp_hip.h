@@ -224,6 +224,24 @@ int conp_pppm_compute(conp_fix *fix, const conp_atoms *atoms);
 int conp_pppm_compute_group_potential(conp_fix *fix, const conp_atoms *atoms, const int *sel /*[nlocal]*/, double *recv /*[nlocal]*/);
 int conp_pppm_compute_particle_potential(conp_fix *fix, const conp_atoms *atoms, int i, double *u);
 
+/* ---- Ewald per-atom potential: the same three entries for the Ewald provider ------------------------------------------------
+ * The reference's KSpaceModuleEwald inherits `return 0.` for both potentials (kspacemodule.h:38-39), so its compute potential/atom
+ * (compute_potential_atom.cpp:165-175) needs a mesh.  Here the k sum is exact, with the handle's own k list and ug:
+ *   S_k = sum_j q_j e^{i k r_j} over every charged owned atom (electrolyte and electrode, the charges in `atoms`),
+ *   g_i = - sum_{k in the half list} 2 ug_k [cos(k r_i) Re S_k + sin(k r_i) Im S_k]      (no self term, as the mesh version)
+ *   u_i = g_i + 2 g_ewald q_i / sqrt(pi)
+ * Targets are any owned atoms, zero-charge probes included.  conp_ewald_compute forms and caches S (COLLECTIVE with decomposed
+ * ranks: each rank contracts its own atoms, S is summed through conp_comm.allreduce_sum; a replicated-atom handle -- several
+ * ranks without conp_fix_set_comm -- computes locally, no collective).  conp_ewald_compute_group_potential (collective):
+ * recv[i] = g_i for owned atoms with sel[i] != 0, from the cached S if a collective entry formed it since the last update, else
+ * from a fresh one.  conp_ewald_compute_particle_potential: u_i, RANK-LOCAL from the cache (one
+ * rank forms it on demand; several ranks: CONP_ERR_STATE unless a collective entry formed it since the last update).  The cache
+ * is dropped by every update, re-neighbouring and set_matrix.  On a `pppm` handle all three return CONP_ERR_STATE;
+ * conp_compute_potential_atom takes its k-space part from here on an Ewald handle (from the mesh on a `pppm` one). */
+int conp_ewald_compute(conp_fix *fix, const conp_atoms *atoms);
+int conp_ewald_compute_group_potential(conp_fix *fix, const conp_atoms *atoms, const int *sel /*[nlocal]*/, double *recv /*[nlocal]*/);
+int conp_ewald_compute_particle_potential(conp_fix *fix, const conp_atoms *atoms, int i, double *u);
+
 /* ---- `compute potential/atom` (compute_potential_atom.cpp:120-345), SURVEY 8f-4 --------------------------------------------
  * per-atom electrostatic potential in volts: pair part over the pair style's half list (:223-308, optional Gaussian `eta`
  * correction for atoms with etasel != 0 = eta_check :313-318), k-space part through the PPPM provider (:165-175 -> the

@@ -97,6 +97,7 @@ SYMBOLS = [
     "conp_fix_set_comm", "conp_rccl_unique_id", "conp_fix_comm_init_rccl", "conp_rccl_available", "conp_fix_comm_destroy_rccl",
     "conp_pppm_make_rho", "conp_pppm_compute_group_potential", "conp_pppm_compute_particle_potential",
     "conp_pppm_keep_density", "conp_pppm_compute",
+    "conp_ewald_compute", "conp_ewald_compute_group_potential", "conp_ewald_compute_particle_potential",
     "conp_compute_potential_atom",
 ]
 
@@ -208,6 +209,9 @@ def load_library():
     if hasattr(lib, "conp_pppm_compute"):
         lib.conp_pppm_compute.argtypes = [vp, C.POINTER(conp_atoms)]
         lib.conp_pppm_keep_density.argtypes = [vp, C.c_int]
+    lib.conp_ewald_compute.argtypes = [vp, C.POINTER(conp_atoms)]
+    lib.conp_ewald_compute_group_potential.argtypes = [vp, C.POINTER(conp_atoms), ip, dp]
+    lib.conp_ewald_compute_particle_potential.argtypes = [vp, C.POINTER(conp_atoms), C.c_int, dp]
     lib.conp_compute_potential_atom.argtypes = [vp, C.POINTER(conp_atoms), C.POINTER(conp_neighlist), ip, ip,
                                                 C.POINTER(conp_potential_args), dp]
     lib.conp_fix_set_comm.argtypes = [vp, C.POINTER(conp_comm)]
@@ -459,6 +463,24 @@ class FixConp:
     def pppm_particle_potential(self, at, i):
         u = C.c_double()
         self._check(self.lib.conp_pppm_compute_particle_potential(self.h, C.byref(self.atoms_view(at)), int(i), C.byref(u)))
+        return u.value
+
+    # -- Ewald per-atom potential (the exact k sum; the `pppm_*` trio's twins for the Ewald provider) ---------------------------
+    def ewald_compute(self, at):
+        """collective under decomposed ranks: the structure factor of every charged owned atom, formed and cached"""
+        self._check(self.lib.conp_ewald_compute(self.h, C.byref(self.atoms_view(at))))
+
+    def ewald_group_potential(self, at, sel):
+        """collective: g_i = - sum_k 2 ug_k [cos(k r_i) Re S_k + sin(k r_i) Im S_k] for owned atoms with sel[i] != 0 (others 0)"""
+        sel = np.ascontiguousarray(sel, np.int32)
+        out = np.zeros(at.nlocal)
+        self._check(self.lib.conp_ewald_compute_group_potential(self.h, C.byref(self.atoms_view(at)), _iptr(sel), _dptr(out)))
+        return out
+
+    def ewald_particle_potential(self, at, i):
+        """rank-local: u_i = g_i + 2 g_ewald q_i / sqrt(pi) from the cached structure factor"""
+        u = C.c_double()
+        self._check(self.lib.conp_ewald_compute_particle_potential(self.h, C.byref(self.atoms_view(at)), int(i), C.byref(u)))
         return u.value
 
     def compute_potential_atom(self, at, pairlist, sel, etasel=None, eta=0.0, pair=True, kspace=True, qsum=True):

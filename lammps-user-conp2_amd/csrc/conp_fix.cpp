@@ -298,6 +298,18 @@ struct conp_fix {
   int pp_elyte_spreads = 0;      // how often the electrolyte atoms were spread onto the mesh (b_cal and density queries)
   DevBuf<double> d_pp_elyte, d_pp_xg, d_pp_qg;
   DevBuf<int> d_pp_iota;
+  // Ewald per-atom potential (conp_ewald_*, conp_compute_potential_atom on an Ewald handle; conp_potential.hip): the structure factor
+  // of every charged owned atom (all ranks' under decomposition) in buffers of its own -- the update's schedule, tables and G are
+  // not touched.  ew_g_valid: d_ew_Gwf holds w o G of the atoms a collective entry last saw; ew_u_valid: ew_u_h holds u_i of every
+  // owned atom (the per-atom entry's cache).  Both are dropped by every update, re-neighbour, set_matrix and k-table setup.
+  bool ew_g_valid = false, ew_u_valid = false;
+  int ew_tables_nb = 0;             // block width and plan the phase-table buffers were zeroed for (padding entries stay zero)
+  long ew_tables_gen = -1;
+  std::vector<double> ew_u_h;
+  DevBuf<double> d_ew_G, d_ew_Gp, d_ew_Gwf, d_ew_x, d_ew_q, d_ew_seeds, d_ew_Rp, d_ew_Tz, d_ew_bk, d_ew_g, d_ew_u;
+  DevBuf<double2> d_ew_Xe, d_ew_Ye;
+  DevBuf<int> d_ew_idx, d_ew_ctptr;
+  DevBuf<SkTile> d_ew_tiles;
   double Btime = 0., Ctime = 0., Ktime = 0.;      // accumulated like :549-552 (seconds)
   hipEvent_t ev_b[3] = {nullptr, nullptr, nullptr};
   bool ev_pending = false;
@@ -551,6 +563,7 @@ struct conp_fix {
     d_ct_ptr.upload(ct_ptr_h, stream);
     sync();
     kspace_ready = true;
+    ew_g_valid = ew_u_valid = false;
     // the electrode tables, the z-class tables and sk_gemm's projection block (d_skproj: raw pointers into d_wfull / d_TzcT, the
     // plan's C_pad) belong to the plan that was just replaced: whoever needs them next rebuilds them (km_a_read)
     tables_current = false;
@@ -684,6 +697,7 @@ struct conp_fix {
     if (!have_blist) throw ConpError(CONP_ERR_STATE, "post_neighbor: no neighbor list (init_list not called)");
     resident_step = -1;
     pp_elyte_valid = pp_u_valid = false;
+    ew_g_valid = ew_u_valid = false;
     static const bool tren = getenv("CONP_TIME_REN") != nullptr;
     auto tm0 = std::chrono::steady_clock::now();
     auto mark = [&](const char *what) {
@@ -2033,6 +2047,7 @@ struct conp_fix {
   void b_cal_device(const double *dx, const double *dq, bool coulyes, bool timed = false) {
     const int ne = idx.elenum_all;
     pp_elyte_valid = pp_u_valid = false;          // positions / charges may have changed: the mesh caches are this update's or nobody's
+    ew_g_valid = ew_u_valid = false;              // (so are the Ewald per-atom potentials)
     const double *ex = decomposed ? d_xg.p : dx, *eq = decomposed ? d_qg.p : dq;
     const int *eidx = decomposed ? d_iota.p : d_elyte_idx.p;
     if (!kspace_ready || !tables_current || d_b == nullptr)
@@ -2926,6 +2941,7 @@ int conp_fix_set_matrix(conp_fix *f, const double *aaa, int runstage) {
   HIP_TRY(hipMemcpyAsync(f->d_A.p, aaa, ne * ne * sizeof(double), hipMemcpyHostToDevice, f->stream));
   f->sync();
   f->runstage = runstage;
+  f->ew_g_valid = f->ew_u_valid = false;
   CONP_GUARD_END
 }
 
@@ -3180,6 +3196,144 @@ void pppm_total_potential(conp_fix *f, const conp_atoms *at) {
   f->sync();                       // d_idx goes out of scope
   f->pp_u_valid = true;
 }
+
+// ---- Ewald per-atom potential (conp_potential.hip) ----
+void need_ewald(conp_fix *f) {
+  if (f->args.pppm)
+    throw ConpError(CONP_ERR_STATE, "conp_ewald_*: this handle's k-space provider is pppm/conp -- use conp_pppm_compute / "
+                                    "conp_pppm_compute_group_potential / conp_pppm_compute_particle_potential");
+  if (!f->kspace_ready) throw ConpError(CONP_ERR_STATE, "conp_ewald_*: no k-space tables yet (setup_post_neighbor or conp_km_conp_setup)");
+}
+// Atoms per block of phase tables: Rp, Tz, seeds and axis tables of a block stay within EW_TABLES (the 16384 / 262144 box takes
+// blocks of a few hundred atoms instead of a 2-GB table over all of them); the split slices of G within EW_SLICES.  With G and
+// w o G (R_pad C_pad doubles each: 5 MB at the headline size) that bounds the scratch of these entries.
+constexpr size_t EW_TABLES = (size_t)80 << 20, EW_SLICES = (size_t)40 << 20;
+int ew_block(const conp_fix *f, int n) {
+  const KPlan &pl = f->plan;
+  const size_t per_atom = ((size_t)pl.R_pad + pl.C_pad + 6 + 2 * ((size_t)pl.kxmax + 2) + 2 * ((size_t)pl.kymax + 1)) * sizeof(double);
+  const int cap = (int)std::max<size_t>(64, std::min<size_t>(8192, EW_TABLES / per_atom / 64 * 64));
+  return std::min(cap, std::max(64, (n + 63) / 64 * 64));
+}
+void ew_reserve(conp_fix *f, int nb_pad) {
+  const KPlan &pl = f->plan;
+  const size_t nrp = (size_t)pl.R_pad * nb_pad, ntz = (size_t)pl.C_pad * nb_pad;
+  const size_t nxe = (size_t)(pl.kxmax + 2) * nb_pad, nye = (size_t)(pl.kymax + 1) * nb_pad;
+  const bool grew = nrp > f->d_ew_Rp.n || ntz > f->d_ew_Tz.n || nxe > f->d_ew_Xe.n || nye > f->d_ew_Ye.n;
+  f->d_ew_Rp.reserve(nrp); f->d_ew_Tz.reserve(ntz); f->d_ew_Xe.reserve(nxe); f->d_ew_Ye.reserve(nye);
+  f->d_ew_seeds.reserve((size_t)6 * nb_pad);
+  // padding rows / columns (planar vectors past np, the kz = 0 sin column, columns past nz) are never written: zero them once per
+  // layout (block width, plan); afterwards every block overwrites the same entries
+  if (!grew && f->ew_tables_nb == nb_pad && f->ew_tables_gen == f->plan_gen) return;
+  HIP_TRY(hipMemsetAsync(f->d_ew_Rp.p, 0, nrp * sizeof(double), f->stream));
+  HIP_TRY(hipMemsetAsync(f->d_ew_Tz.p, 0, ntz * sizeof(double), f->stream));
+  HIP_TRY(hipMemsetAsync(f->d_ew_Xe.p, 0, nxe * sizeof(double2), f->stream));
+  HIP_TRY(hipMemsetAsync(f->d_ew_Ye.p, 0, nye * sizeof(double2), f->stream));
+  f->ew_tables_nb = nb_pad; f->ew_tables_gen = f->plan_gen;
+}
+// phase tables of atoms [b0, b0 + nb) of the compact list d_ew_x, nb_pad columns (stale columns >= nb of an earlier block stay finite)
+void ew_tables(conp_fix *f, int b0, int nb, int nb_pad) {
+  launch_ew_seeds(f->stream, nb, f->d_ew_x.p + 3 * (size_t)b0, f->kt.unitk[0], f->kt.unitk[1], f->kt.unitk[2], f->d_ew_seeds.p);
+  launch_ele_tables(f->stream, f->dplan, f->plan.kzt, nb, nb_pad, f->d_ew_seeds.p, f->d_ew_Xe.p, f->d_ew_Ye.p, f->d_ew_Tz.p, f->d_ew_Rp.p);
+}
+// w o G of every charged owned atom at the positions and charges of `at` (not the update's cached arrays) into d_ew_Gwf.
+// Decomposed ranks: each rank contracts its own atoms, G is summed through the host's all-reduce (km_ewald.cpp:784-785) --
+// COLLECTIVE.  Replicated-atom handles (several ranks without conp_fix_set_comm) hold every atom on every rank: no collective.
+void ewald_structure_factor(conp_fix *f, const conp_atoms *at) {
+  if (at->nlocal + at->nghost != f->nall) throw ConpError(CONP_ERR_STATE, "atom count changed without post_neighbor");
+  const KPlan &pl = f->plan;
+  std::vector<double> xs, qs;
+  for (int i = 0; i < at->nlocal; ++i) {
+    if (at->q[i] == 0) continue;
+    xs.insert(xs.end(), at->x + 3 * (size_t)i, at->x + 3 * (size_t)i + 3);
+    qs.push_back(at->q[i]);
+  }
+  const int n = (int)qs.size();
+  const int nb_pad = ew_block(f, n);
+  const size_t gsz = (size_t)pl.R_pad * pl.C_pad;
+  // split the atoms of a block over slices of G so that the launch keeps ~6 workgroups on every CU (the LDS limit of ew_sk_kernel;
+  // each waits on its chunk loads) -- every split owns a slice: no atomics
+  const int wgs = std::max(1, pl.C_pad / 64 * pl.n_row_tiles);
+  int nsplit = std::max(1, std::min({6 * f->num_cus / wgs + 1, 32, nb_pad / 64}));
+  while (nsplit > 1 && (size_t)nsplit * gsz * sizeof(double) > EW_SLICES) --nsplit;
+  const int ntot = std::max(nb_pad, (n + nb_pad - 1) / nb_pad * nb_pad);
+  xs.resize(3 * (size_t)ntot, 0.0); qs.resize(ntot, 0.0);     // padding atoms carry no charge
+  ew_reserve(f, nb_pad);
+  f->d_ew_x.upload(xs, f->stream); f->d_ew_q.upload(qs, f->stream);
+  f->d_ew_Gp.reserve(gsz * nsplit); f->d_ew_G.reserve(gsz); f->d_ew_Gwf.reserve(gsz);
+  HIP_TRY(hipMemsetAsync(f->d_ew_Gp.p, 0, gsz * nsplit * sizeof(double), f->stream));
+  for (int b0 = 0; b0 < n; b0 += nb_pad) {
+    ew_tables(f, b0, std::min(nb_pad, n - b0), nb_pad);
+    launch_ew_sk(f->stream, f->dplan, nb_pad, nsplit, f->d_ew_Rp.p, f->d_ew_Tz.p, f->d_ew_q.p + b0, f->d_ew_Gp.p);
+  }
+  launch_ew_sk_sum(f->stream, f->dplan, nsplit, f->d_ew_Gp.p, f->d_ew_G.p);
+  if (f->decomposed) {
+    std::vector<double> g(gsz);
+    HIP_TRY(hipMemcpyAsync(g.data(), f->d_ew_G.p, gsz * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+    f->sync();
+    f->rc.sum(g.data(), (int64_t)gsz);
+    HIP_TRY(hipMemcpyAsync(f->d_ew_G.p, g.data(), gsz * sizeof(double), hipMemcpyHostToDevice, f->stream));
+    f->sync();
+  }
+  launch_ew_gw(f->stream, f->dplan, f->d_ew_G.p, f->d_ew_Gwf.p);
+  HIP_TRY(hipGetLastError());
+  f->sync();                       // (the host vectors go out of scope)
+  f->ew_g_valid = true; f->ew_u_valid = false;
+}
+// g_i and u_i = g_i + 2 g_ewald q_i / sqrt(pi) of the owned atoms idx (local indices), at their positions in `at`, from d_ew_Gwf:
+// block by block, the block's phase tables, b_project_kernel, ew_out_kernel.  Rank-local.  g, u: [nlocal], only idx written.
+void ewald_project(conp_fix *f, const conp_atoms *at, const std::vector<int> &idx, double *g, double *u) {
+  const int n = (int)idx.size();
+  if (n == 0) return;
+  const int nb_pad = ew_block(f, n);
+  const int ntot = (n + nb_pad - 1) / nb_pad * nb_pad;
+  std::vector<double> xs(3 * (size_t)ntot, 0.0), qs(ntot, 0.0);
+  for (int k = 0; k < n; ++k) {
+    const int i = idx[k];
+    for (int c = 0; c < 3; ++c) xs[3 * (size_t)k + c] = at->x[3 * (size_t)i + c];
+    qs[k] = at->q[i];
+  }
+  ew_reserve(f, nb_pad);
+  f->d_ew_x.upload(xs, f->stream); f->d_ew_q.upload(qs, f->stream); f->d_ew_idx.upload(idx, f->stream);
+  f->d_ew_tiles.upload(f->tiles_h, f->stream); f->d_ew_ctptr.upload(f->ct_ptr_h, f->stream);
+  f->d_ew_bk.reserve((size_t)4 * nb_pad);
+  f->d_ew_g.reserve(at->nlocal); f->d_ew_u.reserve(at->nlocal);
+  const double selfc = 2.0 * f->env.g_ewald / 1.77245385090551602729;
+  for (int b0 = 0; b0 < n; b0 += nb_pad) {
+    const int nb = std::min(nb_pad, n - b0);
+    ew_tables(f, b0, nb, nb_pad);
+    launch_b_project(f->stream, f->dplan, nb_pad, f->d_ew_ctptr.p, f->d_ew_tiles.p, f->d_ew_Gwf.p, f->d_ew_Rp.p, f->d_ew_Tz.p, f->d_ew_bk.p);
+    launch_ew_out(f->stream, nb, nb_pad, f->d_ew_bk.p, f->d_ew_idx.p + b0, f->d_ew_q.p + b0, selfc, f->d_ew_g.p, f->d_ew_u.p);
+  }
+  std::vector<double> hg(at->nlocal), hu(at->nlocal);
+  HIP_TRY(hipMemcpyAsync(hg.data(), f->d_ew_g.p, (size_t)at->nlocal * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipMemcpyAsync(hu.data(), f->d_ew_u.p, (size_t)at->nlocal * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipGetLastError());
+  f->sync();
+  for (int i : idx) { if (g) g[i] = hg[i]; if (u) u[i] = hu[i]; }
+}
+// the k-space tail of compute potential/atom (compute_potential_atom.cpp:165-175, slab correction :323-345) on the selected owned
+// atoms idx (ascending), whichever provider formed u_i: pot_i -= u_i, + the Gaussian self term of eta atoms, + the slab terms
+// (the sums of q z and q over the owned atoms all-reduced, MPI_Allreduce :331, :337)
+void potential_atom_tail(conp_fix *f, const conp_atoms *at, const conp_potential_args *pa, const int *etasel, const std::vector<int> &idx,
+                         const std::vector<double> &uk, std::vector<double> &pot) {
+  const double MY_PIS = 1.77245385090551602729;
+  for (int i : idx) {
+    pot[i] -= uk[i];
+    if (pa->eta != 0.0 && etasel[i]) pot[i] += pa->eta * at->q[i] * std::sqrt(2.0) / MY_PIS;
+  }
+  if (f->env.slabflag) {
+    const double volume = f->env.xprd * f->env.yprd * f->env.zprd * f->env.slab_volfactor;
+    const double pi2vol = 2 * 3.14159265358979323846 / volume;
+    double slabcorr = 0.0, qsum = 0.0;
+    for (int i = 0; i < at->nlocal; ++i) { slabcorr += 2 * pi2vol * at->q[i] * at->x[3 * (size_t)i + 2]; qsum += at->q[i]; }
+    { double two[2] = {slabcorr, qsum}; f->rc.sum(two, 2); slabcorr = two[0]; qsum = two[1]; }
+    for (int i : idx) {
+      const double z = at->x[3 * (size_t)i + 2];
+      pot[i] += z * slabcorr;
+      if (pa->qsumflag) pot[i] -= pi2vol * qsum * z * z;
+    }
+  }
+}
 }  // namespace
 
 // PPPMCONP keeps the electrolyte brick of every b_cal for its make_rho override (pppm_conp.cpp:172-228, 434-450; elyte_mapped is
@@ -3300,13 +3454,64 @@ int conp_pppm_compute_particle_potential(conp_fix *f, const conp_atoms *at, int 
   CONP_GUARD_END
 }
 
+// The Ewald twins of the three entries above (the reference's KSpaceModuleEwald has none: kspacemodule.h:38-39 return 0).
+// COLLECTIVE under decomposed ranks: the structure factor of all ranks' charged atoms, formed and cached.
+int conp_ewald_compute(conp_fix *f, const conp_atoms *at) {
+  CONP_GUARD_BEGIN
+  if (!f || !at) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->drop_graph();
+  need_ewald(f);
+  ewald_structure_factor(f, at);
+  CONP_GUARD_END
+}
+
+int conp_ewald_compute_group_potential(conp_fix *f, const conp_atoms *at, const int *sel, double *recv) {
+  CONP_GUARD_BEGIN
+  if (!f || !at || !sel || !recv) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->drop_graph();
+  need_ewald(f);
+  // (collective: every rank, whatever it selected) -- unless a collective entry formed it since the last update, re-neighbouring or
+  // set_matrix: those drop the cache on every rank alike, so every rank takes the same branch
+  if (!f->ew_g_valid) ewald_structure_factor(f, at);
+  std::vector<int> idx;
+  for (int i = 0; i < at->nlocal; ++i) if (sel[i]) idx.push_back(i);
+  ewald_project(f, at, idx, recv, nullptr);
+  CONP_GUARD_END
+}
+
+// RANK-LOCAL (compute_potential_atom.cpp:168-174 calls it once per owned atom of the group): the first call after a collective entry
+// projects every owned atom once and keeps u_i; later calls read the cache until the next update.  One rank forms the structure
+// factor on demand; several ranks refuse without a collective entry since the last update.
+int conp_ewald_compute_particle_potential(conp_fix *f, const conp_atoms *at, int i, double *u) {
+  CONP_GUARD_BEGIN
+  if (!f || !at || !u) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->drop_graph();
+  need_ewald(f);
+  if (i < 0 || i >= at->nlocal) throw ConpError(CONP_ERR_ARG, "atom index out of range");
+  if (!f->ew_u_valid || (int)f->ew_u_h.size() != at->nlocal) {
+    if (!f->ew_g_valid) {
+      if (f->decomposed || f->env.nranks > 1)
+        throw ConpError(CONP_ERR_STATE, "conp_ewald_compute_particle_potential is rank-local -- under several MPI ranks the structure "
+                                        "factor has to be formed by a collective call first (conp_ewald_compute / compute_group_potential)");
+      ewald_structure_factor(f, at);
+    }
+    std::vector<int> all(at->nlocal);
+    for (int k = 0; k < at->nlocal; ++k) all[k] = k;
+    f->ew_u_h.assign(at->nlocal, 0.0);
+    ewald_project(f, at, all, nullptr, f->ew_u_h.data());
+    f->ew_u_valid = true;
+  }
+  *u = f->ew_u_h[i];
+  CONP_GUARD_END
+}
+
 int conp_compute_potential_atom(conp_fix *f, const conp_atoms *at, const conp_neighlist *pl, const int *sel, const int *etasel,
                                 const conp_potential_args *pa, double *potential) {
   CONP_GUARD_BEGIN
   f->drop_graph();
   if (!at || !sel || !pa || !potential) throw ConpError(CONP_ERR_ARG, "null argument");
   if (pa->eta != 0.0 && !etasel) throw ConpError(CONP_ERR_ARG, "eta needs the eta_check selection");
-  if (pa->kspaceflag) need_pppm(f);
+  if (pa->kspaceflag) { if (f->args.pppm) need_pppm(f); else need_ewald(f); }    // mesh provider, or the exact Ewald sum
   const int nall = at->nlocal + at->nghost;
   const int ntotal = at->nlocal + (f->env.newton_pair ? at->nghost : 0);
   pppm_upload(f, at);
@@ -3327,7 +3532,16 @@ int conp_compute_potential_atom(conp_fix *f, const conp_atoms *at, const conp_ne
                           f->env.g_ewald, pa->eta, d_pot.p);
   }
   std::vector<double> pot(nall, 0.0), uk(at->nlocal, 0.0);
-  if (pa->kspaceflag) {
+  if (pa->kspaceflag && !f->args.pppm) {
+    // Ewald handle: u_i from the exact k sum of every charged atom (COLLECTIVE under decomposed ranks), the rest as below
+    std::vector<int> idx;
+    for (int i = 0; i < at->nlocal; ++i) if (sel[i]) idx.push_back(i);
+    ewald_structure_factor(f, at);
+    ewald_project(f, at, idx, nullptr, uk.data());
+    HIP_TRY(hipMemcpyAsync(pot.data(), d_pot.p, (size_t)nall * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+    f->sync();
+    potential_atom_tail(f, at, pa, etasel, idx, uk, pot);
+  } else if (pa->kspaceflag) {
     std::vector<int> all;
     for (int i = 0; i < at->nlocal; ++i) if (at->q[i] != 0) all.push_back(i);
     const int n = (int)all.size();
@@ -3354,24 +3568,7 @@ int conp_compute_potential_atom(conp_fix *f, const conp_atoms *at, const conp_ne
     }
     HIP_TRY(hipMemcpyAsync(pot.data(), d_pot.p, (size_t)nall * sizeof(double), hipMemcpyDeviceToHost, f->stream));
     f->sync();
-    const double MY_PIS = 1.77245385090551602729;
-    for (int i : idx) {                                                           // :165-175
-      pot[i] -= uk[i];
-      if (pa->eta != 0.0 && etasel[i]) pot[i] += pa->eta * at->q[i] * std::sqrt(2.0) / MY_PIS;
-    }
-    if (f->env.slabflag) {                                                        // slabcorr :323-345
-      const double volume = f->env.xprd * f->env.yprd * f->env.zprd * f->env.slab_volfactor;
-      const double pi2vol = 2 * 3.14159265358979323846 / volume;
-      double slabcorr = 0.0, qsum = 0.0;
-      for (int i = 0; i < at->nlocal; ++i) { slabcorr += 2 * pi2vol * at->q[i] * at->x[3 * (size_t)i + 2]; qsum += at->q[i]; }
-      { double two[2] = {slabcorr, qsum}; f->rc.sum(two, 2); slabcorr = two[0]; qsum = two[1]; }      // MPI_Allreduce :331, :337
-      for (int i = 0; i < at->nlocal; ++i)
-        if (sel[i]) {
-          const double z = at->x[3 * (size_t)i + 2];
-          pot[i] += z * slabcorr;
-          if (pa->qsumflag) pot[i] -= pi2vol * qsum * z * z;
-        }
-    }
+    potential_atom_tail(f, at, pa, etasel, idx, uk, pot);
   } else {
     HIP_TRY(hipMemcpyAsync(pot.data(), d_pot.p, (size_t)nall * sizeof(double), hipMemcpyDeviceToHost, f->stream));
     f->sync();

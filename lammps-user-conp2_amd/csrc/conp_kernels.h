@@ -117,6 +117,15 @@ void launch_potential_pair(hipStream_t s, int inum, const int *ilist, const int 
                            const int *etasel, int ntypes, const double *cutsq, double cut_coulsq, double g_ewald, double eta,
                            double *potential);
 
+// ---- exact Ewald per-atom potential (conp_potential.hip): structure factor of any atom list, projection onto any atom list -------
+void launch_ew_seeds(hipStream_t s, int n, const double *x /*[n][3]*/, double ux, double uy, double uz, double *seeds /*[6][n]*/);
+void launch_ew_sk(hipStream_t s, const DevPlan &pl, int nb_pad, int nsplit, const double *Rp /*[R_pad][nb_pad]*/,
+                  const double *Tz /*[C_pad][nb_pad]*/, const double *q /*[nb_pad], 0 in padding*/, double *Gp /*[nsplit][R_pad][C_pad] +=*/);
+void launch_ew_sk_sum(hipStream_t s, const DevPlan &pl, int nsplit, const double *Gp, double *G /*[R_pad][C_pad]*/);
+void launch_ew_gw(hipStream_t s, const DevPlan &pl, const double *G, double *Gwf /*w o G, b_project_kernel's order*/);
+void launch_ew_out(hipStream_t s, int n, int nb_pad, const double *bk /*[4][nb_pad]*/, const int *idx, const double *q, double selfc,
+                   double *g_out /*indexed by atom*/, double *u_out);
+
 // ---- the z-window form of the structure-factor contraction (conp_zn.hip, round 5) ------------------------------------------------
 // item = (row tile: 64 planar vectors, chunk range [c0, c1) of the z-ordered electrolyte list, window origin g0 on the grid, slot of
 // its piece [class][128 rows] in the pieces buffer)

@@ -2,12 +2,16 @@
 
 #include <cstring>
 
+#include "fix_conp_hip.h"
+#include "kspacemodule_hip.h"
 #include "pppm_conp_hip.h"
 #ifndef CONP_GLUE_MOCK
 #include "atom.h"
 #include "error.h"
 #include "force.h"
+#include "fix_conp.h"
 #include "kspace.h"
+#include "modify.h"
 #include "neigh_list.h"
 #include "pair.h"
 #include "update.h"
@@ -17,7 +21,7 @@ using namespace LAMMPS_NS;
 
 /* argument grammar of compute_potential_atom.cpp:49-93 */
 ComputePotentialAtomHip::ComputePotentialAtomHip(LAMMPS *lmp, int narg, char **arg)
-    : Compute(lmp, narg, arg), provider(nullptr), nmax(0), molidL(-1), molidR(-1), eta(0.), potential(nullptr) {
+    : Compute(lmp, narg, arg), provider(nullptr), handle_(nullptr), fixconp(nullptr), fixhip(nullptr), nmax(0), molidL(-1), molidR(-1), eta(0.), potential(nullptr) {
   if (narg < 3) error->all(FLERR, "Illegal compute pe/atom command");
   peratom_flag = 1; size_peratom_cols = 0; peatomflag = 1; timeflag = 1; comm_reverse = 1;
   etaflag = false; qsumflag = true;
@@ -46,8 +50,20 @@ ComputePotentialAtomHip::~ComputePotentialAtomHip() { delete[] potential; }
 
 void ComputePotentialAtomHip::setup() {                       /* :97-112 */
   provider = dynamic_cast<PPPMConpHip *>(force->kspace);
-  if (provider == nullptr)
-    error->all(FLERR, "Compute requires a compatible KSpace provider like pppm/conp");   /* here: pppm/conp/hip, which owns the device mesh */
+  handle_ = nullptr; fixconp = nullptr; fixhip = nullptr;
+  if (provider != nullptr) { handle_ = provider->handle(); fixconp = provider->fixconp; return; }
+  /* Ewald (the reference's KSpaceModuleEwald has no potentials, kspacemodule.h:38-39): the library's exact k sums on the handle of
+   * a conp/hip (conq/hip, cond/hip) fix, or of the KSpaceModuleHip provider of the reference's fix conp */
+  for (int f = 0; f < modify->nfix && handle_ == nullptr; ++f) {
+    if (auto *fh = dynamic_cast<FixConpHip *>(modify->fix[f])) {
+      if (fh->handle() != nullptr) { fixhip = fh; handle_ = fh->handle(); }
+    } else if (auto *fc = dynamic_cast<FixConp *>(modify->fix[f])) {
+      auto *km = dynamic_cast<KSpaceModuleHip *>(fc->kspmod);
+      if (km != nullptr && km->handle() != nullptr) { fixconp = fc; handle_ = km->handle(); }
+    }
+  }
+  if (handle_ == nullptr)
+    error->all(FLERR, "Compute requires a compatible KSpace provider like pppm/conp");   /* pppm/conp/hip, or a handle in Ewald mode */
 }
 
 void ComputePotentialAtomHip::compute_peratom() {             /* :120-218 */
@@ -65,7 +81,8 @@ void ComputePotentialAtomHip::compute_peratom() {             /* :120-218 */
   for (int i = 0; i < nall; ++i) {
     sel[i] = (atom->mask[i] & groupbit) ? 1 : 0;
     etasel[i] = (atom->molecule && (atom->molecule[i] == molidL || atom->molecule[i] == molidR)) ? 1 : 0;   /* eta_check :313-318 */
-    if (provider->fixconp) echeck[i] = provider->fixconp->electrode_check(i);
+    if (fixconp) echeck[i] = fixconp->electrode_check(i);
+    else if (fixhip) echeck[i] = fixhip->electrode_check(i);
     for (int c = 0; c < 3; ++c) xflat[3 * (size_t)i + c] = atom->x[i][c];
   }
   conp_atoms at;
@@ -91,7 +108,7 @@ void ComputePotentialAtomHip::compute_peratom() {             /* :120-218 */
   pa.kspaceflag = (kspaceflag && force->kspace && force->kspace->compute_flag) ? 1 : 0;
   pa.qsumflag = qsumflag ? 1 : 0;
   pa.eta = eta;
-  if (conp_compute_potential_atom(provider->handle(), &at, pairflag ? &pl : nullptr, sel.data(), etaflag ? etasel.data() : nullptr, &pa,
+  if (conp_compute_potential_atom(handle_, &at, pairflag ? &pl : nullptr, sel.data(), etaflag ? etasel.data() : nullptr, &pa,
                                   out.data()) != CONP_OK)
     error->all(FLERR, conp_last_error());
   for (int i = 0; i < ntotal; ++i) potential[i] = out[i];

@@ -1,8 +1,9 @@
 /* ComputePotentialAtomHip -- `compute ID group potential/atom/hip [pair] [kspace] [noqsum] [eta ETA molL molR]`: the reference's
  * `compute potential/atom` (compute_potential_atom.h:16, compute_potential_atom.cpp:49-345) with its pair loop, mesh gather and
  * slab correction done by libconp_hip.so in one call (conp_compute_potential_atom).  Same arguments, same errors, same output
- * (per-atom vector in volts).  Needs `kspace_style pppm/conp/hip` when the k-space part is asked for, as the reference needs
- * a "compatible KSpace provider like pppm/conp" (:110). */
+ * (per-atom vector in volts).  The k-space part comes from `kspace_style pppm/conp/hip` (the mesh, as the reference needs a
+ * "compatible KSpace provider like pppm/conp", :110) or, without it, from the exact Ewald sums of the handle of a `conp/hip`
+ * (`conq/hip`, `cond/hip`) fix or of the reference's fix conp with the KSpaceModuleHip provider. */
 #ifdef COMPUTE_CLASS
 
 ComputeStyle(potential/atom/hip,ComputePotentialAtomHip)
@@ -34,6 +35,9 @@ class ComputePotentialAtomHip : public Compute {
 
  private:
   class PPPMConpHip *provider;
+  conp_fix *handle_;                 /* the handle the per-atom call runs on: the pppm style's, or an Ewald one */
+  class FixConp *fixconp;            /* electrode_check: the reference's fix (pppm/conp/hip, KSpaceModuleHip) ... */
+  class FixConpHip *fixhip;          /* ... or the conp/hip fix */
   bool pairflag, kspaceflag, etaflag, qsumflag;
   int nmax, molidL, molidR;
   double eta;

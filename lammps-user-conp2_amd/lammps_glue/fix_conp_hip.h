@@ -42,6 +42,9 @@ class FixConpHip : public Fix {
   void end_of_step() override;
   double compute_scalar() override;
   int modify_param(int, char **) override;
+  /* for ComputePotentialAtomHip under Ewald: the library handle (created in init()) and electrode_check (fix_conp.cpp:599-605) */
+  conp_fix *handle() { return h; }
+  int electrode_check(int i) { return (atom->mask[i] & groupbit) ? 1 : ((atom->mask[i] & jgroupbit) ? -1 : 0); }
 
  private:
   conp_fix_args args;

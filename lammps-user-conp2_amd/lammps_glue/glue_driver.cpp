@@ -5,6 +5,7 @@
 // same library.
 //
 // usage: glue_driver CASEFILE                      one rank, FixConpHip (INTEGRATION.md mode A)
+//        glue_driver CASEFILE compute              mode A, then `compute potential/atom/hip kspace` on the conp/hip fix (Ewald)
 //        glue_driver CASEFILE provider             mode B: the reference's FixConp keeps its loops, only `kspmod` is replaced:
 //                                                  a stand-in for the fix's public members is registered with KSpaceModuleHip
 //                                                  (register_fix, fix_conp.cpp:409) and conp_setup / conp_post_neighbor / a_cal /
@@ -41,6 +42,7 @@
 #include <vector>
 
 #define CONP_GLUE_MOCK 1
+#include "compute_potential_atom_hip.h"
 #include "fix_conp_hip.h"
 #include "kspacemodule_hip.h"
 #include "pppm_conp_hip.h"
@@ -62,6 +64,8 @@ struct Out {
 };
 
 // one rank: its own mock LAMMPS instance, atoms and lists from its case file
+static bool g_compute = false;   // `glue_driver CASEFILE compute`: after the steps, compute potential/atom/hip on the conp/hip fix
+
 int run_case(const char *path, bool provider, int me, int nprocs, MockCommRank *world, Out &out) {
   std::ifstream in(path);
   if (!in) { out.f("ERROR: cannot open %s\n", path); return 1; }
@@ -170,7 +174,7 @@ int run_case(const char *path, bool provider, int me, int nprocs, MockCommRank *
     for (auto &t : toks) cargv.push_back(t.c_str());
     must(conp_parse_fix_args(narg, cargv.data(), ntypes, &fa));
     const int gb = bitmask[group.find(toks[1])], jgb = bitmask[group.find(toks[4])];
-    FixConp fixstub;
+    FixConp fixstub(&lmp);
     fixstub.eta = fa.eta;
     fixstub.check = [&](int i) { return (mask[i] & gb) ? 1 : ((mask[i] & jgb) ? -1 : 0); };
     // the fix's own maps: FixConp::post_neighbor's algorithm (conp_host_index restates it bit-exactly; one rank here -- in the
@@ -269,7 +273,30 @@ int run_case(const char *path, bool provider, int me, int nprocs, MockCommRank *
       out.f("up %d %.17g\n", tag[i0], kspmod->compute_particle_potential(i0));
       force.kspace = &kspace;
       delete pppm_style;                           // LAMMPS deletes its kspace style, not the fix (fix_conp.cpp:207)
-    } else delete kspmod;                          // fix_conp.cpp:207: the fix deletes its Ewald provider; the handle goes with it
+    } else {
+      // the Ewald provider's potentials (exact k sums, conp_ewald_*), group 1 = eleleft, at the charges the atoms carry
+      std::vector<double> recv(nlocal, 0.0);
+      kspmod->compute_group_potential(gb, recv.data());
+      for (int i = 0; i < nlocal; ++i) if (mask[i] & gb) out.f("u %d %.17g\n", tag[i], recv[i]);
+      for (int i = 0; i < nlocal; ++i) out.f("up %d %.17g\n", tag[i], kspmod->compute_particle_potential(i));
+      // `compute pot all potential/atom/hip kspace`: no pppm style, so setup() finds the provider's handle through the fix list
+      // (Modify::fix -> FixConp::kspmod -> KSpaceModuleHip) and the compute runs on the exact Ewald sums
+      Fix *fixes[1] = {&fixstub};
+      modify.fix = fixes; modify.nfix = 1;
+      std::vector<std::string> ctoks = {"pot", "all", "potential/atom/hip", "kspace"};
+      std::vector<char *> cargv;
+      for (auto &t : ctoks) cargv.push_back(const_cast<char *>(t.c_str()));
+      atom.nmax = std::max(atom.nmax, nall);
+      update.eflag_atom = update.ntimestep;                     // (per-atom energy tallied on this step, :121-123)
+      {
+        ComputePotentialAtomHip cpa(&lmp, (int)cargv.size(), cargv.data());
+        cpa.setup();
+        cpa.compute_peratom();
+        for (int i = 0; i < nlocal; ++i) out.f("cp %d %.17g\n", tag[i], cpa.vector_atom[i]);
+      }
+      modify.nfix = 0; modify.fix = nullptr;
+      delete kspmod;                               // fix_conp.cpp:207: the fix deletes its Ewald provider; the handle goes with it
+    }
     return 0;
   }
 
@@ -319,6 +346,23 @@ int run_case(const char *path, bool provider, int me, int nprocs, MockCommRank *
     for (int i = 0; i < nlocal; ++i) for (int c = 0; c < 3; ++c) { fsum[c] += fs[3 * (size_t)i + c]; fabs_ += std::abs(fs[3 * (size_t)i + c]); }
     out.f("f %ld %.17g %.17g %.17g %.17g eng_coul %.17g kspace_energy %.17g\n", ts, fsum[0], fsum[1], fsum[2], fabs_,
           pair.eng_coul, kspace.energy);
+  }
+  if (g_compute) {
+    // `compute pot all potential/atom/hip kspace` without a pppm style: setup() takes the conp/hip fix's handle (Modify::fix)
+    Fix *fixes[1] = {&fix};
+    modify.fix = fixes; modify.nfix = 1;
+    std::vector<std::string> ctoks = {"pot", "all", "potential/atom/hip", "kspace"};
+    std::vector<char *> cargv;
+    for (auto &t : ctoks) cargv.push_back(const_cast<char *>(t.c_str()));
+    atom.nmax = std::max(atom.nmax, nall);
+    update.eflag_atom = update.ntimestep;
+    {
+      ComputePotentialAtomHip cpa(&lmp, (int)cargv.size(), cargv.data());
+      cpa.setup();
+      cpa.compute_peratom();
+      for (int i = 0; i < nlocal; ++i) out.f("cp %d %.17g\n", tag[i], cpa.vector_atom[i]);
+    }
+    modify.nfix = 0; modify.fix = nullptr;
   }
   // GLUE_DRIVER_TIME=N: wall time of N more pre_force calls -- the PCIe-inclusive rate a LAMMPS run would see through the glue
   if (const char *tn = std::getenv("GLUE_DRIVER_TIME")) {
@@ -380,6 +424,7 @@ int main(int argc, char **argv) {
   int rc = 0;
   try {
     MockCommRank *single = nullptr;
+    g_compute = argc > 2 && std::string(argv[2]) == "compute";
     rc = run_case(argv[1], argc > 2 && std::string(argv[2]) == "provider", 0, 1, single, out);
   } catch (const std::exception &e) {
     out.f("ERROR: %s\n", e.what());

@@ -129,3 +129,20 @@ void KSpaceModuleHip::b_cal(double *bbb) {
   fail_if(conp_km_b_cal(h, &at, ball.data()));
   for (int i = 0; i < fixconp->elenum; ++i) bbb[i] = ball[lib_tag2eleall[fixconp->ele2tag[i]]];   /* overwrite (km_ewald.cpp:821) */
 }
+
+/* the exact Ewald potentials of the owned atoms (conp_ewald_*): g_i for the group, u_i = g_i + 2 g_ewald q_i / sqrt(pi) per atom.
+ * compute_particle_potential is rank-local like PPPMConpHip's: under several ranks a call without a collective entry since the last
+ * update is error->one, not a hidden collective. */
+double KSpaceModuleHip::compute_particle_potential(int i) {
+  conp_atoms at = view();
+  double u = 0.0;
+  if (conp_ewald_compute_particle_potential(h, &at, i, &u) != CONP_OK) error->one(FLERR, conp_last_error());
+  return u;
+}
+
+void KSpaceModuleHip::compute_group_potential(int groupbit, double *recv) {
+  conp_atoms at = view();
+  std::vector<int> sel(atom->nlocal);
+  for (int i = 0; i < atom->nlocal; ++i) sel[i] = (atom->mask[i] & groupbit) ? 1 : 0;
+  fail_if(conp_ewald_compute_group_potential(h, &at, sel.data(), recv));
+}

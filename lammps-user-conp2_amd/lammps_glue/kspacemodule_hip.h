@@ -31,8 +31,12 @@ class KSpaceModuleHip : public KSpaceModule, protected Pointers {
   void a_cal(double *aaa) override;                      /* km_ewald.cpp:147-151 : aaa[elenum][elenum_all] +=, k-space part */
   void a_read() override {}                              /* km_ewald.cpp:134-145: the phase tables are built inside a_cal / b_cal */
   void b_cal(double *bbb) override;                      /* km_ewald.cpp:153-167 : bbb[elenum] =, local electrode order */
-  /* update_charge, conp_pre_force, compute_particle_potential, compute_group_potential and return_qsum keep the base-class
-   * defaults, as in KSpaceModuleEwald (the Ewald provider has no mesh potential; `pppm/conp/hip` has: pppm_conp_hip.h). */
+  /* The reference's KSpaceModuleEwald returns 0 for both potentials (kspacemodule.h:38-39); here they are the exact Ewald sums
+   * (conp_ewald_*, include/conp_hip.h), so that compute potential/atom works without a mesh.  update_charge, conp_pre_force and
+   * return_qsum keep the base-class defaults. */
+  double compute_particle_potential(int i) override;                  /* rank-local, from the cached structure factor */
+  void compute_group_potential(int groupbit, double *recv) override;  /* collective */
+  conp_fix *handle() { return h; }
 
  private:
   conp_fix *h;

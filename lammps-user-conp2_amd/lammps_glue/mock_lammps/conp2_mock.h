@@ -11,8 +11,10 @@ namespace LAMMPS_NS {
 
 class KSpaceModule;
 
-class FixConp {                       // stands for `class FixConp : public Fix` -- only what the provider reads
+class FixConp : public Fix {          // `class FixConp : public Fix` (fix_conp.h:34) -- only what the provider and the compute read
  public:
+  explicit FixConp(LAMMPS *l) : Fix(l, 0, nullptr) {}
+  int setmask() override { return 0; }
   int elenum = 0, elenum_all = 0, elytenum = 0;
   int *ele2tag = nullptr, *ele2eleall = nullptr, *tag2eleall = nullptr, *eleall2tag = nullptr;
   KSpaceModule *kspmod = nullptr;

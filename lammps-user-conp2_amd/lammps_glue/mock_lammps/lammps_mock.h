@@ -38,7 +38,8 @@ class Input { public: Variable *variable; };
 class NeighRequest { public: int pair, fix, half, full, occasional, skip, intel; int *iskip, **ijskip; };
 class NeighList { public: int index, inum, occasional; int *ilist, *numneigh, **firstneigh; };
 class Neighbor { public: NeighRequest **requests; int nrequest = 0; int request(void *, int instance = 0); void build(int); void build_one(NeighList *, int preflag = 0); };
-class Modify { public: int find_fix(const std::string &); };
+class Fix;
+class Modify { public: int find_fix(const std::string &); int nfix = 0; Fix **fix = nullptr; };   // (Modify::fix / nfix, modify.h)
 
 class LAMMPS { public: MPI_Comm world = nullptr; Memory *memory; Error *error; Atom *atom; Force *force; Domain *domain; Update *update; Comm *comm; Group *group; Input *input; Neighbor *neighbor; Modify *modify; FILE *screen, *logfile; };
 
