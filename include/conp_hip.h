@@ -328,7 +328,9 @@ int64_t conp_host_pair_rows(int which, const conp_neighlist *list, const conp_at
  * must stay within 2.5 A (in z) of its position at the last conp_fix_post_neighbor -- LAMMPS re-neighbours long before that.  The
  * device-resident entries do not synchronise, so an atom that left its window is seen one call later: that call returns
  * CONP_ERR_NUMERIC (the charges of the updates since the list build are invalid; call conp_fix_post_neighbor and repeat), and the
- * handle uses the full kernels until the next list build.  conp_fix_pre_force (host arrays) repeats the update by itself. */
+ * handle uses the full kernels until the next list build.  This holds for replayed graphs (CONP_GRAPH=1) too.  When the next call
+ * is conp_fix_post_neighbor, it completes the list build at the new positions and then returns CONP_ERR_NUMERIC (the handle is
+ * ready; repeat the update).  conp_fix_pre_force (host arrays) repeats the update by itself. */
 int conp_fix_set_stream(conp_fix *fix, void *hip_stream);
 int conp_fix_bind_device_buffers(conp_fix *fix, double *d_b /*[Ne]*/, double *d_q /*[Ne]*/);
 /* this rank's electrode rows: blocks of ceil(Ne / nranks) rows, so that rank r's rows start at r * ceil(Ne / nranks) */
@@ -380,7 +382,8 @@ enum {
   CONP_PATH_ROWS_HOST = 1 << 7,          /* re-neighbour: electrode rows regrouped on the host */
   CONP_PATH_TIME_SPLIT = 1 << 8,         /* host-buffer hooks: k-space and real-space halves of b_cal in launches of their own (timing log) */
   /* 1 << 9, 1 << 10, 1 << 11: retired (test paths of forms measured slower and removed); ignored when set */
-  CONP_PATH_SK_CLASSIC = 1 << 12         /* large planar systems: sk_gemm over all kz columns instead of the z-window contraction (conp_zn.hip) */
+  CONP_PATH_SK_CLASSIC = 1 << 12,        /* large planar systems: sk_gemm over all kz columns instead of the z-window contraction (conp_zn.hip) */
+  CONP_PATH_ZN_WIDE = 1 << 13            /* z-window: 48 window columns also where 32 would do (the second template form on medium boxes) */
 };
 void conp_debug_set_paths(unsigned mask);
 void conp_debug_set_sk_workgroups(int n);

@@ -106,6 +106,7 @@ SYMBOLS = [
 PATH_PARTIAL_TILES, PATH_A_GENERAL, PATH_INV_PIVOTED, PATH_CG_TWO_LAUNCH, PATH_GEMV_ROWS = 1, 2, 4, 8, 16
 PATH_PHASE_LAUNCH, PATH_PPPM_SPREAD_LAUNCH, PATH_ROWS_HOST, PATH_TIME_SPLIT = 32, 64, 128, 256
 PATH_SK_CLASSIC = 4096      # (512, 1024, 2048: retired test paths, ignored by the library)
+PATH_ZN_WIDE = 8192         # z-window: 48 window columns also where 32 would do
 
 
 class test_paths:

@@ -900,7 +900,7 @@ struct conp_fix {
     }
     if (getenv("CONP_TIME_REN")) std::fprintf(stderr, "  z-window: n %d, %zu ranges x %d row tiles, need %d columns, margin %d\n", n, ranges.size(), nrt, need_max, margin);
     if (need_max > 48 || ranges.empty()) { zn_listed = false; return; }     // too sparse for a window: the classic kernels
-    zn_ncf = need_max <= 32 ? 2 : 3;
+    zn_ncf = need_max <= 32 && !path_on(CONP_PATH_ZN_WIDE) ? 2 : 3;
     // Launch order: workgroups go to the eight XCDs round-robin (block b -> XCD b mod 8, each with an L2 of its own), and the row
     // tiles of one range read the same phase tables and window matrix -- so all row tiles of range r run on XCD r mod 8: an XCD pulls
     // an eighth of the tables through the fabric once and finds them in its L2 for the other row tiles.  The pieces' slots keep
@@ -978,6 +978,21 @@ struct conp_fix {
     mesgf("conp/hip: an electrolyte atom left the z-window of its place in the list (more than %.1f A of z drift since the last "
           "re-neighbouring); the update is repeated with the full structure-factor kernels\n", ZN_DRIFT);
     return true;
+  }
+  // device-resident updates: the flag of the update(s) since the last call is this call's error (conp_hip.h)
+  void zn_raise_if_overflowed() {
+    if (zn_overflowed())
+      throw ConpError(CONP_ERR_NUMERIC, "a device-resident update's z-window overflowed (an electrolyte atom drifted more than 2.5 A in z since "
+                                          "the last conp_fix_post_neighbor): the charges of the updates since then are invalid; the full kernels are used from now on");
+  }
+  // a re-neighbouring: every update before it has completed (the stream is drained), and a flag one of them raised is taken here
+  // -- the list build that follows would otherwise clear it unseen
+  bool zn_take_flag_before_rebuild() {
+    if (!zn_flag_host) return false;
+    sync();
+    const bool raised = *zn_flag_host != 0;
+    *zn_flag_host = 0;
+    return raised;
   }
   // once per plan / z-class table: the window's Fourier transform (Gauss-Legendre quadrature on the host), the grid's phases, P
   void zn_ensure_tables() {
@@ -2536,9 +2551,6 @@ struct conp_fix {
   void update_direct(const double *dx, double *dq, double potdiff) {
     if (decomposed) throw ConpError(CONP_ERR_STATE, "device-resident updates take replicated atoms (conp_env.rank / nranks); "
                                                     "spatially decomposed runs use the host-buffer hooks");
-    if (zn_overflowed())
-      throw ConpError(CONP_ERR_NUMERIC, "a device-resident update's z-window overflowed (an electrolyte atom drifted more than 2.5 A in z since "
-                                          "the last conp_fix_post_neighbor): the charges of the updates since then are invalid; the full kernels are used from now on");
     b_cal_device(dx, dq, true);
     if (can_fuse_solve()) { solve_scatter_fused(dq, potdiff); return; }
     allreduce_b();
@@ -2556,6 +2568,8 @@ struct conp_fix {
   double spec_pot = 0.0;
   bool spec_done = false;
   void update_device(const double *dx, double *dq, double potdiff) {
+    // (a captured graph holds the z-window launches: it is dropped with the path)
+    if (zn_flag_host && *zn_flag_host) { drop_graph(); zn_raise_if_overflowed(); }
     // (the legacy default stream cannot be captured)
     const bool can = !graph_off && stream != nullptr && !prof.on && args.minimizer == CONP_SOLVER_INV && runstage >= 3 &&
                      (!args.cond || cond_ready) && env.nranks == 1;
@@ -2748,7 +2762,12 @@ int conp_fix_setup_post_neighbor(conp_fix *f, const conp_atoms *at) {
 int conp_fix_post_neighbor(conp_fix *f, const conp_atoms *at) {
   CONP_GUARD_BEGIN
   f->drop_graph();
+  const bool overflowed = f->zn_take_flag_before_rebuild();
   f->post_neighbor(at);
+  if (overflowed)
+    throw ConpError(CONP_ERR_NUMERIC, "a device-resident update's z-window overflowed before this re-neighbouring (an electrolyte atom drifted "
+                                      "more than 2.5 A in z): the charges of the updates since the previous list build are invalid; the list "
+                                      "is rebuilt at the new positions");
   CONP_GUARD_END
 }
 

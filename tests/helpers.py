@@ -32,6 +32,38 @@ class OracleRun:
         self.fx.pre_force(potdiff)
 
 
+def oracle_sk_and_b(s, at, alist, blist, rows=None):
+    """the oracle's structure factors and b vector for the atoms as they are now: S(k) from KSpace.sincos_b over the charged
+    electrolyte; b in eleall order, the k-space part from ele_trig + bbb (+ the slab term in slab geometry), the real-space part
+    from blist_only().  `rows` (eleall
+    indices) restricts the k-space part to those electrode atoms (the largest boxes); then b has len(rows) entries.
+    Returns (sr, si, b, kspace) with the KSpace handle open (the caller closes it)."""
+    lib = oracle_py.load(fast=True)
+    lib.orc_set_threads(16)                                  # same arithmetic, OpenMP over k rows
+    o = OracleRun(lib, s, at, alist, blist)                  # post_neighbor only: no A matrix needed for b
+    m = o.fx.maps()
+    loc = {int(t): i for i, t in enumerate(at.tag[:at.nlocal])}
+    sel = np.arange(len(m["eleall2tag"])) if rows is None else np.asarray(rows)
+    xele = np.array([at.x[loc[int(t)]] for t in m["eleall2tag"][sel]])
+    ks = oracle_py.KSpace.from_system(lib, s)
+    sr, si = ks.sincos_b(at.x, at.q, at.echeck, at.nlocal)
+    csk, snk = ks.ele_trig(xele)
+    b = ks.bbb(csk, snk, sr, si)
+    if s.slabflag:                                           # the slab term of b_cal (orc_fix_b_cal)
+        lib.orc_slabcorr(ks.h, at.nlocal, np.ascontiguousarray(at.x), np.ascontiguousarray(at.q),
+                         np.ascontiguousarray(at.echeck, np.int32), len(xele), np.ascontiguousarray(xele), b)
+    breal = np.zeros(len(m["eleall2tag"])); breal[m["ele2eleall"]] = o.fx.blist_only()
+    b += breal[sel]
+    o.fx.close()
+    return sr, si, b, ks
+
+
+def sk_err(sr_g, si_g, sr, si):
+    """largest deviation of the GPU's structure factors from the reference's, relative to the reference's largest entry"""
+    scale = max(np.abs(sr).max(), np.abs(si).max())
+    return float(max(np.abs(sr_g - sr).max(), np.abs(si_g - si).max()) / scale)
+
+
 def rel_err(a, b):
     a, b = np.asarray(a), np.asarray(b)
     den = max(np.max(np.abs(b)), 1e-300)

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from conp_amd import FixConp, capi, neighbor, systems
-from helpers import OracleRun, rel_err
+from helpers import OracleRun, oracle_sk_and_b, rel_err, sk_err
 
 pytestmark = pytest.mark.gpu
 
@@ -171,30 +171,33 @@ def headline():
     fx.close()
 
 
-def test_headline_b_vector_matches_oracle(oracle, headline):
-    """k-space + real-space b at the full benchmark size against the oracle's sincos_b / bbb / blist loops"""
-    import oracle_py
-    s, at, alist, blist, fx = headline
+@pytest.mark.parametrize("mode", ["ffield", "slab"])
+def test_headline_b_vector_matches_oracle(headline, mode):
+    """k-space + real-space b at the full benchmark size against the oracle's sincos_b / bbb / blist loops, on the z-window path
+    (both of the product's geometries; slab: nz = 378, three kz column tiles)"""
+    from test_zwindow_math import zn_grid_of
+    if mode == "ffield":
+        s, at, alist, blist, fx = headline
+    else:
+        s = systems.synthetic_fast(mode="slab")
+        at, alist, blist = neighbor.build_lists(s)
+        fx = FixConp(s)
+        fx.init_lists(alist, blist)
+        fx.setup_post_neighbor(at)
     fx.b_cal(at)
     b_g, _, _ = fx.vectors()
-    o = OracleRun(oracle, s, at, alist, blist)          # post_neighbor only: no A matrix needed for b
-    m = o.fx.maps()
-    loc = {int(t): i for i, t in enumerate(at.tag[:at.nlocal])}
-    xele = np.array([at.x[loc[int(t)]] for t in m["eleall2tag"]])
-    fast = oracle_py.load(fast=True); fast.orc_set_threads(16)    # same arithmetic, OpenMP over k rows
-    ks = oracle_py.KSpace.from_system(fast, s)
-    sr, si = ks.sincos_b(at.x, at.q, at.echeck, at.nlocal)
-    csk, snk = ks.ele_trig(xele)
-    b_o = ks.bbb(csk, snk, sr, si)
-    breal = np.zeros(len(b_o)); breal[m["ele2eleall"]] = o.fx.blist_only()
-    b_o += breal
-    sr_g, si_g = fx.sfac()
-    scale = max(np.abs(sr).max(), np.abs(si).max())
-    assert max(np.abs(sr_g - sr).max(), np.abs(si_g - si).max()) / scale < 1e-11
-    assert rel_err(b_g, b_o) < 1e-10
     info = fx.info()
+    assert info.zn_cols in (32, 48) and info.zn_grid == zn_grid_of(s) and info.n_zclasses == 2
+    sr, si, b_o, ks = oracle_sk_and_b(s, at, alist, blist)
+    sr_g, si_g = fx.sfac()
+    e_s, e_b = sk_err(sr_g, si_g, sr, si), rel_err(b_g, b_o)
+    print(f"headline {mode}: zn_cols {info.zn_cols} zn_grid {info.zn_grid}: S(k) {e_s:.2e}, b {e_b:.2e} of max")
+    assert e_s < 1e-11
+    assert e_b < 1e-10
     assert (info.elenum_all, info.n_elyte_charged) == (4096, 32768) and info.kcount == ks.kcount
-    ks.close(); o.fx.close()
+    ks.close()
+    if mode == "slab":
+        fx.close()
 
 
 def test_headline_charges_are_the_product_of_the_projected_inverse_with_b(headline):

@@ -24,12 +24,25 @@ def library_parameters():
     return W, num, den, g
 
 
+def nz_of(s):
+    """m = 0 .. kzmax of the k plan of System s (conp_host.cpp: nz = kcount_dims[2] + 1), without a GPU"""
+    from conp_amd import capi
+    return int(capi.host_ktables(s)["kcount_dims"][2]) + 1
+
+
+def zn_grid_of(s):
+    """the z grid the library plans for System s: the smallest multiple of 16 at or above num / den * nz, at least 64"""
+    _, num, den, _ = library_parameters()
+    return max(64, (num * nz_of(s) // den + 15) // 16 * 16)
+
+
 def window_error(nz, rng, nl=2048, rows=6, nzc=3):
     W, num, den, gam = library_parameters()
     n = max(64, (num * nz // den + 15) // 16 * 16)
     beta = gam * np.pi * W * (1.0 - nz / n)
     h = 2 * np.pi / n
     a = 0.5 * W * h
+    nl = max(nl, 2 * n)              # at least two atoms per grid cell: a chunk of 16 spans a few cells, as the planner's ranges do
     th = np.sort(rng.uniform(0.0, 2 * np.pi, nl))
     A = rng.normal(size=(rows, nl))
     w = rng.uniform(0.1, 1.0, size=(rows, nz)) * (rng.uniform(size=(rows, nz)) < 0.8)      # weights with a sphere cut
@@ -60,8 +73,18 @@ def window_error(nz, rng, nl=2048, rows=6, nzc=3):
     return np.abs(app - exact).max() / np.abs(exact).max(), n, W
 
 
-@pytest.mark.parametrize("nz", [126, 266, 48])          # headline (ffield), 16384 / 262144, a small plan
+def _gpu_case_nz(name):
+    """nz of the boxes tests/test_gpu_zwindow_oracle.py runs on the z-window path (taken from the k plan, not typed in)"""
+    from test_gpu_zwindow_oracle import CASES
+    return nz_of(CASES[name]())
+
+
+@pytest.mark.parametrize("nz", [126, 266, 48,          # headline (ffield), 16384 / 262144, a small plan
+                                "smallest_grid", "headline_slab", "medium_layers2", "medium_layers4", "rough_ffield",
+                                "rough_slab"])
 def test_window_reproduces_the_trigonometric_sums(nz):
+    if isinstance(nz, str):
+        nz = _gpu_case_nz(nz)
     err, n, W = window_error(nz, np.random.default_rng(nz))
     assert W == 15 and n % 16 == 0 and n >= 3.8 * nz - 16
     assert err < 1e-12, (nz, n, err)
