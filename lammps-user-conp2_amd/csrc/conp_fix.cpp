@@ -576,6 +576,12 @@ struct conp_fix {
       // fix_conp.cpp:401-404: the `pppm` keyword needs the pppm/conp kspace style; here: its mesh and order via conp_env
       if (env.pppm_nx <= 0 || env.pppm_ny <= 0 || env.pppm_nz <= 0 || env.pppm_order <= 0)
         throw ConpError(CONP_ERR_ARG, "Fix conp couldn't detect a pppm/conp kspace style (which is required with the pppm flag)");
+      // a mesh line is transformed in LDS: one that does not fit there (about 3400 points; 5120 for a length that is not
+      // 2,3,5-smooth) could not be launched at all -- refused here instead of at the first update
+      for (const int n : {env.pppm_nx, env.pppm_ny, env.pppm_nz})
+        if (pppm_line_lds_bytes(n) > PPPM_LDS_MAX)
+          throw ConpError(CONP_ERR_ARG, "pppm mesh of " + std::to_string(n) + " points along one axis: a line of it does not fit in the "
+                                        "LDS of a workgroup (" + std::to_string(pppm_line_lds_bytes(n)) + " > " + std::to_string(PPPM_LDS_MAX) + " bytes)");
       const double lo[3] = {env.boxlo_x, env.boxlo_y, env.boxlo_z}, prd[3] = {env.xprd, env.yprd, env.zprd};
       pppm.build(env.pppm_nx, env.pppm_ny, env.pppm_nz, env.pppm_order, env.g_ewald, env.slab_volfactor, lo, prd);
       d_pp_coeff.upload(pppm.rho_coeff, stream); d_pp_green.upload(pppm.greensfn, stream);

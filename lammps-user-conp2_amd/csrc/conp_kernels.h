@@ -110,6 +110,9 @@ void launch_pppm_b(hipStream_t s, const PppmDev &pd, int nl, const int *elyte_id
 void launch_pppm_density(hipStream_t s, const PppmDev &pd, int n, const int *idx, const double *x, const double *q, double *rho,
                          double *slab_scratch /*[>= 1025]*/);
 void launch_pppm_poisson(hipStream_t s, const PppmDev &pd, double *re /*rho in, u_brick out*/, double *im);
+// dynamic LDS (bytes) of the transform of one mesh line of n points; a workgroup of gfx950 has PPPM_LDS_MAX at most
+size_t pppm_line_lds_bytes(int n);
+constexpr size_t PPPM_LDS_MAX = 160 * 1024;
 void launch_pppm_probe(hipStream_t s, const PppmDev &pd, int n, const int *idx, const double *x, const double *q, const double *u,
                        double self, double *out /*indexed by atom*/);
 void launch_potential_pair(hipStream_t s, int inum, const int *ilist, const int *numneigh, const int *first, const int *neigh,

@@ -539,8 +539,28 @@ static bool mesh_smooth(const PppmDev &pd) {
   return fft_factor(pd.nx, fp) && fft_factor(pd.ny, fp) && fft_factor(pd.nz, fp);
 }
 
-// forward (sign -1) or backward 3-D transform.  fused (radix path only): the forward transform takes real input and applies
-// gscale*greensfn on its last pass; the backward one stores only the real part.
+// lines per workgroup (XT = 1 << xs) and dynamic LDS of pppm_fft_kernel for a line of n points: two [n][XT] complex buffers
+// (as many lines as keep them within 64 KB, at most 16; above 1024 points one line: 48 n bytes) and the twiddle table
+static size_t fft_line_lds(int n, int *xs_out) {
+  int xs = 0;
+  while (xs < 4 && (size_t)n * 32 * (2u << xs) <= 64 * 1024) ++xs;
+  *xs_out = xs;
+  return ((size_t)2 * n * (1 << xs)) * sizeof(double2) + (size_t)2 * n * sizeof(double);
+}
+// the same for pppm_dft_kernel (lengths that are not 2,3,5-smooth): [n][XT] re and im within 48 KB, at least one line (32 n bytes)
+static size_t dft_line_lds(int n, int *xt_out) {
+  int XT = (int)(48 * 1024 / ((size_t)n * 16));
+  XT = XT < 1 ? 1 : (XT > 16 ? 16 : XT);
+  *xt_out = XT;
+  return ((size_t)2 * n * XT + 2 * n) * sizeof(double);
+}
+// what a transform along an axis of n points asks of LDS; the caller (linalg_init) refuses a mesh whose line cannot be held
+size_t pppm_line_lds_bytes(int n) {
+  FftPlan fp;
+  int t;
+  return fft_factor(n, fp) ? fft_line_lds(n, &t) : dft_line_lds(n, &t);
+}
+
 // raise a kernel's dynamic-LDS limit only when a launch needs more than it was last given (per device; see conp_kernels.hip)
 struct LdsGrant { std::atomic<size_t> granted[64]; };
 template <typename K>
@@ -580,10 +600,9 @@ static void dft3(hipStream_t s, const PppmDev &pd, double sign, double *re, doub
     FftPlan fp;
     if (fft_factor(n, fp)) {              // 2,3,5-smooth length (every mesh LAMMPS picks): radix FFT
       int xs = 0;
-      while (xs < 4 && (size_t)n * 32 * (2u << xs) <= 64 * 1024) ++xs;
+      const size_t lds = fft_line_lds(n, &xs);
       const int XT = 1 << xs;
       const int nlines = axis == 0 ? pd.ny * pd.nz : (axis == 1 ? pd.nx * pd.nz : pd.nx * pd.ny);
-      const size_t lds = ((size_t)2 * n * XT) * sizeof(double2) + (size_t)2 * n * sizeof(double);
       int flags = 0;
       const double *gmul = nullptr;
       if (fused && sign < 0 && axis == 0) flags |= 1;
@@ -595,10 +614,9 @@ static void dft3(hipStream_t s, const PppmDev &pd, double sign, double *re, doub
                          pd.twid[axis], re, im, xs, flags, gmul, gscale);
       continue;
     }
-    int XT = (int)(48 * 1024 / ((size_t)n * 16));
-    XT = XT < 1 ? 1 : (XT > 16 ? 16 : XT);
+    int XT = 1;
+    const size_t lds = dft_line_lds(n, &XT);
     const int nlines = axis == 0 ? pd.ny * pd.nz : (axis == 1 ? pd.nx * pd.nz : pd.nx * pd.ny);
-    const size_t lds = ((size_t)2 * n * XT + 2 * n) * sizeof(double);
     static LdsGrant g{};
     grant_lds(pppm_dft_kernel, lds, g);
     hipLaunchKernelGGL(pppm_dft_kernel, dim3((nlines + XT - 1) / XT), dim3(256), lds, s, pd.nx, pd.ny, pd.nz, axis, sign,
@@ -628,9 +646,8 @@ static bool poisson_three_launches(hipStream_t s, const PppmDev &pd, double *re,
     hipLaunchKernelGGL(pppm_fft_xy_kernel, dim3(pd.nz), dim3(512), lds_xy, s, pd.nx, pd.ny, -1.0, fpx, fpy, pd.twid[0], pd.twid[1], re, im,
                        rho_in_im ? 2 : 1, 0, pd, PppmSpreadIn{}, BRowArgs{});
   int xs = 0;
-  while (xs < 4 && (size_t)pd.nz * 32 * (2u << xs) <= 64 * 1024) ++xs;
+  const size_t lds_z = fft_line_lds(pd.nz, &xs);
   const int XT = 1 << xs, nlines = pd.nx * pd.ny;
-  const size_t lds_z = ((size_t)2 * pd.nz * XT) * sizeof(double2) + (size_t)2 * pd.nz * sizeof(double);
   grant_lds(pppm_fft_kernel, lds_z, gz);
   hipLaunchKernelGGL(pppm_fft_kernel, dim3((nlines + XT - 1) / XT), dim3(512), lds_z, s, pd.nx, pd.ny, pd.nz, 2, -1.0, fpz, pd.twid[2], re, im,
                      xs, 8, pd.greensfn, gscale);

@@ -1313,7 +1313,7 @@ void orc_multirank_maps(int nprocs, const int *counts_first, const int *tags_fir
  * OFFSET, nlower, nupper) live in LAMMPS src/KSPACE/pppm.cpp @ 27May2021, which is not under /root/reference.  They
  * are restated here from the published Hockney-Eastwood P3M formulation as LAMMPS implements it; the reference's tests
  * hold no numbers for them, so this part is only cross-checked against the Ewald b vector within the PPPM accuracy.
- * The FFT is a plain O(N n) DFT per axis (small meshes only).
+ * The FFT is a plain O(N n) DFT per axis (small meshes only; orc_pppm_set_poisson for the large ones).
  * ===========================================================================================*/
 #define ORC_PPPM_OFFSET 16384
 #define ORC_PPPM_MAXORDER 8
@@ -1498,6 +1498,23 @@ static void orc_dft_axis(double *re, double *im, int nx, int ny, int nz, int axi
 
 static int orc_wrap(int i, int n) { i %= n; return i < 0 ? i + n : i; }
 
+/* elyte_poisson (pppm_conp.cpp:230-267): forward transform, greensfn / N, backward transform, in place.  The transform above is
+ * written for deck-sized meshes; for the production-sized ones the caller may install a faster Poisson step of its own
+ * (orc_pppm_set_poisson: oracle_py's numpy.fft one), pinned against the plain DFT by tests/test_oracle_pin.py.  The hook is
+ * process-wide; NULL restores the plain DFT. */
+typedef void (*orc_poisson_fn)(double *re, double *im, int nx, int ny, int nz, const double *greensfn);
+static orc_poisson_fn orc_poisson_hook = NULL;
+void orc_pppm_set_poisson(orc_poisson_fn f) { orc_poisson_hook = f; }
+
+void orc_pppm_poisson(const orc_pppm *p, double *re, double *im) {
+  const double scaleinv = 1.0 / ((double)p->nx * p->ny * p->nz);
+  int i, c;
+  if (orc_poisson_hook) { orc_poisson_hook(re, im, p->nx, p->ny, p->nz, p->greensfn); return; }
+  for (c = 0; c < 3; ++c) orc_dft_axis(re, im, p->nx, p->ny, p->nz, c, -1);
+  for (i = 0; i < p->nfft; ++i) { re[i] *= scaleinv * p->greensfn[i]; im[i] *= scaleinv * p->greensfn[i]; }
+  for (c = 0; c < 3; ++c) orc_dft_axis(re, im, p->nx, p->ny, p->nz, c, +1);
+}
+
 /* pppm_conp.cpp:269-316 b_cal for electrode coordinates xele[ne][3] (eleall order); bbb[ne] overwritten.
  * u_out (optional, [nfft]) receives the mesh potential. */
 void orc_pppm_b_cal(const orc_pppm *p, int nlocal, const double *x, const double *q, const int *echeck, int ne,
@@ -1507,7 +1524,6 @@ void orc_pppm_b_cal(const orc_pppm *p, int nlocal, const double *x, const double
   double w[3][ORC_PPPM_MAXORDER];
   double slabcorr = 0.0;
   int i, c, l, m, n;
-  const double scaleinv = 1.0 / ((double)nx * ny * nz);
   for (i = 0; i < nlocal; ++i) {   /* elyte_particle_map + elyte_make_rho */
     int g[3];
     double z0;
@@ -1532,9 +1548,7 @@ void orc_pppm_b_cal(const orc_pppm *p, int nlocal, const double *x, const double
     }
     slabcorr += 4 * q[i] * ORC_PI * x[3 * i + 2] / p->volume;
   }
-  for (c = 0; c < 3; ++c) orc_dft_axis(rho, im, nx, ny, nz, c, -1);   /* elyte_poisson */
-  for (i = 0; i < p->nfft; ++i) { rho[i] *= scaleinv * p->greensfn[i]; im[i] *= scaleinv * p->greensfn[i]; }
-  for (c = 0; c < 3; ++c) orc_dft_axis(rho, im, nx, ny, nz, c, +1);
+  orc_pppm_poisson(p, rho, im);   /* elyte_poisson */
   if (u_out) memcpy(u_out, rho, sizeof(double) * p->nfft);
   for (i = 0; i < ne; ++i) {        /* aaa_map_rho weights + the stencil gather of b_cal */
     int g[3];
@@ -1615,13 +1629,9 @@ void orc_pppm_make_rho(const orc_pppm *p, int nlocal, const double *x, const dou
  * compute_potential_atom.cpp:128-130): inverse transform of greensfn / N times the transform of the TOTAL density */
 void orc_pppm_u_brick(const orc_pppm *p, int nlocal, const double *x, const double *q, const int *echeck, double *u) {
   double *im = (double *)calloc(p->nfft, sizeof(double));
-  const double scaleinv = 1.0 / ((double)p->nx * p->ny * p->nz);
-  int i, c;
   memset(u, 0, sizeof(double) * p->nfft);
   orc_pppm_spread(p, nlocal, x, q, echeck, 2, u);
-  for (c = 0; c < 3; ++c) orc_dft_axis(u, im, p->nx, p->ny, p->nz, c, -1);
-  for (i = 0; i < p->nfft; ++i) { u[i] *= scaleinv * p->greensfn[i]; im[i] *= scaleinv * p->greensfn[i]; }
-  for (c = 0; c < 3; ++c) orc_dft_axis(u, im, p->nx, p->ny, p->nz, c, +1);
+  orc_pppm_poisson(p, u, im);
   free(im);
 }
 

@@ -245,10 +245,29 @@ def _nz(a):
     return a if a.size else np.zeros(1, np.int32)
 
 
-class Pppm:
-    """oracle restatement of the PPPM b vector (pppm_conp.cpp b_cal chain); parity unpinned at the LAMMPS boundary"""
+_POISSON_FN = C.CFUNCTYPE(None, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double))
 
-    def __init__(self, lib, s, mesh, order=5):
+
+@_POISSON_FN
+def _fft_poisson(re, im, nx, ny, nz, greensfn):
+    """the oracle's Poisson step (forward transform, greensfn / N, backward transform, in place) through numpy.fft instead of the
+    plain per-axis DFT: same operation on the oracle's own brick and influence function, O(N log N)"""
+    shape = (nz, ny, nx)
+    r = np.ctypeslib.as_array(re, shape); i = np.ctypeslib.as_array(im, shape)
+    f = np.fft.fftn(r + 1j * i)                    # exp(-i k x): the oracle's sign -1
+    f *= np.ctypeslib.as_array(greensfn, shape)
+    u = np.fft.ifftn(f)                            # exp(+i k x) / N
+    r[...] = u.real; i[...] = u.imag
+
+
+class Pppm:
+    """oracle restatement of the PPPM b vector (pppm_conp.cpp b_cal chain); parity unpinned at the LAMMPS boundary.
+    fast=True: every mesh solve of this handle goes through numpy.fft (production-sized meshes; the plain DFT is O(N n))"""
+
+    def __init__(self, lib, s, mesh, order=5, fast=False):
+        self.fast = fast
+        lib.orc_pppm_set_poisson.argtypes = [C.c_void_p]
+        lib.orc_pppm_poisson.argtypes = [C.c_void_p, _dp, _dp]
         lib.orc_pppm_create.restype = C.c_void_p
         lib.orc_pppm_create.argtypes = [C.c_int] * 4 + [C.c_double, C.c_double, C.c_int, _dp, _dp]
         lib.orc_pppm_b_cal.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _ip, C.c_int, _dp, _dp, C.c_void_p]
@@ -257,9 +276,30 @@ class Pppm:
         self.h = lib.orc_pppm_create(mesh[0], mesh[1], mesh[2], order, s.g_ewald, s.slab_volfactor, int(s.slabflag),
                                      np.ascontiguousarray(s.boxlo), np.ascontiguousarray(s.prd))
 
+    def _solver(self):
+        """the process-wide Poisson hook of the oracle, set for the length of one call of a fast handle"""
+        import contextlib
+
+        @contextlib.contextmanager
+        def cm():
+            self.lib.orc_pppm_set_poisson(C.cast(_fft_poisson, C.c_void_p) if self.fast else None)
+            try:
+                yield
+            finally:
+                self.lib.orc_pppm_set_poisson(None)
+        return cm()
+
+    def poisson(self, mesh, rho):
+        """rho [nfft] -> (re, im) of the mesh potential (the imaginary part is rounding only)"""
+        re = np.ascontiguousarray(rho, np.float64).copy(); im = np.zeros(self._nfft(mesh))
+        with self._solver():
+            self.lib.orc_pppm_poisson(self.h, re, im)
+        return re, im
+
     def b_cal(self, x, q, echeck, nlocal, xele):
         b = np.zeros(len(xele))
-        self.lib.orc_pppm_b_cal(self.h, nlocal, np.ascontiguousarray(x), np.ascontiguousarray(q),
+        with self._solver():
+            self.lib.orc_pppm_b_cal(self.h, nlocal, np.ascontiguousarray(x), np.ascontiguousarray(q),
                                 np.ascontiguousarray(echeck, np.int32), len(xele), np.ascontiguousarray(xele), b, None)
         return b
 
@@ -278,7 +318,8 @@ class Pppm:
     def group_potential(self, x, q, echeck, nlocal, sel, particle=False):
         out = np.zeros(nlocal)
         self.lib.orc_pppm_group_potential.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _ip, _ip, C.c_int, _dp]
-        self.lib.orc_pppm_group_potential(self.h, nlocal, np.ascontiguousarray(x), np.ascontiguousarray(q),
+        with self._solver():
+            self.lib.orc_pppm_group_potential(self.h, nlocal, np.ascontiguousarray(x), np.ascontiguousarray(q),
                                           np.ascontiguousarray(echeck, np.int32), np.ascontiguousarray(sel, np.int32), int(particle), out)
         return out
 
@@ -291,7 +332,8 @@ class Pppm:
                                                         C.c_int, C.c_int, C.c_double, C.c_double, _dp]
         vol = float(s.prd[0] * s.prd[1] * s.prd[2] * s.slab_volfactor)
         from conp_amd import systems as _sy
-        self.lib.orc_compute_potential_atom(self.h, at.nlocal, at.nghost, np.ascontiguousarray(at.x), np.ascontiguousarray(at.q),
+        with self._solver():
+            self.lib.orc_compute_potential_atom(self.h, at.nlocal, at.nghost, np.ascontiguousarray(at.x), np.ascontiguousarray(at.q),
                                             np.ascontiguousarray(at.type, np.int32), np.ascontiguousarray(at.echeck, np.int32),
                                             np.ascontiguousarray(sel, np.int32), np.ascontiguousarray(etasel, np.int32), lst.inum,
                                             lst.ilist, lst.numneigh, lst.first, neigh, int(s.newton), s.ntypes,

@@ -68,3 +68,26 @@ def rel_err(a, b):
     a, b = np.asarray(a), np.asarray(b)
     den = max(np.max(np.abs(b)), 1e-300)
     return float(np.max(np.abs(a - b)) / den)
+
+
+def push_outside(s, at, seed=3):
+    """positions as LAMMPS leaves them between re-neighbourings: twelve charged electrolyte atoms put up to 1 A outside the box (two
+    per face), unwrapped, and three more exactly on boxhi, one per direction; the ghosts move with their owners.  Returns the indices
+    of the moved atoms (the three on boxhi last)."""
+    rng = np.random.default_rng(seed)
+    n = at.nlocal
+    cand = np.nonzero((at.echeck[:n] == 0) & (at.q[:n] != 0))[0]
+    moved = rng.choice(cand, 15, replace=False)
+    d = np.zeros((n, 3))
+    for k, i in enumerate(moved):
+        c = k % 3
+        if k >= 12:
+            target = s.boxhi[c]
+        elif (k // 3) % 2:
+            target = s.boxhi[c] + rng.uniform(0.05, 1.0)
+        else:
+            target = s.boxlo[c] - rng.uniform(0.05, 1.0)
+        d[i, c] = target - at.x[i, c]
+        at.x[i, c] = target
+    at.x[n:] += d[at.owner[n:]]
+    return [int(i) for i in moved]

@@ -1,6 +1,7 @@
 """-m gpu: PPPM k-space b vector (`pppm` keyword, SURVEY row a20 / BASELINE configs[3]) against the oracle's restatement of
 pppm_conp.cpp's b_cal chain, and both against the Ewald b within the PPPM accuracy (the only cross-check available:
-LAMMPS' PPPM internals are not part of the reference repository -> parity unpinned at that boundary)."""
+LAMMPS' PPPM internals are not part of the reference repository -> parity unpinned at that boundary).
+The paths that only larger meshes, more atoms, other orders or atoms outside the box select: tests/test_gpu_pppm_sizes.py."""
 import numpy as np
 import pytest
 
