@@ -77,17 +77,14 @@ void ComputePotentialAtomHip::compute_peratom() {             /* :120-218 */
   }
   const int nlocal = atom->nlocal, nall = nlocal + atom->nghost;
   const int ntotal = nlocal + (force->newton ? atom->nghost : 0);
-  sel.resize(nall); etasel.resize(nall); echeck.assign(nall, 0); xflat.resize(3 * (size_t)nall); out.assign(nall, 0.0);
+  sel.resize(nall); etasel.resize(nall); out.assign(nall, 0.0);
   for (int i = 0; i < nall; ++i) {
     sel[i] = (atom->mask[i] & groupbit) ? 1 : 0;
     etasel[i] = (atom->molecule && (atom->molecule[i] == molidL || atom->molecule[i] == molidR)) ? 1 : 0;   /* eta_check :313-318 */
-    if (fixconp) echeck[i] = fixconp->electrode_check(i);
-    else if (fixhip) echeck[i] = fixhip->electrode_check(i);
-    for (int c = 0; c < 3; ++c) xflat[3 * (size_t)i + c] = atom->x[i][c];
   }
-  conp_atoms at;
-  at.nlocal = nlocal; at.nghost = atom->nghost; at.x = xflat.data(); at.q = atom->q; at.type = atom->type; at.tag = atom->tag;
-  at.echeck = echeck.data();
+  conp_atoms at = av.flat(atom, [this](int i) {
+    return fixconp ? fixconp->electrode_check(i) : (fixhip ? fixhip->electrode_check(i) : 0);
+  });
   /* the pair style's half list (:231: force->pair->list), flattened */
   NeighList *l = force->pair->list;
   first.assign(nall, 0); neigh.clear();

@@ -13,9 +13,7 @@ ComputeStyle(potential/atom/hip,ComputePotentialAtomHip)
 #ifndef LMP_COMPUTE_POTENTIAL_ATOM_HIP_H
 #define LMP_COMPUTE_POTENTIAL_ATOM_HIP_H
 
-#include <vector>
-
-#include "conp_hip.h"
+#include "conp_glue_common.h"
 #ifdef CONP_GLUE_MOCK
 #include "mock_lammps/conp2_mock.h"
 #else
@@ -42,8 +40,9 @@ class ComputePotentialAtomHip : public Compute {
   int nmax, molidL, molidR;
   double eta;
   double *potential;
-  std::vector<int> sel, etasel, echeck, first, neigh;
-  std::vector<double> xflat, out;
+  conp_glue::AtomView av;
+  std::vector<int> sel, etasel, first, neigh;
+  std::vector<double> out;
 };
 
 }  // namespace LAMMPS_NS

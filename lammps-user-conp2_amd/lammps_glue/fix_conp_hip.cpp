@@ -3,21 +3,9 @@
 
 #include <cstring>
 
-#ifdef CONP_GLUE_MOCK
-#include "mock_lammps/mpi_mock.h"
-#else
-#include <mpi.h>
-#endif
-
 #ifndef CONP_GLUE_MOCK
-#include "atom.h"
-#include "comm.h"
-#include "domain.h"
-#include "error.h"
-#include "force.h"
 #include "group.h"
 #include "input.h"
-#include "kspace.h"
 #include "modify.h"
 #include "neigh_list.h"
 #include "neigh_request.h"
@@ -27,19 +15,8 @@
 #include "variable.h"
 #endif
 
-#include "conp_mpi_comm.h"
-
 using namespace LAMMPS_NS;
 using namespace FixConst;
-
-// ---- conp_comm on MPI: the collectives FixConp makes on `world` (fix_conp.cpp:415, 492, 523, 535, 643, 822, 1356;
-// km_ewald.cpp:77, 784), handed to the library as callbacks.  ctx = &world.
-// (conp_mpi_comm.h: shared with KSpaceModuleHip, counts checked against MPI's int range)
-using conp_glue::cb_allreduce_sum; using conp_glue::cb_allreduce_max_int; using conp_glue::cb_allgather_int; using conp_glue::cb_allgatherv;
-
-void FixConpHip::fail_if(int status) {
-  if (status != CONP_OK) error->all(FLERR, conp_last_error());
-}
 
 FixConpHip::FixConpHip(LAMMPS *lmp, int narg, char **arg)
     : Fix(lmp, narg, arg), h(nullptr), potdiffvar(-1), arequest(-1), brequest(-1), alist(nullptr), blist(nullptr),
@@ -82,38 +59,21 @@ void FixConpHip::init() {
     for (int i = 0; i < nt1; ++i)
       for (int j = 0; j < nt1; ++j) cutsq_flat[(size_t)i * nt1 + j] = (i && j) ? coulpair->cutsq[i][j] : 0.0;
     int itmp;
-    conp_env env;
-    std::memset(&env, 0, sizeof(env));
-    env.qqrd2e = force->qqrd2e; env.qqr2e = force->qqr2e; env.qe2f = force->qe2f; env.dielectric = force->dielectric;
-    env.newton_pair = force->newton_pair;
-    env.g_ewald = force->kspace->g_ewald; env.accuracy = force->kspace->accuracy;
-    env.slab_volfactor = force->kspace->slab_volfactor; env.slabflag = force->kspace->slabflag;
-    env.xprd = domain->xprd; env.yprd = domain->yprd; env.zprd = domain->zprd; env.boxlo_z = domain->boxlo[2];
-    env.boxlo_x = domain->boxlo[0]; env.boxlo_y = domain->boxlo[1];
+    conp_env env = conp_glue::base_env(force, domain, atom, comm, world, force->kspace);
     // `pppm` keyword (fix_conp.cpp:400-405 looks for a pppm/conp kspace style): the mesh and stencil order LAMMPS' PPPM chose are
     // public KSpace members; with a non-mesh style they stay 0 and the library answers with the reference's error message
     if (args.pppm) {
       env.pppm_nx = force->kspace->nx_pppm; env.pppm_ny = force->kspace->ny_pppm; env.pppm_nz = force->kspace->nz_pppm;
       env.pppm_order = force->kspace->order;
     }
-    env.ntypes = atom->ntypes; env.cutsq = cutsq_flat.data();
+    env.cutsq = cutsq_flat.data();
     env.cut_coul = *(double *)coulpair->extract("cut_coul", itmp);
     env.one_electrode = (groupbit == jgroupbit);                           // :295
-    // several MPI ranks (spatial decomposition): every rank drives its own handle on its own atoms and lists; device -1 lets the
-    // library take GPU (rank mod visible devices), so that ranks of a node spread over its GPUs or share one
-    env.device = comm->nprocs > 1 ? -(2 + conp_glue::node_local_rank(world)) : 0;     // ranks of a NODE spread over its GPUs
-    env.rank = comm->me; env.nranks = comm->nprocs;
     // ghosts that are periodic images of owned atoms are rebuilt on the device; a rank whose ghosts belong to other ranks fails
     // the library's check at post_neighbor and uploads them as they are
     env.ghost_images = 1;
     fail_if(conp_fix_create(&args, &env, &h));
-    if (comm->nprocs > 1) {
-      conp_comm cc;
-      cc.ctx = &world; cc.rank = comm->me; cc.nranks = comm->nprocs;
-      cc.allreduce_sum = cb_allreduce_sum; cc.allreduce_max_int = cb_allreduce_max_int;
-      cc.allgather_int = cb_allgather_int; cc.allgatherv = cb_allgatherv;
-      fail_if(conp_fix_set_comm(h, &cc));
-    }
+    fail_if(conp_glue::install_mpi_comm(h, &world, comm->me, comm->nprocs));
     for (auto &toks : pending_modify) {
       std::vector<const char *> ptrs;
       for (auto &tk : toks) ptrs.push_back(tk.c_str());
@@ -154,17 +114,9 @@ void FixConpHip::init_list(int, NeighList *ptr) {                         // :36
   } else { alist = ptr; blist = ptr; }
 }
 
+// atom->x stays in place: pin_atoms() and the library's check of the pinned pointer in post_force depend on that pointer
 conp_atoms FixConpHip::view() {
-  const int nall = atom->nlocal + atom->nghost;
-  echeck.resize(nall);
-  for (int i = 0; i < nall; ++i)
-    echeck[i] = (atom->mask[i] & groupbit) ? 1 : ((atom->mask[i] & jgroupbit) ? -1 : 0);   // electrode_check :599-605
-  conp_atoms a;
-  // atom->x is a LAMMPS 2-d array (Memory::create): one contiguous [nmax][3] block behind the row pointers
-  a.nlocal = atom->nlocal; a.nghost = atom->nghost; a.x = nall ? &atom->x[0][0] : nullptr; a.q = atom->q; a.type = atom->type;
-  a.tag = atom->tag;
-  a.echeck = echeck.data();
-  return a;
+  return av.in_place(atom, [this](int i) { return electrode_check(i); });
 }
 
 void FixConpHip::PinnedInts::reserve(size_t want) {

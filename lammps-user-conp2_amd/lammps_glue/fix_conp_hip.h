@@ -15,10 +15,8 @@ FixStyle(cond/hip,FixConpHip)
 #include <string>
 #include <vector>
 
-#include "conp_hip.h"
-#ifdef CONP_GLUE_MOCK
-#include "mock_lammps/lammps_mock.h"
-#else
+#include "conp_glue_common.h"
+#ifndef CONP_GLUE_MOCK
 #include "fix.h"
 #endif
 
@@ -72,7 +70,7 @@ class FixConpHip : public Fix {
     size_t size() const { return n; }
     int *data() { return p; }
   };
-  std::vector<int> echeck;
+  conp_glue::AtomView av;
   PinnedInts first_a, first_b, neigh_a, neigh_b;
   const double *pinned_x = nullptr, *pinned_q = nullptr;
   int pinned_n = 0;
@@ -80,7 +78,7 @@ class FixConpHip : public Fix {
   void pin_atoms();
   void push_list(int which, class NeighList *l, PinnedInts &first, PinnedInts &neigh);
   double potdiff_now();
-  void fail_if(int status);
+  void fail_if(int status) { conp_glue::fail_if(error, status); }
   void flush_log();
   void request_smartlist();
 };

@@ -10,9 +10,7 @@
 #ifndef LMP_FIXCONP_KM_HIP_H
 #define LMP_FIXCONP_KM_HIP_H
 
-#include <vector>
-
-#include "conp_hip.h"
+#include "conp_glue_common.h"
 #ifdef CONP_GLUE_MOCK
 #include "mock_lammps/conp2_mock.h"
 #else
@@ -25,7 +23,6 @@ namespace LAMMPS_NS {
 class KSpaceModuleHip : public KSpaceModule, protected Pointers {
  public:
   explicit KSpaceModuleHip(LAMMPS *lmp);
-  ~KSpaceModuleHip() override;
   void conp_setup(bool lowmem) override;                 /* km_ewald.cpp:63-132: handle creation + k tables */
   void conp_post_neighbor(bool, bool) override;          /* km_ewald.cpp:232-275: the handle follows the fix's atoms */
   void a_cal(double *aaa) override;                      /* km_ewald.cpp:147-151 : aaa[elenum][elenum_all] +=, k-space part */
@@ -36,16 +33,12 @@ class KSpaceModuleHip : public KSpaceModule, protected Pointers {
    * return_qsum keep the base-class defaults. */
   double compute_particle_potential(int i) override;                  /* rank-local, from the cached structure factor */
   void compute_group_potential(int groupbit, double *recv) override;  /* collective */
-  conp_fix *handle() { return h; }
+  conp_fix *handle() { return ph.h; }
 
  private:
-  conp_fix *h;
-  bool first;
-  std::vector<int> echeck, lib_tag2eleall, nolist;
-  std::vector<double> xflat, cutsq0;
-  void fail_if(int status);
+  conp_glue::ProviderHandle ph;      /* destroys the handle with the provider */
+  conp_glue::AtomView av;
   conp_atoms view();
-  void refresh_maps();
 };
 
 }  // namespace LAMMPS_NS

@@ -15,9 +15,7 @@ KSpaceStyle(pppm/conp/hip,PPPMConpHip)
 #ifndef LMP_PPPM_CONP_HIP_H
 #define LMP_PPPM_CONP_HIP_H
 
-#include <vector>
-
-#include "conp_hip.h"
+#include "conp_glue_common.h"
 #ifdef CONP_GLUE_MOCK
 #include "mock_lammps/conp2_mock.h"
 #else
@@ -30,7 +28,6 @@ namespace LAMMPS_NS {
 class PPPMConpHip : public PPPM, public KSpaceModule {
  public:
   explicit PPPMConpHip(class LAMMPS *);
-  ~PPPMConpHip() override;
   void conp_setup(bool lowmem) override;                              /* pppm_conp.h:27 + handle creation */
   void conp_post_neighbor(bool, bool) override;                       /* pppm_conp.cpp:66-89 */
   void a_cal(double *aaa) override;                                   /* :91-101 */
@@ -48,15 +45,13 @@ class PPPMConpHip : public PPPM, public KSpaceModule {
   void make_rho() override;
   /* the density the make_rho override (:434-450) hands to PPPM::compute: electrolyte brick + electrode brick, [nz][ny][nx] */
   void total_density(double *density_brick);
-  conp_fix *handle() { return h; }
+  conp_fix *handle() { return ph.h; }
 
  private:
-  conp_fix *h;
-  bool first, bcal_done = false;
+  conp_glue::ProviderHandle ph;      /* destroys the handle with the style */
+  conp_glue::AtomView av;
+  bool bcal_done = false;
   std::vector<double> dens;
-  std::vector<int> echeck, lib_tag2eleall, nolist, sel;
-  std::vector<double> xflat, cutsq0;
-  void fail_if(int status);
   conp_atoms view();
 };
 
