@@ -34,9 +34,17 @@ cases = [("dilute", "ffield", (), "conp", None), ("il_onelayer", "ffield", (), "
 # a mid-size synthetic box whose planar vectors fill several bands of FIVE row fragments (straddling the plan's row tiles), projecting
 # mode + the structure-factor getter's two-slot partial tiles, symmetric solve with Ne not a multiple of its tile
 cases.append(("synthetic", "ffield", (), "conp", None))
+# the same electrode, rough, in a tall slab box: the general A kernel at a ragged last tile (Rp, Tz and zclass are read up to ne_pad),
+# its four-way kz split and two kz column tiles
+cases.append(("synthetic_rough_tall", "slab", (), "conp", None))
 for deck, mode, extra, style, mesh in cases:
-    if deck == "synthetic":
-        s = systems.synthetic_fast(n_cells_x=22, n_cells_y=13, lz=120.0, n_elyte=2048, cutoff=10.0, accuracy_relative=1e-5, g_ewald=0.30)
+    if deck.startswith("synthetic"):
+        s = systems.synthetic_fast(n_cells_x=22, n_cells_y=13, lz=400.0 if "tall" in deck else 120.0, n_elyte=2048, cutoff=10.0,
+                                   accuracy_relative=1e-5, g_ewald=0.30, mode=mode)
+        if "rough" in deck:
+            ele = s.echeck != 0
+            s.x[ele, 2] += np.random.default_rng(4).uniform(-0.05, 0.05, size=int(ele.sum()))
+            assert len(np.unique(s.x[ele, 2])) > 2000
     else:
         s = systems.deck(deck, mode, etypes=(deck != "dilute"), shuffle_seed=3)
     at, alist, blist = neighbor.build_lists(s)

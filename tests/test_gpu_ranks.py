@@ -1,7 +1,9 @@
 """-m gpu: several ranks.  (1) spatially decomposed atoms with the conp_comm callbacks (the LAMMPS-MPI route; here two / three
 processes share cuda:0 and the callbacks run on torch.distributed gloo) against the one-rank result; (2) the RCCL data plane
 inside the library -- a one-rank communicator exercises every RCCL call site (all-reduce of b and of the sharded A build,
-in-place all-gather of q, row-sharded S and its re-assembly) on the one GPU this box has; several GPUs are the driver's bench."""
+in-place all-gather of q, row-sharded S and its re-assembly) on the one GPU this box has; several GPUs are the driver's bench;
+(3) the sharded A build on decks with 28 and 210 tiles, two and three ranks.  Out of scope: the by_range real-space split of a_cal
+(setup_sharded && !decomposed) exists only under a multi-rank RCCL communicator, which one GPU cannot form."""
 import os
 import sys
 
@@ -152,6 +154,112 @@ def test_decomposed_ranks_match_one_rank(name, axis, world, solver):
         for r in range(world):
             assert np.array_equal(out[r]["eleall2tag"], out[0]["eleall2tag"])
             assert rel_err(out[r]["S"], S1[np.ix_(perm, perm)]) < 1e-8
+
+
+def _make_tiled(name):
+    """decks whose electrode spans many 128 x 128 tiles, so that the cyclic dealing gives every rank several"""
+    import dataclasses
+    from test_gpu_parity import rough
+    base = name.replace("_newton", "")
+    s = {"il_onelayer_ffield": lambda: systems.deck("il_onelayer", "ffield"),                       # 832 atoms: 28 tiles, z-class kernel
+         "il_onelayer_rough": lambda: rough(systems.deck("il_onelayer", "ffield")),                 # general kernel + nsplit
+         "cond2_ffield": lambda: systems.deck("cond2", "ffield")}[base]()          # 2496 atoms: 210 tiles, 52 z values -> general kernel
+    return dataclasses.replace(s, newton=True) if name.endswith("_newton") else s
+
+
+def _tiled_worker(rank, world, port, name, axis, out):
+    import torch.distributed as dist
+    sys.path.insert(0, os.path.join(ROOT, "lammps-user-conp2_amd"))
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    s = _make_tiled(name)
+    at, alist, blist = neighbor.build_lists_decomposed(s, world, axis=axis)[rank]
+    fx = FixConp(s, device=0, rank=rank, nranks=world)
+    fx.set_comm_torch()
+    fx.init_lists(alist, blist)
+    fx.setup_post_neighbor(at)
+    fx.a_cal(at)                                # tiles rank, rank + world, ...; diagonal and slab term on rank 0; all-reduce inside
+    A = fx.matrix()
+    nzc = fx.info().n_zclasses
+    fx.close()
+    # (a handle whose A was built by hand has left the setup stage: the hooks run on a fresh one, all ranks in step)
+    fx = FixConp(s, device=0, rank=rank, nranks=world)
+    fx.set_comm_torch()
+    fx.init_lists(alist, blist)
+    fx.setup_post_neighbor(at)
+    fx.setup_pre_force(at, 0, s.potdiff)
+    at.q[at.echeck == 0] *= 1.25
+    fx.pre_force(at, 1, 0.4)
+    q = {int(t): float(v) for t, v, e in zip(at.tag[:at.nlocal], at.q[:at.nlocal], at.echeck[:at.nlocal]) if e}
+    out[rank] = dict(A=A, q=q, sc=fx.compute_scalar(), eleall2tag=fx.maps()["eleall2tag"].copy(), elenum=fx.info().elenum, nzc=nzc)
+    fx.close()
+    dist.destroy_process_group()
+
+
+# (the third case splits along z in three: the middle rank holds electrolyte only -- it owns no electrode atom and no real-space
+# row, and still builds its share of the k-space tiles)
+@pytest.mark.parametrize("name,axis,world,nzc,tiles,every_rank_owns_electrode", [
+    ("il_onelayer_ffield", 0, 2, 2, 28, True), ("il_onelayer_ffield", 2, 3, 2, 28, False), ("il_onelayer_rough", 1, 3, 0, 28, True),
+    ("cond2_ffield", 0, 2, 52, 210, True), ("il_onelayer_ffield_newton", 0, 2, 2, 28, True)],
+    ids=["il_onelayer-x2", "il_onelayer-z3_middle_rank_without_electrode_atoms", "il_onelayer_rough-y3", "cond2-x2",
+         "il_onelayer_newton-x2"])
+def test_sharded_a_build_with_several_tiles_per_rank(name, axis, world, nzc, tiles, every_rank_owns_electrode):
+    """setup_sharded(): the lower-triangle tiles of A dealt cyclically to 2 / 3 ranks (tile_first = rank, tile_stride = nranks),
+    diagonal and slab term on rank 0 only, real-space rows by owner, the partial matrices summed through conp_comm -- on decks with
+    28 and 210 tiles, where every rank really gets several.  Every element is written by one rank's tile and at most one rank's
+    real-space row, so each rank's A must be the one-rank A (permuted by tag) to rounding of the row sums: 1e-11 of the largest
+    entry (TOL_A); then the setup is finished and one update made: charges and scalar to 1e-9 as in the test above.
+    Not covered: the by_range real-space split (setup_sharded && !decomposed) only exists under a multi-rank RCCL communicator,
+    which one GPU cannot form."""
+    import torch.multiprocessing as mp
+    s = _make_tiled(name)
+    at, alist, blist = neighbor.build_lists(s)
+    fx = FixConp(s)
+    fx.init_lists(alist, blist)
+    fx.setup_post_neighbor(at)
+    fx.a_cal(at)
+    A1 = fx.matrix()
+    ne = A1.shape[0]
+    nb = (ne + 127) // 128
+    assert fx.info().n_zclasses == nzc and nb * (nb + 1) // 2 == tiles and tiles >= 4 * world
+    fx.close()
+    fx = FixConp(s)
+    fx.init_lists(alist, blist)
+    fx.setup_post_neighbor(at)
+    fx.setup_pre_force(at, 0, s.potdiff)
+    at.q[at.echeck == 0] *= 1.25
+    fx.pre_force(at, 1, 0.4)
+    ele = at.echeck[:at.nlocal] != 0
+    q1 = {int(t): float(q) for t, q in zip(at.tag[:at.nlocal][ele], at.q[:at.nlocal][ele])}
+    sc1 = fx.compute_scalar()
+    tags1 = fx.maps()["eleall2tag"]
+    fx.close()
+    mgr = mp.Manager(); out = mgr.dict()
+    port = 29300 + (os.getpid() + 7 * axis + world) % 250
+    mp.spawn(_tiled_worker, args=(world, port, name, axis, out), nprocs=world, join=True)
+    res = [out[r] for r in range(world)]
+    owns = [o["elenum"] for o in res]
+    assert sum(owns) == ne
+    if every_rank_owns_electrode:
+        assert min(owns) > 0, owns
+    else:
+        assert owns[1] == 0 and owns[0] > 0 and owns[2] > 0, owns
+    pos1 = {int(t): i for i, t in enumerate(tags1)}
+    perm = np.array([pos1[int(t)] for t in res[0]["eleall2tag"]])
+    A_ref = A1[np.ix_(perm, perm)]
+    allq = {}
+    for r, o in enumerate(res):
+        assert np.array_equal(o["eleall2tag"], res[0]["eleall2tag"]) and o["nzc"] == nzc
+        e_a = rel_err(o["A"], A_ref)
+        print(f"{name} axis {axis} world {world} rank {r}: owns {o['elenum']} electrode atoms, A vs one rank {e_a:.2e} of max")
+        assert e_a < 1e-11
+        assert np.array_equal(o["A"], o["A"].T)
+        assert o["sc"] == pytest.approx(sc1, rel=1e-9, abs=1e-12)
+        assert not (set(o["q"]) & set(allq))
+        allq.update(o["q"])
+    assert sorted(allq) == sorted(q1)
+    scale = max(abs(v) for v in q1.values())
+    assert max(abs(allq[t] - q1[t]) for t in q1) < 1e-9 * scale
 
 
 def _rccl_worker(rank, world, port, out):
