@@ -242,6 +242,31 @@ int conp_ewald_compute(conp_fix *fix, const conp_atoms *atoms);
 int conp_ewald_compute_group_potential(conp_fix *fix, const conp_atoms *atoms, const int *sel /*[nlocal]*/, double *recv /*[nlocal]*/);
 int conp_ewald_compute_particle_potential(conp_fix *fix, const conp_atoms *atoms, int i, double *u);
 
+/* ---- Ewald reciprocal-space forces, energy, virial: what a KSpace style's compute() does after the charge update -------------
+ * The textbook Ewald sum over the handle's own half list (conp_fix_get_ktables; ug_k = 4 pi / V exp(-k^2 / 4 g^2) / k^2, V with the
+ * slab factor), at the positions and charges of `atoms`; S_k as above, qs = env.qqrd2e, g = env.g_ewald, Q = sum q, Q2 = sum q^2,
+ * M = sum q z, M2 = sum q z^2 over all ranks' owned atoms:
+ *   f_i   += qs q_i sum_k 2 ug_k k [sin(k r_i) Re S_k - cos(k r_i) Im S_k]                        (accumulated, like atom->f)
+ *   energy = qs [sum_k ug_k |S_k|^2 - g Q2 / sqrt(pi) - (pi / 2) Q^2 / (g^2 V)]
+ *   virial = qs sum_k ug_k |S_k|^2 (delta_ab - 2 (1 / k^2 + 1 / (4 g^2)) k_a k_b)                 (xx, yy, zz, xy, xz, yz)
+ *   eatom_i = qs [-q_i u_i / 2 - (pi / 2) q_i Q / (g^2 V)]                                        (sum_i eatom_i = energy)
+ * With env.slabflag (L = zprd slab_volfactor): energy += qs 2 pi (M^2 - Q M2 - Q^2 L^2 / 12) / V,
+ * f_iz += qs (-4 pi / V) q_i (M - Q z_i), eatom_i += qs (2 pi / V) q_i (z_i M - (M2 + Q z_i^2) / 2 - Q L^2 / 12).
+ * Uses the cached S if a collective entry formed it since the last update, else forms it (the cache is valid afterwards).
+ * The cached S is that of the x and q the collective entry saw and is valid for exactly those: only an update (b_cal), a
+ * re-neighbouring, set_matrix or new k tables drop it -- a pre_force that skips its update (everynum > 1) does not, nor does a call
+ * with moved atoms or changed charges, which would contract the old S with the new phases and return CONP_OK.  A caller whose atoms
+ * may have changed since S was formed (a KSpace style's compute() on every MD or minimizer step) calls conp_ewald_compute(fix, atoms)
+ * first: that forms S of the atoms it is given, unconditionally.
+ * COLLECTIVE with decomposed ranks (S unless cached, and the four sums, through conp_comm.allreduce_sum): every rank returns the
+ * same global energy and virial, and the forces and eatom of its owned atoms.  A replicated-atom handle computes locally.
+ * Zero-charge atoms: f untouched, eatom 0.  Any output may be NULL.  On a `pppm` handle: CONP_ERR_STATE. */
+int conp_ewald_compute_forces(conp_fix *fix, const conp_atoms *atoms,
+                              double *f      /* [nlocal][3], accumulated; NULL: none */,
+                              double *energy /* 1, NULL ok */,
+                              double *virial /* [6], NULL ok */,
+                              double *eatom  /* [nlocal], overwritten, NULL ok */);
+
 /* ---- `compute potential/atom` (compute_potential_atom.cpp:120-345), SURVEY 8f-4 --------------------------------------------
  * per-atom electrostatic potential in volts: pair part over the pair style's half list (:223-308, optional Gaussian `eta`
  * correction for atoms with etasel != 0 = eta_check :313-318), k-space part through the PPPM provider (:165-175 -> the

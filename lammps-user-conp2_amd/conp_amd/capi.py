@@ -98,6 +98,7 @@ SYMBOLS = [
     "conp_pppm_make_rho", "conp_pppm_compute_group_potential", "conp_pppm_compute_particle_potential",
     "conp_pppm_keep_density", "conp_pppm_compute",
     "conp_ewald_compute", "conp_ewald_compute_group_potential", "conp_ewald_compute_particle_potential",
+    "conp_ewald_compute_forces",
     "conp_compute_potential_atom",
 ]
 
@@ -213,6 +214,7 @@ def load_library():
     lib.conp_ewald_compute.argtypes = [vp, C.POINTER(conp_atoms)]
     lib.conp_ewald_compute_group_potential.argtypes = [vp, C.POINTER(conp_atoms), ip, dp]
     lib.conp_ewald_compute_particle_potential.argtypes = [vp, C.POINTER(conp_atoms), C.c_int, dp]
+    lib.conp_ewald_compute_forces.argtypes = [vp, C.POINTER(conp_atoms), dp, dp, dp, dp]
     lib.conp_compute_potential_atom.argtypes = [vp, C.POINTER(conp_atoms), C.POINTER(conp_neighlist), ip, ip,
                                                 C.POINTER(conp_potential_args), dp]
     lib.conp_fix_set_comm.argtypes = [vp, C.POINTER(conp_comm)]
@@ -483,6 +485,19 @@ class FixConp:
         u = C.c_double()
         self._check(self.lib.conp_ewald_compute_particle_potential(self.h, C.byref(self.atoms_view(at)), int(i), C.byref(u)))
         return u.value
+
+    def ewald_forces(self, at, energy=True, virial=True, eatom=False, f=None):
+        """collective under decomposed ranks: reciprocal-space forces [nlocal][3] (added to `f`, zeros by default), energy, virial
+        (xx, yy, zz, xy, xz, yz) and per-atom energies of the owned atoms -> (f, E, W, e); what was not asked for is None"""
+        f = np.zeros((at.nlocal, 3)) if f is None else f
+        assert f.dtype == np.float64 and f.flags.c_contiguous and f.shape == (at.nlocal, 3)
+        en = C.c_double() if energy else None
+        w = np.zeros(6) if virial else None
+        e = np.zeros(at.nlocal) if eatom else None
+        self._check(self.lib.conp_ewald_compute_forces(self.h, C.byref(self.atoms_view(at)), _dptr(f),
+                                                       C.byref(en) if energy else None, _dptr(w) if virial else None,
+                                                       _dptr(e) if eatom else None))
+        return f, (en.value if energy else None), w, e
 
     def compute_potential_atom(self, at, pairlist, sel, etasel=None, eta=0.0, pair=True, kspace=True, qsum=True):
         sel = np.ascontiguousarray(sel, np.int32)

@@ -307,6 +307,8 @@ struct conp_fix {
   long ew_tables_gen = -1;
   std::vector<double> ew_u_h;
   DevBuf<double> d_ew_G, d_ew_Gp, d_ew_Gwf, d_ew_x, d_ew_q, d_ew_seeds, d_ew_Rp, d_ew_Tz, d_ew_bk, d_ew_g, d_ew_u;
+  DevBuf<double> d_ew_kv, d_ew_ev, d_ew_f, d_ew_e;      // conp_ewald_compute_forces: (ug, k) per listed k, the seven sums, outputs
+  long ew_kv_gen = -1;
   DevBuf<double2> d_ew_Xe, d_ew_Ye;
   DevBuf<int> d_ew_idx, d_ew_ctptr;
   DevBuf<SkTile> d_ew_tiles;
@@ -3336,6 +3338,91 @@ void ewald_project(conp_fix *f, const conp_atoms *at, const std::vector<int> &id
   f->sync();
   for (int i : idx) { if (g) g[i] = hg[i]; if (u) u[i] = hu[i]; }
 }
+// ---- exact Ewald forces, energy, virial ----
+// f_i += qqrd2e q_i grad g_i (+ slab) on every charged owned atom, from d_ew_Gwf at the atoms' positions in `at`: ewald_project's
+// blocking with ew_force_kernel in b_project_kernel's place; energy and virial from d_ew_G.  The sums of q, q^2, q z, q z^2 over the
+// owned atoms are all-reduced under decomposed ranks (COLLECTIVE there); S itself is the caller's business (ew_g_valid).
+void ewald_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy, double *virial, double *eatom) {
+  const double MY_PI = 3.14159265358979323846, MY_PIS = 1.77245385090551602729;
+  const KTables &kt = f->kt;
+  const double g = f->env.g_ewald, qs = f->env.qqrd2e, V = kt.volume;
+  std::vector<int> idx;
+  double four[4] = {0.0, 0.0, 0.0, 0.0};              // Q, Q2, M, M2
+  for (int i = 0; i < at->nlocal; ++i) {
+    const double q = at->q[i], z = at->x[3 * (size_t)i + 2];
+    if (q == 0) continue;
+    idx.push_back(i);
+    four[0] += q; four[1] += q * q; four[2] += q * z; four[3] += q * z * z;
+  }
+  if (f->decomposed) f->rc.sum(four, 4);
+  const double Q = four[0], Q2 = four[1], M = four[2], M2 = four[3];
+  const double L = f->env.zprd * f->env.slab_volfactor;
+  if (energy || virial) {
+    const int K = kt.kcount;
+    if (f->ew_kv_gen != f->plan_gen) {
+      std::vector<double> kv((size_t)4 * K);
+      for (int k = 0; k < K; ++k) {
+        kv[k] = kt.ug[k];
+        kv[(size_t)K + k] = kt.unitk[0] * kt.kxvecs[k]; kv[2 * (size_t)K + k] = kt.unitk[1] * kt.kyvecs[k];
+        kv[3 * (size_t)K + k] = kt.unitk[2] * kt.kzvecs[k];
+      }
+      f->d_ew_kv.upload(kv, f->stream);
+      f->sync();                     // (kv goes out of scope)
+      f->ew_kv_gen = f->plan_gen;
+    }
+    const int nwg = ew_energy_virial_workgroups(K);
+    f->d_ew_ev.reserve((size_t)7 * (nwg + 1));
+    launch_ew_energy_virial(f->stream, K, f->plan.C_pad, KPlan::PT, f->d_sf_row_a.p, f->d_sf_col_c.p, f->d_k_sign.p, f->d_ew_kv.p, g,
+                            f->d_ew_G.p, f->d_ew_ev.p + 7, f->d_ew_ev.p);
+    double s7[7];
+    HIP_TRY(hipMemcpyAsync(s7, f->d_ew_ev.p, 7 * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(hipGetLastError());
+    f->sync();
+    if (energy) {
+      double e = s7[0] - g * Q2 / MY_PIS - 0.5 * MY_PI * Q * Q / (g * g * V);
+      if (f->env.slabflag) e += 2.0 * MY_PI * (M * M - Q * M2 - Q * Q * L * L / 12.0) / V;
+      *energy = qs * e;
+    }
+    if (virial) for (int c = 0; c < 6; ++c) virial[c] = qs * s7[1 + c];
+  }
+  if (eatom) std::fill(eatom, eatom + at->nlocal, 0.0);
+  const int n = (int)idx.size();
+  if (n == 0 || (!fout && !eatom)) return;
+  const int nb_pad = ew_block(f, n);
+  const int ntot = (n + nb_pad - 1) / nb_pad * nb_pad;
+  std::vector<double> xs(3 * (size_t)ntot, 0.0), qv(ntot, 0.0);
+  for (int k = 0; k < n; ++k) {
+    const int i = idx[k];
+    for (int c = 0; c < 3; ++c) xs[3 * (size_t)k + c] = at->x[3 * (size_t)i + c];
+    qv[k] = at->q[i];
+  }
+  ew_reserve(f, nb_pad);
+  f->d_ew_x.upload(xs, f->stream); f->d_ew_q.upload(qv, f->stream); f->d_ew_idx.upload(idx, f->stream);
+  f->d_ew_tiles.upload(f->tiles_h, f->stream); f->d_ew_ctptr.upload(f->ct_ptr_h, f->stream);
+  f->d_ew_bk.reserve((size_t)16 * nb_pad);
+  f->d_ew_f.reserve(3 * (size_t)at->nlocal); f->d_ew_e.reserve(at->nlocal);
+  EwForceOut o{};
+  o.qs = qs; o.selfc = 2.0 * g / MY_PIS; o.ecoef = 0.5 * MY_PI * Q / (g * g * V);
+  o.slab = f->env.slabflag ? 1 : 0;
+  o.fz_pref = -4.0 * MY_PI / V; o.e_pref = 2.0 * MY_PI / V; o.M = M; o.M2 = M2; o.Q = Q; o.L2_12 = L * L / 12.0;
+  for (int b0 = 0; b0 < n; b0 += nb_pad) {
+    const int nb = std::min(nb_pad, n - b0);
+    ew_tables(f, b0, nb, nb_pad);
+    launch_ew_force(f->stream, f->dplan, f->plan.kzt, kt.unitk[0], kt.unitk[1], kt.unitk[2], nb_pad, f->d_ew_ctptr.p, f->d_ew_tiles.p,
+                    f->d_ew_Gwf.p, f->d_ew_Rp.p, f->d_ew_Tz.p, f->d_ew_bk.p);
+    launch_ew_force_out(f->stream, nb, nb_pad, f->d_ew_bk.p, f->d_ew_idx.p + b0, f->d_ew_q.p + b0, f->d_ew_x.p + 3 * (size_t)b0, o,
+                        f->d_ew_f.p, f->d_ew_e.p);
+  }
+  std::vector<double> hf(3 * (size_t)at->nlocal), he(at->nlocal);
+  HIP_TRY(hipMemcpyAsync(hf.data(), f->d_ew_f.p, hf.size() * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipMemcpyAsync(he.data(), f->d_ew_e.p, he.size() * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(hipGetLastError());
+  f->sync();
+  for (int i : idx) {
+    if (fout) for (int c = 0; c < 3; ++c) fout[3 * (size_t)i + c] += hf[3 * (size_t)i + c];
+    if (eatom) eatom[i] = he[i];
+  }
+}
 // the k-space tail of compute potential/atom (compute_potential_atom.cpp:165-175, slab correction :323-345) on the selected owned
 // atoms idx (ascending), whichever provider formed u_i: pot_i -= u_i, + the Gaussian self term of eta atoms, + the slab terms
 // (the sums of q z and q over the owned atoms all-reduced, MPI_Allreduce :331, :337)
@@ -3527,6 +3614,19 @@ int conp_ewald_compute_particle_potential(conp_fix *f, const conp_atoms *at, int
     f->ew_u_valid = true;
   }
   *u = f->ew_u_h[i];
+  CONP_GUARD_END
+}
+
+// Reciprocal-space forces, energy, virial and per-atom energy of all owned atoms at the charges of the call -- what a KSpace style's
+// compute() leaves in atom->f, energy, virial, eatom.  COLLECTIVE under decomposed ranks (S unless cached; always the four sums).
+int conp_ewald_compute_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy, double *virial, double *eatom) {
+  CONP_GUARD_BEGIN
+  if (!f || !at) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->drop_graph();
+  need_ewald(f);
+  if (!f->ew_g_valid) ewald_structure_factor(f, at);
+  else if (at->nlocal + at->nghost != f->nall) throw ConpError(CONP_ERR_STATE, "atom count changed without post_neighbor");
+  ewald_forces(f, at, fout, energy, virial, eatom);
   CONP_GUARD_END
 }
 

@@ -1,6 +1,8 @@
 // Launch wrappers of the gfx950 kernels (conp_kernels.hip).  All pointers are device pointers unless noted.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
+#include <cstddef>
 #include <cstdint>
 #include "../../include/conp_hip.h"      // CONP_PATH_* (the test hooks of the C ABI)
 
@@ -13,6 +15,23 @@ namespace conp {
 bool path_on(unsigned bit);
 int debug_sk_workgroups();
 const char *env_knob(const char *name);      // operational knob: getenv + one line on stderr the first time a set knob is read
+
+// raise a kernel's dynamic-LDS limit, only when a launch needs more than it was last given: per-update launches must not
+// pay a runtime call each (the decks' updates are bound by host launch cost)
+// The attribute is per device: the cache is indexed by the calling thread's current device (handles on several GPUs in one
+// process are supported, conp_env.device), and atomic because hosts may drive handles from different threads (a lost race
+// only sets the attribute twice).
+struct DynLdsCache { std::atomic<size_t> granted[64]; };
+template <typename K>
+void ensure_dyn_lds(K kernel, size_t bytes, DynLdsCache &cache) {
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  std::atomic<size_t> &g = cache.granted[dev & 63];
+  if (bytes <= g.load(std::memory_order_relaxed)) return;
+  // a refusal is not remembered: the launch that follows fails and the caller's hipGetLastError reports it
+  if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess)
+    g.store(bytes, std::memory_order_relaxed);
+}
 
 struct DevPlan {              // device copy of KPlan geometry
   int np, nz, n_row_tiles, n_col_tiles, R_pad, C_pad, kxmax, kymax;
@@ -128,6 +147,24 @@ void launch_ew_sk_sum(hipStream_t s, const DevPlan &pl, int nsplit, const double
 void launch_ew_gw(hipStream_t s, const DevPlan &pl, const double *G, double *Gwf /*w o G, b_project_kernel's order*/);
 void launch_ew_out(hipStream_t s, int n, int nb_pad, const double *bk /*[4][nb_pad]*/, const int *idx, const double *q, double selfc,
                    double *g_out /*indexed by atom*/, double *u_out);
+
+// exact Ewald forces, energy and virial (conp_ewald_compute_forces)
+// out: [4 quantities: g, dg/dx, dg/dy, dg/dz][4 parts][nb_pad], the parts to be added as (p0 + p1) + (p2 + p3)
+void launch_ew_force(hipStream_t s, const DevPlan &pl, int kzt, double ux, double uy, double uz, int nb_pad, const int *ct_ptr,
+                     const SkTile *tiles, const double *Gwf, const double *Rp, const double *Tz, double *out);
+int ew_energy_virial_workgroups(int K);
+// sums[7] = sum_k ug |S_k|^2 and the six virial sums (xx, yy, zz, xy, xz, yz), without qqrd2e.  kv: [4][K] = ug, kx, ky, kz of the
+// reference's k list; part: [ew_energy_virial_workgroups(K)][7] scratch
+void launch_ew_energy_virial(hipStream_t s, int K, int C_pad, int PT, const int *sf_row_a, const int *sf_col_c, const int *k_sign,
+                             const double *kv, double g_ewald, const double *G, double *part, double *sums);
+struct EwForceOut {
+  double qs, selfc, ecoef /*(pi / 2) Q / (g^2 V)*/;
+  int slab;
+  double fz_pref /*-4 pi / V*/, e_pref /*2 pi / V*/, M, M2, Q, L2_12 /*L^2 / 12*/;
+};
+void launch_ew_force_out(hipStream_t s, int n, int nb_pad, const double *bk /*[4][4][nb_pad]*/, const int *idx, const double *q,
+                         const double *x /*[n][3]*/, const EwForceOut &o, double *fo /*[nlocal][3], written at idx*/,
+                         double *eo /*[nlocal]*/);
 
 // ---- the z-window form of the structure-factor contraction (conp_zn.hip, round 5) ------------------------------------------------
 // item = (row tile: 64 planar vectors, chunk range [c0, c1) of the z-ordered electrolyte list, window origin g0 on the grid, slot of

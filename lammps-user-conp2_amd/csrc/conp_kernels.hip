@@ -254,22 +254,7 @@ void launch_elyte_phase(hipStream_t s, int nl, int nl_pad, const int *elyte_idx,
 //    build first, multiply second).  Partial tiles go to part[segment] in fragment-major order (sk_part_off); sk_reduce sums a
 //    tile's segments in a fixed order (deterministic).
 // ================================================================================================
-// raise a kernel's dynamic-LDS limit, only when a launch needs more than it was last given: per-update launches must not
-// pay a runtime call each (the decks' updates are bound by host launch cost)
-// The attribute is per device: the cache is indexed by the calling thread's current device (handles on several GPUs in one
-// process are supported, conp_env.device), and atomic because hosts may drive handles from different threads (a lost race
-// only sets the attribute twice).
-struct DynLdsCache { std::atomic<size_t> granted[64]; };
-template <typename K>
-static void ensure_dyn_lds(K kernel, size_t bytes, DynLdsCache &cache) {
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  std::atomic<size_t> &g = cache.granted[dev & 63];
-  if (bytes <= g.load(std::memory_order_relaxed)) return;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  g.store(bytes, std::memory_order_relaxed);
-}
-
+// (the dynamic-LDS limit of a kernel: ensure_dyn_lds, conp_kernels.h)
 constexpr int SK_J = 16;
 // LDS operand panel: panel[feature][16 atoms], NO padding -- the atom column is XOR-swizzled with the low four bits of the
 // feature index: element (feature, atom j) lives at feature * 16 + (j ^ (feature & 15)).  An MFMA fragment read (16 consecutive

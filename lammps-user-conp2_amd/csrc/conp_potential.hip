@@ -9,7 +9,10 @@
 // 1e-11 of the potential, not bit parity with libm).  Sources: ew_sk_kernel adds Rp diag(q) Tz^T of the block into split slices of
 // G on the matrix cores; ew_sk_sum_kernel adds the slices in a fixed order.  Targets: b_project_kernel (conp_kernels.hip) with w o G;
 // ew_out_kernel adds its four parts and scatters g_i, u_i to the atoms' local indices.
+// The reciprocal-space forces, energy and virial (conp_ewald_compute_forces) are the same projection with its
+// derivatives: ew_force_kernel, ew_energy_virial_kernel, ew_force_out_kernel below.
 #include "conp_kernels.h"
+#include <algorithm>
 
 namespace conp {
 
@@ -117,6 +120,205 @@ __global__ __launch_bounds__(256) void ew_out_kernel(int n, int nb_pad, const do
   u_out[idx[i]] = g + selfc * q[i];
 }
 
+// ---- exact Ewald forces, energy and virial (conp_ewald_compute_forces) ---------------------------------------
+// At fixed S the force on atom i is qqrd2e q_i grad g_i: the gradient of b_project_kernel's bilinear form through the atom's own
+// phase columns.  d/dx and d/dy act on Rp (d cos theta = -k sin theta, d sin theta = k cos theta: a row's derivative is its (a, b)
+// partner row -- 64 rows away in the row tile -- times -+ k_x or k_y of the planar vector); d/dz acts on Tz (a column's derivative is
+// its (c, s) partner column -- 8 columns away in the 16-column fragment -- times -+ k_z of the column):
+//     H  = (w G) Tz          g     = - sum_r Rp[r] H[r]
+//     Hz = (w G) dTz/dz      dg/dz = - sum_r Rp[r] Hz[r]
+//     dg/dx = - sum_r s_r kx_r Rp[r ^ 64] H[r]   (s_r = -1 on 'a' rows, +1 on 'b' rows), dg/dy likewise with ky_r = sgn ky
+// ew_force_kernel is b_project_kernel with a second accumulator set: the (w G) fragments are read once and feed both products; the
+// B operands of Hz are the staged Tz values of the partner k-step (k-step i ^ 2 of a group of eight: 4 columns per k-step), scaled
+// in registers.  Units and parts are b_project_kernel's; the two accumulator sets and the sixteen running sums of a lane take twice
+// its registers, so a workgroup is 8 waves (256 registers each) where b_project_kernel has 16: a part's units are dealt to 8 waves.
+// out[(4 quantity + part) ne_pad + i], quantity = g, dg/dx, dg/dy, dg/dz
+__global__ __launch_bounds__(512) void ew_force_kernel(int C_pad, int ne_pad, int n_col_tiles, int kzt, double ux, double uy, double uz,
+                                                        const int *__restrict__ ct_ptr, const SkTile *__restrict__ tiles,
+                                                        const int *__restrict__ p_ikx, const int *__restrict__ p_iky,
+                                                        const int *__restrict__ p_sgn, const double *__restrict__ Gwf,
+                                                        const double *__restrict__ Rp, const double *__restrict__ Tz,
+                                                        double *__restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  double *tz = reinterpret_cast<double *>(smem);          // [4 atom fragments][160 columns][16 atoms]
+  double *red = tz + 4 * 160 * 16;                         // [4 quantities][8 waves][64]
+  const int part = blockIdx.y;
+  const int i0 = blockIdx.x * 64;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int fr = lane & 15, fk = lane >> 4;
+  double psum[4][4];
+#pragma unroll
+  for (int v = 0; v < 4; ++v)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) psum[v][c] = 0.0;
+  for (int ct = 0; ct < n_col_tiles; ++ct) {
+    const int tb = ct_ptr[ct], te = ct_ptr[ct + 1];
+    if (te <= tb) continue;
+    int nba_max = 0;
+    for (int k = tb; k < te; ++k) nba_max = tiles[k].nba > nba_max ? tiles[k].nba : nba_max;
+    for (int h = 0; h < 2; ++h) {                        // columns [160 h, 160 h + 160) of the tile = k-steps [40 h, 40 h + 40)
+      if (40 * h >= 8 * nba_max) break;
+      __syncthreads();
+      for (int e = t; e < 160 * 64; e += 512) {
+        const int col = e >> 6, a = e & 63;
+        tz[((a >> 4) * 160 + col) * 16 + (a & 15)] = Tz[(size_t)(ct * 320 + 160 * h + col) * ne_pad + i0 + a];
+      }
+      __syncthreads();
+      const int nu = 8 * (te - tb);
+      for (int u = part + 4 * wave; u < nu; u += 32) {
+        const SkTile tl = tiles[tb + (u >> 3)];
+        const int rf = tl.rt * 8 + (u & 7);
+        const int ks0 = 40 * h, ks1 = 8 * tl.nba < 40 * (h + 1) ? 8 * tl.nba : 40 * (h + 1);
+        if (ks1 <= ks0) continue;
+        d4 acc[4], accz[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { acc[c] = (d4){0.0, 0.0, 0.0, 0.0}; accz[c] = (d4){0.0, 0.0, 0.0, 0.0}; }
+        const double *ap = Gwf + ((size_t)rf * (C_pad / 4) + (size_t)ct * 80) * 64 + lane;
+        const double *bp = tz + fk * 16 + fr;
+        double an[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) an[i] = ap[(size_t)(ks0 + i) * 64];
+#pragma unroll 1
+        for (int tg = ks0; tg < ks1; tg += 8) {
+          double ac[8];
+#pragma unroll
+          for (int i = 0; i < 8; ++i) ac[i] = an[i];
+          if (tg + 8 < ks1) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) an[i] = ap[(size_t)(tg + 8 + i) * 64];
+          }
+          const double *bq = bp + 64 * (tg - ks0);
+          // k-step tg + i holds the tile's columns 4 (tg + i) + fk: fragment 2 (tg / 8) + (i >> 2), cos columns for i & 2 == 0,
+          // kz index (within the fragment) 4 (i & 1) + fk
+          const double kz0 = uz * (double)(ct * kzt + 2 * tg + fk);
+          double b[8][4];
+#pragma unroll
+          for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) b[i][c] = bq[64 * i + c * 160 * 16];
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            const double kz = kz0 + uz * (double)(8 * (i >> 2) + 4 * (i & 1));
+            const double sk = (i & 2) ? kz : -kz;          // d cos = -kz sin, d sin = kz cos
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+              acc[c] = MFMA_F64(ac[i], b[i][c], acc[c]);
+              accz[c] = MFMA_F64(ac[i], sk * b[i ^ 2][c], accz[c]);
+            }
+          }
+        }
+        const bool brow = (u & 4) != 0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = 16 * rf + fk + 4 * r;
+          const int p = 64 * tl.rt + 16 * (u & 3) + fk + 4 * r;
+          const double sg = brow ? 1.0 : -1.0;
+          const double kx = sg * ux * (double)p_ikx[p], ky = sg * uy * (double)(p_sgn[p] * p_iky[p]);
+          const double *rp = Rp + (size_t)row * ne_pad + i0 + fr;
+          const double *rq = Rp + (size_t)(row ^ 64) * ne_pad + i0 + fr;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            const double own = rp[16 * c], oth = rq[16 * c] * acc[c][r];
+            psum[0][c] += own * acc[c][r];
+            psum[1][c] += kx * oth;
+            psum[2][c] += ky * oth;
+            psum[3][c] += own * accz[c][r];
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < 4; ++v)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) { psum[v][c] += __shfl_xor(psum[v][c], 16, 64); psum[v][c] += __shfl_xor(psum[v][c], 32, 64); }
+  __syncthreads();
+  if (lane < 16) {
+#pragma unroll
+    for (int v = 0; v < 4; ++v)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) red[(v * 8 + wave) * 64 + 16 * c + lane] = psum[v][c];
+  }
+  __syncthreads();
+  if (t < 256) {
+    const int v = t >> 6, a = t & 63;
+    double sum = 0.0;
+    for (int w = 0; w < 8; ++w) sum += red[(v * 8 + w) * 64 + a];
+    out[(size_t)(4 * v + part) * ne_pad + i0 + a] = -sum;
+  }
+}
+
+// The seven k-sums of the energy and the virial from G: per listed k (the reference's half list) |S_k|^2 from the four entries
+// sfac_gather_kernel reads, e_k = ug_k |S_k|^2, v_ab = e_k (delta_ab - 2 (1 / k^2 + 1 / (4 g^2)) k_a k_b).  Thread t of workgroup b
+// adds the terms k = 256 b + t, + 256 gridDim.x, ... in that order, the workgroup adds its threads in a binary tree, and the last
+// launch (final = 1, one workgroup) adds the workgroups' rows the same way: a fixed order for a given K.
+// kv: [4][K] = ug, kx, ky, kz.  part: [gridDim.x][7] = sum e, xx, yy, zz, xy, xz, yz
+__global__ __launch_bounds__(256) void ew_energy_virial_kernel(int K, int C_pad, int PT, const int *__restrict__ row_a,
+                                                               const int *__restrict__ col_c, const int *__restrict__ k_sign,
+                                                               const double *__restrict__ kv, double inv4g2, const double *__restrict__ G,
+                                                               const double *__restrict__ in, int nin, double *__restrict__ part,
+                                                               int final) {
+  __shared__ double sh[7][256];
+  const int t = threadIdx.x;
+  double a[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (final) {
+    for (int j = t; j < nin; j += 256)
+#pragma unroll
+      for (int v = 0; v < 7; ++v) a[v] += in[(size_t)j * 7 + v];
+  } else {
+    for (int k = blockIdx.x * 256 + t; k < K; k += 256 * gridDim.x) {
+      const size_t ra = (size_t)row_a[k] * C_pad, rb = (size_t)(row_a[k] + PT) * C_pad;
+      const int cc = col_c[k], cs = col_c[k] + 8;
+      const double CC = G[ra + cc], CS = G[ra + cs], SC = G[rb + cc], SS = G[rb + cs];
+      const double sg = (double)k_sign[k];
+      const double sr = CC - sg * SS, si = SC + sg * CS;
+      const double kx = kv[(size_t)K + k], ky = kv[2 * (size_t)K + k], kz = kv[3 * (size_t)K + k];
+      const double e = kv[k] * (sr * sr + si * si);
+      const double vt = -2.0 * (1.0 / (kx * kx + ky * ky + kz * kz) + inv4g2) * e;
+      a[0] += e;
+      a[1] += e + vt * kx * kx; a[2] += e + vt * ky * ky; a[3] += e + vt * kz * kz;
+      a[4] += vt * kx * ky; a[5] += vt * kx * kz; a[6] += vt * ky * kz;
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < 7; ++v) sh[v][t] = a[v];
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s)
+#pragma unroll
+      for (int v = 0; v < 7; ++v) sh[v][t] += sh[v][t + s];
+    __syncthreads();
+  }
+  if (t < 7) part[(size_t)blockIdx.x * 7 + t] = sh[t][0];
+}
+
+// the four parts of ew_force_kernel's four quantities in b_project's fixed order; force (with the slab term), per-atom energy,
+// scattered to the targets' local indices.  fo: [nlocal][3] and eo: [nlocal], overwritten at idx (the host accumulates)
+__global__ __launch_bounds__(256) void ew_force_out_kernel(int n, int nb_pad, const double *__restrict__ bk, const int *__restrict__ idx,
+                                                           const double *__restrict__ q, const double *__restrict__ x, EwForceOut o,
+                                                           double *__restrict__ fo, double *__restrict__ eo) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double v[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const double *b = bk + (size_t)(4 * c) * nb_pad + i;
+    v[c] = (b[0] + b[(size_t)nb_pad]) + (b[2 * (size_t)nb_pad] + b[3 * (size_t)nb_pad]);
+  }
+  const double qi = q[i], z = x[3 * (size_t)i + 2];
+  double fz = qi * v[3];
+  double e = -0.5 * qi * (v[0] + o.selfc * qi) - o.ecoef * qi;
+  if (o.slab) {
+    fz += o.fz_pref * qi * (o.M - o.Q * z);
+    e += o.e_pref * qi * (z * o.M - 0.5 * (o.M2 + o.Q * z * z) - o.Q * o.L2_12);
+  }
+  const size_t a = (size_t)idx[i];
+  fo[3 * a] = o.qs * (qi * v[1]);
+  fo[3 * a + 1] = o.qs * (qi * v[2]);
+  fo[3 * a + 2] = o.qs * fz;
+  eo[a] = o.qs * e;
+}
+
 void launch_ew_seeds(hipStream_t s, int n, const double *x, double ux, double uy, double uz, double *seeds) {
   if (n <= 0) return;
   hipLaunchKernelGGL(ew_seeds_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, x, ux, uy, uz, seeds);
@@ -143,6 +345,33 @@ void launch_ew_out(hipStream_t s, int n, int nb_pad, const double *bk, const int
                    double *u_out) {
   if (n <= 0) return;
   hipLaunchKernelGGL(ew_out_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, nb_pad, bk, idx, q, selfc, g_out, u_out);
+}
+
+void launch_ew_force(hipStream_t s, const DevPlan &pl, int kzt, double ux, double uy, double uz, int nb_pad, const int *ct_ptr,
+                     const SkTile *tiles, const double *Gwf, const double *Rp, const double *Tz, double *out) {
+  const size_t lds = ((size_t)4 * 160 * 16 + 4 * 8 * 64) * sizeof(double);
+  static DynLdsCache granted{};
+  ensure_dyn_lds(ew_force_kernel, lds, granted);
+  hipLaunchKernelGGL(ew_force_kernel, dim3(nb_pad / 64, 4), dim3(512), lds, s, pl.C_pad, nb_pad, pl.n_col_tiles, kzt, ux, uy, uz, ct_ptr,
+                     tiles, pl.p_ikx, pl.p_iky, pl.p_sgn, Gwf, Rp, Tz, out);
+}
+
+int ew_energy_virial_workgroups(int K) { return std::max(1, std::min(256, (K + 255) / 256)); }
+
+void launch_ew_energy_virial(hipStream_t s, int K, int C_pad, int PT, const int *sf_row_a, const int *sf_col_c, const int *k_sign,
+                             const double *kv, double g_ewald, const double *G, double *part, double *sums) {
+  const int nwg = ew_energy_virial_workgroups(K);
+  const double inv4g2 = 1.0 / (4.0 * g_ewald * g_ewald);
+  hipLaunchKernelGGL(ew_energy_virial_kernel, dim3(nwg), dim3(256), 0, s, K, C_pad, PT, sf_row_a, sf_col_c, k_sign, kv, inv4g2, G,
+                     (const double *)nullptr, 0, part, 0);
+  hipLaunchKernelGGL(ew_energy_virial_kernel, dim3(1), dim3(256), 0, s, K, C_pad, PT, sf_row_a, sf_col_c, k_sign, kv, inv4g2, G,
+                     (const double *)part, nwg, sums, 1);
+}
+
+void launch_ew_force_out(hipStream_t s, int n, int nb_pad, const double *bk, const int *idx, const double *q, const double *x,
+                         const EwForceOut &o, double *fo, double *eo) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(ew_force_out_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, nb_pad, bk, idx, q, x, o, fo, eo);
 }
 
 }  // namespace conp

@@ -6,6 +6,9 @@
 //
 // usage: glue_driver CASEFILE                      one rank, FixConpHip (INTEGRATION.md mode A)
 //        glue_driver CASEFILE compute              mode A, then `compute potential/atom/hip kspace` on the conp/hip fix (Ewald)
+//        glue_driver CASEFILE kspace               mode A with `kspace_style ewald/conp/hip` as force->kspace: on every step, after the
+//                                                  fix's pre_force, compute(eflag, vflag) on the fix's handle; output per step
+//                                                  "kf STEP TAG FX FY FZ", "kea STEP TAG E" per owned atom, "ke STEP ENERGY", "kv STEP W[6]"
 //        glue_driver CASEFILE provider             mode B: the reference's FixConp keeps its loops, only `kspmod` is replaced:
 //                                                  a stand-in for the fix's public members is registered with KSpaceModuleHip
 //                                                  (register_fix, fix_conp.cpp:409) and conp_setup / conp_post_neighbor / a_cal /
@@ -35,6 +38,7 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -43,6 +47,7 @@
 
 #define CONP_GLUE_MOCK 1
 #include "compute_potential_atom_hip.h"
+#include "ewald_conp_hip.h"
 #include "fix_conp_hip.h"
 #include "kspacemodule_hip.h"
 #include "pppm_conp_hip.h"
@@ -64,6 +69,7 @@ struct Out {
 };
 
 // one rank: its own mock LAMMPS instance, atoms and lists from its case file
+static bool g_kspace = false;    // `glue_driver CASEFILE kspace`: EwaldConpHip is the kspace style, compute() on every step
 static bool g_compute = false;   // `glue_driver CASEFILE compute`: after the steps, compute potential/atom/hip on the conp/hip fix
 
 int run_case(const char *path, bool provider, int me, int nprocs, MockCommRank *world, Out &out) {
@@ -72,7 +78,7 @@ int run_case(const char *path, bool provider, int me, int nprocs, MockCommRank *
 
   LAMMPS lmp{};
   Memory memory; Error error; Atom atom{}; Force force{}; Domain domain{}; Update update{}; Comm comm{}; Group group{};
-  Variable variable; Input input{}; Neighbor neighbor{}; Modify modify; KSpace kspace{}; Pair pair{};
+  Variable variable; Input input{}; Neighbor neighbor{}; Modify modify; KSpace kspace(&lmp); Pair pair{};
   lmp.world = world;
   lmp.memory = &memory; lmp.error = &error; lmp.atom = &atom; lmp.force = &force; lmp.domain = &domain; lmp.update = &update;
   lmp.comm = &comm; lmp.group = &group; lmp.input = &input; lmp.neighbor = &neighbor; lmp.modify = &modify;
@@ -300,7 +306,23 @@ int run_case(const char *path, bool provider, int me, int nprocs, MockCommRank *
     return 0;
   }
 
+  // `kspace_style ewald/conp/hip 1e-6` + `kspace_modify gewald G force A slab S`: the style object is force->kspace before any init()
+  // runs, its own init() comes before the fixes' (LAMMPS::init: force->init(), then modify->init()), and FixConpHip::init reads
+  // g_ewald & co. from it
+  std::unique_ptr<EwaldConpHip> ew;
+  if (g_kspace) {
+    ew.reset(new EwaldConpHip(&lmp));
+    char acc[] = "1e-6";
+    char *sargv[1] = {acc};
+    ew->settings(1, sargv);
+    ew->g_ewald = kspace.g_ewald; ew->accuracy_absolute = kspace.accuracy; ew->two_charge_force = force.qqr2e;
+    ew->slab_volfactor = kspace.slab_volfactor; ew->slabflag = kspace.slabflag; ew->energy = 0.0;
+    force.kspace = ew.get();
+    ew->init();
+  }
   FixConpHip fix(&lmp, narg, fargv.data());
+  Fix *fixes[1] = {&fix};
+  if (g_kspace) { modify.fix = fixes; modify.nfix = 1; atom.nmax = std::max(atom.nmax, nall); }
   for (auto &ml : modify_lines) {                    // fix_modify arrives before init(), as in an input script
     std::vector<char *> margv;
     for (auto &t : ml) margv.push_back(const_cast<char *>(t.c_str()));
@@ -335,6 +357,19 @@ int run_case(const char *path, bool provider, int me, int nprocs, MockCommRank *
     } else {
       if (reneigh) { fix.pre_exchange(); fix.post_neighbor(); }      // Verlet::run: pre_exchange ... neighbor->build ... post_neighbor
       fix.pre_force(0);
+    }
+    if (g_kspace) {
+      // what Verlet does after the fixes' pre_force, on EVERY step, whether or not the fix updated the charges on it:
+      // force->kspace->compute(eflag, vflag), here with the global and per-atom energy and the global virial; atom->f starts from zero
+      std::fill(fs.begin(), fs.end(), 0.0);
+      ew->compute(3, 1);
+      for (int i = 0; i < nlocal; ++i) {
+        out.f("kf %ld %d %.17g %.17g %.17g\n", ts, tag[i], fs[3 * (size_t)i], fs[3 * (size_t)i + 1], fs[3 * (size_t)i + 2]);
+        out.f("kea %ld %d %.17g\n", ts, tag[i], ew->eatom[i]);
+      }
+      out.f("ke %ld %.17g\n", ts, ew->energy);
+      out.f("kv %ld %.17g %.17g %.17g %.17g %.17g %.17g\n", ts, ew->virial[0], ew->virial[1], ew->virial[2], ew->virial[3], ew->virial[4],
+            ew->virial[5]);
     }
     std::fill(fs.begin(), fs.end(), 0.0);
     if (fix.setmask() & FixConst::POST_FORCE) fix.post_force(0);
@@ -425,6 +460,7 @@ int main(int argc, char **argv) {
   try {
     MockCommRank *single = nullptr;
     g_compute = argc > 2 && std::string(argv[2]) == "compute";
+    g_kspace = argc > 2 && std::string(argv[2]) == "kspace";
     rc = run_case(argv[1], argc > 2 && std::string(argv[2]) == "provider", 0, 1, single, out);
   } catch (const std::exception &e) {
     out.f("ERROR: %s\n", e.what());

@@ -22,13 +22,11 @@ class Error { public: [[noreturn]] void all(const char *, int, const std::string
 class Memory {};
 class Atom { public: int nlocal, nghost, ntypes, nmax = 0; bigint natoms; double **x, **f, *q; int *type, *mask, *molecule = nullptr; tagint *tag; int map(tagint);
              int *map_array = nullptr; int map_size = 0; };
-class KSpace { public: double g_ewald, accuracy, slab_volfactor, energy; int slabflag; int nx_pppm = 0, ny_pppm = 0, nz_pppm = 0, order = 0;
-               int compute_flag = 1, tip4pflag = 0; double qsum = 0.0;
-               virtual ~KSpace() {} virtual void setup(); };
+class KSpace;
 class NeighList;
 class Pair { public: double **cutsq; double eng_coul, virial[6]; double cut_coul = 0.0; NeighList *list = nullptr; virtual ~Pair() {} virtual void *extract(const char *, int &); void ev_tally(int, int, int, int, double, double, double, double, double, double); };
 class Force { public: double qqrd2e, qqr2e, qe2f, dielectric; int newton_pair, newton = 0; KSpace *kspace; Pair *pair; Pair *pair_match(const std::string &, int, int nsub = 0); };
-class Domain { public: double xprd, yprd, zprd, zprd_half, boxlo[3]; };
+class Domain { public: double xprd, yprd, zprd, zprd_half, boxlo[3]; int triclinic = 0; };
 class Update { public: bigint ntimestep, laststep, eflag_atom = 0; char *integrate_style; };
 class Comm { public: int me, nprocs; };
 class Group { public: int *bitmask; int find(const std::string &); int ngroup = 0; std::string names[32]; };
@@ -55,16 +53,40 @@ class Pointers {
   Group *&group; Input *&input; Neighbor *&neighbor; Modify *&modify; FILE *&screen; FILE *&logfile;
 };
 
+// KSpace (kspace.h) as far as the glue touches it: the settings the handles read, and what a style's compute() fills -- energy,
+// virial, eatom -- after ev_init() has decoded eflag / vflag (ENERGY_GLOBAL = 1, ENERGY_ATOM = 2; VIRIAL_PAIR = 1, VIRIAL_FDOTR = 2,
+// VIRIAL_ATOM = 4, VIRIAL_CENTROID = 8).  What `kspace_style NAME args` and `kspace_modify` leave in the base class: settings(), and
+// accuracy_relative / accuracy_absolute (`kspace_modify force`), from which a style's init() forms `accuracy` in force units with
+// two_charge_force (the force between two unit charges one Angstrom apart; the host sets it, KSpace's constructor does in LAMMPS)
+class KSpace : protected Pointers {
+ public:
+  explicit KSpace(LAMMPS *l) : Pointers(l) {}
+  double g_ewald, accuracy, slab_volfactor, energy; int slabflag; int nx_pppm = 0, ny_pppm = 0, nz_pppm = 0, order = 0;
+  int compute_flag = 1, tip4pflag = 0; double qsum = 0.0;
+  double virial[6] = {0, 0, 0, 0, 0, 0}; double *eatom = nullptr;
+  int evflag = 0, eflag_global = 0, eflag_atom = 0, vflag_global = 0, vflag_atom = 0;
+  double accuracy_relative = 0.0, accuracy_absolute = -1.0, two_charge_force = 0.0;
+  virtual ~KSpace() {}
+  virtual void settings(int, char **) {}
+  virtual void init() {}
+  virtual void setup();
+  virtual void compute(int, int) {}
+ protected:
+  void ev_init(int eflag, int vflag);
+ private:
+  std::vector<double> eatom_store;
+};
+
 // LAMMPS' PPPM kspace style and Compute base, as far as pppm_conp_hip.* / compute_potential_atom_hip.* touch them
 // PPPM::compute (pppm.cpp @ 27May2021) begins with  particle_map(); make_rho();  -- both virtual -- then sums the ghost planes into
 // their owners (gc->reverse_comm), copies the owned brick to the FFT layout (brick2fft) and solves.  The mock runs the two virtuals
 // on a brick that covers the rank's share of the mesh plus `order` ghost planes on every side (one rank: the whole mesh), folds the
 // ghost planes back periodically and keeps the result (`density_fft`, [nz][ny][nx]): what the real class would transform.
 typedef double FFT_SCALAR;
-class PPPM : public KSpace, protected Pointers {
+class PPPM : public KSpace {
  public:
-  explicit PPPM(LAMMPS *l) : Pointers(l) {}
-  virtual void compute(int eflag, int vflag);
+  explicit PPPM(LAMMPS *l) : KSpace(l) {}
+  void compute(int eflag, int vflag) override;
   virtual void particle_map() { ++base_particle_map_calls; }
   virtual void make_rho();                      // (the real one clears the brick and spreads every charged atom: counted here)
   int base_particle_map_calls = 0, base_make_rho_calls = 0;

@@ -6,7 +6,9 @@ Three cases: the headline box (4096 electrode + 32768 electrolyte, ffield) with 
 4096 electrode atoms as targets, and the 16384 / 262144 box (all atoms).  Per case: ms per conp_ewald_compute (the structure factor
 of every charged atom), ms per conp_ewald_compute_group_potential right after it (the projection onto the targets: the group entry
 reuses the cached structure factor) and their sum (what one `compute potential/atom` costs), after W warm-up calls as bench.py warms
-up its update.  Prints one JSON line per case."""
+up its update.  Prints one JSON line per case.  For the headline box with all atoms as targets the same process also times
+conp_ewald_compute_forces for all atoms on the cached structure factor (forces, energy, virial) beside the
+group potential: ms_forces in that case's line."""
 import argparse
 import json
 import os
@@ -43,6 +45,18 @@ def measure(fx, at, sel, reps, warmup):
     return 1e3 * t_s / reps, 1e3 * t_p / reps
 
 
+def measure_forces(fx, at, reps, warmup):
+    """conp_ewald_compute_forces on the structure factor a conp_ewald_compute cached: the counterpart of the projection above"""
+    f = np.zeros((at.nlocal, 3))
+    fx.ewald_compute(at)
+    for _ in range(warmup):
+        fx.ewald_forces(at, f=f)
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fx.ewald_forces(at, f=f)
+    return 1e3 * (time.perf_counter() - t0) / reps
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -65,9 +79,11 @@ def main():
         sel = np.ones(n, np.int32) if which == "all" else (at.echeck[:n] != 0).astype(np.int32)
         t_s, t_p = measure(fx, at, sel, args.reps, args.warmup)
         info = fx.info()
-        print(json.dumps(dict(box=name, targets=which, n_targets=int(sel.sum()), n_atoms=int(n), kcount=int(info.kcount),
-                              ms_ewald_compute=round(t_s, 4), ms_projection=round(t_p, 4), ms_total=round(t_s + t_p, 4), reps=args.reps, warmup=args.warmup)),
-              flush=True)
+        rec = dict(box=name, targets=which, n_targets=int(sel.sum()), n_atoms=int(n), kcount=int(info.kcount),
+                   ms_ewald_compute=round(t_s, 4), ms_projection=round(t_p, 4), ms_total=round(t_s + t_p, 4), reps=args.reps, warmup=args.warmup)
+        if (name, which) == ("headline", "all"):
+            rec["ms_forces"] = round(measure_forces(fx, at, args.reps, args.warmup), 4)
+        print(json.dumps(rec), flush=True)
     for s, at, fx in handles.values():
         fx.close()
 
