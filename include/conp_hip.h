@@ -267,6 +267,33 @@ int conp_ewald_compute_forces(conp_fix *fix, const conp_atoms *atoms,
                               double *virial /* [6], NULL ok */,
                               double *eatom  /* [nlocal], overwritten, NULL ok */);
 
+/* ---- PPPM reciprocal-space forces, energy, virial: the mesh twin of conp_ewald_compute_forces --------------
+ * PPPM::compute with ik differentiation (LAMMPS pppm.cpp @ 27May2021: make_rho, poisson_ik, fieldforce_ik, fieldforce_peratom's
+ * energy, slabcorr) on the handle's mesh, at the positions and charges of `atoms`.  rho^ = forward transform of the density brick,
+ * G = the handle's greensfn, N = nx ny nz, V = xprd yprd zprd slab_volfactor, qs = env.qqrd2e, g = env.g_ewald,
+ * k = (2 pi / xprd mx, 2 pi / yprd my, 2 pi / (zprd slab_volfactor) mz) with m = i - n floor(2 i / n) per axis, Q, Q2, M, M2 as above:
+ *   energy  = qs [(V / 2) sum_k G_k |rho^_k|^2 / N^2 - g Q2 / sqrt(pi) - (pi / 2) Q^2 / (g^2 V)]
+ *   virial  = qs (V / 2) sum_k G_k |rho^_k|^2 / N^2 (delta_ab - 2 (1 / k^2 + 1 / (4 g^2)) k_a k_b)   (k = 0: nothing; xx, yy, zz, xy, xz, yz)
+ *   E_a     = Re IFFT[-i k_a G_k rho^_k / N]          (minus the gradient of the mesh potential u = IFFT[G rho^ / N])
+ *   f_i    += qs q_i sum_stencil w E(mesh point)      (the order^3 stencil weights of the b vector's gather; accumulated)
+ *   eatom_i = qs [q_i u_i / 2 - g q_i^2 / sqrt(pi) - (pi / 2) q_i Q / (g^2 V)],  u_i = sum_stencil w u     (sum_i eatom_i = energy)
+ * With env.slabflag the three slab terms of conp_ewald_compute_forces (PPPM::slabcorr and Ewald::slabcorr are the same formulas).
+ * The density is the one conp_pppm_make_rho returns for the same `atoms`.  It is spread from the atoms of THIS call, every call: the
+ * electrolyte brick kept by conp_pppm_keep_density is that of the update's positions, and the handle cannot tell whether the atoms
+ * have moved since (a pre_force that skips its update does not drop it), so it is never used here -- the entry never contracts a
+ * stale brick with moved atoms, whatever was kept.  conp_info.pppm_elyte_spreads counts one spread per call.
+ * Afterwards the mesh-potential cache is what conp_pppm_compute leaves: conp_pppm_compute_particle_potential works without another
+ * mesh solve.
+ * COLLECTIVE with decomposed ranks, the mesh replicated as for conp_pppm_compute: one tagged gather of all ranks' charged atoms, the
+ * four sums through conp_comm.allreduce_sum, and one more allreduce_sum that hands rank 0's seven mesh sums to everybody; every rank
+ * returns the same energy and virial (bit for bit) and the forces and eatom of its owned atoms.
+ * Zero-charge atoms: f untouched, eatom 0.  Any output may be NULL.  On an Ewald handle: CONP_ERR_STATE. */
+int conp_pppm_compute_forces(conp_fix *fix, const conp_atoms *atoms,
+                             double *f      /* [nlocal][3], accumulated; NULL: none */,
+                             double *energy /* 1, NULL ok */,
+                             double *virial /* [6] xx,yy,zz,xy,xz,yz, NULL ok */,
+                             double *eatom  /* [nlocal], overwritten, NULL ok */);
+
 /* ---- `compute potential/atom` (compute_potential_atom.cpp:120-345), SURVEY 8f-4 --------------------------------------------
  * per-atom electrostatic potential in volts: pair part over the pair style's half list (:223-308, optional Gaussian `eta`
  * correction for atoms with etasel != 0 = eta_check :313-318), k-space part through the PPPM provider (:165-175 -> the

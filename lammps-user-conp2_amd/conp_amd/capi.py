@@ -98,7 +98,7 @@ SYMBOLS = [
     "conp_pppm_make_rho", "conp_pppm_compute_group_potential", "conp_pppm_compute_particle_potential",
     "conp_pppm_keep_density", "conp_pppm_compute",
     "conp_ewald_compute", "conp_ewald_compute_group_potential", "conp_ewald_compute_particle_potential",
-    "conp_ewald_compute_forces",
+    "conp_ewald_compute_forces", "conp_pppm_compute_forces",
     "conp_compute_potential_atom",
 ]
 
@@ -215,6 +215,7 @@ def load_library():
     lib.conp_ewald_compute_group_potential.argtypes = [vp, C.POINTER(conp_atoms), ip, dp]
     lib.conp_ewald_compute_particle_potential.argtypes = [vp, C.POINTER(conp_atoms), C.c_int, dp]
     lib.conp_ewald_compute_forces.argtypes = [vp, C.POINTER(conp_atoms), dp, dp, dp, dp]
+    lib.conp_pppm_compute_forces.argtypes = [vp, C.POINTER(conp_atoms), dp, dp, dp, dp]
     lib.conp_compute_potential_atom.argtypes = [vp, C.POINTER(conp_atoms), C.POINTER(conp_neighlist), ip, ip,
                                                 C.POINTER(conp_potential_args), dp]
     lib.conp_fix_set_comm.argtypes = [vp, C.POINTER(conp_comm)]
@@ -497,6 +498,23 @@ class FixConp:
         self._check(self.lib.conp_ewald_compute_forces(self.h, C.byref(self.atoms_view(at)), _dptr(f),
                                                        C.byref(en) if energy else None, _dptr(w) if virial else None,
                                                        _dptr(e) if eatom else None))
+        return f, (en.value if energy else None), w, e
+
+    def pppm_compute_forces(self, at, energy=True, virial=True, eatom=False, f=None, forces=True):
+        """the mesh twin of ewald_forces (`pppm` handles; collective under decomposed ranks): PPPM reciprocal-space forces [nlocal][3]
+        (added to `f`, zeros by default; forces=False: none), energy, virial (xx, yy, zz, xy, xz, yz) and per-atom energies of the owned
+        atoms -> (f, E, W, e); what was not asked for is None"""
+        if forces:
+            f = np.zeros((at.nlocal, 3)) if f is None else f
+            assert f.dtype == np.float64 and f.flags.c_contiguous and f.shape == (at.nlocal, 3)
+        else:
+            f = None
+        en = C.c_double() if energy else None
+        w = np.zeros(6) if virial else None
+        e = np.zeros(at.nlocal) if eatom else None
+        self._check(self.lib.conp_pppm_compute_forces(self.h, C.byref(self.atoms_view(at)), _dptr(f) if forces else None,
+                                                      C.byref(en) if energy else None, _dptr(w) if virial else None,
+                                                      _dptr(e) if eatom else None))
         return f, (en.value if energy else None), w, e
 
     def compute_potential_atom(self, at, pairlist, sel, etasel=None, eta=0.0, pair=True, kspace=True, qsum=True):

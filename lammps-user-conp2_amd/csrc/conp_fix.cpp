@@ -297,6 +297,8 @@ struct conp_fix {
   bool pp_keep = false, pp_elyte_valid = false, pp_u_valid = false;
   int pp_elyte_spreads = 0;      // how often the electrolyte atoms were spread onto the mesh (b_cal and density queries)
   DevBuf<double> d_pp_elyte, d_pp_xg, d_pp_qg;
+  DevBuf<double> d_pp_ex, d_pp_ey, d_pp_kpart, d_pp_fo, d_pp_eo;      // conp_pppm_compute_forces: E_x, E_y bricks, the seven sums, outputs
+  DevBuf<int> d_pp_fidx;
   DevBuf<int> d_pp_iota;
   // Ewald per-atom potential (conp_ewald_*, conp_compute_potential_atom on an Ewald handle; conp_potential.hip): the structure factor
   // of every charged owned atom (all ranks' under decomposition) in buffers of its own -- the update's schedule, tables and G are
@@ -3423,6 +3425,107 @@ void ewald_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energ
     if (eatom) eatom[i] = he[i];
   }
 }
+// ---- PPPM forces, energy, virial ----
+// PPPM::compute with ik differentiation on the handle's mesh, at the positions and charges of `at`: the brick of every charged atom is
+// spread afresh on every call (a kept electrolyte brick is that of the update's positions: never contracted with atoms that may have
+// moved), forward transform, pppm_kspace_kernel, two packed backward transforms, pppm_force_gather_kernel on the charged owned atoms.
+// COLLECTIVE under decomposed ranks like pppm_total_potential (one tagged gather, a replicated mesh) plus the four sums.  Leaves u in
+// d_pp_re (pp_u_valid), as conp_pppm_compute does.
+void pppm_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy, double *virial, double *eatom) {
+  const double MY_PI = 3.14159265358979323846, MY_PIS = 1.77245385090551602729;
+  const double g = f->env.g_ewald, qs = f->env.qqrd2e;
+  const double L = f->env.zprd * f->env.slab_volfactor, V = f->env.xprd * f->env.yprd * L;
+  std::vector<int> idx;
+  double four[4] = {0.0, 0.0, 0.0, 0.0};              // Q, Q2, M, M2
+  for (int i = 0; i < at->nlocal; ++i) {
+    const double q = at->q[i], z = at->x[3 * (size_t)i + 2];
+    if (q == 0) continue;
+    idx.push_back(i);
+    four[0] += q; four[1] += q * q; four[2] += q * z; four[3] += q * z * z;
+  }
+  const int n = (int)idx.size();
+  pppm_upload(f, at);
+  f->d_pp_scratch.reserve(2048);
+  if (f->decomposed) {
+    const PpGather ga = pppm_gather_all(f, at);
+    f->rc.sum(four, 4);
+    launch_pppm_density(f->stream, f->dpppm, ga.n[2], f->d_pp_iota.p, f->d_pp_xg.p, f->d_pp_qg.p, f->d_pp_re.p, f->d_pp_scratch.p);
+  }
+  if (idx.empty()) idx.push_back(0);
+  f->d_pp_fidx.upload(idx, f->stream);
+  if (!f->decomposed) {
+    f->prof.begin("pppm_f_spread", f->stream);
+    launch_pppm_density(f->stream, f->dpppm, n, f->d_pp_fidx.p, f->d_x.p, f->d_q.p, f->d_pp_re.p, f->d_pp_scratch.p);
+    f->prof.end(f->stream);
+  }
+  ++f->pp_elyte_spreads;
+  f->pp_u_valid = false;
+  const double Q = four[0], Q2 = four[1], M = four[2], M2 = four[3];
+  const size_t nf = (size_t)f->dpppm.nfft;
+  const bool fields = fout != nullptr && n > 0;
+  if (fields) { f->d_pp_ex.reserve(nf); f->d_pp_ey.reserve(nf); }
+  const int nwg = pppm_kspace_workgroups(f->dpppm.nfft);
+  f->d_pp_kpart.reserve((size_t)7 * (nwg + 1));
+  const double uk[3] = {2.0 * MY_PI / f->env.xprd, 2.0 * MY_PI / f->env.yprd, 2.0 * MY_PI / L};
+  f->prof.begin("pppm_f_forward", f->stream);
+  launch_pppm_forward(f->stream, f->dpppm, f->d_pp_re.p, f->d_pp_im.p);
+  f->prof.end(f->stream);
+  f->prof.begin("pppm_f_kspace", f->stream);
+  launch_pppm_kspace(f->stream, f->dpppm, uk, g, V, f->d_pp_re.p, f->d_pp_im.p, fields ? f->d_pp_ex.p : nullptr,
+                     fields ? f->d_pp_ey.p : nullptr, f->d_pp_kpart.p + 7, f->d_pp_kpart.p);
+  f->prof.end(f->stream);
+  f->prof.begin("pppm_f_backward", f->stream);
+  launch_pppm_backward(f->stream, f->dpppm, f->d_pp_re.p, f->d_pp_im.p);
+  if (fields) launch_pppm_backward(f->stream, f->dpppm, f->d_pp_ex.p, f->d_pp_ey.p);
+  f->prof.end(f->stream);
+  f->pp_im_clean = false;
+  double s7[7];
+  HIP_TRY(hipMemcpyAsync(s7, f->d_pp_kpart.p, 7 * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+  const bool per_atom = n > 0 && (fout || eatom);
+  std::vector<double> hf, he;
+  if (per_atom) {
+    if (fout) f->d_pp_fo.reserve(3 * (size_t)at->nlocal);
+    if (eatom) f->d_pp_eo.reserve(at->nlocal);
+    EwForceOut o{};
+    o.qs = qs; o.selfc = 2.0 * g / MY_PIS; o.ecoef = 0.5 * MY_PI * Q / (g * g * V);
+    o.slab = f->env.slabflag ? 1 : 0;
+    o.fz_pref = -4.0 * MY_PI / V; o.e_pref = 2.0 * MY_PI / V; o.M = M; o.M2 = M2; o.Q = Q; o.L2_12 = L * L / 12.0;
+    f->prof.begin("pppm_f_gather", f->stream);
+    launch_pppm_force_gather(f->stream, f->dpppm, n, f->d_pp_fidx.p, f->d_x.p, f->d_q.p, fout ? f->d_pp_ex.p : nullptr, f->d_pp_ey.p,
+                             f->d_pp_im.p, f->d_pp_re.p, o, fout ? f->d_pp_fo.p : nullptr, eatom ? f->d_pp_eo.p : nullptr);
+    f->prof.end(f->stream);
+    if (fout) {
+      hf.resize(3 * (size_t)at->nlocal);
+      HIP_TRY(hipMemcpyAsync(hf.data(), f->d_pp_fo.p, hf.size() * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+    }
+    if (eatom) {
+      he.resize(at->nlocal);
+      HIP_TRY(hipMemcpyAsync(he.data(), f->d_pp_eo.p, he.size() * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  f->sync();
+  f->pp_u_valid = true;
+  if (f->decomposed) {
+    // every rank spread the same atoms, but a mesh point's contributions arrive in no fixed order (atomic adds): the bricks agree to
+    // rounding only.  Rank 0's sums are everybody's (x + 0 + .. + 0 = x): the same energy and virial on every rank, bit for bit.
+    if (f->env.rank != 0) std::fill(s7, s7 + 7, 0.0);
+    f->rc.sum(s7, 7);
+  }
+  if (energy) {
+    double e = s7[0] - g * Q2 / MY_PIS - 0.5 * MY_PI * Q * Q / (g * g * V);
+    if (f->env.slabflag) e += 2.0 * MY_PI * (M * M - Q * M2 - Q * Q * L * L / 12.0) / V;
+    *energy = qs * e;
+  }
+  if (virial) for (int c = 0; c < 6; ++c) virial[c] = qs * s7[1 + c];
+  if (eatom) std::fill(eatom, eatom + at->nlocal, 0.0);
+  if (!per_atom) return;
+  for (int k = 0; k < n; ++k) {
+    const int i = idx[k];
+    if (fout) for (int c = 0; c < 3; ++c) fout[3 * (size_t)i + c] += hf[3 * (size_t)i + c];
+    if (eatom) eatom[i] = he[i];
+  }
+}
 // the k-space tail of compute potential/atom (compute_potential_atom.cpp:165-175, slab correction :323-345) on the selected owned
 // atoms idx (ascending), whichever provider formed u_i: pot_i -= u_i, + the Gaussian self term of eta atoms, + the slab terms
 // (the sums of q z and q over the owned atoms all-reduced, MPI_Allreduce :331, :337)
@@ -3627,6 +3730,20 @@ int conp_ewald_compute_forces(conp_fix *f, const conp_atoms *at, double *fout, d
   if (!f->ew_g_valid) ewald_structure_factor(f, at);
   else if (at->nlocal + at->nghost != f->nall) throw ConpError(CONP_ERR_STATE, "atom count changed without post_neighbor");
   ewald_forces(f, at, fout, energy, virial, eatom);
+  CONP_GUARD_END
+}
+
+// The mesh twin of conp_ewald_compute_forces: what PPPM::compute leaves in atom->f, energy, virial, eatom.  COLLECTIVE under
+// decomposed ranks.  Valid on a `pppm` handle only.
+int conp_pppm_compute_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy, double *virial, double *eatom) {
+  CONP_GUARD_BEGIN
+  if (!f || !at) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->drop_graph();
+  if (!f->args.pppm)
+    throw ConpError(CONP_ERR_STATE, "conp_pppm_compute_forces: this handle's k-space provider is the Ewald sum -- use "
+                                    "conp_ewald_compute_forces");
+  need_pppm(f);
+  pppm_forces(f, at, fout, energy, virial, eatom);
   CONP_GUARD_END
 }
 

@@ -134,6 +134,19 @@ size_t pppm_line_lds_bytes(int n);
 constexpr size_t PPPM_LDS_MAX = 160 * 1024;
 void launch_pppm_probe(hipStream_t s, const PppmDev &pd, int n, const int *idx, const double *x, const double *q, const double *u,
                        double self, double *out /*indexed by atom*/);
+// reciprocal-space forces, energy and virial through the mesh (conp_pppm_compute_forces)
+struct EwForceOut;
+int pppm_kspace_workgroups(int nfft);
+// forward: rho (in `re`: the brick of every charged atom) -> rho^ in (re, im).  kspace: sums[7] = (V / 2) sum G |rho^|^2 / N^2 and the
+// six virial sums (without qqrd2e); (re, im) <- the packed spectrum of u and E_z, (pre, pim) <- that of E_x and E_y (both NULL: no
+// field bricks).  backward: a packed brick -> its two real fields.
+void launch_pppm_forward(hipStream_t s, const PppmDev &pd, double *re, double *im);
+void launch_pppm_kspace(hipStream_t s, const PppmDev &pd, const double uk[3], double g_ewald, double volume, double *re, double *im,
+                        double *pre, double *pim, double *part /*[pppm_kspace_workgroups][7]*/, double *sums /*[7]*/);
+void launch_pppm_backward(hipStream_t s, const PppmDev &pd, double *re, double *im);
+void launch_pppm_force_gather(hipStream_t s, const PppmDev &pd, int n, const int *idx, const double *x, const double *q, const double *ex,
+                              const double *ey, const double *ez, const double *u /*NULL with eo == NULL*/, const EwForceOut &o,
+                              double *fo /*[nlocal][3], written at idx; NULL: none*/, double *eo /*[nlocal]; NULL: none*/);
 void launch_potential_pair(hipStream_t s, int inum, const int *ilist, const int *numneigh, const int *first, const int *neigh,
                            int nlocal, int newton, const double *x, const double *q, const int *type, const int *sel,
                            const int *etasel, int ntypes, const double *cutsq, double cut_coulsq, double g_ewald, double eta,
@@ -162,6 +175,18 @@ struct EwForceOut {
   int slab;
   double fz_pref /*-4 pi / V*/, e_pref /*2 pi / V*/, M, M2, Q, L2_12 /*L^2 / 12*/;
 };
+// the tail both k-space force entries share (Ewald::slabcorr and PPPM::slabcorr are the same formulas): atom a with charge qi at
+// height z, g = minus its k-space potential (no self term), (fx, fy, fz) = qi times the field -> slab force, per-atom energy, qqrd2e
+__device__ __forceinline__ void kspace_atom_out(const EwForceOut &o, double qi, double z, double g, double fx, double fy, double fz,
+                                                size_t a, double *__restrict__ fo, double *__restrict__ eo) {
+  double e = -0.5 * qi * (g + o.selfc * qi) - o.ecoef * qi;
+  if (o.slab) {
+    fz += o.fz_pref * qi * (o.M - o.Q * z);
+    e += o.e_pref * qi * (z * o.M - 0.5 * (o.M2 + o.Q * z * z) - o.Q * o.L2_12);
+  }
+  if (fo) { fo[3 * a] = o.qs * fx; fo[3 * a + 1] = o.qs * fy; fo[3 * a + 2] = o.qs * fz; }
+  if (eo) eo[a] = o.qs * e;
+}
 void launch_ew_force_out(hipStream_t s, int n, int nb_pad, const double *bk /*[4][4][nb_pad]*/, const int *idx, const double *q,
                          const double *x /*[n][3]*/, const EwForceOut &o, double *fo /*[nlocal][3], written at idx*/,
                          double *eo /*[nlocal]*/);

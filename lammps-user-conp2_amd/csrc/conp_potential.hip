@@ -305,18 +305,8 @@ __global__ __launch_bounds__(256) void ew_force_out_kernel(int n, int nb_pad, co
     const double *b = bk + (size_t)(4 * c) * nb_pad + i;
     v[c] = (b[0] + b[(size_t)nb_pad]) + (b[2 * (size_t)nb_pad] + b[3 * (size_t)nb_pad]);
   }
-  const double qi = q[i], z = x[3 * (size_t)i + 2];
-  double fz = qi * v[3];
-  double e = -0.5 * qi * (v[0] + o.selfc * qi) - o.ecoef * qi;
-  if (o.slab) {
-    fz += o.fz_pref * qi * (o.M - o.Q * z);
-    e += o.e_pref * qi * (z * o.M - 0.5 * (o.M2 + o.Q * z * z) - o.Q * o.L2_12);
-  }
-  const size_t a = (size_t)idx[i];
-  fo[3 * a] = o.qs * (qi * v[1]);
-  fo[3 * a + 1] = o.qs * (qi * v[2]);
-  fo[3 * a + 2] = o.qs * fz;
-  eo[a] = o.qs * e;
+  const double qi = q[i];
+  kspace_atom_out(o, qi, x[3 * (size_t)i + 2], v[0], qi * v[1], qi * v[2], qi * v[3], (size_t)idx[i], fo, eo);
 }
 
 void launch_ew_seeds(hipStream_t s, int n, const double *x, double ux, double uy, double uz, double *seeds) {

@@ -778,6 +778,189 @@ void launch_pppm_probe(hipStream_t s, const PppmDev &pd, int n, const int *idx, 
   hipLaunchKernelGGL(pppm_probe_kernel, dim3((n + 3) / 4), dim3(256), 0, s, pd, n, idx, x, q, u, self, out);
 }
 
+// ---- reciprocal-space forces, energy and virial through the mesh (conp_pppm_compute_forces) ----------------
+// PPPM::compute with ik differentiation after the forward transform (pppm.cpp @ 27May2021: poisson_ik, fieldforce_ik, slabcorr).
+
+// a complex 3-D transform in place, nothing fused into it: the plane kernel where a z-plane fits (x and y in one launch), else one
+// launch per axis -- the radix kernel for 2,3,5-smooth lengths, the plain DFT for the others.  real_in: `im` is not read.
+static void dft3_complex(hipStream_t s, const PppmDev &pd, double sign, double *re, double *im, bool real_in) {
+  const int dims[3] = {pd.nx, pd.ny, pd.nz};
+  int axis0 = 0;
+  FftPlan fpx, fpy;
+  const size_t lds_xy = (size_t)2 * pd.nx * pd.ny * sizeof(double2) + (size_t)2 * (pd.nx + pd.ny) * sizeof(double);
+  if (fft_factor(pd.nx, fpx) && fft_factor(pd.ny, fpy) && lds_xy <= 128 * 1024) {
+    static LdsGrant g{};
+    grant_lds(pppm_fft_xy_kernel, lds_xy, g);
+    hipLaunchKernelGGL(pppm_fft_xy_kernel, dim3(pd.nz), dim3(512), lds_xy, s, pd.nx, pd.ny, sign, fpx, fpy, pd.twid[0], pd.twid[1], re, im,
+                       real_in ? 1 : 0, 0, pd, PppmSpreadIn{}, BRowArgs{});
+    axis0 = 2;
+  } else if (real_in && !fft_factor(pd.nx, fpx)) {
+    hipLaunchKernelGGL(zero_kernel, dim3(512), dim3(256), 0, s, (size_t)pd.nfft, im);      // (the plain DFT reads both parts)
+  }
+  for (int axis = axis0; axis < 3; ++axis) {
+    const int n = dims[axis];
+    const int nlines = axis == 0 ? pd.ny * pd.nz : (axis == 1 ? pd.nx * pd.nz : pd.nx * pd.ny);
+    FftPlan fp;
+    if (fft_factor(n, fp)) {
+      int xs = 0;
+      const size_t lds = fft_line_lds(n, &xs);
+      const int XT = 1 << xs;
+      static LdsGrant g{};
+      grant_lds(pppm_fft_kernel, lds, g);
+      hipLaunchKernelGGL(pppm_fft_kernel, dim3((nlines + XT - 1) / XT), dim3(512), lds, s, pd.nx, pd.ny, pd.nz, axis, sign, fp,
+                         pd.twid[axis], re, im, xs, (real_in && axis == 0) ? 1 : 0, (const double *)nullptr, 1.0);
+      continue;
+    }
+    int XT = 1;
+    const size_t lds = dft_line_lds(n, &XT);
+    static LdsGrant g{};
+    grant_lds(pppm_dft_kernel, lds, g);
+    hipLaunchKernelGGL(pppm_dft_kernel, dim3((nlines + XT - 1) / XT), dim3(256), lds, s, pd.nx, pd.ny, pd.nz, axis, sign,
+                       pd.twid[axis], re, im, XT);
+  }
+}
+
+// One launch over the spectrum rho^ (re, im) of the density brick: phi = G rho^ / N, the seven sums
+//   e_k = (V / 2) G |rho^|^2 / N^2,   v_ab = e_k (delta_ab - 2 (1 / k^2 + 1 / (4 g^2)) k_a k_b)       (k = 0: nothing)
+// and the spectra of the four real fields wanted, packed two by two into complex bricks (the inverse transform of A + i B is
+// a + i b when A and B are spectra of real fields):
+//   (re, im)   <- phi + i (-i kz phi) = (1 + kz) phi        -> backward: u in `re`, E_z in `im`
+//   (pre, pim) <- -i kx phi + i (-i ky phi)                 -> backward: E_x in `pre`, E_y in `pim`
+// E = -grad u: the force on a positive charge.  For an even length the gradient's term at its own axis' Nyquist index is anti-Hermitian
+// ALONE (its partner is itself): its inverse is imaginary, PPPM::poisson_ik drops it with the imaginary part; packed, it would land
+// in the partner field, so it is zeroed here (the sums keep it, as PPPM's do).
+// Sums: thread t of workgroup b adds its points b 256 + t, + 256 gridDim.x, ... in that order, the workgroup adds its threads in a
+// binary tree, and the last launch (final = 1, one workgroup) adds the workgroups' rows the same way: a fixed order for a given mesh,
+// no atomics (ew_energy_virial_kernel's scheme).  part: [gridDim.x][7] = sum e, xx, yy, zz, xy, xz, yz
+struct PppmKspace {
+  int nx, ny, nz, nfft;
+  double uk[3];            // 2 pi / (xprd, yprd, zprd slab_volfactor)
+  double inv4g2, scaleinv, half_v;
+};
+__global__ __launch_bounds__(256) void pppm_kspace_kernel(PppmKspace a, const double *__restrict__ greensfn, double *__restrict__ re,
+                                                          double *__restrict__ im, double *__restrict__ pre, double *__restrict__ pim,
+                                                          const double *__restrict__ in, int nin, double *__restrict__ part, int final) {
+  __shared__ double sh[7][256];
+  const int t = threadIdx.x;
+  double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (final) {
+    for (int j = t; j < nin; j += 256)
+#pragma unroll
+      for (int v = 0; v < 7; ++v) acc[v] += in[(size_t)j * 7 + v];
+  } else {
+    const int nxy = a.nx * a.ny;
+    for (int n = blockIdx.x * 256 + t; n < a.nfft; n += 256 * gridDim.x) {
+      const int iz = n / nxy, r = n - iz * nxy, iy = r / a.nx, ix = r - iy * a.nx;
+      const int mx = ix - a.nx * (2 * ix / a.nx), my = iy - a.ny * (2 * iy / a.ny), mz = iz - a.nz * (2 * iz / a.nz);
+      const double kx = a.uk[0] * mx, ky = a.uk[1] * my, kz = a.uk[2] * mz;
+      const double g = greensfn[n], rr = re[n], ri = im[n];
+      const double sqk = kx * kx + ky * ky + kz * kz;
+      if (sqk != 0.0) {
+        const double e = a.half_v * (a.scaleinv * a.scaleinv * g * (rr * rr + ri * ri));
+        const double vt = -2.0 * (1.0 / sqk + a.inv4g2) * e;
+        acc[0] += e;
+        acc[1] += e + vt * kx * kx; acc[2] += e + vt * ky * ky; acc[3] += e + vt * kz * kz;
+        acc[4] += vt * kx * ky; acc[5] += vt * kx * kz; acc[6] += vt * ky * kz;
+      }
+      const double pr = (a.scaleinv * g) * rr, pi = (a.scaleinv * g) * ri;
+      const double fx = 2 * ix == a.nx ? 0.0 : kx, fy = 2 * iy == a.ny ? 0.0 : ky, fz = 2 * iz == a.nz ? 0.0 : kz;
+      re[n] = pr + fz * pr; im[n] = pi + fz * pi;
+      if (pre) { pre[n] = fx * pi + fy * pr; pim[n] = fy * pi - fx * pr; }
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < 7; ++v) sh[v][t] = acc[v];
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s)
+#pragma unroll
+      for (int v = 0; v < 7; ++v) sh[v][t] += sh[v][t + s];
+    __syncthreads();
+  }
+  if (t < 7) part[(size_t)blockIdx.x * 7 + t] = sh[t][0];
+}
+
+int pppm_kspace_workgroups(int nfft) { const int w = (nfft + 255) / 256; return w < 1 ? 1 : (w > 1024 ? 1024 : w); }
+
+// fieldforce_ik + the per-atom energy of fieldforce_peratom + slabcorr, one wavefront per charged owned atom: the order^3 stencil
+// over the field bricks (and u when `eo` is wanted) with pppm_probe_kernel's weights and index conventions -- lanes take (z, y)
+// stencil rows, a shuffle tree adds them -- then kspace_atom_out (the Ewald entry's tail: qs q_i, slab force, e_i), scattered by local
+// index.  Every atom is written by its own wave: no atomics.  fo: [nlocal][3], eo: [nlocal], overwritten at idx (the host accumulates)
+__global__ __launch_bounds__(256) void pppm_force_gather_kernel(PppmDev pd, int n, const int *__restrict__ idx, const double *__restrict__ x,
+                                                                const double *__restrict__ q, const double *__restrict__ ex,
+                                                                const double *__restrict__ ey, const double *__restrict__ ez,
+                                                                const double *__restrict__ u, EwForceOut o, double *__restrict__ fo,
+                                                                double *__restrict__ eo) {
+  __shared__ double coeff[64];
+  if (threadIdx.x < pd.order * pd.order) coeff[threadIdx.x] = pd.rho_coeff[threadIdx.x];
+  __syncthreads();
+  // the wave's 3 x order stencil weights live in LDS (one lane each: compute_rho1d for one k), not in a per-lane array that
+  // run-time indices would push to scratch; a wave reads only what it wrote itself
+  __shared__ double wsh[4][3][8];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int k = blockIdx.x * 4 + wave;
+  if (k >= n) return;
+  const int i = idx[k];
+  const double xs0 = (x[3 * (size_t)i] - pd.boxlo[0]) * pd.delinv[0];
+  const double xs1 = (x[3 * (size_t)i + 1] - pd.boxlo[1]) * pd.delinv[1];
+  const double xs2 = (x[3 * (size_t)i + 2] - pd.boxlo[2]) * pd.delinv[2];
+  const int g0 = static_cast<int>(xs0 + pd.shift) - 16384, g1 = static_cast<int>(xs1 + pd.shift) - 16384;
+  const int g2 = static_cast<int>(xs2 + pd.shift) - 16384;
+  if (lane < 24) {
+    const int c = lane >> 3, kk = lane & 7;
+    const double dx = c == 0 ? g0 + pd.shiftone - xs0 : (c == 1 ? g1 + pd.shiftone - xs1 : g2 + pd.shiftone - xs2);
+    if (kk < pd.order) wsh[wave][c][kk] = rho1d_one(coeff, pd.order, dx, kk);
+  }
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  const double (*w)[8] = wsh[wave];
+  const int o2 = pd.order * pd.order;
+  double ax = 0.0, ay = 0.0, az = 0.0, au = 0.0;
+  for (int row = lane; row < o2; row += 64) {
+    const int nn = row / pd.order, m = row - nn * pd.order;
+    const int mz = pwrap(nn + pd.nlower + g2, pd.nz), my = pwrap(m + pd.nlower + g1, pd.ny);
+    const double y0 = w[2][nn] * w[1][m];
+    const size_t line = ((size_t)mz * pd.ny + my) * pd.nx;
+    for (int l = 0; l < pd.order; ++l) {
+      const size_t p = line + pwrap(l + pd.nlower + g0, pd.nx);
+      const double x0 = y0 * w[0][l];
+      if (ex) { ax += x0 * ex[p]; ay += x0 * ey[p]; az += x0 * ez[p]; }
+      if (eo) au += x0 * u[p];
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    ax += __shfl_down(ax, off, 64); ay += __shfl_down(ay, off, 64); az += __shfl_down(az, off, 64); au += __shfl_down(au, off, 64);
+  }
+  if (lane == 0) {
+    const double qi = q[i];
+    kspace_atom_out(o, qi, x[3 * (size_t)i + 2], -au, qi * ax, qi * ay, qi * az, (size_t)i, fo, eo);
+  }
+}
+
+// The three steps between the spread and the gather.  forward: rho (in `re`, the brick of every charged atom) -> rho^ in (re, im).
+// kspace: sums[7] (without qqrd2e) and the packed spectra (pre == nullptr: no forces wanted, phi only); part:
+// [pppm_kspace_workgroups(nfft)][7] scratch.  backward: one packed brick -> its two real fields (u in `re`, E_z in `im`; E_x, E_y).
+void launch_pppm_forward(hipStream_t s, const PppmDev &pd, double *re, double *im) { dft3_complex(s, pd, -1.0, re, im, true); }
+void launch_pppm_backward(hipStream_t s, const PppmDev &pd, double *re, double *im) { dft3_complex(s, pd, +1.0, re, im, false); }
+void launch_pppm_kspace(hipStream_t s, const PppmDev &pd, const double uk[3], double g_ewald, double volume, double *re, double *im,
+                        double *pre, double *pim, double *part, double *sums) {
+  PppmKspace a{};
+  a.nx = pd.nx; a.ny = pd.ny; a.nz = pd.nz; a.nfft = pd.nfft;
+  for (int c = 0; c < 3; ++c) a.uk[c] = uk[c];
+  a.inv4g2 = 1.0 / (4.0 * g_ewald * g_ewald); a.scaleinv = 1.0 / ((double)pd.nx * pd.ny * pd.nz); a.half_v = 0.5 * volume;
+  const int nwg = pppm_kspace_workgroups(pd.nfft);
+  hipLaunchKernelGGL(pppm_kspace_kernel, dim3(nwg), dim3(256), 0, s, a, pd.greensfn, re, im, pre, pim, (const double *)nullptr, 0, part, 0);
+  hipLaunchKernelGGL(pppm_kspace_kernel, dim3(1), dim3(256), 0, s, a, pd.greensfn, (double *)nullptr, (double *)nullptr,
+                     (double *)nullptr, (double *)nullptr, (const double *)part, nwg, sums, 1);
+}
+
+void launch_pppm_force_gather(hipStream_t s, const PppmDev &pd, int n, const int *idx, const double *x, const double *q, const double *ex,
+                              const double *ey, const double *ez, const double *u, const EwForceOut &o, double *fo, double *eo) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(pppm_force_gather_kernel, dim3((n + 3) / 4), dim3(256), 0, s, pd, n, idx, x, q, ex, ey, ez, u, o, fo, eo);
+}
+
 // ---- compute potential/atom, pair part (compute_potential_atom.cpp:223-308): one wavefront per list owner -------------------
 __global__ __launch_bounds__(256) void potential_pair_kernel(int inum, const int *__restrict__ ilist, const int *__restrict__ numneigh,
                                                              const int *__restrict__ first, const int *__restrict__ neigh, int nlocal,

@@ -9,6 +9,14 @@
 //        glue_driver CASEFILE kspace               mode A with `kspace_style ewald/conp/hip` as force->kspace: on every step, after the
 //                                                  fix's pre_force, compute(eflag, vflag) on the fix's handle; output per step
 //                                                  "kf STEP TAG FX FY FZ", "kea STEP TAG E" per owned atom, "ke STEP ENERGY", "kv STEP W[6]"
+//        glue_driver CASEFILE pppmforce [vatom|ad|nohandle]
+//                                                  mode A with the `pppm` keyword and `kspace_style pppm/conp/hip ACC device` as
+//                                                  force->kspace: on every step, after the fix's pre_force, compute(eflag, vflag) on
+//                                                  the fix's handle (conp_pppm_compute_forces); output as in the kspace mode.  The third
+//                                                  word asks for the per-atom virial / sets kspace_modify diff ad / hides the fix
+//                                                  from Modify::fix: each stops with the style's message
+//        glue_driver CASEFILE pppmhost             the provider mode with `kspace_style pppm/conp/hip ACC` (no `device`) parsed by the
+//                                                  style's settings(): the same output as `provider`
 //        glue_driver CASEFILE provider             mode B: the reference's FixConp keeps its loops, only `kspmod` is replaced:
 //                                                  a stand-in for the fix's public members is registered with KSpaceModuleHip
 //                                                  (register_fix, fix_conp.cpp:409) and conp_setup / conp_post_neighbor / a_cal /
@@ -70,6 +78,9 @@ struct Out {
 
 // one rank: its own mock LAMMPS instance, atoms and lists from its case file
 static bool g_kspace = false;    // `glue_driver CASEFILE kspace`: EwaldConpHip is the kspace style, compute() on every step
+static bool g_pppmforce = false; // `glue_driver CASEFILE pppmforce`: PPPMConpHip in device mode is the kspace style, compute() on every step
+static std::string g_pppm_variant; // its third word
+static bool g_pppmhost = false;  // `glue_driver CASEFILE pppmhost`
 static bool g_compute = false;   // `glue_driver CASEFILE compute`: after the steps, compute potential/atom/hip on the conp/hip fix
 
 int run_case(const char *path, bool provider, int me, int nprocs, MockCommRank *world, Out &out) {
@@ -232,6 +243,12 @@ int run_case(const char *path, bool provider, int me, int nprocs, MockCommRank *
       pppm_style->slabflag = kspace.slabflag; pppm_style->energy = 0.0;
       pppm_style->nx_pppm = kspace.nx_pppm; pppm_style->ny_pppm = kspace.ny_pppm; pppm_style->nz_pppm = kspace.nz_pppm;
       pppm_style->order = kspace.order;
+      if (g_pppmhost) {
+        char acc[] = "1e-4";
+        char *sargv[1] = {acc};
+        pppm_style->settings(1, sargv);
+        if (pppm_style->device_compute()) throw std::runtime_error("pppm/conp/hip without `device` selected the device compute()");
+      }
       force.kspace = pppm_style;
       kspmod = dynamic_cast<KSpaceModule *>(force.kspace);      // fix_conp.cpp:402
       if (kspmod == nullptr) throw std::runtime_error("Fix conp couldn't detect a pppm/conp kspace style (which is required with the pppm flag)");
@@ -320,8 +337,23 @@ int run_case(const char *path, bool provider, int me, int nprocs, MockCommRank *
     force.kspace = ew.get();
     ew->init();
   }
+  // `kspace_style pppm/conp/hip 1e-4 device`: the mesh is what PPPM::init would have chosen (the case file's); FixConpHip::init reads
+  // it off force->kspace
+  std::unique_ptr<PPPMConpHip> pf;
+  if (g_pppmforce) {
+    pf.reset(new PPPMConpHip(&lmp));
+    char acc[] = "1e-4", dev[] = "device";
+    char *sargv[2] = {acc, dev};
+    pf->settings(2, sargv);
+    pf->g_ewald = kspace.g_ewald; pf->accuracy = kspace.accuracy; pf->slab_volfactor = kspace.slab_volfactor;
+    pf->slabflag = kspace.slabflag; pf->energy = 0.0;
+    pf->nx_pppm = kspace.nx_pppm; pf->ny_pppm = kspace.ny_pppm; pf->nz_pppm = kspace.nz_pppm; pf->order = kspace.order;
+    if (g_pppm_variant == "ad") pf->differentiation_flag = 1;
+    force.kspace = pf.get();
+  }
   FixConpHip fix(&lmp, narg, fargv.data());
   Fix *fixes[1] = {&fix};
+  if (g_pppmforce) { atom.nmax = std::max(atom.nmax, nall); if (g_pppm_variant != "nohandle") { modify.fix = fixes; modify.nfix = 1; } }
   if (g_kspace) { modify.fix = fixes; modify.nfix = 1; atom.nmax = std::max(atom.nmax, nall); }
   for (auto &ml : modify_lines) {                    // fix_modify arrives before init(), as in an input script
     std::vector<char *> margv;
@@ -370,6 +402,18 @@ int run_case(const char *path, bool provider, int me, int nprocs, MockCommRank *
       out.f("ke %ld %.17g\n", ts, ew->energy);
       out.f("kv %ld %.17g %.17g %.17g %.17g %.17g %.17g\n", ts, ew->virial[0], ew->virial[1], ew->virial[2], ew->virial[3], ew->virial[4],
             ew->virial[5]);
+    }
+    if (g_pppmforce) {
+      // Verlet after the fixes' pre_force, on every step: force->kspace->compute(eflag, vflag); atom->f starts from zero
+      std::fill(fs.begin(), fs.end(), 0.0);
+      pf->compute(3, g_pppm_variant == "vatom" ? 5 : 1);
+      for (int i = 0; i < nlocal; ++i) {
+        out.f("kf %ld %d %.17g %.17g %.17g\n", ts, tag[i], fs[3 * (size_t)i], fs[3 * (size_t)i + 1], fs[3 * (size_t)i + 2]);
+        out.f("kea %ld %d %.17g\n", ts, tag[i], pf->eatom[i]);
+      }
+      out.f("ke %ld %.17g\n", ts, pf->energy);
+      out.f("kv %ld %.17g %.17g %.17g %.17g %.17g %.17g\n", ts, pf->virial[0], pf->virial[1], pf->virial[2], pf->virial[3], pf->virial[4],
+            pf->virial[5]);
     }
     std::fill(fs.begin(), fs.end(), 0.0);
     if (fix.setmask() & FixConst::POST_FORCE) fix.post_force(0);
@@ -461,7 +505,10 @@ int main(int argc, char **argv) {
     MockCommRank *single = nullptr;
     g_compute = argc > 2 && std::string(argv[2]) == "compute";
     g_kspace = argc > 2 && std::string(argv[2]) == "kspace";
-    rc = run_case(argv[1], argc > 2 && std::string(argv[2]) == "provider", 0, 1, single, out);
+    g_pppmforce = argc > 2 && std::string(argv[2]) == "pppmforce";
+    g_pppm_variant = g_pppmforce && argc > 3 ? argv[3] : "";
+    g_pppmhost = argc > 2 && std::string(argv[2]) == "pppmhost";
+    rc = run_case(argv[1], argc > 2 && (std::string(argv[2]) == "provider" || g_pppmhost), 0, 1, single, out);
   } catch (const std::exception &e) {
     out.f("ERROR: %s\n", e.what());
     rc = 2;

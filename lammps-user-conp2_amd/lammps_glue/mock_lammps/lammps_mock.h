@@ -87,6 +87,8 @@ class PPPM : public KSpace {
  public:
   explicit PPPM(LAMMPS *l) : KSpace(l) {}
   void compute(int eflag, int vflag) override;
+  void settings(int, char **) override;         // kspace_style pppm ACCURACY
+  int differentiation_flag = 0;                 // kspace_modify diff: 0 ik, 1 ad
   virtual void particle_map() { ++base_particle_map_calls; }
   virtual void make_rho();                      // (the real one clears the brick and spreads every charged atom: counted here)
   int base_particle_map_calls = 0, base_make_rho_calls = 0;

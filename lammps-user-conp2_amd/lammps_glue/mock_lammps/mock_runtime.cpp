@@ -1,6 +1,7 @@
 // Minimal bodies for the interface mock (lammps_mock.h) -- a test host for the glue, NOT LAMMPS.
 // Errors become C++ exceptions so that the driver can report the message the glue passed to error->all().
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <stdexcept>
@@ -90,6 +91,10 @@ void PPPM::mock_allocate() {
     brick_planes[z] = brick_rows.data() + (size_t)z * ey - nylo_out;
   }
   density_brick = brick_planes.data() - nzlo_out;
+}
+void PPPM::settings(int narg, char **arg) {
+  if (narg < 1) error->all(FLERR, "Illegal kspace_style pppm command");
+  accuracy_relative = std::fabs(utils::numeric(FLERR, arg[0], false, lmp));
 }
 void PPPM::make_rho() {
   ++base_make_rho_calls;

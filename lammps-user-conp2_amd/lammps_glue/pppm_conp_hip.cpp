@@ -1,7 +1,11 @@
 #include "pppm_conp_hip.h"
 
+#include <cstring>
+
 #ifndef CONP_GLUE_MOCK
+#include "domain.h"
 #include "fix_conp.h"
+#include "modify.h"
 #endif
 
 using namespace LAMMPS_NS;
@@ -82,4 +86,43 @@ void PPPMConpHip::compute_group_potential(int groupbit, double *recv) {
 void PPPMConpHip::total_density(double *density_brick) {
   conp_atoms at = view();
   fail_if(error, conp_pppm_make_rho(ph.h, &at, density_brick, nullptr, nullptr));
+}
+
+/* kspace_style pppm/conp/hip ACCURACY [device] -- the optional second word selects the device compute() */
+void PPPMConpHip::settings(int narg, char **arg) {
+  if (narg == 2) {
+    if (std::strcmp(arg[1], "device") != 0) error->all(FLERR, "Illegal kspace_style pppm/conp/hip command: the optional second word is `device`");
+    device_mode = true;
+    narg = 1;
+  }
+  PPPM::settings(narg, arg);
+}
+
+/* the handle compute() runs on: the style's own (the reference's fix conp registered and b_cal has created it), else that of a
+ * conp/hip fix (found through Modify::fix like `compute potential/atom/hip` and ewald/conp/hip do); the library refuses a handle
+ * without the `pppm` keyword */
+conp_fix *PPPMConpHip::force_handle() {
+  if (ph.h != nullptr) return ph.h;
+  for (int f = 0; f < modify->nfix; ++f)
+    if (auto *fh = dynamic_cast<FixConpHip *>(modify->fix[f]))
+      if (fh->handle() != nullptr) { fixhip = fh; return fh->handle(); }
+  fixhip = nullptr;
+  return nullptr;
+}
+
+void PPPMConpHip::compute(int eflag, int vflag) {
+  if (!device_mode) { PPPM::compute(eflag, vflag); return; }
+  ev_init(eflag, vflag);
+  if (vflag_atom) error->all(FLERR, "kspace_style pppm/conp/hip device does not tally a per-atom virial");
+  if (domain->triclinic) error->all(FLERR, "kspace_style pppm/conp/hip device does not support a triclinic box");
+  if (differentiation_flag != 0) error->all(FLERR, "kspace_style pppm/conp/hip device supports kspace_modify diff ik only");
+  conp_fix *h = force_handle();
+  if (h == nullptr)
+    error->all(FLERR, "kspace_style pppm/conp/hip device needs a fix with the pppm keyword: a conp/hip fix, or fix conp after its first b_cal");
+  conp_atoms at = av.flat(atom, [this](int i) { return fixconp ? fixconp->electrode_check(i) : (fixhip ? fixhip->electrode_check(i) : 0); });
+  /* atom->f is one contiguous [nmax][3] block behind the row pointers (Memory::create): accumulated in place.  The entry spreads the
+   * atoms it is given on every call, so steps on which the fix skips its update get the forces of the moved atoms */
+  double *f = atom->nlocal ? &atom->f[0][0] : nullptr;
+  fail_if(error, conp_pppm_compute_forces(h, &at, f, eflag_global ? &energy : nullptr, vflag_global ? virial : nullptr,
+                                          eflag_atom ? eatom : nullptr));
 }

@@ -5,7 +5,11 @@
  *   - `compute potential/atom` (compute_potential_atom.cpp:103-111) finds a provider with mesh potentials,
  *   - FixConpHip's `pppm` keyword reads the mesh (nx_pppm, ny_pppm, nz_pppm, order) off it like off any PPPM style.
  * What it serves through the C ABI: b_cal (pppm_conp.cpp:269-316), a_cal (:91-101: the Ewald matrix), compute_particle_potential /
- * compute_group_potential (:452-534), and the density bricks of ele_make_rho / make_rho (:385-450) for a host that wants them. */
+ * compute_group_potential (:452-534), and the density bricks of ele_make_rho / make_rho (:385-450) for a host that wants them.
+ * `kspace_style pppm/conp/hip ACCURACY device` (opt-in): compute() itself runs on the device -- atom->x / q / f go to
+ * conp_pppm_compute_forces on the handle of the style (the reference's fix conp registered with it) or of a
+ * conp/hip fix with the `pppm` keyword; energy, virial and eatom are set from it.  ik differentiation only; no per-atom virial, no
+ * triclinic box (each stops with an error).  Without the word compute() is LAMMPS' own, with the two overrides above. */
 #ifdef KSPACE_CLASS
 
 KSpaceStyle(pppm/conp/hip,PPPMConpHip)
@@ -16,6 +20,7 @@ KSpaceStyle(pppm/conp/hip,PPPMConpHip)
 #define LMP_PPPM_CONP_HIP_H
 
 #include "conp_glue_common.h"
+#include "fix_conp_hip.h"
 #ifdef CONP_GLUE_MOCK
 #include "mock_lammps/conp2_mock.h"
 #else
@@ -46,11 +51,16 @@ class PPPMConpHip : public PPPM, public KSpaceModule {
   /* the density the make_rho override (:434-450) hands to PPPM::compute: electrolyte brick + electrode brick, [nz][ny][nx] */
   void total_density(double *density_brick);
   conp_fix *handle() { return ph.h; }
+  void settings(int, char **) override;                               /* ACCURACY [device] */
+  void compute(int eflag, int vflag) override;                        /* device mode: conp_pppm_compute_forces; else PPPM::compute */
+  bool device_compute() const { return device_mode; }
 
  private:
   conp_glue::ProviderHandle ph;      /* destroys the handle with the style */
   conp_glue::AtomView av;
-  bool bcal_done = false;
+  bool bcal_done = false, device_mode = false;
+  FixConpHip *fixhip = nullptr;      /* device mode without a registered fix conp: the conp/hip fix whose handle serves compute() */
+  conp_fix *force_handle();
   std::vector<double> dens;
   conp_atoms view();
 };
