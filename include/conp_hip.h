@@ -391,6 +391,32 @@ int conp_fix_b_cal_device(conp_fix *fix, const double *d_x, const double *d_q);
 int conp_fix_solve_device(conp_fix *fix, double potdiff);
 int conp_fix_scatter_device(conp_fix *fix, double *d_q_atoms, double potdiff);
 int conp_fix_pre_force_device(conp_fix *fix, const double *d_x, double *d_q, double potdiff);
+/* ---- device-resident k-space forces: conp_ewald_compute_forces / conp_pppm_compute_forces without a host round trip (DESIGN.md
+ * section 14) -- the force half of a device-resident step.
+ * Pointers and layout: ALL pointers are device pointers.  d_x / d_q have the layout of conp_fix_pre_force_device (owned atoms first,
+ * then ghosts); nlocal is that of the last (setup_)post_neighbor.
+ * Formulas: those of conp_ewald_compute_forces / conp_pppm_compute_forces above (DESIGN.md sections 12, 13); d_ev[0] is their energy,
+ * d_ev[1..6] their virial.
+ * Asynchronous (the names end in _device): everything is enqueued on the handle's stream (conp_fix_set_stream) and the results are
+ * valid once the stream has reached that point.  After the first call at a given size a call makes no device allocation, no copy to
+ * the host and no stream or device synchronisation (the first call may allocate) -- a conp_fix_pre_force_device followed by a force
+ * entry on the same stream needs no synchronisation between them.
+ * No cache: S (`pppm`: the density brick) is formed from the d_x, d_q of the call, every call -- the handle cannot know whether
+ * device arrays have changed, so the cached S and an electrolyte brick kept by conp_pppm_keep_density are never used.  Afterwards the
+ * host entries' caches (the structure factor and per-atom potentials of conp_ewald_*, the mesh potential of conp_pppm_compute) are
+ * dropped: the scratch they describe has been overwritten, and the host entries form what they need again from their own `atoms`.
+ * conp_info.pppm_elyte_spreads counts one spread per PPPM call.
+ * Targets: every owned atom, no compaction -- the launch shapes depend on nlocal only.  A zero-charge atom adds exactly 0.0 to its
+ * force, its d_eatom entry is 0, and it contributes nothing to S or to Q, Q2, M, M2.
+ * Ranks: a handle with conp_fix_set_comm (decomposed) returns CONP_ERR_STATE (device-resident entries take replicated atoms); a
+ * replicated-atom handle computes locally, as the host entries do.
+ * Errors: CONP_ERR_STATE on the other provider's handle and before the k tables / the mesh exist; CONP_ERR_ARG for a NULL d_x or
+ * d_q; all three outputs NULL: CONP_OK, nothing done. */
+int conp_ewald_compute_forces_device(conp_fix *fix, const double *d_x, const double *d_q,
+                                     double *d_f     /* [nlocal][3], accumulated; NULL: none */,
+                                     double *d_ev    /* [7]: energy, then virial xx,yy,zz,xy,xz,yz; overwritten; NULL ok */,
+                                     double *d_eatom /* [nlocal], overwritten; NULL ok */);
+int conp_pppm_compute_forces_device(conp_fix *fix, const double *d_x, const double *d_q, double *d_f, double *d_ev, double *d_eatom);
 /* per-kernel timing of the last N updates via HIP events on the library's stream (bench.py roofline leg).
  * enable: 0 off, 1 a pair of events around every kernel, 2 around every 4th launch of the dominant kernel (sk_gemm) only --
  * cheap enough to stay on inside a timed region (an event pair drains the queue around the kernel it brackets). */
@@ -422,7 +448,9 @@ int conp_debug_check_guards(void);
  * DESIGN.md section 2 -- what tests/ compares the default paths with (A/B inside one process).  Process-wide bit mask, read when a
  * handle is created (CONP_PATH_ROWS_HOST, CONP_PATH_PPPM_SPREAD_LAUNCH: at every call).  The first handle created with a
  * non-zero mask says so on stderr.  conp_debug_set_sk_workgroups: workgroup count of the structure-factor launch (0 = the
- * library's choice), for the tests that cover heavily split tiles on a small deck.  Not meant for production runs. */
+ * library's choice), for the tests that cover heavily split tiles on a small deck.  conp_debug_set_ew_block: cap of the atom block of
+ * the conp_ewald_* entries' phase tables (0 = the library's choice; else n rounded up to a multiple of 64), process-wide and read at
+ * every call, for the tests that run several blocks and a ragged last one on a deck.  Not meant for production runs. */
 enum {
   CONP_PATH_PARTIAL_TILES = 1 << 0,      /* planar electrodes: partial tiles + reducing launch instead of the projecting epilogue */
   CONP_PATH_A_GENERAL = 1 << 1,          /* A k-space part: the general (planar, kz) contraction instead of the z-class one */
@@ -439,6 +467,7 @@ enum {
 };
 void conp_debug_set_paths(unsigned mask);
 void conp_debug_set_sk_workgroups(int n);
+void conp_debug_set_ew_block(int n);
 
 
 /* ---- the fix's log file (fix_conp.cpp:119 `outf`) ----

@@ -91,7 +91,7 @@ SYMBOLS = [
     "conp_fix_set_stream",
     "conp_fix_bind_device_buffers", "conp_fix_row_range", "conp_fix_b_cal_device", "conp_fix_solve_device",
     "conp_fix_scatter_device", "conp_fix_pre_force_device", "conp_fix_profile", "conp_fix_profile_read", "conp_debug_check_guards",
-    "conp_debug_set_paths", "conp_debug_set_sk_workgroups",
+    "conp_debug_set_paths", "conp_debug_set_sk_workgroups", "conp_debug_set_ew_block",
     "conp_fix_pin_host_arrays", "conp_fix_unpin_host_arrays", "conp_host_alloc", "conp_host_free",
     "conp_fix_write_timing", "conp_fix_log_drain", "conp_fix_mesg_drain",
     "conp_fix_set_comm", "conp_rccl_unique_id", "conp_fix_comm_init_rccl", "conp_rccl_available", "conp_fix_comm_destroy_rccl",
@@ -99,6 +99,7 @@ SYMBOLS = [
     "conp_pppm_keep_density", "conp_pppm_compute",
     "conp_ewald_compute", "conp_ewald_compute_group_potential", "conp_ewald_compute_particle_potential",
     "conp_ewald_compute_forces", "conp_pppm_compute_forces",
+    "conp_ewald_compute_forces_device", "conp_pppm_compute_forces_device",
     "conp_compute_potential_atom",
 ]
 
@@ -129,6 +130,12 @@ class test_paths:
         lib.conp_debug_set_paths(0)
         lib.conp_debug_set_sk_workgroups(0)
         return False
+
+
+def set_ew_block(n: int):
+    """test hook (conp_debug_set_ew_block): cap of the atom block of the conp_ewald_* entries, rounded up to a multiple of 64;
+    0 = the library's choice.  Process-wide, read at every call"""
+    load_library().conp_debug_set_ew_block(int(n))
 
 
 def load_library():
@@ -216,6 +223,11 @@ def load_library():
     lib.conp_ewald_compute_particle_potential.argtypes = [vp, C.POINTER(conp_atoms), C.c_int, dp]
     lib.conp_ewald_compute_forces.argtypes = [vp, C.POINTER(conp_atoms), dp, dp, dp, dp]
     lib.conp_pppm_compute_forces.argtypes = [vp, C.POINTER(conp_atoms), dp, dp, dp, dp]
+    if hasattr(lib, "conp_ewald_compute_forces_device"):      # (comparison builds loaded through CONP_LIB lack these)
+        lib.conp_ewald_compute_forces_device.argtypes = [vp, vp, vp, vp, vp, vp]
+        lib.conp_pppm_compute_forces_device.argtypes = [vp, vp, vp, vp, vp, vp]
+        lib.conp_debug_set_ew_block.argtypes = [C.c_int]
+        lib.conp_debug_set_ew_block.restype = None
     lib.conp_compute_potential_atom.argtypes = [vp, C.POINTER(conp_atoms), C.POINTER(conp_neighlist), ip, ip,
                                                 C.POINTER(conp_potential_args), dp]
     lib.conp_fix_set_comm.argtypes = [vp, C.POINTER(conp_comm)]
@@ -637,6 +649,17 @@ class FixConp:
 
     def pre_force_device(self, d_x: int, d_q: int, potdiff):
         self._check(self.lib.conp_fix_pre_force_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q), potdiff))
+
+    def ewald_forces_device(self, d_x: int, d_q: int, d_f: int = 0, d_ev: int = 0, d_eatom: int = 0):
+        """conp_ewald_compute_forces_device: raw device pointers (0 = NULL), enqueued on the handle's stream, no synchronisation;
+        d_f [nlocal][3] is added to, d_ev [7] (energy, virial xx, yy, zz, xy, xz, yz) and d_eatom [nlocal] are overwritten"""
+        self._check(self.lib.conp_ewald_compute_forces_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q), C.c_void_p(d_f),
+                                                              C.c_void_p(d_ev), C.c_void_p(d_eatom)))
+
+    def pppm_forces_device(self, d_x: int, d_q: int, d_f: int = 0, d_ev: int = 0, d_eatom: int = 0):
+        """conp_pppm_compute_forces_device: the mesh twin of ewald_forces_device (`pppm` handles)"""
+        self._check(self.lib.conp_pppm_compute_forces_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q), C.c_void_p(d_f),
+                                                             C.c_void_p(d_ev), C.c_void_p(d_eatom)))
 
     def profile(self, enable):
         """0 off, 1 events around every kernel, 2 around the dominant kernel only (conp_hip.h)"""

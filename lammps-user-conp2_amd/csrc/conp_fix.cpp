@@ -314,6 +314,12 @@ struct conp_fix {
   DevBuf<double2> d_ew_Xe, d_ew_Ye;
   DevBuf<int> d_ew_idx, d_ew_ctptr;
   DevBuf<SkTile> d_ew_tiles;
+  // the device-resident force entries (conp_*_compute_forces_device): Q, Q2, M, M2 of the call's atoms with the
+  // workgroups' partial rows behind them; the plan whose tile lists d_ew_tiles / d_ew_ctptr hold; how many leading entries of
+  // d_pp_iota are the identity list 0, 1, 2, ... (pppm_gather_all, the only other writer, resets it)
+  DevBuf<double> d_kf_sums;
+  long ew_tiles_gen = -1;
+  int pp_iota_n = 0;
   double Btime = 0., Ctime = 0., Ktime = 0.;      // accumulated like :549-552 (seconds)
   hipEvent_t ev_b[3] = {nullptr, nullptr, nullptr};
   bool ev_pending = false;
@@ -3184,6 +3190,7 @@ PpGather pppm_gather_all(conp_fix *f, const conp_atoms *at) {
   }
   if (iota.empty()) iota.push_back(0);
   f->d_pp_iota.upload(iota, f->stream);
+  f->pp_iota_n = 0;
   f->d_pp_xg.upload(xs, f->stream); f->d_pp_qg.upload(qs, f->stream);
   f->sync();                       // (the host vectors go out of scope)
   return g;
@@ -3240,7 +3247,8 @@ constexpr size_t EW_TABLES = (size_t)80 << 20, EW_SLICES = (size_t)40 << 20;
 int ew_block(const conp_fix *f, int n) {
   const KPlan &pl = f->plan;
   const size_t per_atom = ((size_t)pl.R_pad + pl.C_pad + 6 + 2 * ((size_t)pl.kxmax + 2) + 2 * ((size_t)pl.kymax + 1)) * sizeof(double);
-  const int cap = (int)std::max<size_t>(64, std::min<size_t>(8192, EW_TABLES / per_atom / 64 * 64));
+  int cap = (int)std::max<size_t>(64, std::min<size_t>(8192, EW_TABLES / per_atom / 64 * 64));
+  if (debug_ew_block() > 0) cap = debug_ew_block();      // test hook (conp_debug_set_ew_block): several blocks on a deck
   return std::min(cap, std::max(64, (n + 63) / 64 * 64));
 }
 void ew_reserve(conp_fix *f, int nb_pad) {
@@ -3259,11 +3267,13 @@ void ew_reserve(conp_fix *f, int nb_pad) {
   HIP_TRY(hipMemsetAsync(f->d_ew_Ye.p, 0, nye * sizeof(double2), f->stream));
   f->ew_tables_nb = nb_pad; f->ew_tables_gen = f->plan_gen;
 }
-// phase tables of atoms [b0, b0 + nb) of the compact list d_ew_x, nb_pad columns (stale columns >= nb of an earlier block stay finite)
-void ew_tables(conp_fix *f, int b0, int nb, int nb_pad) {
-  launch_ew_seeds(f->stream, nb, f->d_ew_x.p + 3 * (size_t)b0, f->kt.unitk[0], f->kt.unitk[1], f->kt.unitk[2], f->d_ew_seeds.p);
+// phase tables of the nb atoms at xb (device, [nb][3]), nb_pad columns (stale columns >= nb of an earlier block stay finite)
+void ew_tables_at(conp_fix *f, const double *xb, int nb, int nb_pad) {
+  launch_ew_seeds(f->stream, nb, xb, f->kt.unitk[0], f->kt.unitk[1], f->kt.unitk[2], f->d_ew_seeds.p);
   launch_ele_tables(f->stream, f->dplan, f->plan.kzt, nb, nb_pad, f->d_ew_seeds.p, f->d_ew_Xe.p, f->d_ew_Ye.p, f->d_ew_Tz.p, f->d_ew_Rp.p);
 }
+// ... of atoms [b0, b0 + nb) of the compact list d_ew_x
+void ew_tables(conp_fix *f, int b0, int nb, int nb_pad) { ew_tables_at(f, f->d_ew_x.p + 3 * (size_t)b0, nb, nb_pad); }
 // w o G of every charged owned atom at the positions and charges of `at` (not the update's cached arrays) into d_ew_Gwf.
 // Decomposed ranks: each rank contracts its own atoms, G is summed through the host's all-reduce (km_ewald.cpp:784-785) --
 // COLLECTIVE.  Replicated-atom handles (several ranks without conp_fix_set_comm) hold every atom on every rank: no collective.
@@ -3526,6 +3536,136 @@ void pppm_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy
     if (eatom) eatom[i] = he[i];
   }
 }
+// ---- device-resident k-space forces ----
+// What the two entries share: the refusals, Q, Q2, M, M2 of the call's atoms into d_kf_sums[0..3], the parameter blocks.
+void kspace_device_check(conp_fix *f, const double *dx, const double *dq) {
+  if (f->decomposed) throw ConpError(CONP_ERR_STATE, "device-resident updates take replicated atoms (conp_env.rank / nranks); "
+                                                     "spatially decomposed runs use the host-buffer hooks");
+  if (!dx || !dq) throw ConpError(CONP_ERR_ARG, "null argument");
+}
+void kspace_four_sums(conp_fix *f, int n, const double *dx, const double *dq) {
+  f->d_kf_sums.reserve((size_t)4 * (kspace_four_sums_workgroups(n) + 1));
+  launch_kspace_four_sums(f->stream, n, dx, dq, f->d_kf_sums.p + 4, f->d_kf_sums.p);
+}
+KspaceFinish kspace_finish_args(const conp_fix *f, double V, double L) {
+  const double MY_PI = 3.14159265358979323846, MY_PIS = 1.77245385090551602729, g = f->env.g_ewald;
+  KspaceFinish a{};
+  a.qs = f->env.qqrd2e; a.g_pis = g / MY_PIS; a.qcoef = 0.5 * MY_PI / (g * g * V);
+  a.slab = f->env.slabflag ? 1 : 0; a.slab_pref = 2.0 * MY_PI / V; a.L2_12 = L * L / 12.0;
+  return a;
+}
+// (Q, M, M2 stay zero and ecoef lacks its factor Q: kspace_out_from_sums completes the block on the device)
+EwForceOut kspace_out_args(const conp_fix *f, double V, double L) {
+  const double MY_PI = 3.14159265358979323846, MY_PIS = 1.77245385090551602729, g = f->env.g_ewald;
+  EwForceOut o{};
+  o.qs = f->env.qqrd2e; o.selfc = 2.0 * g / MY_PIS; o.ecoef = 0.5 * MY_PI / (g * g * V);
+  o.slab = f->env.slabflag ? 1 : 0;
+  o.fz_pref = -4.0 * MY_PI / V; o.e_pref = 2.0 * MY_PI / V; o.L2_12 = L * L / 12.0;
+  return o;
+}
+// ewald_structure_factor + ewald_forces on the caller's device arrays, every owned atom a column and a target (a zero charge adds
+// zeros): nothing but launches, device-to-device copies and memsets on the handle's stream once the buffers have their sizes.
+void ewald_forces_device(conp_fix *f, const double *dx, const double *dq, double *df, double *dev, double *deatom) {
+  const KTables &kt = f->kt;
+  const KPlan &pl = f->plan;
+  const double L = f->env.zprd * f->env.slab_volfactor;
+  const int n = f->nlocal_cur;
+  if (n <= 0) { if (dev) HIP_TRY(hipMemsetAsync(dev, 0, 7 * sizeof(double), f->stream)); return; }
+  const int nb_pad = ew_block(f, n);
+  const int ntot = (n + nb_pad - 1) / nb_pad * nb_pad;
+  const size_t gsz = (size_t)pl.R_pad * pl.C_pad;
+  const int wgs = std::max(1, pl.C_pad / 64 * pl.n_row_tiles);                   // (ewald_structure_factor's split of a block over slices)
+  int nsplit = std::max(1, std::min({6 * f->num_cus / wgs + 1, 32, nb_pad / 64}));
+  while (nsplit > 1 && (size_t)nsplit * gsz * sizeof(double) > EW_SLICES) --nsplit;
+  ew_reserve(f, nb_pad);
+  // q once into the padded buffer: the last block's padding columns carry no charge; x is read in place, block by block
+  f->d_ew_q.reserve(ntot);
+  HIP_TRY(hipMemcpyAsync(f->d_ew_q.p, dq, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, f->stream));
+  if (ntot > n) HIP_TRY(hipMemsetAsync(f->d_ew_q.p + n, 0, (size_t)(ntot - n) * sizeof(double), f->stream));
+  f->d_ew_Gp.reserve(gsz * nsplit); f->d_ew_G.reserve(gsz); f->d_ew_Gwf.reserve(gsz);
+  HIP_TRY(hipMemsetAsync(f->d_ew_Gp.p, 0, gsz * nsplit * sizeof(double), f->stream));
+  f->ew_g_valid = f->ew_u_valid = false;         // the host entries' scratch is overwritten from here on
+  for (int b0 = 0; b0 < n; b0 += nb_pad) {
+    ew_tables_at(f, dx + 3 * (size_t)b0, std::min(nb_pad, n - b0), nb_pad);
+    launch_ew_sk(f->stream, f->dplan, nb_pad, nsplit, f->d_ew_Rp.p, f->d_ew_Tz.p, f->d_ew_q.p + b0, f->d_ew_Gp.p);
+  }
+  launch_ew_sk_sum(f->stream, f->dplan, nsplit, f->d_ew_Gp.p, f->d_ew_G.p);
+  launch_ew_gw(f->stream, f->dplan, f->d_ew_G.p, f->d_ew_Gwf.p);
+  kspace_four_sums(f, n, dx, dq);
+  if (dev) {
+    const int K = kt.kcount;
+    if (f->ew_kv_gen != f->plan_gen) {           // (once per plan, as in ewald_forces)
+      std::vector<double> kv((size_t)4 * K);
+      for (int k = 0; k < K; ++k) {
+        kv[k] = kt.ug[k];
+        kv[(size_t)K + k] = kt.unitk[0] * kt.kxvecs[k]; kv[2 * (size_t)K + k] = kt.unitk[1] * kt.kyvecs[k];
+        kv[3 * (size_t)K + k] = kt.unitk[2] * kt.kzvecs[k];
+      }
+      f->d_ew_kv.upload(kv, f->stream);
+      f->sync();                     // (kv goes out of scope)
+      f->ew_kv_gen = f->plan_gen;
+    }
+    f->d_ew_ev.reserve((size_t)7 * (ew_energy_virial_workgroups(K) + 1));
+    launch_ew_energy_virial(f->stream, K, pl.C_pad, KPlan::PT, f->d_sf_row_a.p, f->d_sf_col_c.p, f->d_k_sign.p, f->d_ew_kv.p, f->env.g_ewald,
+                            f->d_ew_G.p, f->d_ew_ev.p + 7, f->d_ew_ev.p);
+    launch_kspace_finish(f->stream, kspace_finish_args(f, kt.volume, L), f->d_ew_ev.p, f->d_kf_sums.p, dev);
+  }
+  if (df || deatom) {
+    if (f->ew_tiles_gen != f->plan_gen) {        // the tile lists change with the plan only (the host entries upload the same bytes)
+      f->d_ew_tiles.upload(f->tiles_h, f->stream); f->d_ew_ctptr.upload(f->ct_ptr_h, f->stream);
+      f->sync();
+      f->ew_tiles_gen = f->plan_gen;
+    }
+    f->d_ew_bk.reserve((size_t)16 * nb_pad);
+    const EwForceOut o = kspace_out_args(f, kt.volume, L);
+    for (int b0 = 0; b0 < n; b0 += nb_pad) {
+      const int nb = std::min(nb_pad, n - b0);
+      if (ntot > nb_pad) ew_tables_at(f, dx + 3 * (size_t)b0, nb, nb_pad);       // (one block: its tables are still there)
+      launch_ew_force(f->stream, f->dplan, pl.kzt, kt.unitk[0], kt.unitk[1], kt.unitk[2], nb_pad, f->d_ew_ctptr.p, f->d_ew_tiles.p,
+                      f->d_ew_Gwf.p, f->d_ew_Rp.p, f->d_ew_Tz.p, f->d_ew_bk.p);
+      launch_ew_force_out_device(f->stream, nb, nb_pad, f->d_ew_bk.p, f->d_ew_q.p + b0, dx + 3 * (size_t)b0, o, f->d_kf_sums.p, b0, df,
+                                 deatom);
+    }
+  }
+  HIP_TRY(hipGetLastError());
+}
+// pppm_forces on the caller's device arrays: the brick of every owned atom through the identity list, the mesh solve, the gather
+// on every owned atom; the seven sums stay on the device (kspace_finish_kernel reads them).
+void pppm_forces_device(conp_fix *f, const double *dx, const double *dq, double *df, double *dev, double *deatom) {
+  const double MY_PI = 3.14159265358979323846;
+  const double L = f->env.zprd * f->env.slab_volfactor, V = f->env.xprd * f->env.yprd * L;
+  const int n = f->nlocal_cur;
+  if (n <= 0) { if (dev) HIP_TRY(hipMemsetAsync(dev, 0, 7 * sizeof(double), f->stream)); return; }
+  if (f->pp_iota_n < n) {
+    std::vector<int> iota(n);
+    for (int i = 0; i < n; ++i) iota[i] = i;
+    f->d_pp_iota.upload(iota, f->stream);
+    f->sync();                       // (iota goes out of scope)
+    f->pp_iota_n = n;
+  }
+  f->d_pp_scratch.reserve(2048);
+  f->pp_u_valid = false;             // d_pp_re is overwritten from here on
+  launch_pppm_density(f->stream, f->dpppm, n, f->d_pp_iota.p, dx, dq, f->d_pp_re.p, f->d_pp_scratch.p);
+  ++f->pp_elyte_spreads;
+  kspace_four_sums(f, n, dx, dq);
+  const size_t nf = (size_t)f->dpppm.nfft;
+  const bool fields = df != nullptr, per_atom = df || deatom;
+  if (fields) { f->d_pp_ex.reserve(nf); f->d_pp_ey.reserve(nf); }
+  f->d_pp_kpart.reserve((size_t)7 * (pppm_kspace_workgroups(f->dpppm.nfft) + 1));
+  const double uk[3] = {2.0 * MY_PI / f->env.xprd, 2.0 * MY_PI / f->env.yprd, 2.0 * MY_PI / L};
+  launch_pppm_forward(f->stream, f->dpppm, f->d_pp_re.p, f->d_pp_im.p);
+  launch_pppm_kspace(f->stream, f->dpppm, uk, f->env.g_ewald, V, f->d_pp_re.p, f->d_pp_im.p, fields ? f->d_pp_ex.p : nullptr,
+                     fields ? f->d_pp_ey.p : nullptr, f->d_pp_kpart.p + 7, f->d_pp_kpart.p);
+  f->pp_im_clean = false;
+  if (dev) launch_kspace_finish(f->stream, kspace_finish_args(f, V, L), f->d_pp_kpart.p, f->d_kf_sums.p, dev);
+  if (per_atom) {
+    launch_pppm_backward(f->stream, f->dpppm, f->d_pp_re.p, f->d_pp_im.p);
+    if (fields) launch_pppm_backward(f->stream, f->dpppm, f->d_pp_ex.p, f->d_pp_ey.p);
+    launch_pppm_force_gather_device(f->stream, f->dpppm, n, dx, dq, fields ? f->d_pp_ex.p : nullptr, f->d_pp_ey.p, f->d_pp_im.p,
+                                    f->d_pp_re.p, kspace_out_args(f, V, L), f->d_kf_sums.p, df, deatom);
+  }
+  HIP_TRY(hipGetLastError());
+}
 // the k-space tail of compute potential/atom (compute_potential_atom.cpp:165-175, slab correction :323-345) on the selected owned
 // atoms idx (ascending), whichever provider formed u_i: pot_i -= u_i, + the Gaussian self term of eta atoms, + the slab terms
 // (the sums of q z and q over the owned atoms all-reduced, MPI_Allreduce :331, :337)
@@ -3744,6 +3884,30 @@ int conp_pppm_compute_forces(conp_fix *f, const conp_atoms *at, double *fout, do
                                     "conp_ewald_compute_forces");
   need_pppm(f);
   pppm_forces(f, at, fout, energy, virial, eatom);
+  CONP_GUARD_END
+}
+
+// The device-resident twins: device pointers, everything enqueued on the handle's stream, no
+// synchronisation, S / the density brick formed from the arrays of the call; the host entries' caches are dropped.
+int conp_ewald_compute_forces_device(conp_fix *f, const double *d_x, const double *d_q, double *d_f, double *d_ev, double *d_eatom) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->drop_graph();
+  need_ewald(f);
+  kspace_device_check(f, d_x, d_q);
+  if (!d_f && !d_ev && !d_eatom) return CONP_OK;
+  ewald_forces_device(f, d_x, d_q, d_f, d_ev, d_eatom);
+  CONP_GUARD_END
+}
+
+int conp_pppm_compute_forces_device(conp_fix *f, const double *d_x, const double *d_q, double *d_f, double *d_ev, double *d_eatom) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->drop_graph();
+  need_pppm(f);
+  kspace_device_check(f, d_x, d_q);
+  if (!d_f && !d_ev && !d_eatom) return CONP_OK;
+  pppm_forces_device(f, d_x, d_q, d_f, d_ev, d_eatom);
   CONP_GUARD_END
 }
 

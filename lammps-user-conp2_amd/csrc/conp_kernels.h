@@ -14,6 +14,7 @@ namespace conp {
 // CONP_TIME_HOST / _REN.  Decided experiments ("measured, not kept") are recorded in DESIGN-LOG.md, not kept as switches.
 bool path_on(unsigned bit);
 int debug_sk_workgroups();
+int debug_ew_block();                        // conp_debug_set_ew_block: cap of the Ewald entries' block width (0: the library's choice)
 const char *env_knob(const char *name);      // operational knob: getenv + one line on stderr the first time a set knob is read
 
 // raise a kernel's dynamic-LDS limit, only when a launch needs more than it was last given: per-update launches must not
@@ -177,6 +178,9 @@ struct EwForceOut {
 };
 // the tail both k-space force entries share (Ewald::slabcorr and PPPM::slabcorr are the same formulas): atom a with charge qi at
 // height z, g = minus its k-space potential (no self term), (fx, fy, fz) = qi times the field -> slab force, per-atom energy, qqrd2e
+// ADD: the device-resident entries accumulate into the caller's force array (one lane owns one atom: load, add, store); the host
+// entries overwrite a scratch array
+template <bool ADD = false>
 __device__ __forceinline__ void kspace_atom_out(const EwForceOut &o, double qi, double z, double g, double fx, double fy, double fz,
                                                 size_t a, double *__restrict__ fo, double *__restrict__ eo) {
   double e = -0.5 * qi * (g + o.selfc * qi) - o.ecoef * qi;
@@ -184,12 +188,43 @@ __device__ __forceinline__ void kspace_atom_out(const EwForceOut &o, double qi, 
     fz += o.fz_pref * qi * (o.M - o.Q * z);
     e += o.e_pref * qi * (z * o.M - 0.5 * (o.M2 + o.Q * z * z) - o.Q * o.L2_12);
   }
-  if (fo) { fo[3 * a] = o.qs * fx; fo[3 * a + 1] = o.qs * fy; fo[3 * a + 2] = o.qs * fz; }
+  if (fo) {
+    if (ADD) { fo[3 * a] += o.qs * fx; fo[3 * a + 1] += o.qs * fy; fo[3 * a + 2] += o.qs * fz; }
+    else { fo[3 * a] = o.qs * fx; fo[3 * a + 1] = o.qs * fy; fo[3 * a + 2] = o.qs * fz; }
+  }
   if (eo) eo[a] = o.qs * e;
+}
+// the device-resident entries' EwForceOut: Q, M, M2 from the four sums on the device (four = Q, Q2, M, M2), and o.ecoef arrives
+// as (pi / 2) / (g^2 V), without its factor Q
+__device__ __forceinline__ EwForceOut kspace_out_from_sums(EwForceOut o, const double *__restrict__ four) {
+  o.Q = four[0]; o.M = four[2]; o.M2 = four[3];
+  o.ecoef *= o.Q;
+  return o;
 }
 void launch_ew_force_out(hipStream_t s, int n, int nb_pad, const double *bk /*[4][4][nb_pad]*/, const int *idx, const double *q,
                          const double *x /*[n][3]*/, const EwForceOut &o, double *fo /*[nlocal][3], written at idx*/,
                          double *eo /*[nlocal]*/);
+
+// ---- device-resident k-space forces (conp_ewald_compute_forces_device / conp_pppm_compute_forces_device) ----
+// sums[4] = Q, Q2, M, M2 = the sums of q, q^2, q z, q z^2 over the atoms [0, n), in ew_energy_virial_kernel's fixed order (no
+// atomics).  part: [kspace_four_sums_workgroups(n)][4] scratch
+int kspace_four_sums_workgroups(int n);
+void launch_kspace_four_sums(hipStream_t s, int n, const double *x /*[n][3]*/, const double *q, double *part, double *sums);
+// ev[7] = energy and the six virial components from the seven k-space sums s7 (launch_ew_energy_virial / launch_pppm_kspace) and
+// the four sums: what the host entries evaluate after their synchronisation
+struct KspaceFinish {
+  double qs, g_pis /*g / sqrt(pi)*/, qcoef /*(pi / 2) / (g^2 V)*/, slab_pref /*2 pi / V*/, L2_12 /*L^2 / 12*/;
+  int slab;
+};
+void launch_kspace_finish(hipStream_t s, const KspaceFinish &a, const double *s7, const double *four, double *ev);
+// launch_ew_force_out for the atoms [base, base + n) themselves (no index list): q, x are the block's, Q, M, M2 and the factor of
+// o.ecoef come from `four` (kspace_out_from_sums), fo is ADDED to, eo overwritten
+void launch_ew_force_out_device(hipStream_t s, int n, int nb_pad, const double *bk, const double *q, const double *x, const EwForceOut &o,
+                                const double *four, int base, double *fo /*[nlocal][3], +=; NULL: none*/, double *eo /*[nlocal]; NULL: none*/);
+// launch_pppm_force_gather likewise, every atom [0, n) a target
+void launch_pppm_force_gather_device(hipStream_t s, const PppmDev &pd, int n, const double *x, const double *q, const double *ex,
+                                     const double *ey, const double *ez, const double *u, const EwForceOut &o, const double *four,
+                                     double *fo, double *eo);
 
 // ---- the z-window form of the structure-factor contraction (conp_zn.hip, round 5) ------------------------------------------------
 // item = (row tile: 64 planar vectors, chunk range [c0, c1) of the z-ordered electrolyte list, window origin g0 on the grid, slot of

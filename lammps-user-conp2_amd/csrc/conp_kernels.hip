@@ -35,6 +35,7 @@ const char *env_knob(const char *name) {
 }
 static std::atomic<unsigned> g_paths{0};
 static std::atomic<int> g_sk_nwg{0};
+static std::atomic<int> g_ew_block{0};
 bool path_on(unsigned bit) {
   const unsigned m = g_paths.load(std::memory_order_relaxed);
   if (m & bit) {
@@ -45,8 +46,10 @@ bool path_on(unsigned bit) {
   return false;
 }
 int debug_sk_workgroups() { return g_sk_nwg.load(std::memory_order_relaxed); }
+int debug_ew_block() { return g_ew_block.load(std::memory_order_relaxed); }
 extern "C" void conp_debug_set_paths(unsigned mask) { g_paths.store(mask, std::memory_order_relaxed); }
 extern "C" void conp_debug_set_sk_workgroups(int n) { g_sk_nwg.store(n > 0 ? n : 0, std::memory_order_relaxed); }
+extern "C" void conp_debug_set_ew_block(int n) { g_ew_block.store(n > 0 ? (n + 63) / 64 * 64 : 0, std::memory_order_relaxed); }
 
 __device__ double block_sum_1024(double v, double *red);
 

@@ -293,10 +293,13 @@ __global__ __launch_bounds__(256) void ew_energy_virial_kernel(int K, int C_pad,
 }
 
 // the four parts of ew_force_kernel's four quantities in b_project's fixed order; force (with the slab term), per-atom energy,
-// scattered to the targets' local indices.  fo: [nlocal][3] and eo: [nlocal], overwritten at idx (the host accumulates)
+// scattered to the targets' local indices.  fo: [nlocal][3] and eo: [nlocal], overwritten at idx (the host accumulates).
+// DEV (the device-resident entry): atom i of the block is atom base + i itself, Q, M, M2 are read from `four`, fo is added to
+template <bool DEV>
 __global__ __launch_bounds__(256) void ew_force_out_kernel(int n, int nb_pad, const double *__restrict__ bk, const int *__restrict__ idx,
                                                            const double *__restrict__ q, const double *__restrict__ x, EwForceOut o,
-                                                           double *__restrict__ fo, double *__restrict__ eo) {
+                                                           const double *__restrict__ four, int base, double *__restrict__ fo,
+                                                           double *__restrict__ eo) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   double v[4];
@@ -306,7 +309,58 @@ __global__ __launch_bounds__(256) void ew_force_out_kernel(int n, int nb_pad, co
     v[c] = (b[0] + b[(size_t)nb_pad]) + (b[2 * (size_t)nb_pad] + b[3 * (size_t)nb_pad]);
   }
   const double qi = q[i];
-  kspace_atom_out(o, qi, x[3 * (size_t)i + 2], v[0], qi * v[1], qi * v[2], qi * v[3], (size_t)idx[i], fo, eo);
+  if (DEV)
+    kspace_atom_out<true>(kspace_out_from_sums(o, four), qi, x[3 * (size_t)i + 2], v[0], qi * v[1], qi * v[2], qi * v[3],
+                          (size_t)base + i, fo, eo);
+  else
+    kspace_atom_out(o, qi, x[3 * (size_t)i + 2], v[0], qi * v[1], qi * v[2], qi * v[3], (size_t)idx[i], fo, eo);
+}
+
+// Q, Q2, M, M2 over the atoms [0, n) (zero charges add exact zeros) in ew_energy_virial_kernel's scheme: thread t of workgroup b
+// adds the atoms 256 b + t, + 256 gridDim.x, ... in that order, the workgroup adds its threads in a binary tree, and the last launch
+// (final = 1, one workgroup) adds the workgroups' rows the same way: a fixed order for a given n, no atomics.  part: [gridDim.x][4]
+__global__ __launch_bounds__(256) void kspace_four_sums_kernel(int n, const double *__restrict__ x, const double *__restrict__ q,
+                                                               const double *__restrict__ in, int nin, double *__restrict__ part,
+                                                               int final) {
+  __shared__ double sh[4][256];
+  const int t = threadIdx.x;
+  double a[4] = {0.0, 0.0, 0.0, 0.0};
+  if (final) {
+    for (int j = t; j < nin; j += 256)
+#pragma unroll
+      for (int v = 0; v < 4; ++v) a[v] += in[(size_t)j * 4 + v];
+  } else {
+    for (int i = blockIdx.x * 256 + t; i < n; i += 256 * gridDim.x) {
+      const double qi = q[i], z = x[3 * (size_t)i + 2];
+      a[0] += qi; a[1] += qi * qi; a[2] += qi * z; a[3] += qi * z * z;
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < 4; ++v) sh[v][t] = a[v];
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s)
+#pragma unroll
+      for (int v = 0; v < 4; ++v) sh[v][t] += sh[v][t + s];
+    __syncthreads();
+  }
+  if (t < 4) part[(size_t)blockIdx.x * 4 + t] = sh[t][0];
+}
+
+// ev[0] = qs (s7[0] - g Q2 / sqrt(pi) - (pi / 2) Q^2 / (g^2 V) [+ 2 pi (M^2 - Q M2 - Q^2 L^2 / 12) / V]), ev[1 + c] = qs s7[1 + c]:
+// the host entries' expressions, one lane per output
+__global__ __launch_bounds__(64) void kspace_finish_kernel(KspaceFinish a, const double *__restrict__ s7, const double *__restrict__ four,
+                                                          double *__restrict__ ev) {
+#pragma clang fp contract(off)
+  const int t = threadIdx.x;
+  if (t >= 7) return;
+  double v = s7[t];
+  if (t == 0) {
+    const double Q = four[0], Q2 = four[1], M = four[2], M2 = four[3];
+    v = v - a.g_pis * Q2 - a.qcoef * Q * Q;
+    if (a.slab) v += a.slab_pref * (M * M - Q * M2 - Q * Q * a.L2_12);
+  }
+  ev[t] = a.qs * v;
 }
 
 void launch_ew_seeds(hipStream_t s, int n, const double *x, double ux, double uy, double uz, double *seeds) {
@@ -361,7 +415,27 @@ void launch_ew_energy_virial(hipStream_t s, int K, int C_pad, int PT, const int 
 void launch_ew_force_out(hipStream_t s, int n, int nb_pad, const double *bk, const int *idx, const double *q, const double *x,
                          const EwForceOut &o, double *fo, double *eo) {
   if (n <= 0) return;
-  hipLaunchKernelGGL(ew_force_out_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, nb_pad, bk, idx, q, x, o, fo, eo);
+  hipLaunchKernelGGL(ew_force_out_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, s, n, nb_pad, bk, idx, q, x, o,
+                     (const double *)nullptr, 0, fo, eo);
+}
+
+void launch_ew_force_out_device(hipStream_t s, int n, int nb_pad, const double *bk, const double *q, const double *x, const EwForceOut &o,
+                                const double *four, int base, double *fo, double *eo) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(ew_force_out_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, s, n, nb_pad, bk, (const int *)nullptr, q, x, o,
+                     four, base, fo, eo);
+}
+
+int kspace_four_sums_workgroups(int n) { return std::max(1, std::min(256, (n + 255) / 256)); }
+
+void launch_kspace_four_sums(hipStream_t s, int n, const double *x, const double *q, double *part, double *sums) {
+  const int nwg = kspace_four_sums_workgroups(n);
+  hipLaunchKernelGGL(kspace_four_sums_kernel, dim3(nwg), dim3(256), 0, s, n, x, q, (const double *)nullptr, 0, part, 0);
+  hipLaunchKernelGGL(kspace_four_sums_kernel, dim3(1), dim3(256), 0, s, n, x, q, (const double *)part, nwg, sums, 1);
+}
+
+void launch_kspace_finish(hipStream_t s, const KspaceFinish &a, const double *s7, const double *four, double *ev) {
+  hipLaunchKernelGGL(kspace_finish_kernel, dim3(1), dim3(64), 0, s, a, s7, four, ev);
 }
 
 }  // namespace conp

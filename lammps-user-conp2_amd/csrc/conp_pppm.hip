@@ -886,10 +886,13 @@ int pppm_kspace_workgroups(int nfft) { const int w = (nfft + 255) / 256; return 
 // over the field bricks (and u when `eo` is wanted) with pppm_probe_kernel's weights and index conventions -- lanes take (z, y)
 // stencil rows, a shuffle tree adds them -- then kspace_atom_out (the Ewald entry's tail: qs q_i, slab force, e_i), scattered by local
 // index.  Every atom is written by its own wave: no atomics.  fo: [nlocal][3], eo: [nlocal], overwritten at idx (the host accumulates)
+// DEV (the device-resident entry): atom k itself (no index list), Q, M, M2 read from `four`, fo added to
+template <bool DEV>
 __global__ __launch_bounds__(256) void pppm_force_gather_kernel(PppmDev pd, int n, const int *__restrict__ idx, const double *__restrict__ x,
                                                                 const double *__restrict__ q, const double *__restrict__ ex,
                                                                 const double *__restrict__ ey, const double *__restrict__ ez,
-                                                                const double *__restrict__ u, EwForceOut o, double *__restrict__ fo,
+                                                                const double *__restrict__ u, EwForceOut o,
+                                                                const double *__restrict__ four, double *__restrict__ fo,
                                                                 double *__restrict__ eo) {
   __shared__ double coeff[64];
   if (threadIdx.x < pd.order * pd.order) coeff[threadIdx.x] = pd.rho_coeff[threadIdx.x];
@@ -900,7 +903,7 @@ __global__ __launch_bounds__(256) void pppm_force_gather_kernel(PppmDev pd, int 
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int k = blockIdx.x * 4 + wave;
   if (k >= n) return;
-  const int i = idx[k];
+  const int i = DEV ? k : idx[k];
   const double xs0 = (x[3 * (size_t)i] - pd.boxlo[0]) * pd.delinv[0];
   const double xs1 = (x[3 * (size_t)i + 1] - pd.boxlo[1]) * pd.delinv[1];
   const double xs2 = (x[3 * (size_t)i + 2] - pd.boxlo[2]) * pd.delinv[2];
@@ -934,7 +937,8 @@ __global__ __launch_bounds__(256) void pppm_force_gather_kernel(PppmDev pd, int 
   }
   if (lane == 0) {
     const double qi = q[i];
-    kspace_atom_out(o, qi, x[3 * (size_t)i + 2], -au, qi * ax, qi * ay, qi * az, (size_t)i, fo, eo);
+    if (DEV) kspace_atom_out<true>(kspace_out_from_sums(o, four), qi, x[3 * (size_t)i + 2], -au, qi * ax, qi * ay, qi * az, (size_t)i, fo, eo);
+    else kspace_atom_out(o, qi, x[3 * (size_t)i + 2], -au, qi * ax, qi * ay, qi * az, (size_t)i, fo, eo);
   }
 }
 
@@ -958,7 +962,16 @@ void launch_pppm_kspace(hipStream_t s, const PppmDev &pd, const double uk[3], do
 void launch_pppm_force_gather(hipStream_t s, const PppmDev &pd, int n, const int *idx, const double *x, const double *q, const double *ex,
                               const double *ey, const double *ez, const double *u, const EwForceOut &o, double *fo, double *eo) {
   if (n <= 0) return;
-  hipLaunchKernelGGL(pppm_force_gather_kernel, dim3((n + 3) / 4), dim3(256), 0, s, pd, n, idx, x, q, ex, ey, ez, u, o, fo, eo);
+  hipLaunchKernelGGL(pppm_force_gather_kernel<false>, dim3((n + 3) / 4), dim3(256), 0, s, pd, n, idx, x, q, ex, ey, ez, u, o,
+                     (const double *)nullptr, fo, eo);
+}
+
+void launch_pppm_force_gather_device(hipStream_t s, const PppmDev &pd, int n, const double *x, const double *q, const double *ex,
+                                     const double *ey, const double *ez, const double *u, const EwForceOut &o, const double *four,
+                                     double *fo, double *eo) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(pppm_force_gather_kernel<true>, dim3((n + 3) / 4), dim3(256), 0, s, pd, n, (const int *)nullptr, x, q, ex, ey, ez, u,
+                     o, four, fo, eo);
 }
 
 // ---- compute potential/atom, pair part (compute_potential_atom.cpp:223-308): one wavefront per list owner -------------------
