@@ -417,6 +417,33 @@ int conp_ewald_compute_forces_device(conp_fix *fix, const double *d_x, const dou
                                      double *d_ev    /* [7]: energy, then virial xx,yy,zz,xy,xz,yz; overwritten; NULL ok */,
                                      double *d_eatom /* [nlocal], overwritten; NULL ok */);
 int conp_pppm_compute_forces_device(conp_fix *fix, const double *d_x, const double *d_q, double *d_f, double *d_ev, double *d_eatom);
+
+/* ---- per-atom virial of the k-space force entries: the missing output of a KSpace style's compute() ------
+ * Each entry is its sibling above with one more trailing output, vatom [nlocal][6] in the order xx, yy, zz, xy, xz, yz, so that
+ * S / the density brick and the forward transform are formed once per step for all outputs.  Notation of the siblings: the half
+ * list with ug_k, qs = env.qqrd2e, g = env.g_ewald, S_k of the atoms of the call,
+ *   vg_ab(k) = delta_ab - 2 (1 / k^2 + 1 / (4 g^2)) k_a k_b.
+ * Ewald (LAMMPS Ewald::compute's vatom), with A_i(k) = cos(k r_i) Re S_k + sin(k r_i) Im S_k:
+ *   vatom_i,ab = qs q_i sum_k ug_k vg_ab(k) A_i(k)                  (sum_i vatom_i,ab = the entry's virial, as sum_i q_i A_i = |S_k|^2)
+ * PPPM (poisson_peratom / fieldforce_peratom of pppm.cpp @ 27May2021, ik), with phi_k = G_k rho^_k / N:
+ *   v_ab = Re IFFT[vg_ab(k) phi_k]   (k = 0: nothing),   vatom_i,ab = qs q_i / 2 sum_stencil w v_ab(mesh point)
+ * with the stencil weights of the force gather.  For an even mesh length an off-diagonal component on the plane where exactly one
+ * of its two axes sits at m = -n / 2 has an imaginary inverse, which the real part drops (both axes there: kept).
+ * The slab correction adds nothing to the per-atom virial (as in LAMMPS).  A zero-charge atom's six entries are exactly 0.0.  The
+ * array is overwritten, like eatom.
+ * vatom == NULL: the sibling -- the Ewald entries return the same bits, the PPPM entries agree to the rounding the spread's atomic
+ * adds allow.  Everything else is the sibling's contract word for word: the cache rules of the host entries; for the _device entries
+ * no cache and no allocation / host copy / synchronisation after the first call, all outputs NULL -> CONP_OK, nothing done;
+ * CONP_ERR_STATE on the other provider's handle, and for a decomposed handle on the _device entries.  The host entries are COLLECTIVE
+ * under decomposed ranks exactly as the siblings are; the per-atom virial needs no collective of its own (S / the mesh is global). */
+int conp_ewald_compute_forces_vatom(conp_fix *fix, const conp_atoms *atoms, double *f, double *energy, double *virial, double *eatom,
+                                    double *vatom /* [nlocal][6] xx,yy,zz,xy,xz,yz, overwritten, NULL ok */);
+int conp_pppm_compute_forces_vatom(conp_fix *fix, const conp_atoms *atoms, double *f, double *energy, double *virial, double *eatom,
+                                   double *vatom /* [nlocal][6], overwritten, NULL ok */);
+int conp_ewald_compute_forces_vatom_device(conp_fix *fix, const double *d_x, const double *d_q, double *d_f, double *d_ev, double *d_eatom,
+                                           double *d_vatom /* [nlocal][6], overwritten; NULL ok */);
+int conp_pppm_compute_forces_vatom_device(conp_fix *fix, const double *d_x, const double *d_q, double *d_f, double *d_ev, double *d_eatom,
+                                          double *d_vatom /* [nlocal][6], overwritten; NULL ok */);
 /* per-kernel timing of the last N updates via HIP events on the library's stream (bench.py roofline leg).
  * enable: 0 off, 1 a pair of events around every kernel, 2 around every 4th launch of the dominant kernel (sk_gemm) only --
  * cheap enough to stay on inside a timed region (an event pair drains the queue around the kernel it brackets). */

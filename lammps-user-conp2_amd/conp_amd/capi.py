@@ -100,6 +100,8 @@ SYMBOLS = [
     "conp_ewald_compute", "conp_ewald_compute_group_potential", "conp_ewald_compute_particle_potential",
     "conp_ewald_compute_forces", "conp_pppm_compute_forces",
     "conp_ewald_compute_forces_device", "conp_pppm_compute_forces_device",
+    "conp_ewald_compute_forces_vatom", "conp_pppm_compute_forces_vatom",
+    "conp_ewald_compute_forces_vatom_device", "conp_pppm_compute_forces_vatom_device",
     "conp_compute_potential_atom",
 ]
 
@@ -226,6 +228,11 @@ def load_library():
     if hasattr(lib, "conp_ewald_compute_forces_device"):      # (comparison builds loaded through CONP_LIB lack these)
         lib.conp_ewald_compute_forces_device.argtypes = [vp, vp, vp, vp, vp, vp]
         lib.conp_pppm_compute_forces_device.argtypes = [vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "conp_ewald_compute_forces_vatom"):
+        lib.conp_ewald_compute_forces_vatom.argtypes = [vp, C.POINTER(conp_atoms), dp, dp, dp, dp, dp]
+        lib.conp_pppm_compute_forces_vatom.argtypes = [vp, C.POINTER(conp_atoms), dp, dp, dp, dp, dp]
+        lib.conp_ewald_compute_forces_vatom_device.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        lib.conp_pppm_compute_forces_vatom_device.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         lib.conp_debug_set_ew_block.argtypes = [C.c_int]
         lib.conp_debug_set_ew_block.restype = None
     lib.conp_compute_potential_atom.argtypes = [vp, C.POINTER(conp_atoms), C.POINTER(conp_neighlist), ip, ip,
@@ -529,6 +536,29 @@ class FixConp:
                                                       _dptr(e) if eatom else None))
         return f, (en.value if energy else None), w, e
 
+    def _forces_vatom(self, entry, at, energy, virial, eatom, f, forces, vatom):
+        if forces:
+            f = np.zeros((at.nlocal, 3)) if f is None else f
+            assert f.dtype == np.float64 and f.flags.c_contiguous and f.shape == (at.nlocal, 3)
+        else:
+            f = None
+        en = C.c_double() if energy else None
+        w = np.zeros(6) if virial else None
+        e = np.zeros(at.nlocal) if eatom else None
+        v = np.full((at.nlocal, 6), np.nan) if vatom else None        # (overwritten by the entry, zero-charge rows included)
+        self._check(entry(self.h, C.byref(self.atoms_view(at)), _dptr(f) if forces else None, C.byref(en) if energy else None,
+                          _dptr(w) if virial else None, _dptr(e) if eatom else None, _dptr(v) if vatom else None))
+        return f, (en.value if energy else None), w, e, v
+
+    def ewald_forces_vatom(self, at, energy=True, virial=True, eatom=False, f=None, forces=True, vatom=True):
+        """conp_ewald_compute_forces_vatom: ewald_forces with the per-atom virial [nlocal][6] (xx, yy, zz, xy, xz, yz) as one more
+        output -> (f, E, W, e, v); what was not asked for is None"""
+        return self._forces_vatom(self.lib.conp_ewald_compute_forces_vatom, at, energy, virial, eatom, f, forces, vatom)
+
+    def pppm_forces_vatom(self, at, energy=True, virial=True, eatom=False, f=None, forces=True, vatom=True):
+        """conp_pppm_compute_forces_vatom: the mesh twin of ewald_forces_vatom (`pppm` handles)"""
+        return self._forces_vatom(self.lib.conp_pppm_compute_forces_vatom, at, energy, virial, eatom, f, forces, vatom)
+
     def compute_potential_atom(self, at, pairlist, sel, etasel=None, eta=0.0, pair=True, kspace=True, qsum=True):
         sel = np.ascontiguousarray(sel, np.int32)
         es = None if etasel is None else np.ascontiguousarray(etasel, np.int32)
@@ -660,6 +690,16 @@ class FixConp:
         """conp_pppm_compute_forces_device: the mesh twin of ewald_forces_device (`pppm` handles)"""
         self._check(self.lib.conp_pppm_compute_forces_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q), C.c_void_p(d_f),
                                                              C.c_void_p(d_ev), C.c_void_p(d_eatom)))
+
+    def ewald_forces_vatom_device(self, d_x: int, d_q: int, d_f: int = 0, d_ev: int = 0, d_eatom: int = 0, d_vatom: int = 0):
+        """conp_ewald_compute_forces_vatom_device: ewald_forces_device with d_vatom [nlocal][6] (xx, yy, zz, xy, xz, yz), overwritten"""
+        self._check(self.lib.conp_ewald_compute_forces_vatom_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q), C.c_void_p(d_f),
+                                                                    C.c_void_p(d_ev), C.c_void_p(d_eatom), C.c_void_p(d_vatom)))
+
+    def pppm_forces_vatom_device(self, d_x: int, d_q: int, d_f: int = 0, d_ev: int = 0, d_eatom: int = 0, d_vatom: int = 0):
+        """conp_pppm_compute_forces_vatom_device: the mesh twin of ewald_forces_vatom_device (`pppm` handles)"""
+        self._check(self.lib.conp_pppm_compute_forces_vatom_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q), C.c_void_p(d_f),
+                                                                   C.c_void_p(d_ev), C.c_void_p(d_eatom), C.c_void_p(d_vatom)))
 
     def profile(self, enable):
         """0 off, 1 events around every kernel, 2 around the dominant kernel only (conp_hip.h)"""

@@ -298,6 +298,8 @@ struct conp_fix {
   int pp_elyte_spreads = 0;      // how often the electrolyte atoms were spread onto the mesh (b_cal and density queries)
   DevBuf<double> d_pp_elyte, d_pp_xg, d_pp_qg;
   DevBuf<double> d_pp_ex, d_pp_ey, d_pp_kpart, d_pp_fo, d_pp_eo;      // conp_pppm_compute_forces: E_x, E_y bricks, the seven sums, outputs
+  DevBuf<double> d_pp_v[6], d_pp_vo;           // ..._vatom: the six v_ab bricks (xx, yy, zz, xy, xz, yz), the per-atom virial (section 15)
+  DevBuf<double> d_ew_Gwf2, d_ew_vk, d_ew_v;   // conp_ewald_compute_forces_vatom: (c o w) o G, ew_vatom_kernel's parts, the per-atom virial
   DevBuf<int> d_pp_fidx;
   DevBuf<int> d_pp_iota;
   // Ewald per-atom potential (conp_ewald_*, conp_compute_potential_atom on an Ewald handle; conp_potential.hip): the structure factor
@@ -3354,7 +3356,8 @@ void ewald_project(conp_fix *f, const conp_atoms *at, const std::vector<int> &id
 // f_i += qqrd2e q_i grad g_i (+ slab) on every charged owned atom, from d_ew_Gwf at the atoms' positions in `at`: ewald_project's
 // blocking with ew_force_kernel in b_project_kernel's place; energy and virial from d_ew_G.  The sums of q, q^2, q z, q z^2 over the
 // owned atoms are all-reduced under decomposed ranks (COLLECTIVE there); S itself is the caller's business (ew_g_valid).
-void ewald_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy, double *virial, double *eatom) {
+void ewald_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy, double *virial, double *eatom,
+                  double *vatom = nullptr /*[nlocal][6], overwritten: the per-atom virial*/) {
   const double MY_PI = 3.14159265358979323846, MY_PIS = 1.77245385090551602729;
   const KTables &kt = f->kt;
   const double g = f->env.g_ewald, qs = f->env.qqrd2e, V = kt.volume;
@@ -3398,8 +3401,9 @@ void ewald_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energ
     if (virial) for (int c = 0; c < 6; ++c) virial[c] = qs * s7[1 + c];
   }
   if (eatom) std::fill(eatom, eatom + at->nlocal, 0.0);
+  if (vatom) std::fill(vatom, vatom + 6 * (size_t)at->nlocal, 0.0);
   const int n = (int)idx.size();
-  if (n == 0 || (!fout && !eatom)) return;
+  if (n == 0 || (!fout && !eatom && !vatom)) return;
   const int nb_pad = ew_block(f, n);
   const int ntot = (n + nb_pad - 1) / nb_pad * nb_pad;
   std::vector<double> xs(3 * (size_t)ntot, 0.0), qv(ntot, 0.0);
@@ -3413,6 +3417,11 @@ void ewald_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energ
   f->d_ew_tiles.upload(f->tiles_h, f->stream); f->d_ew_ctptr.upload(f->ct_ptr_h, f->stream);
   f->d_ew_bk.reserve((size_t)16 * nb_pad);
   f->d_ew_f.reserve(3 * (size_t)at->nlocal); f->d_ew_e.reserve(at->nlocal);
+  if (vatom) {
+    f->d_ew_Gwf2.reserve((size_t)f->plan.R_pad * f->plan.C_pad); f->d_ew_vk.reserve((size_t)24 * nb_pad);
+    f->d_ew_v.reserve(6 * (size_t)at->nlocal);
+    launch_ew_gw2(f->stream, f->dplan, f->plan.kzt, kt.unitk[0], kt.unitk[1], kt.unitk[2], g, f->d_ew_G.p, f->d_ew_Gwf2.p);
+  }
   EwForceOut o{};
   o.qs = qs; o.selfc = 2.0 * g / MY_PIS; o.ecoef = 0.5 * MY_PI * Q / (g * g * V);
   o.slab = f->env.slabflag ? 1 : 0;
@@ -3424,6 +3433,16 @@ void ewald_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energ
                     f->d_ew_Gwf.p, f->d_ew_Rp.p, f->d_ew_Tz.p, f->d_ew_bk.p);
     launch_ew_force_out(f->stream, nb, nb_pad, f->d_ew_bk.p, f->d_ew_idx.p + b0, f->d_ew_q.p + b0, f->d_ew_x.p + 3 * (size_t)b0, o,
                         f->d_ew_f.p, f->d_ew_e.p);
+    if (vatom) {
+      launch_ew_vatom(f->stream, f->dplan, f->plan.kzt, kt.unitk[0], kt.unitk[1], kt.unitk[2], nb_pad, f->d_ew_ctptr.p, f->d_ew_tiles.p,
+                      f->d_ew_Gwf2.p, f->d_ew_Rp.p, f->d_ew_Tz.p, f->d_ew_vk.p);
+      launch_ew_vatom_out(f->stream, nb, nb_pad, f->d_ew_bk.p, f->d_ew_vk.p, f->d_ew_idx.p + b0, f->d_ew_q.p + b0, qs, f->d_ew_v.p);
+    }
+  }
+  std::vector<double> hv;
+  if (vatom) {
+    hv.resize(6 * (size_t)at->nlocal);
+    HIP_TRY(hipMemcpyAsync(hv.data(), f->d_ew_v.p, hv.size() * sizeof(double), hipMemcpyDeviceToHost, f->stream));
   }
   std::vector<double> hf(3 * (size_t)at->nlocal), he(at->nlocal);
   HIP_TRY(hipMemcpyAsync(hf.data(), f->d_ew_f.p, hf.size() * sizeof(double), hipMemcpyDeviceToHost, f->stream));
@@ -3433,6 +3452,7 @@ void ewald_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energ
   for (int i : idx) {
     if (fout) for (int c = 0; c < 3; ++c) fout[3 * (size_t)i + c] += hf[3 * (size_t)i + c];
     if (eatom) eatom[i] = he[i];
+    if (vatom) for (int c = 0; c < 6; ++c) vatom[6 * (size_t)i + c] = hv[6 * (size_t)i + c];
   }
 }
 // ---- PPPM forces, energy, virial ----
@@ -3441,7 +3461,8 @@ void ewald_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energ
 // moved), forward transform, pppm_kspace_kernel, two packed backward transforms, pppm_force_gather_kernel on the charged owned atoms.
 // COLLECTIVE under decomposed ranks like pppm_total_potential (one tagged gather, a replicated mesh) plus the four sums.  Leaves u in
 // d_pp_re (pp_u_valid), as conp_pppm_compute does.
-void pppm_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy, double *virial, double *eatom) {
+void pppm_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy, double *virial, double *eatom,
+                 double *vatom = nullptr /*[nlocal][6], overwritten: the per-atom virial*/) {
   const double MY_PI = 3.14159265358979323846, MY_PIS = 1.77245385090551602729;
   const double g = f->env.g_ewald, qs = f->env.qqrd2e;
   const double L = f->env.zprd * f->env.slab_volfactor, V = f->env.xprd * f->env.yprd * L;
@@ -3480,6 +3501,13 @@ void pppm_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy
   f->prof.begin("pppm_f_forward", f->stream);
   launch_pppm_forward(f->stream, f->dpppm, f->d_pp_re.p, f->d_pp_im.p);
   f->prof.end(f->stream);
+  const bool want_v = vatom != nullptr && n > 0;
+  double *vb[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (want_v) {                      // (rho^ is still in (re, im): the kspace launch below overwrites it)
+    for (int c = 0; c < 6; ++c) { f->d_pp_v[c].reserve(nf); vb[c] = f->d_pp_v[c].p; }
+    launch_pppm_vatom_spectra(f->stream, f->dpppm, uk, g, f->d_pp_re.p, f->d_pp_im.p, vb);
+    for (int c = 0; c < 6; c += 2) launch_pppm_backward(f->stream, f->dpppm, vb[c], vb[c + 1]);
+  }
   f->prof.begin("pppm_f_kspace", f->stream);
   launch_pppm_kspace(f->stream, f->dpppm, uk, g, V, f->d_pp_re.p, f->d_pp_im.p, fields ? f->d_pp_ex.p : nullptr,
                      fields ? f->d_pp_ey.p : nullptr, f->d_pp_kpart.p + 7, f->d_pp_kpart.p);
@@ -3492,7 +3520,13 @@ void pppm_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy
   double s7[7];
   HIP_TRY(hipMemcpyAsync(s7, f->d_pp_kpart.p, 7 * sizeof(double), hipMemcpyDeviceToHost, f->stream));
   const bool per_atom = n > 0 && (fout || eatom);
-  std::vector<double> hf, he;
+  std::vector<double> hf, he, hv;
+  if (want_v) {
+    f->d_pp_vo.reserve(6 * (size_t)at->nlocal);
+    launch_pppm_vatom_gather(f->stream, f->dpppm, n, f->d_pp_fidx.p, f->d_x.p, f->d_q.p, vb, qs, f->d_pp_vo.p);
+    hv.resize(6 * (size_t)at->nlocal);
+    HIP_TRY(hipMemcpyAsync(hv.data(), f->d_pp_vo.p, hv.size() * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+  }
   if (per_atom) {
     if (fout) f->d_pp_fo.reserve(3 * (size_t)at->nlocal);
     if (eatom) f->d_pp_eo.reserve(at->nlocal);
@@ -3529,6 +3563,12 @@ void pppm_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy
   }
   if (virial) for (int c = 0; c < 6; ++c) virial[c] = qs * s7[1 + c];
   if (eatom) std::fill(eatom, eatom + at->nlocal, 0.0);
+  if (vatom) {
+    std::fill(vatom, vatom + 6 * (size_t)at->nlocal, 0.0);
+    if (want_v)
+      for (int k = 0; k < n; ++k)
+        for (int c = 0; c < 6; ++c) vatom[6 * (size_t)idx[k] + c] = hv[6 * (size_t)idx[k] + c];
+  }
   if (!per_atom) return;
   for (int k = 0; k < n; ++k) {
     const int i = idx[k];
@@ -3565,7 +3605,8 @@ EwForceOut kspace_out_args(const conp_fix *f, double V, double L) {
 }
 // ewald_structure_factor + ewald_forces on the caller's device arrays, every owned atom a column and a target (a zero charge adds
 // zeros): nothing but launches, device-to-device copies and memsets on the handle's stream once the buffers have their sizes.
-void ewald_forces_device(conp_fix *f, const double *dx, const double *dq, double *df, double *dev, double *deatom) {
+void ewald_forces_device(conp_fix *f, const double *dx, const double *dq, double *df, double *dev, double *deatom,
+                         double *dvatom = nullptr /*[nlocal][6], overwritten*/) {
   const KTables &kt = f->kt;
   const KPlan &pl = f->plan;
   const double L = f->env.zprd * f->env.slab_volfactor;
@@ -3610,28 +3651,39 @@ void ewald_forces_device(conp_fix *f, const double *dx, const double *dq, double
                             f->d_ew_G.p, f->d_ew_ev.p + 7, f->d_ew_ev.p);
     launch_kspace_finish(f->stream, kspace_finish_args(f, kt.volume, L), f->d_ew_ev.p, f->d_kf_sums.p, dev);
   }
-  if (df || deatom) {
+  if (df || deatom || dvatom) {
     if (f->ew_tiles_gen != f->plan_gen) {        // the tile lists change with the plan only (the host entries upload the same bytes)
       f->d_ew_tiles.upload(f->tiles_h, f->stream); f->d_ew_ctptr.upload(f->ct_ptr_h, f->stream);
       f->sync();
       f->ew_tiles_gen = f->plan_gen;
     }
     f->d_ew_bk.reserve((size_t)16 * nb_pad);
+    if (dvatom) {
+      f->d_ew_Gwf2.reserve(gsz); f->d_ew_vk.reserve((size_t)24 * nb_pad);
+      launch_ew_gw2(f->stream, f->dplan, pl.kzt, kt.unitk[0], kt.unitk[1], kt.unitk[2], f->env.g_ewald, f->d_ew_G.p, f->d_ew_Gwf2.p);
+    }
     const EwForceOut o = kspace_out_args(f, kt.volume, L);
     for (int b0 = 0; b0 < n; b0 += nb_pad) {
       const int nb = std::min(nb_pad, n - b0);
       if (ntot > nb_pad) ew_tables_at(f, dx + 3 * (size_t)b0, nb, nb_pad);       // (one block: its tables are still there)
       launch_ew_force(f->stream, f->dplan, pl.kzt, kt.unitk[0], kt.unitk[1], kt.unitk[2], nb_pad, f->d_ew_ctptr.p, f->d_ew_tiles.p,
                       f->d_ew_Gwf.p, f->d_ew_Rp.p, f->d_ew_Tz.p, f->d_ew_bk.p);
-      launch_ew_force_out_device(f->stream, nb, nb_pad, f->d_ew_bk.p, f->d_ew_q.p + b0, dx + 3 * (size_t)b0, o, f->d_kf_sums.p, b0, df,
-                                 deatom);
+      if (df || deatom)
+        launch_ew_force_out_device(f->stream, nb, nb_pad, f->d_ew_bk.p, f->d_ew_q.p + b0, dx + 3 * (size_t)b0, o, f->d_kf_sums.p, b0, df,
+                                   deatom);
+      if (dvatom) {
+        launch_ew_vatom(f->stream, f->dplan, pl.kzt, kt.unitk[0], kt.unitk[1], kt.unitk[2], nb_pad, f->d_ew_ctptr.p, f->d_ew_tiles.p,
+                        f->d_ew_Gwf2.p, f->d_ew_Rp.p, f->d_ew_Tz.p, f->d_ew_vk.p);
+        launch_ew_vatom_out_device(f->stream, nb, nb_pad, f->d_ew_bk.p, f->d_ew_vk.p, f->d_ew_q.p + b0, f->env.qqrd2e, b0, dvatom);
+      }
     }
   }
   HIP_TRY(hipGetLastError());
 }
 // pppm_forces on the caller's device arrays: the brick of every owned atom through the identity list, the mesh solve, the gather
 // on every owned atom; the seven sums stay on the device (kspace_finish_kernel reads them).
-void pppm_forces_device(conp_fix *f, const double *dx, const double *dq, double *df, double *dev, double *deatom) {
+void pppm_forces_device(conp_fix *f, const double *dx, const double *dq, double *df, double *dev, double *deatom,
+                        double *dvatom = nullptr /*[nlocal][6], overwritten*/) {
   const double MY_PI = 3.14159265358979323846;
   const double L = f->env.zprd * f->env.slab_volfactor, V = f->env.xprd * f->env.yprd * L;
   const int n = f->nlocal_cur;
@@ -3654,6 +3706,13 @@ void pppm_forces_device(conp_fix *f, const double *dx, const double *dq, double 
   f->d_pp_kpart.reserve((size_t)7 * (pppm_kspace_workgroups(f->dpppm.nfft) + 1));
   const double uk[3] = {2.0 * MY_PI / f->env.xprd, 2.0 * MY_PI / f->env.yprd, 2.0 * MY_PI / L};
   launch_pppm_forward(f->stream, f->dpppm, f->d_pp_re.p, f->d_pp_im.p);
+  if (dvatom) {                      // (rho^ is still in (re, im): the kspace launch below overwrites it)
+    double *vb[6];
+    for (int c = 0; c < 6; ++c) { f->d_pp_v[c].reserve(nf); vb[c] = f->d_pp_v[c].p; }
+    launch_pppm_vatom_spectra(f->stream, f->dpppm, uk, f->env.g_ewald, f->d_pp_re.p, f->d_pp_im.p, vb);
+    for (int c = 0; c < 6; c += 2) launch_pppm_backward(f->stream, f->dpppm, vb[c], vb[c + 1]);
+    launch_pppm_vatom_gather(f->stream, f->dpppm, n, nullptr, dx, dq, vb, f->env.qqrd2e, dvatom);
+  }
   launch_pppm_kspace(f->stream, f->dpppm, uk, f->env.g_ewald, V, f->d_pp_re.p, f->d_pp_im.p, fields ? f->d_pp_ex.p : nullptr,
                      fields ? f->d_pp_ey.p : nullptr, f->d_pp_kpart.p + 7, f->d_pp_kpart.p);
   f->pp_im_clean = false;
@@ -3908,6 +3967,57 @@ int conp_pppm_compute_forces_device(conp_fix *f, const double *d_x, const double
   kspace_device_check(f, d_x, d_q);
   if (!d_f && !d_ev && !d_eatom) return CONP_OK;
   pppm_forces_device(f, d_x, d_q, d_f, d_ev, d_eatom);
+  CONP_GUARD_END
+}
+
+// The four force entries with the per-atom virial as one more output: S / the density brick and the forward
+// transform are formed once for all outputs.  vatom == NULL: the sibling, call for call.
+int conp_ewald_compute_forces_vatom(conp_fix *f, const conp_atoms *at, double *fout, double *energy, double *virial, double *eatom,
+                                    double *vatom) {
+  CONP_GUARD_BEGIN
+  if (!f || !at) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->drop_graph();
+  need_ewald(f);
+  if (!f->ew_g_valid) ewald_structure_factor(f, at);
+  else if (at->nlocal + at->nghost != f->nall) throw ConpError(CONP_ERR_STATE, "atom count changed without post_neighbor");
+  ewald_forces(f, at, fout, energy, virial, eatom, vatom);
+  CONP_GUARD_END
+}
+
+int conp_pppm_compute_forces_vatom(conp_fix *f, const conp_atoms *at, double *fout, double *energy, double *virial, double *eatom,
+                                   double *vatom) {
+  CONP_GUARD_BEGIN
+  if (!f || !at) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->drop_graph();
+  if (!f->args.pppm)
+    throw ConpError(CONP_ERR_STATE, "conp_pppm_compute_forces_vatom: this handle's k-space provider is the Ewald sum -- use "
+                                    "conp_ewald_compute_forces_vatom");
+  need_pppm(f);
+  pppm_forces(f, at, fout, energy, virial, eatom, vatom);
+  CONP_GUARD_END
+}
+
+int conp_ewald_compute_forces_vatom_device(conp_fix *f, const double *d_x, const double *d_q, double *d_f, double *d_ev, double *d_eatom,
+                                           double *d_vatom) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->drop_graph();
+  need_ewald(f);
+  kspace_device_check(f, d_x, d_q);
+  if (!d_f && !d_ev && !d_eatom && !d_vatom) return CONP_OK;
+  ewald_forces_device(f, d_x, d_q, d_f, d_ev, d_eatom, d_vatom);
+  CONP_GUARD_END
+}
+
+int conp_pppm_compute_forces_vatom_device(conp_fix *f, const double *d_x, const double *d_q, double *d_f, double *d_ev, double *d_eatom,
+                                          double *d_vatom) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->drop_graph();
+  need_pppm(f);
+  kspace_device_check(f, d_x, d_q);
+  if (!d_f && !d_ev && !d_eatom && !d_vatom) return CONP_OK;
+  pppm_forces_device(f, d_x, d_q, d_f, d_ev, d_eatom, d_vatom);
   CONP_GUARD_END
 }
 

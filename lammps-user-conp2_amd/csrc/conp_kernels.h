@@ -226,6 +226,26 @@ void launch_pppm_force_gather_device(hipStream_t s, const PppmDev &pd, int n, co
                                      const double *ey, const double *ez, const double *u, const EwForceOut &o, const double *four,
                                      double *fo, double *eo);
 
+// ---- per-atom virial of both k-space force entries (conp_*_compute_forces_vatom[_device]) --------------------
+// (c o w) o G in launch_ew_gw's order, c = 1 / k^2 + 1 / (4 g^2) of the entry's planar vector and kz
+void launch_ew_gw2(hipStream_t s, const DevPlan &pl, int kzt, double ux, double uy, double uz, double g_ewald, const double *G,
+                   double *Gwf2);
+// out: [6 quantities: KK_xx, KK_yy, KK_xy, KK_zz, KK_xz, KK_yz][4 parts][nb_pad], KK_ab = sum_k 2 ug c k_a k_b A_i(k); two launches
+void launch_ew_vatom(hipStream_t s, const DevPlan &pl, int kzt, double ux, double uy, double uz, int nb_pad, const int *ct_ptr,
+                     const SkTile *tiles, const double *Gwf2, const double *Rp, const double *Tz, double *out);
+// vo[idx[i]][6] (or vo[base + i][6]) = qs q_i (delta_ab (-g_i / 2) - KK_ab), xx yy zz xy xz yz; bk: launch_ew_force's output
+void launch_ew_vatom_out(hipStream_t s, int n, int nb_pad, const double *bk, const double *vk, const int *idx, const double *q, double qs,
+                         double *vo);
+void launch_ew_vatom_out_device(hipStream_t s, int n, int nb_pad, const double *bk, const double *vk, const double *q, double qs, int base,
+                                double *vo);
+// the six packed spectra vg_ab phi from rho^ (re, im; read BEFORE launch_pppm_kspace overwrites them):
+// (v[0], v[1]) <- xx + i yy, (v[2], v[3]) <- zz + i xy, (v[4], v[5]) <- xz + i yz; launch_pppm_backward on each pair gives the fields
+void launch_pppm_vatom_spectra(hipStream_t s, const PppmDev &pd, const double uk[3], double g_ewald, const double *re, const double *im,
+                               double *const v[6]);
+// v: the six fields in the order xx, yy, zz, xy, xz, yz.  idx == NULL: every atom [0, n) a target.  vo: [nlocal][6], written at idx
+void launch_pppm_vatom_gather(hipStream_t s, const PppmDev &pd, int n, const int *idx, const double *x, const double *q,
+                              double *const v[6], double qs, double *vo);
+
 // ---- the z-window form of the structure-factor contraction (conp_zn.hip, round 5) ------------------------------------------------
 // item = (row tile: 64 planar vectors, chunk range [c0, c1) of the z-ordered electrolyte list, window origin g0 on the grid, slot of
 // its piece [class][128 rows] in the pieces buffer)

@@ -363,6 +363,196 @@ __global__ __launch_bounds__(64) void kspace_finish_kernel(KspaceFinish a, const
   ev[t] = a.qs * v;
 }
 
+// ---- per-atom virial of the exact Ewald sum (conp_ewald_compute_forces_vatom) -------------------------------
+// vatom_i,ab = qs q_i sum_k ug_k (delta_ab - 2 c_k k_a k_b) A_i(k), c_k = 1 / k^2 + 1 / (4 g^2).  The delta part is -g_i / 2 (the force
+// kernel's first quantity).  The k_a k_b part, KK_ab = sum_k 2 ug_k c_k k_a k_b A_i(k), is minus the Hessian at fixed S of the
+// projection with the second weight set w' = c o w:
+//     H' = (w' G) Tz       KK_xx, KK_yy, KK_xy = sum_r (kx_r^2, ky_r^2, kx_r ky_r) Rp[r] H'[r]
+//     H'zz = (w' G) (kz^2 Tz)                      KK_zz = sum_r Rp[r] H'zz[r]
+//     H'z = (w' G) dTz/dz   KK_xz, KK_yz = - sum_r s_r (kx_r, ky_r) Rp[r ^ 64] H'z[r]     (ew_force_kernel's partner rows and columns)
+
+// (c o w) o G in ew_gw_kernel's order; c of entry (r, t) from the planar vector of row r and the kz index of column t
+__global__ __launch_bounds__(256) void ew_gw2_kernel(int R_pad, int C_pad, int kzt, double ux, double uy, double uz, double inv4g2,
+                                                     const int *__restrict__ p_ikx, const int *__restrict__ p_iky,
+                                                     const double *__restrict__ wfull, const double *__restrict__ G,
+                                                     double *__restrict__ Gwf2) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (size_t)R_pad * C_pad) return;
+  const int r = (int)(e / C_pad), c = (int)(e - (size_t)r * C_pad);
+  const double w = wfull[e];
+  double v = 0.0;
+  if (w != 0.0) {
+    const int p = 64 * (r >> 7) + (r & 63);
+    const int ct = c / 320, cl = c - 320 * ct, m = ct * kzt + 8 * (cl >> 4) + (cl & 7);
+    const double kx = ux * (double)p_ikx[p], ky = uy * (double)p_iky[p], kz = uz * (double)m;
+    v = w * (1.0 / (kx * kx + ky * ky + kz * kz) + inv4g2) * G[e];
+  }
+  Gwf2[((size_t)(r >> 4) * (C_pad / 4) + (c >> 2)) * 64 + 16 * (c & 3) + (r & 15)] = v;
+}
+
+// ew_force_kernel's loop with the chains above, in two passes so that a pass holds at most two accumulator sets and four running
+// sums per atom fragment (the force kernel's register budget, no scratch):
+//   PASS 0: H' and H'zz -> out quantities 0..3 = KK_xx, KK_yy, KK_xy, KK_zz        PASS 1: H'z -> out quantities 4, 5 = KK_xz, KK_yz
+// out[(4 quantity + part) ne_pad + i]; units, parts and the order of every sum are ew_force_kernel's
+template <int PASS>
+__global__ __launch_bounds__(512) void ew_vatom_kernel(int C_pad, int ne_pad, int n_col_tiles, int kzt, double ux, double uy, double uz,
+                                                        const int *__restrict__ ct_ptr, const SkTile *__restrict__ tiles,
+                                                        const int *__restrict__ p_ikx, const int *__restrict__ p_iky,
+                                                        const int *__restrict__ p_sgn, const double *__restrict__ Gwf2,
+                                                        const double *__restrict__ Rp, const double *__restrict__ Tz,
+                                                        double *__restrict__ out) {
+  constexpr int NQ = PASS == 0 ? 4 : 2;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  double *tz = reinterpret_cast<double *>(smem);          // [4 atom fragments][160 columns][16 atoms]
+  double *red = tz + 4 * 160 * 16;                         // [NQ quantities][8 waves][64]
+  const int part = blockIdx.y;
+  const int i0 = blockIdx.x * 64;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int fr = lane & 15, fk = lane >> 4;
+  double psum[NQ][4];
+#pragma unroll
+  for (int v = 0; v < NQ; ++v)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) psum[v][c] = 0.0;
+  for (int ct = 0; ct < n_col_tiles; ++ct) {
+    const int tb = ct_ptr[ct], te = ct_ptr[ct + 1];
+    if (te <= tb) continue;
+    int nba_max = 0;
+    for (int k = tb; k < te; ++k) nba_max = tiles[k].nba > nba_max ? tiles[k].nba : nba_max;
+    for (int h = 0; h < 2; ++h) {                        // columns [160 h, 160 h + 160) of the tile = k-steps [40 h, 40 h + 40)
+      if (40 * h >= 8 * nba_max) break;
+      __syncthreads();
+      for (int e = t; e < 160 * 64; e += 512) {
+        const int col = e >> 6, a = e & 63;
+        tz[((a >> 4) * 160 + col) * 16 + (a & 15)] = Tz[(size_t)(ct * 320 + 160 * h + col) * ne_pad + i0 + a];
+      }
+      __syncthreads();
+      const int nu = 8 * (te - tb);
+      for (int u = part + 4 * wave; u < nu; u += 32) {
+        const SkTile tl = tiles[tb + (u >> 3)];
+        const int rf = tl.rt * 8 + (u & 7);
+        const int ks0 = 40 * h, ks1 = 8 * tl.nba < 40 * (h + 1) ? 8 * tl.nba : 40 * (h + 1);
+        if (ks1 <= ks0) continue;
+        d4 acc[4], accz[4];                               // PASS 0: H', H'zz.  PASS 1: accz = H'z (acc unused)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { acc[c] = (d4){0.0, 0.0, 0.0, 0.0}; accz[c] = (d4){0.0, 0.0, 0.0, 0.0}; }
+        const double *ap = Gwf2 + ((size_t)rf * (C_pad / 4) + (size_t)ct * 80) * 64 + lane;
+        const double *bp = tz + fk * 16 + fr;
+        double an[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) an[i] = ap[(size_t)(ks0 + i) * 64];
+#pragma unroll 1
+        for (int tg = ks0; tg < ks1; tg += 8) {
+          double ac[8];
+#pragma unroll
+          for (int i = 0; i < 8; ++i) ac[i] = an[i];
+          if (tg + 8 < ks1) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) an[i] = ap[(size_t)(tg + 8 + i) * 64];
+          }
+          const double *bq = bp + 64 * (tg - ks0);
+          const double kz0 = uz * (double)(ct * kzt + 2 * tg + fk);      // (ew_force_kernel: the kz of k-step tg + i)
+          double b[8][4];
+#pragma unroll
+          for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) b[i][c] = bq[64 * i + c * 160 * 16];
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            const double kz = kz0 + uz * (double)(8 * (i >> 2) + 4 * (i & 1));
+            if (PASS == 0) {
+              const double kz2 = kz * kz;
+#pragma unroll
+              for (int c = 0; c < 4; ++c) {
+                acc[c] = MFMA_F64(ac[i], b[i][c], acc[c]);
+                accz[c] = MFMA_F64(ac[i], kz2 * b[i][c], accz[c]);
+              }
+            } else {
+              const double sk = (i & 2) ? kz : -kz;        // d cos = -kz sin, d sin = kz cos
+#pragma unroll
+              for (int c = 0; c < 4; ++c) accz[c] = MFMA_F64(ac[i], sk * b[i ^ 2][c], accz[c]);
+            }
+          }
+        }
+        const bool brow = (u & 4) != 0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = 16 * rf + fk + 4 * r;
+          const int p = 64 * tl.rt + 16 * (u & 3) + fk + 4 * r;
+          const double kx = ux * (double)p_ikx[p], ky = uy * (double)(p_sgn[p] * p_iky[p]);
+          if (PASS == 0) {
+            const double *rp = Rp + (size_t)row * ne_pad + i0 + fr;
+            const double kxx = kx * kx, kyy = ky * ky, kxy = kx * ky;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+              const double own = rp[16 * c], hv = own * acc[c][r];
+              psum[0][c] += kxx * hv;
+              psum[1][c] += kyy * hv;
+              psum[2][c] += kxy * hv;
+              psum[3][c] += own * accz[c][r];
+            }
+          } else {
+            const double sg = brow ? 1.0 : -1.0;
+            const double *rq = Rp + (size_t)(row ^ 64) * ne_pad + i0 + fr;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+              const double oth = rq[16 * c] * accz[c][r];
+              psum[0][c] += sg * kx * oth;
+              psum[1][c] += sg * ky * oth;
+            }
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < NQ; ++v)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) { psum[v][c] += __shfl_xor(psum[v][c], 16, 64); psum[v][c] += __shfl_xor(psum[v][c], 32, 64); }
+  __syncthreads();
+  if (lane < 16) {
+#pragma unroll
+    for (int v = 0; v < NQ; ++v)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) red[(v * 8 + wave) * 64 + 16 * c + lane] = psum[v][c];
+  }
+  __syncthreads();
+  if (t < 64 * NQ) {
+    const int v = t >> 6, a = t & 63;
+    double sum = 0.0;
+    for (int w = 0; w < 8; ++w) sum += red[(v * 8 + w) * 64 + a];
+    out[(size_t)(4 * ((PASS == 0 ? 0 : 4) + v) + part) * ne_pad + i0 + a] = PASS == 0 ? sum : -sum;
+  }
+}
+
+// vo[a][6] = qs q_i (delta_ab (-g_i / 2) - KK_ab) in the order xx, yy, zz, xy, xz, yz: g_i from the force kernel's first quantity
+// (bk), KK from ew_vatom_kernel (vk: xx, yy, xy, zz, xz, yz), each the four parts in b_project's fixed order.  A zero charge writes
+// exact zeros.  DEV: atom i of the block is atom base + i itself; else scattered to idx
+template <bool DEV>
+__global__ __launch_bounds__(256) void ew_vatom_out_kernel(int n, int nb_pad, const double *__restrict__ bk, const double *__restrict__ vk,
+                                                           const int *__restrict__ idx, const double *__restrict__ q, double qs, int base,
+                                                           double *__restrict__ vo) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double g = (bk[i] + bk[(size_t)nb_pad + i]) + (bk[2 * (size_t)nb_pad + i] + bk[3 * (size_t)nb_pad + i]);
+  double kk[6];
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    const double *b = vk + (size_t)(4 * c) * nb_pad + i;
+    kk[c] = (b[0] + b[(size_t)nb_pad]) + (b[2 * (size_t)nb_pad] + b[3 * (size_t)nb_pad]);
+  }
+  const double qi = q[i], d = -0.5 * g;
+  double *v = vo + 6 * (DEV ? (size_t)base + i : (size_t)idx[i]);
+  if (qi == 0.0) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) v[c] = 0.0;
+    return;
+  }
+  const double s = qs * qi;
+  v[0] = s * (d - kk[0]); v[1] = s * (d - kk[1]); v[2] = s * (d - kk[3]);
+  v[3] = s * (-kk[2]); v[4] = s * (-kk[4]); v[5] = s * (-kk[5]);
+}
+
 void launch_ew_seeds(hipStream_t s, int n, const double *x, double ux, double uy, double uz, double *seeds) {
   if (n <= 0) return;
   hipLaunchKernelGGL(ew_seeds_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, x, ux, uy, uz, seeds);
@@ -424,6 +614,38 @@ void launch_ew_force_out_device(hipStream_t s, int n, int nb_pad, const double *
   if (n <= 0) return;
   hipLaunchKernelGGL(ew_force_out_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, s, n, nb_pad, bk, (const int *)nullptr, q, x, o,
                      four, base, fo, eo);
+}
+
+void launch_ew_gw2(hipStream_t s, const DevPlan &pl, int kzt, double ux, double uy, double uz, double g_ewald, const double *G,
+                   double *Gwf2) {
+  const size_t n = (size_t)pl.R_pad * pl.C_pad;
+  hipLaunchKernelGGL(ew_gw2_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pl.R_pad, pl.C_pad, kzt, ux, uy, uz,
+                     1.0 / (4.0 * g_ewald * g_ewald), pl.p_ikx, pl.p_iky, pl.wfull, G, Gwf2);
+}
+
+void launch_ew_vatom(hipStream_t s, const DevPlan &pl, int kzt, double ux, double uy, double uz, int nb_pad, const int *ct_ptr,
+                     const SkTile *tiles, const double *Gwf2, const double *Rp, const double *Tz, double *out) {
+  const size_t lds = ((size_t)4 * 160 * 16 + 4 * 8 * 64) * sizeof(double);
+  static DynLdsCache g0{}, g1{};
+  ensure_dyn_lds(ew_vatom_kernel<0>, lds, g0);
+  ensure_dyn_lds(ew_vatom_kernel<1>, lds, g1);
+  hipLaunchKernelGGL(ew_vatom_kernel<0>, dim3(nb_pad / 64, 4), dim3(512), lds, s, pl.C_pad, nb_pad, pl.n_col_tiles, kzt, ux, uy, uz,
+                     ct_ptr, tiles, pl.p_ikx, pl.p_iky, pl.p_sgn, Gwf2, Rp, Tz, out);
+  hipLaunchKernelGGL(ew_vatom_kernel<1>, dim3(nb_pad / 64, 4), dim3(512), lds, s, pl.C_pad, nb_pad, pl.n_col_tiles, kzt, ux, uy, uz,
+                     ct_ptr, tiles, pl.p_ikx, pl.p_iky, pl.p_sgn, Gwf2, Rp, Tz, out);
+}
+
+void launch_ew_vatom_out(hipStream_t s, int n, int nb_pad, const double *bk, const double *vk, const int *idx, const double *q, double qs,
+                         double *vo) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(ew_vatom_out_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, s, n, nb_pad, bk, vk, idx, q, qs, 0, vo);
+}
+
+void launch_ew_vatom_out_device(hipStream_t s, int n, int nb_pad, const double *bk, const double *vk, const double *q, double qs, int base,
+                                double *vo) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(ew_vatom_out_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, s, n, nb_pad, bk, vk, (const int *)nullptr, q, qs,
+                     base, vo);
 }
 
 int kspace_four_sums_workgroups(int n) { return std::max(1, std::min(256, (n + 255) / 256)); }

@@ -942,6 +942,96 @@ __global__ __launch_bounds__(256) void pppm_force_gather_kernel(PppmDev pd, int 
   }
 }
 
+// ---- per-atom virial through the mesh (conp_pppm_compute_forces_vatom) --------------------------------------
+// poisson_peratom / fieldforce_peratom of pppm.cpp @ 27May2021 (ik): v_ab = Re IFFT[vg_ab phi], vg_ab = delta_ab - 2 (1 / k^2 +
+// 1 / (4 g^2)) k_a k_b, vatom_i,ab = qs q_i / 2 sum_stencil w v_ab.  Runs on rho^ BEFORE pppm_kspace_kernel overwrites it and writes
+// the six spectra packed two by two, pppm_kspace_kernel's way: (v0r, v0i) <- xx + i yy, (v1r, v1i) <- zz + i xy, (v2r, v2i) <- xz + i yz.
+// An off-diagonal component on a plane where exactly ONE of its two axes sits at its Nyquist index is its own partner with the
+// opposite sign: its inverse is imaginary, PPPM drops it with the imaginary part; packed, it would land in the partner field, so it
+// is zeroed.  With both axes at Nyquist the term is Hermitian and stays.
+__global__ __launch_bounds__(256) void pppm_vatom_spectra_kernel(PppmKspace a, const double *__restrict__ greensfn,
+                                                                 const double *__restrict__ re, const double *__restrict__ im,
+                                                                 double *__restrict__ v0r, double *__restrict__ v0i,
+                                                                 double *__restrict__ v1r, double *__restrict__ v1i,
+                                                                 double *__restrict__ v2r, double *__restrict__ v2i) {
+  const int nxy = a.nx * a.ny;
+  for (int n = blockIdx.x * 256 + threadIdx.x; n < a.nfft; n += 256 * gridDim.x) {
+    const int iz = n / nxy, r = n - iz * nxy, iy = r / a.nx, ix = r - iy * a.nx;
+    const int mx = ix - a.nx * (2 * ix / a.nx), my = iy - a.ny * (2 * iy / a.ny), mz = iz - a.nz * (2 * iz / a.nz);
+    const double kx = a.uk[0] * mx, ky = a.uk[1] * my, kz = a.uk[2] * mz;
+    const double sqk = kx * kx + ky * ky + kz * kz;
+    double xx = 0.0, yy = 0.0, zz = 0.0, xy = 0.0, xz = 0.0, yz = 0.0, pr = 0.0, pi = 0.0;
+    if (sqk != 0.0) {
+      const double g = greensfn[n];
+      pr = (a.scaleinv * g) * re[n]; pi = (a.scaleinv * g) * im[n];
+      const double vt = -2.0 * (1.0 / sqk + a.inv4g2);
+      const bool nqx = 2 * ix == a.nx, nqy = 2 * iy == a.ny, nqz = 2 * iz == a.nz;
+      xx = 1.0 + vt * kx * kx; yy = 1.0 + vt * ky * ky; zz = 1.0 + vt * kz * kz;
+      xy = nqx != nqy ? 0.0 : vt * kx * ky;
+      xz = nqx != nqz ? 0.0 : vt * kx * kz;
+      yz = nqy != nqz ? 0.0 : vt * ky * kz;
+    }
+    v0r[n] = xx * pr - yy * pi; v0i[n] = xx * pi + yy * pr;
+    v1r[n] = zz * pr - xy * pi; v1i[n] = zz * pi + xy * pr;
+    v2r[n] = xz * pr - yz * pi; v2i[n] = xz * pi + yz * pr;
+  }
+}
+
+// pppm_force_gather_kernel's stencil over the six v_ab bricks: one wavefront per target atom, vo[atom][6] = qs q_i / 2 times the six
+// stencil sums, in the order xx, yy, zz, xy, xz, yz.  Every atom is written by its own wave: no atomics.  A zero charge writes exact
+// zeros.  DEV: atom k itself (no index list)
+template <bool DEV>
+__global__ __launch_bounds__(256) void pppm_vatom_gather_kernel(PppmDev pd, int n, const int *__restrict__ idx, const double *__restrict__ x,
+                                                                const double *__restrict__ q, const double *__restrict__ vxx,
+                                                                const double *__restrict__ vyy, const double *__restrict__ vzz,
+                                                                const double *__restrict__ vxy, const double *__restrict__ vxz,
+                                                                const double *__restrict__ vyz, double qs, double *__restrict__ vo) {
+  __shared__ double coeff[64];
+  if (threadIdx.x < pd.order * pd.order) coeff[threadIdx.x] = pd.rho_coeff[threadIdx.x];
+  __syncthreads();
+  __shared__ double wsh[4][3][8];                 // (the wave's 3 x order stencil weights, as in pppm_force_gather_kernel)
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int k = blockIdx.x * 4 + wave;
+  if (k >= n) return;
+  const int i = DEV ? k : idx[k];
+  const double xs0 = (x[3 * (size_t)i] - pd.boxlo[0]) * pd.delinv[0];
+  const double xs1 = (x[3 * (size_t)i + 1] - pd.boxlo[1]) * pd.delinv[1];
+  const double xs2 = (x[3 * (size_t)i + 2] - pd.boxlo[2]) * pd.delinv[2];
+  const int g0 = static_cast<int>(xs0 + pd.shift) - 16384, g1 = static_cast<int>(xs1 + pd.shift) - 16384;
+  const int g2 = static_cast<int>(xs2 + pd.shift) - 16384;
+  if (lane < 24) {
+    const int c = lane >> 3, kk = lane & 7;
+    const double dx = c == 0 ? g0 + pd.shiftone - xs0 : (c == 1 ? g1 + pd.shiftone - xs1 : g2 + pd.shiftone - xs2);
+    if (kk < pd.order) wsh[wave][c][kk] = rho1d_one(coeff, pd.order, dx, kk);
+  }
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  const double (*w)[8] = wsh[wave];
+  const int o2 = pd.order * pd.order;
+  double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int row = lane; row < o2; row += 64) {
+    const int nn = row / pd.order, m = row - nn * pd.order;
+    const int mz = pwrap(nn + pd.nlower + g2, pd.nz), my = pwrap(m + pd.nlower + g1, pd.ny);
+    const double y0 = w[2][nn] * w[1][m];
+    const size_t line = ((size_t)mz * pd.ny + my) * pd.nx;
+    for (int l = 0; l < pd.order; ++l) {
+      const size_t p = line + pwrap(l + pd.nlower + g0, pd.nx);
+      const double x0 = y0 * w[0][l];
+      a[0] += x0 * vxx[p]; a[1] += x0 * vyy[p]; a[2] += x0 * vzz[p];
+      a[3] += x0 * vxy[p]; a[4] += x0 * vxz[p]; a[5] += x0 * vyz[p];
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+    for (int c = 0; c < 6; ++c) a[c] += __shfl_down(a[c], off, 64);
+  if (lane == 0) {
+    const double qi = q[i], s = 0.5 * qs * qi;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) vo[6 * (size_t)i + c] = qi == 0.0 ? 0.0 : s * a[c];
+  }
+}
+
 // The three steps between the spread and the gather.  forward: rho (in `re`, the brick of every charged atom) -> rho^ in (re, im).
 // kspace: sums[7] (without qqrd2e) and the packed spectra (pre == nullptr: no forces wanted, phi only); part:
 // [pppm_kspace_workgroups(nfft)][7] scratch.  backward: one packed brick -> its two real fields (u in `re`, E_z in `im`; E_x, E_y).
@@ -972,6 +1062,28 @@ void launch_pppm_force_gather_device(hipStream_t s, const PppmDev &pd, int n, co
   if (n <= 0) return;
   hipLaunchKernelGGL(pppm_force_gather_kernel<true>, dim3((n + 3) / 4), dim3(256), 0, s, pd, n, (const int *)nullptr, x, q, ex, ey, ez, u,
                      o, four, fo, eo);
+}
+
+void launch_pppm_vatom_spectra(hipStream_t s, const PppmDev &pd, const double uk[3], double g_ewald, const double *re, const double *im,
+                               double *const v[6]) {
+  PppmKspace a{};
+  a.nx = pd.nx; a.ny = pd.ny; a.nz = pd.nz; a.nfft = pd.nfft;
+  for (int c = 0; c < 3; ++c) a.uk[c] = uk[c];
+  a.inv4g2 = 1.0 / (4.0 * g_ewald * g_ewald); a.scaleinv = 1.0 / ((double)pd.nx * pd.ny * pd.nz);
+  hipLaunchKernelGGL(pppm_vatom_spectra_kernel, dim3(pppm_kspace_workgroups(pd.nfft)), dim3(256), 0, s, a, pd.greensfn, re, im, v[0], v[1],
+                     v[2], v[3], v[4], v[5]);
+}
+
+void launch_pppm_vatom_gather(hipStream_t s, const PppmDev &pd, int n, const int *idx, const double *x, const double *q,
+                              double *const v[6], double qs, double *vo) {
+  if (n <= 0) return;
+  // the packed bricks after their backward transforms: v[0..5] = xx, yy, zz, xy, xz, yz
+  if (idx)
+    hipLaunchKernelGGL(pppm_vatom_gather_kernel<false>, dim3((n + 3) / 4), dim3(256), 0, s, pd, n, idx, x, q, v[0], v[1], v[2], v[3], v[4],
+                       v[5], qs, vo);
+  else
+    hipLaunchKernelGGL(pppm_vatom_gather_kernel<true>, dim3((n + 3) / 4), dim3(256), 0, s, pd, n, idx, x, q, v[0], v[1], v[2], v[3], v[4],
+                       v[5], qs, vo);
 }
 
 // ---- compute potential/atom, pair part (compute_potential_atom.cpp:223-308): one wavefront per list owner -------------------

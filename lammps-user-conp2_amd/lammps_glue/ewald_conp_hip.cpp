@@ -19,8 +19,7 @@ void EwaldConpHip::settings(int narg, char **arg) {
 }
 
 /* `accuracy` in force units as Ewald::init forms it; g_ewald is NOT estimated from it here: the fix (FixConpHip::init, conp_env) and
- * the coul/long pair style read force->kspace->g_ewald, so it has to come from `kspace_modify gewald`.  Orthogonal boxes only; no
- * per-atom virial (checked in compute()).
+ * the coul/long pair style read force->kspace->g_ewald, so it has to come from `kspace_modify gewald`.  Orthogonal boxes only.
  * The fix creates its handle in its own init / setup, after this one: the lookup is repeated at the first compute(). */
 void EwaldConpHip::init() {
   if (domain->triclinic) error->all(FLERR, "kspace_style ewald/conp/hip does not support a triclinic box");
@@ -45,7 +44,6 @@ void EwaldConpHip::find_handle() {
 
 void EwaldConpHip::compute(int eflag, int vflag) {
   ev_init(eflag, vflag);
-  if (vflag_atom) error->all(FLERR, "kspace_style ewald/conp/hip does not tally a per-atom virial");
   if (handle_ == nullptr) find_handle();
   if (handle_ == nullptr) error->all(FLERR, "kspace_style ewald/conp/hip needs a conp/hip fix (or fix conp with the hip provider)");
   conp_atoms at = av.flat(atom, [this](int i) { return fixconp ? fixconp->electrode_check(i) : fixhip->electrode_check(i); });
@@ -55,6 +53,8 @@ void EwaldConpHip::compute(int eflag, int vflag) {
    * the fix's last update, and the atoms move between updates (fix ... N with N > 1, the reference fix's skipped b_cal, minimize,
    * a second run).  When the fix did update this step nothing is cached yet, so this is the formation the entry would do itself. */
   fail_if(error, conp_ewald_compute(handle_, &at));
-  fail_if(error, conp_ewald_compute_forces(handle_, &at, f, eflag_global ? &energy : nullptr, vflag_global ? virial : nullptr,
-                                           eflag_atom ? eatom : nullptr));
+  /* vatom is one contiguous [nmax][6] block behind its row pointers, like atom->f; its owned rows are overwritten (Ewald::compute's
+   * per-atom virial; with vatom NULL the entry is conp_ewald_compute_forces bit for bit) */
+  fail_if(error, conp_ewald_compute_forces_vatom(handle_, &at, f, eflag_global ? &energy : nullptr, vflag_global ? virial : nullptr,
+                                                 eflag_atom ? eatom : nullptr, vflag_atom && atom->nlocal ? &vatom[0][0] : nullptr));
 }

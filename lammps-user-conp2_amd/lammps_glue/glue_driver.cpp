@@ -6,9 +6,11 @@
 //
 // usage: glue_driver CASEFILE                      one rank, FixConpHip (INTEGRATION.md mode A)
 //        glue_driver CASEFILE compute              mode A, then `compute potential/atom/hip kspace` on the conp/hip fix (Ewald)
-//        glue_driver CASEFILE kspace               mode A with `kspace_style ewald/conp/hip` as force->kspace: on every step, after the
+//        glue_driver CASEFILE kspace [vatom]       mode A with `kspace_style ewald/conp/hip` as force->kspace: on every step, after the
 //                                                  fix's pre_force, compute(eflag, vflag) on the fix's handle; output per step
-//                                                  "kf STEP TAG FX FY FZ", "kea STEP TAG E" per owned atom, "ke STEP ENERGY", "kv STEP W[6]"
+//                                                  "kf STEP TAG FX FY FZ", "kea STEP TAG E" per owned atom, "ke STEP ENERGY", "kv STEP W[6]".
+//                                                  With the word `vatom` compute() is asked for the per-atom virial too (vflag | 4)
+//                                                  and "kva STEP TAG V[6]" (xx yy zz xy xz yz) follows per owned atom
 //        glue_driver CASEFILE pppmforce [vatom|ad|nohandle]
 //                                                  mode A with the `pppm` keyword and `kspace_style pppm/conp/hip ACC device` as
 //                                                  force->kspace: on every step, after the fix's pre_force, compute(eflag, vflag) on
@@ -77,6 +79,7 @@ struct Out {
 };
 
 // one rank: its own mock LAMMPS instance, atoms and lists from its case file
+static bool g_kspace_vatom = false;   // `... kspace vatom`: compute() is asked for the per-atom virial too, "kva" lines follow
 static bool g_kspace = false;    // `glue_driver CASEFILE kspace`: EwaldConpHip is the kspace style, compute() on every step
 static bool g_pppmforce = false; // `glue_driver CASEFILE pppmforce`: PPPMConpHip in device mode is the kspace style, compute() on every step
 static std::string g_pppm_variant; // its third word
@@ -394,11 +397,15 @@ int run_case(const char *path, bool provider, int me, int nprocs, MockCommRank *
       // what Verlet does after the fixes' pre_force, on EVERY step, whether or not the fix updated the charges on it:
       // force->kspace->compute(eflag, vflag), here with the global and per-atom energy and the global virial; atom->f starts from zero
       std::fill(fs.begin(), fs.end(), 0.0);
-      ew->compute(3, 1);
+      ew->compute(3, g_kspace_vatom ? 5 : 1);
       for (int i = 0; i < nlocal; ++i) {
         out.f("kf %ld %d %.17g %.17g %.17g\n", ts, tag[i], fs[3 * (size_t)i], fs[3 * (size_t)i + 1], fs[3 * (size_t)i + 2]);
         out.f("kea %ld %d %.17g\n", ts, tag[i], ew->eatom[i]);
       }
+      if (g_kspace_vatom)
+        for (int i = 0; i < nlocal; ++i)
+          out.f("kva %ld %d %.17g %.17g %.17g %.17g %.17g %.17g\n", ts, tag[i], ew->vatom[i][0], ew->vatom[i][1], ew->vatom[i][2],
+                ew->vatom[i][3], ew->vatom[i][4], ew->vatom[i][5]);
       out.f("ke %ld %.17g\n", ts, ew->energy);
       out.f("kv %ld %.17g %.17g %.17g %.17g %.17g %.17g\n", ts, ew->virial[0], ew->virial[1], ew->virial[2], ew->virial[3], ew->virial[4],
             ew->virial[5]);
@@ -505,6 +512,7 @@ int main(int argc, char **argv) {
     MockCommRank *single = nullptr;
     g_compute = argc > 2 && std::string(argv[2]) == "compute";
     g_kspace = argc > 2 && std::string(argv[2]) == "kspace";
+    g_kspace_vatom = g_kspace && argc > 3 && std::string(argv[3]) == "vatom";
     g_pppmforce = argc > 2 && std::string(argv[2]) == "pppmforce";
     g_pppm_variant = g_pppmforce && argc > 3 ? argv[3] : "";
     g_pppmhost = argc > 2 && std::string(argv[2]) == "pppmhost";

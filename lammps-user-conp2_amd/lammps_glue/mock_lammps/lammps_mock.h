@@ -54,7 +54,7 @@ class Pointers {
 };
 
 // KSpace (kspace.h) as far as the glue touches it: the settings the handles read, and what a style's compute() fills -- energy,
-// virial, eatom -- after ev_init() has decoded eflag / vflag (ENERGY_GLOBAL = 1, ENERGY_ATOM = 2; VIRIAL_PAIR = 1, VIRIAL_FDOTR = 2,
+// virial, eatom, vatom ([nmax][6] behind row pointers, one contiguous block as Memory::create makes it) -- after ev_init() has decoded eflag / vflag (ENERGY_GLOBAL = 1, ENERGY_ATOM = 2; VIRIAL_PAIR = 1, VIRIAL_FDOTR = 2,
 // VIRIAL_ATOM = 4, VIRIAL_CENTROID = 8).  What `kspace_style NAME args` and `kspace_modify` leave in the base class: settings(), and
 // accuracy_relative / accuracy_absolute (`kspace_modify force`), from which a style's init() forms `accuracy` in force units with
 // two_charge_force (the force between two unit charges one Angstrom apart; the host sets it, KSpace's constructor does in LAMMPS)
@@ -63,7 +63,7 @@ class KSpace : protected Pointers {
   explicit KSpace(LAMMPS *l) : Pointers(l) {}
   double g_ewald, accuracy, slab_volfactor, energy; int slabflag; int nx_pppm = 0, ny_pppm = 0, nz_pppm = 0, order = 0;
   int compute_flag = 1, tip4pflag = 0; double qsum = 0.0;
-  double virial[6] = {0, 0, 0, 0, 0, 0}; double *eatom = nullptr;
+  double virial[6] = {0, 0, 0, 0, 0, 0}; double *eatom = nullptr; double **vatom = nullptr;
   int evflag = 0, eflag_global = 0, eflag_atom = 0, vflag_global = 0, vflag_atom = 0;
   double accuracy_relative = 0.0, accuracy_absolute = -1.0, two_charge_force = 0.0;
   virtual ~KSpace() {}
@@ -74,7 +74,8 @@ class KSpace : protected Pointers {
  protected:
   void ev_init(int eflag, int vflag);
  private:
-  std::vector<double> eatom_store;
+  std::vector<double> eatom_store, vatom_store;
+  std::vector<double *> vatom_rows;
 };
 
 // LAMMPS' PPPM kspace style and Compute base, as far as pppm_conp_hip.* / compute_potential_atom_hip.* touch them

@@ -123,13 +123,20 @@ void Error::warning(const char *, int, const std::string &msg) { std::fprintf(st
 int Atom::map(tagint t) { return (t >= 0 && t < map_size) ? map_array[t] : -1; }
 
 void KSpace::setup() {}
-void KSpace::ev_init(int eflag, int vflag) {       // KSpace::ev_init / ev_setup: the flags, eatom sized to the atoms and cleared
+void KSpace::ev_init(int eflag, int vflag) {       // KSpace::ev_init / ev_setup: the flags, eatom / vatom sized to the atoms and cleared
   evflag = (eflag || vflag) ? 1 : 0;
   eflag_global = eflag & 1; eflag_atom = eflag & 2;
   vflag_global = vflag & 3; vflag_atom = vflag & 12;
   if (eflag_atom) {
     eatom_store.assign((size_t)std::max(atom->nmax, atom->nlocal + atom->nghost), 0.0);
     eatom = eatom_store.data();
+  }
+  if (vflag_atom) {
+    const size_t n = (size_t)std::max(atom->nmax, atom->nlocal + atom->nghost);
+    vatom_store.assign(6 * std::max<size_t>(n, 1), 0.0);
+    vatom_rows.resize(std::max<size_t>(n, 1));
+    for (size_t i = 0; i < vatom_rows.size(); ++i) vatom_rows[i] = vatom_store.data() + 6 * i;
+    vatom = vatom_rows.data();
   }
 }
 

@@ -1,6 +1,6 @@
 """The k-space force half of a step from host arrays and from device arrays, in one process.
 
-    python tools/kspace_device_time.py [--reps N] [--warmup W]
+    python tools/kspace_device_time.py [--reps N] [--warmup W] [--vatom]
 
 Two boxes (il_onelayer; the headline box of bench.py: 4096 electrode + 32768 electrolyte atoms, ffield), both providers (the exact
 Ewald sum; PPPM on the meshes of tools/pppm_force_time.py).  Per box and provider, after W warm-up calls each:
@@ -9,6 +9,9 @@ Ewald sum; PPPM on the meshes of tools/pppm_force_time.py).  Per box and provide
   device entry   conp_*_compute_forces_device on device copies of the same atoms (d_f, d_ev): N calls enqueued back to back, ONE
                  synchronisation behind the last.  wall = (enqueue + the final wait) / N; host = the enqueue loop alone / N, the time
                  the host thread spends inside the calls.  A host time near the wall time would mean the entry waits for the device.
+  --vatom        also times conp_*_compute_forces_vatom_device (d_f, d_ev, d_vatom: DESIGN.md section 15) the same way, in the same
+                 process behind the existing entry: ms_vatom_device_wall / ms_vatom_device_host_thread and their ratio to the entry
+                 without the per-atom virial
 Prints one JSON line per box and provider.  Needs a GPU: there is no fall-back."""
 import argparse
 import json
@@ -27,6 +30,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--vatom", action="store_true", help="also time the entries with the per-atom virial")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -44,6 +48,7 @@ def main():
         d_q = torch.from_numpy(at.q.copy()).cuda()
         d_f = torch.zeros((n, 3), dtype=torch.float64, device="cuda")
         d_ev = torch.zeros(7, dtype=torch.float64, device="cuda")
+        d_v = torch.zeros((n, 6), dtype=torch.float64, device="cuda")
         for provider in ("ewald", "pppm"):
             if provider == "ewald":
                 fx = FixConp(s)
@@ -55,14 +60,29 @@ def main():
                 def host():
                     fx.ewald_compute(at)
                     fx.ewald_forces(at, f=f)
-                entry = fx.ewald_forces_device
+                entry, ventry = fx.ewald_forces_device, fx.ewald_forces_vatom_device
             else:
                 def host():
                     fx.pppm_compute_forces(at, f=f)
-                entry = fx.pppm_forces_device
+                entry, ventry = fx.pppm_forces_device, fx.pppm_forces_vatom_device
 
             def device():
                 entry(d_x.data_ptr(), d_q.data_ptr(), d_f.data_ptr(), d_ev.data_ptr(), 0)
+
+            def device_vatom():
+                ventry(d_x.data_ptr(), d_q.data_ptr(), d_f.data_ptr(), d_ev.data_ptr(), 0, d_v.data_ptr())
+
+            def timed(call):
+                for _ in range(args.warmup):
+                    call()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(args.reps):
+                    call()
+                t1 = time.perf_counter()
+                torch.cuda.synchronize()
+                t2 = time.perf_counter()
+                return 1e3 * (t2 - t0) / args.reps, 1e3 * (t1 - t0) / args.reps
             for _ in range(args.warmup):
                 host()
             torch.cuda.synchronize()
@@ -70,20 +90,15 @@ def main():
             for _ in range(args.reps):
                 host()
             ms_host = 1e3 * (time.perf_counter() - t0) / args.reps
-            for _ in range(args.warmup):
-                device()
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(args.reps):
-                device()
-            t1 = time.perf_counter()
-            torch.cuda.synchronize()
-            t2 = time.perf_counter()
-            ms_dev_wall, ms_dev_thread = 1e3 * (t2 - t0) / args.reps, 1e3 * (t1 - t0) / args.reps
+            ms_dev_wall, ms_dev_thread = timed(device)
             rec = dict(box=name, provider=provider, n_atoms=int(n), mesh=list(mesh) if provider == "pppm" else None,
                        kcount=int(fx.info().kcount), ms_host_pair_wall=round(ms_host, 4), ms_host_pair_host_thread=round(ms_host, 4),
                        ms_device_wall=round(ms_dev_wall, 4), ms_device_host_thread=round(ms_dev_thread, 4),
                        host_over_device=round(ms_host / ms_dev_wall, 3), reps=args.reps, warmup=args.warmup)
+            if args.vatom:
+                ms_v_wall, ms_v_thread = timed(device_vatom)
+                rec.update(ms_vatom_device_wall=round(ms_v_wall, 4), ms_vatom_device_host_thread=round(ms_v_thread, 4),
+                           vatom_over_device=round(ms_v_wall / ms_dev_wall, 3))
             print(json.dumps(rec), flush=True)
             fx.close()
 
