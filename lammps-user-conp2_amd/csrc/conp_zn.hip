@@ -18,6 +18,7 @@
 // as sk_reduce_kernel leaves them, for b_project_kernel.
 #include <hip/hip_runtime.h>
 
+#include <stdexcept>
 #include <type_traits>
 
 #include "conp_kernels.h"
@@ -113,6 +114,25 @@ __global__ __launch_bounds__(256, NCF == 2 ? 4 : 3) void zn_gemm_kernel(DevPlan 
   for (int f = 0; f < 2; ++f)
 #pragma unroll
     for (int c = 0; c < NCF; ++c) acc[f][c] = (d4){0.0, 0.0, 0.0, 0.0};
+  // The epilogue's class table, addressed like the tables above: P[((rt * nzc + c) * n + g) * 64 + v] = descriptor (row tile, wave, first
+  // class of a batch: SGPRs) + this lane's grid column (VGPR, bytes) + class within the batch (SGPR).  Everything is known here, and
+  // the one integer division (the window origin on the periodic grid) is a scalar one in the prologue's shadow; a lane's columns
+  // g0 + 16 cf + 4 r + fk wrap by one conditional subtraction (16 NCF <= 64 <= n: the host's grid has at least 64 points; launch_zn_gemm checks it).
+  constexpr int CB = 3;                                      // classes in flight
+  const double *Pw = nullptr;
+  __amdgpu_buffer_rsrc_t rp = rx;
+  unsigned pbase = 0, pnb = 0, pso[CB] = {};
+  unsigned pofs[NCF][4];
+  double pv[CB][NCF][4];
+  if constexpr (!RAW) {
+    int gb = it.g0 % n;
+    gb = __builtin_amdgcn_readfirstlane(gb < 0 ? gb + n : gb);
+    Pw = P + (size_t)it.rt * nzc * n * 64 + 16 * wave;
+    rp = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(Pw), (short)0, -1, 0x00020000);
+    pbase = ((unsigned)(gb + fk) * 64u + (unsigned)fr) * 8u; pnb = (unsigned)n * 512u;
+#pragma unroll
+    for (int k = 0; k < CB; ++k) pso[k] = __builtin_amdgcn_readfirstlane((unsigned)max(min(k, nzc - 1), 0) * pnb);
+  }
   // Per chunk and wave: 8 NCF MFMAs (56 of their 64 cycles each on the SIMD's vector port, which every other VALU instruction of every
   // wave shares: profiles/r05_pipe_share.txt) and the next chunk's 32 panel values.  No VALU instruction goes into addresses (buffer
   // loads; LDS addresses are loop-invariant registers + immediates, the loop being unrolled over the two panel buffers).  k-steps 0..2
@@ -135,12 +155,13 @@ __global__ __launch_bounds__(256, NCF == 2 ? 4 : 3) void zn_gemm_kernel(DevPlan 
     double2 X[NV], Y[NV];
     double wB[4][NCF];                                        // window fragments of the current chunk, per k-step
     auto load_xy = [&](int u, int ch) {
-      const int cr = min(ch, it.c1 - 1) - it.c0;              // (past the range's end: the last chunk again, not used)
+      const int cr = min(ch, it.c1 - 1) - it.c0;              // (chunk c1 -- asked for by the last chunk but one, or by the prologue of a
+                                                              //  range of one chunk, whose partial waits count on it: the last chunk again, not used)
       X[u] = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rx, xby[u], cr * (int)(nrx16 * 16), 0));
       Y[u] = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(ry, yby[u], cr * (int)(nry16 * 16), 0));
     };
-    auto load_w = [&](int half, int ch) {                     // k-steps 2 half, 2 half + 1 of chunk ch
-      const int cr = min(ch, it.c1 - 1) - it.c0;
+    auto load_w = [&](int half, int ch) {                     // k-steps 2 half, 2 half + 1 of chunk ch (< c1: the last chunk asks for none)
+      const int cr = ch - it.c0;
 #pragma unroll
       for (int c = 0; c < NCF; ++c) {
         const double2 v = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rb, bby + 2048 * c + 16 * half, cr * (16 * NCF * 16 * 8), 0));
@@ -172,22 +193,38 @@ __global__ __launch_bounds__(256, NCF == 2 ? 4 : 3) void zn_gemm_kernel(DevPlan 
     double fa[2][2];                                          // two fragment sets; on entry to a chunk set 0 holds its k-step 0
     auto frag = [&](const double *pn, int ks, int set) { fa[set][0] = pn[rdA[ks]]; fa[set][1] = pn[rdA[ks] + 16 * ZN_LD]; };
     frag(panel0, 0, 0);
-    auto chunk = [&](int ch, auto bufc) {
+    const int nfull = it.c1 - it.c0 - 1;                      // all chunks but the last, two bodies for the two panel buffers
+    // LAST (the range's last chunk, peeled): nothing is left to build or to fetch for a next chunk -- X[], Y[] and the window
+    // registers are dead, and the gaps carry the first CB classes' slice of P instead (a lane's column offset, then its three
+    // loads), so that the table arrives under the last MFMAs and not behind them.
+    auto chunk = [&](int ch, auto bufc, auto lastc) {
       constexpr int BUF = decltype(bufc)::value;
-      const double *pn = BUF ? panel1 : panel0;
+      constexpr bool LAST = decltype(lastc)::value;
+      const double *pn = LAST ? ((nfull & 1) ? panel1 : panel0) : BUF ? panel1 : panel0;   // (one LAST body: its panel by the count's parity)
       double *pw = BUF ? panel0 : panel1;
       double sy = 0.0, va = 0.0, vb = 0.0, vc = 0.0, vd = 0.0, t2 = 0.0, t4 = 0.0;
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
         const int cur = ks & 1, nx = cur ^ 1;
-        frag(ks < 3 ? pn : pw, ks < 3 ? ks + 1 : 0, nx);      // (k-step 3: the next chunk's k-step 0 -- its panel is complete)
+        if (!(LAST && ks == 3)) frag(ks < 3 ? pn : pw, ks < 3 ? ks + 1 : 0, nx);   // (k-step 3: the next chunk's k-step 0 -- its panel is complete)
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int m = 0; m < 2 * NCF; ++m) {
           const int f = m & 1, c = m >> 1;
           acc[f][c] = ZN_MFMA(wB[ks][c], fa[cur][f], acc[f][c]);
           const int g = 4 * ks + m;                           // gap behind this MFMA: slice g of the build (k-steps 0..2, four gaps each)
-          if (ks < 3 && m < 4) {
+          if constexpr (LAST) {
+            if constexpr (!RAW) {
+              if (ks < 3 && m < 4 && g < 4 * NCF) {
+                const int cf = g >> 2, r = g & 3;
+                const unsigned o = pbase + (unsigned)(16 * cf + 4 * r) * 512u;
+                pofs[cf][r] = min(o, o - pnb);                // (o < n * 512 exactly when the column is below n)
+#pragma unroll
+                for (int k = 0; k < CB; ++k)
+                  pv[k][cf][r] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rp, pofs[cf][r], pso[k], 0));
+              }
+            }
+          } else if (ks < 3 && m < 4) {
             if constexpr (PAIRED) {                           // six slices per pair: a+, a-, b+, b-, the four panel writes, the fetches
               const int u = g / 6, part = g - 6 * u;
               if (part == 0) { t2 = X[u].y * Y[u].y; va = X[u].x * Y[u].x - t2; }
@@ -207,18 +244,20 @@ __global__ __launch_bounds__(256, NCF == 2 ? 4 : 3) void zn_gemm_kernel(DevPlan 
           }
           __builtin_amdgcn_sched_barrier(0);
         }
-        if (ks & 1) { load_w(ks >> 1, ch + 1); __builtin_amdgcn_sched_barrier(0); }
+        if (!LAST && (ks & 1)) { load_w(ks >> 1, ch + 1); __builtin_amdgcn_sched_barrier(0); }
       }
 #ifdef ZN_TIMELINE
       if (t == 0 && (blockIdx.x & 255) == 0 && (blockIdx.x >> 8) < 16 && ch - it.c0 < 64) zn_tl_chunks[(blockIdx.x >> 8) * 64 + ch - it.c0] = wall_clock64();
 #endif
     };
-    const int nmax = it.c1 - it.c0;
 #ifndef ZN_SKIP_MAIN
-    for (int i = 0; i < nmax; i += 2) {
-      chunk(it.c0 + i, std::integral_constant<int, 0>());
-      if (i + 1 < nmax) chunk(it.c0 + i + 1, std::integral_constant<int, 1>());
+    constexpr std::integral_constant<int, 0> b0{};
+    constexpr std::integral_constant<int, 1> b1{};
+    for (int i = 0; i < nfull; i += 2) {
+      chunk(it.c0 + i, b0, std::false_type());
+      if (i + 1 < nfull) chunk(it.c0 + i + 1, b1, std::false_type());
     }
+    if (nfull >= 0) chunk(it.c1 - 1, b0, std::true_type());
 #endif
   };
   if (it.paired) run(std::true_type()); else run(std::false_type());
@@ -243,27 +282,33 @@ __global__ __launch_bounds__(256, NCF == 2 ? 4 : 3) void zn_gemm_kernel(DevPlan 
   // P[((rt * nzc + c) * n + g) * 64 + v]: the 16 lanes fr read 128 contiguous bytes.  The table comes from the Infinity Cache at best
   // (13 MB a run, never twice through one L2), so the fetches of CB classes are in flight together.
   double *out = pieces + (size_t)it.slot * piece_stride + 16 * wave + fr;
-  unsigned gofs[NCF][4];                                      // this lane's grid columns x 64 (the grid is periodic; n is any integer)
-#pragma unroll
-  for (int cf = 0; cf < NCF; ++cf)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { int g = (it.g0 + 16 * cf + 4 * r + fk) % n; gofs[cf][r] = (unsigned)(g < 0 ? g + n : g) * 64u; }
-  const double *Pw = P + (size_t)it.rt * nzc * n * 64 + 16 * wave + fr;
-  constexpr int CB = 3;
-#ifdef ZN_SKIP_EPI
-  for (int cb = 0; cb < 1; cb += CB) {
+#ifdef ZN_SKIP_MAIN
+  {                                                           // (diagnostic build without the main loop: the peeled chunk's fetches here)
 #else
-  for (int cb = 0; cb < nzc; cb += CB) {
+  if (it.c1 <= it.c0) {                                       // (an empty range runs no chunk)
 #endif
-    double pv[CB][NCF][4];
 #pragma unroll
-    for (int k = 0; k < CB; ++k) {
-      const double *pc = Pw + (size_t)min(cb + k, nzc - 1) * n * 64;
+    for (int cf = 0; cf < NCF; ++cf)
 #pragma unroll
-      for (int cf = 0; cf < NCF; ++cf)
+      for (int r = 0; r < 4; ++r) {
+        const unsigned o = pbase + (unsigned)(16 * cf + 4 * r) * 512u;
+        pofs[cf][r] = min(o, o - pnb);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) pv[k][cf][r] = pc[gofs[cf][r]];
-    }
+        for (int k = 0; k < CB; ++k) pv[k][cf][r] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rp, pofs[cf][r], pso[k], 0));
+      }
+  }
+#ifdef ZN_SKIP_EPI
+  const int ncls = min(nzc, CB);
+#else
+  const int ncls = nzc;
+#endif
+  // a batch: the sums of the CB classes in pv[] (cb .. cb + CB - 1); MORE: class cb + CB + k is requested into pv[k] as soon as class
+  // cb + k's products are formed, before its exchanges -- CB classes stay in flight over the whole table (a second set of registers
+  // for a whole batch ahead does not fit beside the accumulators: 2 x 24 NCF + 16 NCF registers)
+  auto batch = [&](int cb, auto morec) {
+    constexpr bool MORE = decltype(morec)::value;
+    __amdgpu_buffer_rsrc_t rn = rp;
+    if constexpr (MORE) rn = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(Pw + (size_t)(cb + CB) * n * 64), (short)0, -1, 0x00020000);
 #pragma unroll
     for (int k = 0; k < CB; ++k) {
       double s0 = 0.0, s1 = 0.0;
@@ -271,11 +316,21 @@ __global__ __launch_bounds__(256, NCF == 2 ? 4 : 3) void zn_gemm_kernel(DevPlan 
       for (int cf = 0; cf < NCF; ++cf)
 #pragma unroll
         for (int r = 0; r < 4; ++r) { s0 += acc[0][cf][r] * pv[k][cf][r]; s1 += acc[1][cf][r] * pv[k][cf][r]; }
+      if constexpr (MORE) {
+        const unsigned so = __builtin_amdgcn_readfirstlane((unsigned)min(k, ncls - 1 - cb - CB) * pnb);
+#pragma unroll
+        for (int cf = 0; cf < NCF; ++cf)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) pv[k][cf][r] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rn, pofs[cf][r], so, 0));
+      }
       s0 += __shfl_xor(s0, 16, 64); s1 += __shfl_xor(s1, 16, 64);
       s0 += __shfl_xor(s0, 32, 64); s1 += __shfl_xor(s1, 32, 64);
-      if (fk == 0 && cb + k < nzc) { out[(cb + k) * 128] = s0; out[(cb + k) * 128 + 64] = s1; }
+      if (fk == 0 && cb + k < ncls) { out[(cb + k) * 128] = s0; out[(cb + k) * 128 + 64] = s1; }
     }
-  }
+  };
+  int cb = 0;
+  for (; cb + CB < ncls; cb += CB) batch(cb, std::true_type());
+  if (cb < ncls) batch(cb, std::false_type());
 #ifdef ZN_TIMELINE
   __syncthreads();
   ZN_STAMP(3);
@@ -305,7 +360,9 @@ static void zn_gemm_launch(hipStream_t s, const DevPlan &pl, const ZnItem *items
 void launch_zn_gemm(hipStream_t s, const DevPlan &pl, int ncf, const ZnItem *items, int nitems, const double2 *Xt, const double2 *Yt,
                     const double *Bt, const double *P, int n, int nzc, double *pieces, int piece_stride) {
   if (nitems <= 0) return;
-  if (P == nullptr) {                                        // no class table: the raw windows (rough electrodes)
+  // the kernel wraps a lane's columns g0 mod n + fk + 16 cf + 4 r (<= n - 1 + 3 + 16 NCF - 4) by ONE subtraction of n
+  if (P != nullptr && n < 16 * ncf) throw std::invalid_argument("zn_gemm: the z grid is shorter than a window");
+  if (P == nullptr) {                                      // no class table: the raw windows (rough electrodes)
     if (ncf == 2) zn_gemm_launch<2, true>(s, pl, items, nitems, Xt, Yt, Bt, P, n, nzc, pieces, piece_stride);
     else zn_gemm_launch<3, true>(s, pl, items, nitems, Xt, Yt, Bt, P, n, nzc, pieces, piece_stride);
   } else if (ncf == 2) zn_gemm_launch<2, false>(s, pl, items, nitems, Xt, Yt, Bt, P, n, nzc, pieces, piece_stride);
