@@ -444,6 +444,65 @@ int conp_ewald_compute_forces_vatom_device(conp_fix *fix, const double *d_x, con
                                            double *d_vatom /* [nlocal][6], overwritten; NULL ok */);
 int conp_pppm_compute_forces_vatom_device(conp_fix *fix, const double *d_x, const double *d_q, double *d_f, double *d_ev, double *d_eatom,
                                           double *d_vatom /* [nlocal][6], overwritten; NULL ok */);
+
+/* ---- real-space pair forces: `pair_style lj/cut/coul/long` (and coul/long) on the device -----------------
+ * The pair loop of LAMMPS' pair_lj_cut_coul_long.cpp @ 27May2021 with ncoultablebits = 0 over the pair style's half list, with
+ * Pair::ev_tally's energy, virial and per-atom tallies.  g = env.g_ewald, qs = env.qqrd2e, newton = env.newton_pair.  For every listed
+ * pair (owner i, neighbour entry jraw): sb = (jraw >> 30) & 3, j = jraw & 0x3FFFFFFF, fc = special_coul[sb], fl = special_lj[sb],
+ * del = x_i - x_j, rsq = |del|^2; the pair is skipped unless rsq < cutsq[ti][tj]; rsq is not guarded against zero (as in LAMMPS).
+ *   r2inv = 1 / rsq
+ *   if rsq < cut_coul^2:          (plain cut_coul^2 -- not the min(cut_coul, 5.8 / g)^2 of the fix's own pair kernels)
+ *     r = sqrt(rsq), x = g r, e = exp(-x^2), t = 1 / (1 + 0.3275911 x)
+ *     erfc = t (0.254829592 + t (-0.284496736 + t (1.421413741 + t (-1.453152027 + t 1.061405429)))) e      (part of the definition)
+ *     pre = qs q_i q_j / r;  forcecoul = pre (erfc + 1.12837917 x e);  ecoul = pre erfc
+ *     if fc < 1: forcecoul -= (1 - fc) pre;  ecoul -= (1 - fc) pre
+ *   if cut_ljsq != NULL and rsq < cut_ljsq[ti][tj]:
+ *     r6inv = r2inv^3;  forcelj = r6inv (lj1 r6inv - lj2);  evdwl = fl (r6inv (lj3 r6inv - lj4) - offset)
+ *   fpair = (forcecoul + fl forcelj) r2inv
+ *   f_i += del fpair;   if newton or j < nlocal: f_j -= del fpair
+ * Tally: w = 1 with newton on, else (i < nlocal) / 2 + (j < nlocal) / 2;  eng_vdwl += w evdwl, eng_coul += w ecoul,
+ * virial += w fpair (dx^2, dy^2, dz^2, dx dy, dx dz, dy dz);  eatom gets (evdwl + ecoul) / 2 and vatom fpair / 2 times the six products,
+ * once for i (if newton or i < nlocal) and once for j (if newton or j < nlocal).  Hence sum eatom = eng_vdwl + eng_coul and
+ * sum vatom = virial; with newton on the ghost entries of f, eatom, vatom carry what LAMMPS' reverse communication would fold back,
+ * with newton off ghost entries are not touched.
+ * Order: conp_pair_set_params (once per run, or after pair_coeff changes) -> conp_pair_set_list (at every re-neighbour) ->
+ * conp_pair_compute / conp_pair_compute_device (every step).  Before set_params or set_list both compute entries return
+ * CONP_ERR_STATE.  The list and nall are those of the last conp_pair_set_list; the tables and the list are copied (uploaded), the
+ * caller's arrays need not stay.  conp_pair_set_list may synchronise and allocate; it checks that every index of the list is < nall, and a list it refuses (CONP_ERR_ARG) leaves the handle without one.
+ * The entries work on Ewald and on `pppm` handles.  They are rank-local, never collective: with decomposed ranks each rank passes
+ * its own atoms and list, and the sums over ranks and the reverse communication of ghost forces stay with the caller, as in LAMMPS.
+ * No cache: every call uses the x and q it is given.
+ * Reproducibility: eng and virial are summed in a fixed order and are bit-identical from run to run on the same input; f, eatom and
+ * vatom are accumulated with atomic adds and reproduce to rounding only. */
+typedef struct {
+  int ntypes;                         /* must equal env.ntypes */
+  const double *cutsq;                /* [(ntypes+1)^2] the PAIR style's cutsq = max(cut_lj, cut_coul)^2 per type pair */
+  double cut_coul;
+  const double *cut_ljsq, *lj1, *lj2, *lj3, *lj4, *offset;   /* [(ntypes+1)^2] each; cut_ljsq == NULL: no LJ part (coul/long) */
+  double special_lj[4], special_coul[4];                     /* [0] is 1.0 */
+} conp_pair_params;
+int conp_pair_set_params(conp_fix *fix, const conp_pair_params *p);             /* copied; once per run or after pair_coeff changes */
+int conp_pair_set_list(conp_fix *fix, const conp_neighlist *list, int nall);    /* the pair style's half list, uploaded; at every re-neighbour */
+/* Host arrays.  atoms->nlocal + atoms->nghost must equal the nall of conp_pair_set_list (else CONP_ERR_ARG); type is atoms->type.
+ * x and q go to the device once, through the handle's upload path when nall is that of the last (setup_)post_neighbor (so
+ * env.ghost_images 0 and 1 both work), else by a plain copy.  Synchronous.  NULL atoms: CONP_ERR_ARG; all outputs NULL: CONP_OK,
+ * nothing done. */
+int conp_pair_compute(conp_fix *fix, const conp_atoms *atoms,
+                      double *f      /* [nall][3] accumulated like atom->f; NULL: none */,
+                      double *eng    /* [2] eng_vdwl, eng_coul; NULL ok */,
+                      double *virial /* [6] xx,yy,zz,xy,xz,yz; NULL ok */,
+                      double *eatom  /* [nall] overwritten; NULL ok */,
+                      double *vatom  /* [nall][6] overwritten; NULL ok */);
+/* Device arrays: ALL pointers are ordinary device memory, d_x / d_q / d_f in the layout of conp_fix_pre_force_device (owned atoms
+ * first, then ghosts; d_f [nall][3]).  type and nlocal are those of the last (setup_)post_neighbor, whose atom count must equal the
+ * nall of conp_pair_set_list (else CONP_ERR_STATE); those types were checked against [0, ntypes] there (one outside: CONP_ERR_ARG here).  Everything is enqueued on the handle's stream (conp_fix_set_stream); after the
+ * first call at a given nall and list size a call makes no device allocation, no copy to the host and no synchronisation (the
+ * contract of DESIGN.md section 14): conp_fix_pre_force_device, a k-space force entry and this one follow each other on one stream
+ * without a synchronisation between them.  NULL d_x or d_q: CONP_ERR_ARG; all outputs NULL: CONP_OK, nothing done. */
+int conp_pair_compute_device(conp_fix *fix, const double *d_x, const double *d_q,
+                             double *d_f /* [nall][3] accumulated */, double *d_ev /* [8]: eng_vdwl, eng_coul, virial[6]; overwritten */,
+                             double *d_eatom /* [nall] */, double *d_vatom /* [nall][6] */);
+
 /* per-kernel timing of the last N updates via HIP events on the library's stream (bench.py roofline leg).
  * enable: 0 off, 1 a pair of events around every kernel, 2 around every 4th launch of the dominant kernel (sk_gemm) only --
  * cheap enough to stay on inside a timed region (an event pair drains the queue around the kernel it brackets). */

@@ -68,6 +68,13 @@ class conp_potential_args(C.Structure):
     _fields_ = [("pairflag", C.c_int), ("kspaceflag", C.c_int), ("qsumflag", C.c_int), ("eta", C.c_double)]
 
 
+class conp_pair_params(C.Structure):
+    _fields_ = [("ntypes", C.c_int), ("cutsq", C.POINTER(C.c_double)), ("cut_coul", C.c_double),
+                ("cut_ljsq", C.POINTER(C.c_double)), ("lj1", C.POINTER(C.c_double)), ("lj2", C.POINTER(C.c_double)),
+                ("lj3", C.POINTER(C.c_double)), ("lj4", C.POINTER(C.c_double)), ("offset", C.POINTER(C.c_double)),
+                ("special_lj", C.c_double * 4), ("special_coul", C.c_double * 4)]
+
+
 class conp_info(C.Structure):
     _fields_ = [("elenum", C.c_int), ("elenum_all", C.c_int), ("elytenum", C.c_int), ("maxtag_all", C.c_int),
                 ("runstage", C.c_int), ("kcount", C.c_int), ("kcount_flat", C.c_int), ("kcount_expand", C.c_int),
@@ -103,6 +110,7 @@ SYMBOLS = [
     "conp_ewald_compute_forces_vatom", "conp_pppm_compute_forces_vatom",
     "conp_ewald_compute_forces_vatom_device", "conp_pppm_compute_forces_vatom_device",
     "conp_compute_potential_atom",
+    "conp_pair_set_params", "conp_pair_set_list", "conp_pair_compute", "conp_pair_compute_device",
 ]
 
 
@@ -235,6 +243,11 @@ def load_library():
         lib.conp_pppm_compute_forces_vatom_device.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         lib.conp_debug_set_ew_block.argtypes = [C.c_int]
         lib.conp_debug_set_ew_block.restype = None
+    if hasattr(lib, "conp_pair_compute"):                      # (comparison builds loaded through CONP_LIB lack these)
+        lib.conp_pair_set_params.argtypes = [vp, C.POINTER(conp_pair_params)]
+        lib.conp_pair_set_list.argtypes = [vp, C.POINTER(conp_neighlist), C.c_int]
+        lib.conp_pair_compute.argtypes = [vp, C.POINTER(conp_atoms), dp, dp, dp, dp, dp]
+        lib.conp_pair_compute_device.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     lib.conp_compute_potential_atom.argtypes = [vp, C.POINTER(conp_atoms), C.POINTER(conp_neighlist), ip, ip,
                                                 C.POINTER(conp_potential_args), dp]
     lib.conp_fix_set_comm.argtypes = [vp, C.POINTER(conp_comm)]
@@ -700,6 +713,50 @@ class FixConp:
         """conp_pppm_compute_forces_vatom_device: the mesh twin of ewald_forces_vatom_device (`pppm` handles)"""
         self._check(self.lib.conp_pppm_compute_forces_vatom_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q), C.c_void_p(d_f),
                                                                    C.c_void_p(d_ev), C.c_void_p(d_eatom), C.c_void_p(d_vatom)))
+
+    # -- pair forces of lj/cut/coul/long: set_params -> set_list -> compute / compute_device ----------------
+    def pair_set_params(self, cutsq, cut_coul, lj=None, special_lj=(1.0, 1.0, 1.0, 1.0), special_coul=(1.0, 1.0, 1.0, 1.0)):
+        """conp_pair_set_params: cutsq [(ntypes+1)^2] and, with the LJ part, lj = dict(cut_ljsq, lj1, lj2, lj3, lj4, offset) of arrays
+        of the same shape (None: coul/long); copied by the library"""
+        nt1 = self.s.ntypes + 1
+        arr = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(nt1 * nt1))
+        null = C.POINTER(C.c_double)()
+        cs = arr(cutsq)
+        tabs = {k: arr(lj[k]) for k in ("cut_ljsq", "lj1", "lj2", "lj3", "lj4", "offset")} if lj is not None else {}
+        p = conp_pair_params(ntypes=self.s.ntypes, cutsq=_dptr(cs), cut_coul=float(cut_coul),
+                             special_lj=(C.c_double * 4)(*special_lj), special_coul=(C.c_double * 4)(*special_coul),
+                             **{k: (_dptr(tabs[k]) if lj is not None else null) for k in ("cut_ljsq", "lj1", "lj2", "lj3", "lj4", "offset")})
+        self._check(self.lib.conp_pair_set_params(self.h, C.byref(p)))
+
+    def pair_set_list(self, lst, nall):
+        """conp_pair_set_list: the pair style's half list (uploaded) and the atom count it indexes"""
+        neigh = lst.neigh if lst.neigh.size else np.zeros(1, np.int32)
+        v = conp_neighlist(inum=lst.inum, ilist=_iptr(lst.ilist), numneigh=_iptr(lst.numneigh), first=_iptr(lst.first),
+                           neigh=_iptr(neigh), nneigh=int(lst.neigh.size))
+        self._check(self.lib.conp_pair_set_list(self.h, C.byref(v), int(nall)))
+
+    def pair_compute(self, at, forces=True, eng=True, virial=True, eatom=True, vatom=True, f=None):
+        """conp_pair_compute on host arrays -> (f [nall][3] (added to `f`, zeros by default), eng [2], W [6], eatom [nall],
+        vatom [nall][6]); what was not asked for is None"""
+        n = at.nlocal + at.nghost
+        if forces:
+            f = np.zeros((n, 3)) if f is None else f
+            assert f.dtype == np.float64 and f.flags.c_contiguous and f.shape == (n, 3)
+        else:
+            f = None
+        e2 = np.full(2, np.nan) if eng else None
+        w = np.full(6, np.nan) if virial else None
+        ea = np.full(n, np.nan) if eatom else None
+        va = np.full((n, 6), np.nan) if vatom else None
+        ptr = lambda a: _dptr(a) if a is not None else None
+        self._check(self.lib.conp_pair_compute(self.h, C.byref(self.atoms_view(at)), ptr(f), ptr(e2), ptr(w), ptr(ea), ptr(va)))
+        return f, e2, w, ea, va
+
+    def pair_compute_device(self, d_x: int, d_q: int, d_f: int = 0, d_ev: int = 0, d_eatom: int = 0, d_vatom: int = 0):
+        """conp_pair_compute_device: raw device pointers (0 = NULL), enqueued on the handle's stream, no synchronisation; d_f [nall][3]
+        is added to, d_ev [8] (eng_vdwl, eng_coul, virial xx, yy, zz, xy, xz, yz), d_eatom [nall], d_vatom [nall][6] are overwritten"""
+        self._check(self.lib.conp_pair_compute_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q), C.c_void_p(d_f), C.c_void_p(d_ev),
+                                                      C.c_void_p(d_eatom), C.c_void_p(d_vatom)))
 
     def profile(self, enable):
         """0 off, 1 events around every kernel, 2 around the dominant kernel only (conp_hip.h)"""

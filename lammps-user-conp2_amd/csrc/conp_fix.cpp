@@ -657,6 +657,8 @@ struct conp_fix {
   void upload_atoms_static(const conp_atoms *at) {
     nall = at->nlocal + at->nghost;
     ren_upload(d_type, at->type, (size_t)nall);
+    types_in_range = true;                       // conp_pair_compute_device indexes its type-pair table with these
+    for (int i = 0; i < nall; ++i) if (at->type[i] < 0 || at->type[i] > env.ntypes) { types_in_range = false; break; }
     // one pass: the (atom, eleall) pairs of every owned / ghost electrode atom -- the charge scatter list, and what the device
     // fills its atom -> eleall table from (launch_atom2eleall below)
     ele_pairs_h.clear();
@@ -2526,6 +2528,143 @@ struct conp_fix {
     if (vir) for (int k = 0; k < 6; ++k) vir[k] = acc[1 + k];
   }
 
+  // ---- pair forces of lj/cut/coul/long over the pair style's own half list (conp_pair.hip) ----------------
+  // set_params copies the per-type-pair tables (one 8-double record per pair), set_list uploads the list and sizes every buffer a
+  // compute call needs: the device entry then allocates nothing.
+  bool pair_have_params = false, pair_have_list = false;
+  bool types_in_range = false;                   // every atoms->type of the last (setup_)post_neighbor lies in [0, ntypes]
+  int pair_nall = 0, pair_inum = 0, pair_ntab = 0;
+  double pair_cut_coul = 0.0, pair_special_lj[4] = {1, 1, 1, 1}, pair_special_coul[4] = {1, 1, 1, 1};
+  DevBuf<double> d_pair_tab, d_pair_part, d_pair_x, d_pair_q, d_pair_f, d_pair_ev, d_pair_ea, d_pair_va;
+  DevBuf<double4> d_pair_xq;
+  DevBuf<int> d_pair_ilist, d_pair_numneigh, d_pair_first, d_pair_neigh, d_pair_type;
+  std::vector<double> pair_out_h;
+
+  void pair_set_params(const conp_pair_params *p) {
+    if (p->ntypes != env.ntypes) throw ConpError(CONP_ERR_ARG, "conp_pair_set_params: ntypes differs from the handle's");
+    if (!p->cutsq) throw ConpError(CONP_ERR_ARG, "conp_pair_set_params: cutsq is NULL");
+    if (p->cut_ljsq && (!p->lj1 || !p->lj2 || !p->lj3 || !p->lj4 || !p->offset))
+      throw ConpError(CONP_ERR_ARG, "conp_pair_set_params: cut_ljsq without lj1..lj4 and offset");
+    const int nt1 = env.ntypes + 1;
+    std::vector<double> tab((size_t)nt1 * nt1 * PAIR_TAB_W, 0.0);
+    for (int k = 0; k < nt1 * nt1; ++k) {
+      double *t = &tab[(size_t)k * PAIR_TAB_W];
+      t[0] = p->cutsq[k];
+      if (p->cut_ljsq) { t[1] = p->cut_ljsq[k]; t[2] = p->lj1[k]; t[3] = p->lj2[k]; t[4] = p->lj3[k]; t[5] = p->lj4[k]; t[6] = p->offset[k]; }
+      // (no LJ part: cut_ljsq stays 0, and rsq < 0 never holds)
+    }
+    sync();                                       // no kernel may be reading the old table
+    d_pair_tab.upload(tab, stream);
+    sync();                                       // `tab` leaves scope
+    pair_ntab = nt1 * nt1;
+    pair_cut_coul = p->cut_coul;
+    for (int k = 0; k < 4; ++k) { pair_special_lj[k] = p->special_lj[k]; pair_special_coul[k] = p->special_coul[k]; }
+    pair_have_params = true;
+  }
+
+  void pair_set_list(const conp_neighlist *l, int nall_) {
+    pair_have_list = false;                       // a list that is refused leaves the handle without one
+    if (nall_ < 0 || l->inum < 0 || l->inum > nall_ || l->nneigh < 0) throw ConpError(CONP_ERR_ARG, "conp_pair_set_list: bad sizes");
+    if (l->inum > 0 && (!l->ilist || !l->numneigh || !l->first)) throw ConpError(CONP_ERR_ARG, "conp_pair_set_list: null list array");
+    if (l->nneigh > 0 && !l->neigh) throw ConpError(CONP_ERR_ARG, "conp_pair_set_list: null neighbour array");
+    for (int ii = 0; ii < l->inum; ++ii) {        // every index a kernel will use is checked here, once per list
+      const int i = l->ilist[ii];
+      if (i < 0 || i >= nall_) throw ConpError(CONP_ERR_ARG, "conp_pair_set_list: list owner outside [0, nall)");
+      const int64_t a = l->first[i], n = l->numneigh[i];
+      if (a < 0 || n < 0 || a + n > l->nneigh) throw ConpError(CONP_ERR_ARG, "conp_pair_set_list: a row leaves the neighbour array");
+      for (int64_t k = a; k < a + n; ++k)
+        if ((l->neigh[k] & 0x3FFFFFFF) >= nall_) throw ConpError(CONP_ERR_ARG, "conp_pair_set_list: neighbour index outside [0, nall)");
+    }
+    sync();
+    d_pair_ilist.upload(l->ilist, (size_t)l->inum, stream);
+    d_pair_numneigh.upload(l->numneigh, (size_t)(l->inum > 0 ? nall_ : 0), stream);
+    d_pair_first.upload(l->first, (size_t)(l->inum > 0 ? nall_ : 0), stream);
+    d_pair_neigh.upload(l->neigh, (size_t)l->nneigh, stream);
+    d_pair_part.reserve((size_t)std::max(l->inum, 1) * 8);
+    d_pair_xq.reserve((size_t)std::max(nall_, 1));
+    d_pair_ev.reserve(8);
+    sync();                                       // the caller's arrays need not stay
+    pair_nall = nall_; pair_inum = l->inum;
+    pair_have_list = true;
+  }
+
+  void pair_need_ready(const char *who) const {
+    if (!pair_have_params) throw ConpError(CONP_ERR_STATE, std::string(who) + " before conp_pair_set_params");
+    if (!pair_have_list) throw ConpError(CONP_ERR_STATE, std::string(who) + " before conp_pair_set_list");
+  }
+
+  // pack + force kernel (+ finish) on the stream; eatom / vatom are overwritten: zeroed first, then accumulated
+  void pair_enqueue(const double *dx, const double *dq, const int *dtype, int nlocal_, double *df, double *dev, double *dea, double *dva) {
+    PairArgs a;
+    a.inum = pair_inum; a.ilist = d_pair_ilist.p; a.numneigh = d_pair_numneigh.p; a.first = d_pair_first.p; a.neigh = d_pair_neigh.p;
+    a.nlocal = nlocal_; a.newton = env.newton_pair != 0;
+    a.xq = d_pair_xq.p; a.type = dtype; a.nt1 = env.ntypes + 1; a.ntab = pair_ntab; a.tab = d_pair_tab.p;
+    a.cut_coulsq = pair_cut_coul * pair_cut_coul; a.g_ewald = env.g_ewald; a.qqrd2e = env.qqrd2e;
+    for (int k = 0; k < 4; ++k) { a.special_lj[k] = pair_special_lj[k]; a.special_coul[k] = pair_special_coul[k]; }
+    a.f = df; a.eatom = dea; a.vatom = dva; a.part = d_pair_part.p;
+    if (dea && pair_nall > 0) HIP_TRY(hipMemsetAsync(dea, 0, (size_t)pair_nall * sizeof(double), stream));
+    if (dva && pair_nall > 0) HIP_TRY(hipMemsetAsync(dva, 0, (size_t)pair_nall * 6 * sizeof(double), stream));
+    prof.begin("pair_force", stream);
+    launch_pair_pack(stream, pair_nall, dx, dq, d_pair_xq.p);
+    launch_pair_force(stream, a, dev);
+    prof.end(stream);
+    HIP_TRY(hipGetLastError());
+  }
+
+  void pair_compute_host(const conp_atoms *at, double *f, double *eng, double *vir, double *eatom, double *vatom) {
+    pair_need_ready("conp_pair_compute");
+    const int n = at->nlocal + at->nghost;
+    if (at->nlocal < 0 || at->nghost < 0 || n != pair_nall)
+      throw ConpError(CONP_ERR_ARG, "conp_pair_compute: nlocal + nghost differs from the nall of conp_pair_set_list");
+    if (!f && !eng && !vir && !eatom && !vatom) return;
+    if (n > 0 && (!at->x || !at->q || !at->type)) throw ConpError(CONP_ERR_ARG, "conp_pair_compute: null atom array");
+    for (int i = 0; i < n; ++i)
+      if (at->type[i] < 0 || at->type[i] > env.ntypes) throw ConpError(CONP_ERR_ARG, "conp_pair_compute: atom type outside [0, ntypes]");
+    const double *dx, *dq;
+    if (n == nall && n > 0 && at->nlocal == nlocal_cur && d_x.n >= (size_t)n * 3) {   // the atoms of the last post_neighbor: the handle's upload path (ghost_images)
+      upload_xq(at);
+      resident_step = -1;
+      dx = d_x.p; dq = d_q.p;
+    } else {
+      sync();
+      d_pair_x.upload(at->x, (size_t)n * 3, stream); d_pair_q.upload(at->q, (size_t)n, stream);
+      dx = d_pair_x.p; dq = d_pair_q.p;
+    }
+    d_pair_type.upload(at->type, (size_t)n, stream);
+    const size_t nf = f ? (size_t)n * 3 : 0, ne = eatom ? (size_t)n : 0, nv = vatom ? (size_t)n * 6 : 0;
+    const bool ev = eng || vir;
+    if (f) { d_pair_f.reserve(std::max<size_t>(nf, 1)); if (nf) HIP_TRY(hipMemsetAsync(d_pair_f.p, 0, nf * sizeof(double), stream)); }
+    if (eatom) d_pair_ea.reserve(std::max<size_t>(ne, 1));
+    if (vatom) d_pair_va.reserve(std::max<size_t>(nv, 1));
+    pair_enqueue(dx, dq, d_pair_type.p, at->nlocal, f ? d_pair_f.p : nullptr, ev ? d_pair_ev.p : nullptr, eatom ? d_pair_ea.p : nullptr,
+                 vatom ? d_pair_va.p : nullptr);
+    pair_out_h.resize(nf + ne + nv + 8);
+    double *h = pair_out_h.data();
+    if (nf) HIP_TRY(hipMemcpyAsync(h, d_pair_f.p, nf * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (ne) HIP_TRY(hipMemcpyAsync(h + nf, d_pair_ea.p, ne * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (nv) HIP_TRY(hipMemcpyAsync(h + nf + ne, d_pair_va.p, nv * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (ev) HIP_TRY(hipMemcpyAsync(h + nf + ne + nv, d_pair_ev.p, 8 * sizeof(double), hipMemcpyDeviceToHost, stream));
+    sync();
+    for (size_t k = 0; k < nf; ++k) f[k] += h[k];
+    if (ne) std::memcpy(eatom, h + nf, ne * sizeof(double));
+    if (nv) std::memcpy(vatom, h + nf + ne, nv * sizeof(double));
+    const double *e8 = h + nf + ne + nv;
+    if (eng) { eng[0] = e8[0]; eng[1] = e8[1]; }
+    if (vir) for (int k = 0; k < 6; ++k) vir[k] = e8[2 + k];
+  }
+
+  void pair_compute_device(const double *dx, const double *dq, double *df, double *dev, double *dea, double *dva) {
+    if (!dx || !dq) throw ConpError(CONP_ERR_ARG, "null argument");
+    pair_need_ready("conp_pair_compute_device");
+    if (nall <= 0 || pair_nall != nall || d_type.n < (size_t)nall)
+      throw ConpError(CONP_ERR_STATE, "conp_pair_compute_device: the nall of conp_pair_set_list is not the atom count of the last "
+                                      "post_neighbor (whose type array the entry reads)");
+    if (!types_in_range)
+      throw ConpError(CONP_ERR_ARG, "conp_pair_compute_device: an atom type of the last post_neighbor lies outside [0, ntypes]");
+    if (!df && !dev && !dea && !dva) return;
+    pair_enqueue(dx, dq, d_type.p, nlocal_cur, df, dev, dea, dva);
+  }
+
   // fix_conp.cpp:677-695 b_cal / update_bk
   void b_cal(const conp_atoms *at) {
     if (at->nlocal + at->nghost != nall) throw ConpError(CONP_ERR_STATE, "atom count changed without post_neighbor");
@@ -4018,6 +4157,42 @@ int conp_pppm_compute_forces_vatom_device(conp_fix *f, const double *d_x, const 
   kspace_device_check(f, d_x, d_q);
   if (!d_f && !d_ev && !d_eatom && !d_vatom) return CONP_OK;
   pppm_forces_device(f, d_x, d_q, d_f, d_ev, d_eatom, d_vatom);
+  CONP_GUARD_END
+}
+
+// ---- pair forces of lj/cut/coul/long: set_params -> set_list -> compute / compute_device -------------------
+int conp_pair_set_params(conp_fix *f, const conp_pair_params *p) {
+  CONP_GUARD_BEGIN
+  if (!f || !p) throw ConpError(CONP_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(f->env.device));
+  f->drop_graph();
+  f->pair_set_params(p);
+  CONP_GUARD_END
+}
+
+int conp_pair_set_list(conp_fix *f, const conp_neighlist *l, int nall) {
+  CONP_GUARD_BEGIN
+  if (!f || !l) throw ConpError(CONP_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(f->env.device));
+  f->drop_graph();
+  f->pair_set_list(l, nall);
+  CONP_GUARD_END
+}
+
+int conp_pair_compute(conp_fix *f, const conp_atoms *at, double *fo, double *eng, double *virial, double *eatom, double *vatom) {
+  CONP_GUARD_BEGIN
+  if (!f || !at) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->drop_graph();
+  f->pair_compute_host(at, fo, eng, virial, eatom, vatom);
+  CONP_GUARD_END
+}
+
+int conp_pair_compute_device(conp_fix *f, const double *d_x, const double *d_q, double *d_f, double *d_ev, double *d_eatom,
+                             double *d_vatom) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->drop_graph();
+  f->pair_compute_device(d_x, d_q, d_f, d_ev, d_eatom, d_vatom);
   CONP_GUARD_END
 }
 

@@ -332,6 +332,26 @@ void launch_post_force(hipStream_t s, int inum, const int *ilist, const int *num
                        int nall, int newton, const double *x,
                        const double *q, const int *type, const int *atom2eleall, RealParams rp, double qqrd2e, double *f,
                        double *acc /*[9]: eng_coul, virial[6], sum q^2 of owned electrode atoms, contributing pairs*/, bool clear_f);
+// ---- pair forces of lj/cut/coul/long over the pair style's half list (conp_pair.hip) ----
+constexpr int PAIR_TAB_W = 8;            // doubles per type pair: cutsq, cut_ljsq, lj1, lj2, lj3, lj4, offset, (pad)
+constexpr int PAIR_LDS_ENTRIES = 256;    // type pairs, (ntypes + 1)^2, the LDS form of the table holds (16 KB); more: read from global
+struct PairArgs {
+  int inum;
+  const int *ilist, *numneigh, *first, *neigh;
+  int nlocal, newton;
+  const double4 *xq;                     // [nall] (x, y, z, q), launch_pair_pack
+  const int *type;                       // [nall]
+  int nt1, ntab;                         // ntypes + 1, its square
+  const double *tab;                     // [ntab][PAIR_TAB_W]
+  double cut_coulsq, g_ewald, qqrd2e;
+  double special_lj[4], special_coul[4];
+  double *f;                             // [nall][3] accumulated, or NULL
+  double *eatom, *vatom;                 // [nall], [nall][6]: accumulated (the caller zeroes them), or NULL
+  double *part;                          // [inum][8] scratch rows of the eight sums (needed with ev != NULL)
+};
+void launch_pair_pack(hipStream_t s, int nall, const double *x, const double *q, double4 *xq);
+// ev [8] = eng_vdwl, eng_coul, virial xx, yy, zz, xy, xz, yz (overwritten, summed in a fixed order), or NULL
+void launch_pair_force(hipStream_t s, const PairArgs &a, double *ev);
 void launch_left_sum(hipStream_t s, int ne, const int *elecheck, const double *v, double *out);
 void launch_results_out(hipStream_t s, int ne, const int *elecheck, const double *v, double *scal, bool do_left, const double *qele,
                         double *host_q /*page-locked host memory*/, double *host_scal);

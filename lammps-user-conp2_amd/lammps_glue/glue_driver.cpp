@@ -11,6 +11,13 @@
 //                                                  "kf STEP TAG FX FY FZ", "kea STEP TAG E" per owned atom, "ke STEP ENERGY", "kv STEP W[6]".
 //                                                  With the word `vatom` compute() is asked for the per-atom virial too (vflag | 4)
 //                                                  and "kva STEP TAG V[6]" (xx yy zz xy xz yz) follows per owned atom
+//        glue_driver CASEFILE pair [vatom|table]   mode A with `pair_style lj/cut/coul/long/conp/hip` as force->pair: on every step, after the
+//                                                  fix's pre_force, compute(eflag, vflag) on the fix's handle with atom->f cleared; the
+//                                                  style's tables come from the optional block behind the steps (below).  Output per step:
+//                                                  "pf STEP INDEX FX FY FZ" and "pea STEP INDEX E" for all nlocal + nghost atoms,
+//                                                  "pe STEP EVDWL ECOUL", "pv STEP W[6]", "pls STEP N" (list uploads so far); with `vatom`
+//                                                  also "pva STEP INDEX V[6]"; `table` leaves pair_modify table at LAMMPS' default 12:
+//                                                  compute() stops with the style's message
 //        glue_driver CASEFILE pppmforce [vatom|ad|nohandle]
 //                                                  mode A with the `pppm` keyword and `kspace_style pppm/conp/hip ACC device` as
 //                                                  force->kspace: on every step, after the fix's pre_force, compute(eflag, vflag) on
@@ -40,6 +47,8 @@
 //   nmodify { ntok tok... } ...                          fix_modify lines
 //   narg tok...                                          the fix command
 //   nsteps { ntimestep potdiff_value reneighbor(0/1) has_x(0/1) [x y z per atom] } ...
+//   optional, read by the `pair` mode only:  "pair" cut_coul  cutsq cut_ljsq lj1 lj2 lj3 lj4 offset [(ntypes+1)^2 each]
+//                                            special_lj[4] special_coul[4]
 // output (stdout): "scalar STEP VALUE", "q STEP TAG VALUE" for owned electrode atoms, "f STEP ..." sums, "ERROR: msg" + exit 2.
 #include <chrono>
 #include <cstdarg>
@@ -60,6 +69,7 @@
 #include "ewald_conp_hip.h"
 #include "fix_conp_hip.h"
 #include "kspacemodule_hip.h"
+#include "pair_lj_cut_coul_long_conp_hip.h"
 #include "pppm_conp_hip.h"
 
 using namespace LAMMPS_NS;
@@ -84,6 +94,8 @@ static bool g_kspace = false;    // `glue_driver CASEFILE kspace`: EwaldConpHip 
 static bool g_pppmforce = false; // `glue_driver CASEFILE pppmforce`: PPPMConpHip in device mode is the kspace style, compute() on every step
 static std::string g_pppm_variant; // its third word
 static bool g_pppmhost = false;  // `glue_driver CASEFILE pppmhost`
+static bool g_pair = false;      // `glue_driver CASEFILE pair`: PairLJCutCoulLongConpHip is the pair style, compute() on every step
+static std::string g_pair_variant; // its third word
 static bool g_compute = false;   // `glue_driver CASEFILE compute`: after the steps, compute potential/atom/hip on the conp/hip fix
 
 int run_case(const char *path, bool provider, int me, int nprocs, MockCommRank *world, Out &out) {
@@ -92,7 +104,7 @@ int run_case(const char *path, bool provider, int me, int nprocs, MockCommRank *
 
   LAMMPS lmp{};
   Memory memory; Error error; Atom atom{}; Force force{}; Domain domain{}; Update update{}; Comm comm{}; Group group{};
-  Variable variable; Input input{}; Neighbor neighbor{}; Modify modify; KSpace kspace(&lmp); Pair pair{};
+  Variable variable; Input input{}; Neighbor neighbor{}; Modify modify; KSpace kspace(&lmp); Pair pair(&lmp);
   lmp.world = world;
   lmp.memory = &memory; lmp.error = &error; lmp.atom = &atom; lmp.force = &force; lmp.domain = &domain; lmp.update = &update;
   lmp.comm = &comm; lmp.group = &group; lmp.input = &input; lmp.neighbor = &neighbor; lmp.modify = &modify;
@@ -376,12 +388,40 @@ int run_case(const char *path, bool provider, int me, int nprocs, MockCommRank *
   update.ntimestep = 0;
   int nsteps;
   in >> nsteps;
+  struct Step { long ts; double pd; int reneigh, has_x; std::vector<double> x; };
+  std::vector<Step> steps(nsteps);
+  for (auto &st : steps) {
+    in >> st.ts >> st.pd >> st.reneigh >> st.has_x;
+    if (st.has_x) { st.x.resize(xs.size()); for (double &v : st.x) in >> v; }
+  }
+  // `pair_style lj/cut/coul/long/conp/hip` + pair_coeff + `pair_modify table 0` + special_bonds: the tables init_one() would leave
+  // in the base class come from the case file's optional block; the style's list is the generic half list (list 0)
+  std::unique_ptr<PairLJCutCoulLongConpHip> ps;
+  if (g_pair) {
+    std::string word;
+    in >> word;
+    if (word != "pair") throw std::runtime_error("the pair mode needs the case file's pair block");
+    ps.reset(new PairLJCutCoulLongConpHip(&lmp));
+    ps->mock_allocate(ntypes);
+    in >> ps->cut_coul;
+    for (int k = 0; k < 7; ++k)
+      for (int i = 0; i < nt1; ++i)
+        for (int j = 0; j < nt1; ++j) in >> ps->mock_table(k)[i][j];
+    for (double &v : force.special_lj) in >> v;
+    for (double &v : force.special_coul) in >> v;
+    if (!in) throw std::runtime_error("the case file's pair block is short");
+    ps->ncoultablebits = g_pair_variant == "table" ? 12 : 0;
+    ps->list = &lists.front().nl;
+    force.pair = ps.get();
+    modify.fix = fixes; modify.nfix = 1; atom.nmax = std::max(atom.nmax, nall);
+  }
   // Verlet::setup order: modify->setup_post_neighbor(), then modify->setup_pre_force()
   bool first = true;
   for (int s = 0; s < nsteps; ++s) {
-    long ts; double pd; int reneigh, has_x;
-    in >> ts >> pd >> reneigh >> has_x;
-    if (has_x) for (size_t k = 0; k < xs.size(); ++k) in >> xs[k];
+    const long ts = steps[s].ts; const double pd = steps[s].pd; const int reneigh = steps[s].reneigh;
+    if (steps[s].has_x) std::copy(steps[s].x.begin(), steps[s].x.end(), xs.begin());
+    neighbor.ago = (first || reneigh) ? 0 : neighbor.ago + 1;      // Neighbor::decide / build: 0 on a step that rebuilt the lists
+    if (first || reneigh) ++neighbor.ncalls;
     update.ntimestep = ts; update.laststep = -1;
     if (s == nsteps - 1) update.laststep = ts;
     variable.value = pd;
@@ -410,6 +450,23 @@ int run_case(const char *path, bool provider, int me, int nprocs, MockCommRank *
       out.f("kv %ld %.17g %.17g %.17g %.17g %.17g %.17g\n", ts, ew->virial[0], ew->virial[1], ew->virial[2], ew->virial[3], ew->virial[4],
             ew->virial[5]);
     }
+    if (g_pair) {
+      // Verlet after the fixes' pre_force: force_clear(), then force->pair->compute(eflag, vflag)
+      std::fill(fs.begin(), fs.end(), 0.0);
+      const bool va = g_pair_variant == "vatom";
+      ps->compute(3, va ? 5 : 1);
+      for (int i = 0; i < nall; ++i) {
+        out.f("pf %ld %d %.17g %.17g %.17g\n", ts, i, fs[3 * (size_t)i], fs[3 * (size_t)i + 1], fs[3 * (size_t)i + 2]);
+        out.f("pea %ld %d %.17g\n", ts, i, ps->eatom[i]);
+        if (va)
+          out.f("pva %ld %d %.17g %.17g %.17g %.17g %.17g %.17g\n", ts, i, ps->vatom[i][0], ps->vatom[i][1], ps->vatom[i][2],
+                ps->vatom[i][3], ps->vatom[i][4], ps->vatom[i][5]);
+      }
+      out.f("pe %ld %.17g %.17g\n", ts, ps->eng_vdwl, ps->eng_coul);
+      out.f("pv %ld %.17g %.17g %.17g %.17g %.17g %.17g\n", ts, ps->virial[0], ps->virial[1], ps->virial[2], ps->virial[3],
+            ps->virial[4], ps->virial[5]);
+      out.f("pls %ld %d\n", ts, ps->list_uploads());
+    }
     if (g_pppmforce) {
       // Verlet after the fixes' pre_force, on every step: force->kspace->compute(eflag, vflag); atom->f starts from zero
       std::fill(fs.begin(), fs.end(), 0.0);
@@ -431,7 +488,7 @@ int run_case(const char *path, bool provider, int me, int nprocs, MockCommRank *
     double fsum[3] = {0, 0, 0}, fabs_ = 0;
     for (int i = 0; i < nlocal; ++i) for (int c = 0; c < 3; ++c) { fsum[c] += fs[3 * (size_t)i + c]; fabs_ += std::abs(fs[3 * (size_t)i + c]); }
     out.f("f %ld %.17g %.17g %.17g %.17g eng_coul %.17g kspace_energy %.17g\n", ts, fsum[0], fsum[1], fsum[2], fabs_,
-          pair.eng_coul, kspace.energy);
+          force.pair->eng_coul, kspace.energy);
   }
   if (g_compute) {
     // `compute pot all potential/atom/hip kspace` without a pppm style: setup() takes the conp/hip fix's handle (Modify::fix)
@@ -516,6 +573,8 @@ int main(int argc, char **argv) {
     g_pppmforce = argc > 2 && std::string(argv[2]) == "pppmforce";
     g_pppm_variant = g_pppmforce && argc > 3 ? argv[3] : "";
     g_pppmhost = argc > 2 && std::string(argv[2]) == "pppmhost";
+    g_pair = argc > 2 && std::string(argv[2]) == "pair";
+    g_pair_variant = g_pair && argc > 3 ? argv[3] : "";
     rc = run_case(argv[1], argc > 2 && (std::string(argv[2]) == "provider" || g_pppmhost), 0, 1, single, out);
   } catch (const std::exception &e) {
     out.f("ERROR: %s\n", e.what());

@@ -24,8 +24,10 @@ class Atom { public: int nlocal, nghost, ntypes, nmax = 0; bigint natoms; double
              int *map_array = nullptr; int map_size = 0; };
 class KSpace;
 class NeighList;
-class Pair { public: double **cutsq; double eng_coul, virial[6]; double cut_coul = 0.0; NeighList *list = nullptr; virtual ~Pair() {} virtual void *extract(const char *, int &); void ev_tally(int, int, int, int, double, double, double, double, double, double); };
-class Force { public: double qqrd2e, qqr2e, qe2f, dielectric; int newton_pair, newton = 0; KSpace *kspace; Pair *pair; Pair *pair_match(const std::string &, int, int nsub = 0); };
+class Pair;
+class Force { public: double qqrd2e, qqr2e, qe2f, dielectric; int newton_pair, newton = 0; KSpace *kspace; Pair *pair;
+              double special_lj[4] = {1.0, 1.0, 1.0, 1.0}, special_coul[4] = {1.0, 1.0, 1.0, 1.0};   // special_bonds (force.h), [0] is 1.0
+              Pair *pair_match(const std::string &, int, int nsub = 0); };
 class Domain { public: double xprd, yprd, zprd, zprd_half, boxlo[3]; int triclinic = 0; };
 class Update { public: bigint ntimestep, laststep, eflag_atom = 0; char *integrate_style; };
 class Comm { public: int me, nprocs; };
@@ -35,7 +37,9 @@ class Variable { public: int find(const char *); int equalstyle(int); double com
 class Input { public: Variable *variable; };
 class NeighRequest { public: int pair, fix, half, full, occasional, skip, intel; int *iskip, **ijskip; };
 class NeighList { public: int index, inum, occasional; int *ilist, *numneigh, **firstneigh; };
-class Neighbor { public: NeighRequest **requests; int nrequest = 0; int request(void *, int instance = 0); void build(int); void build_one(NeighList *, int preflag = 0); };
+class Neighbor { public: NeighRequest **requests; int nrequest = 0;
+                 int ago = 0; bigint ncalls = 0;   // steps since the last build (0 on a re-neighbouring step) and the number of builds (neighbor.h)
+                 int request(void *, int instance = 0); void build(int); void build_one(NeighList *, int preflag = 0); };
 class Fix;
 class Modify { public: int find_fix(const std::string &); int nfix = 0; Fix **fix = nullptr; };   // (Modify::fix / nfix, modify.h)
 
@@ -51,6 +55,54 @@ class Pointers {
  protected:
   LAMMPS *lmp; MPI_Comm &world; Memory *&memory; Error *&error; Atom *&atom; Force *&force; Domain *&domain; Update *&update; Comm *&comm;
   Group *&group; Input *&input; Neighbor *&neighbor; Modify *&modify; FILE *&screen; FILE *&logfile;
+};
+
+// Pair (pair.h) as far as the glue touches it: what the fix reads (cutsq, extract("cut_coul"), the accumulators it adds its
+// post-force correction to) and what a pair style's compute() fills after ev_init() has decoded eflag / vflag like KSpace's:
+// eng_vdwl, eng_coul, virial (zeroed by ev_init), eatom [nmax], vatom [nmax][6] (one contiguous block behind row pointers, zeroed).
+class Pair : protected Pointers {
+ public:
+  explicit Pair(LAMMPS *l) : Pointers(l) {}
+  virtual ~Pair() {}
+  double **cutsq = nullptr;
+  double eng_vdwl = 0.0, eng_coul = 0.0, virial[6] = {0, 0, 0, 0, 0, 0};
+  double *eatom = nullptr, **vatom = nullptr;
+  double cut_coul = 0.0;
+  int ncoultablebits = 12;                       // pair_modify table N (pair.h; LAMMPS' default is 12, `table 0` switches tables off)
+  int no_virial_fdotr = 0;
+  int evflag = 0, eflag_either = 0, eflag_global = 0, eflag_atom = 0, vflag_either = 0, vflag_global = 0, vflag_atom = 0, vflag_fdotr = 0;
+  NeighList *list = nullptr;
+  virtual void compute(int, int) {}
+  virtual void *extract(const char *, int &);
+  void ev_tally(int, int, int, int, double, double, double, double, double, double);
+ protected:
+  void ev_init(int eflag, int vflag);
+ private:
+  std::vector<double> eatom_store, vatom_store;
+  std::vector<double *> vatom_rows;
+};
+
+// LAMMPS' PairLJCutCoulLong (pair_lj_cut_coul_long.h) as far as the conp/hip style reads it: the per-type-pair tables init_one()
+// leaves behind ([ntypes + 1][ntypes + 1] behind row pointers) and cut_coul.  compute() is the CPU pair loop in LAMMPS; the mock
+// only counts its calls.  mock_allocate() stands for allocate(): it makes the tables, the test host fills them.
+class PairLJCutCoulLong : public Pair {
+ public:
+  explicit PairLJCutCoulLong(LAMMPS *l) : Pair(l) {}
+  void compute(int, int) override { ++base_compute_calls; }
+  void *extract(const char *, int &) override;
+  int base_compute_calls = 0;
+  void mock_allocate(int ntypes);
+ protected:
+  double cut_lj_global = 0.0;
+  double **cut_lj = nullptr, **cut_ljsq = nullptr, **epsilon = nullptr, **sigma = nullptr;
+  double **lj1 = nullptr, **lj2 = nullptr, **lj3 = nullptr, **lj4 = nullptr, **offset = nullptr;
+  double cut_coulsq = 0.0;
+ public:
+  // (the test host's way to the protected tables, in the order cutsq, cut_ljsq, lj1, lj2, lj3, lj4, offset)
+  double **mock_table(int k) { double **tabs[7] = {cutsq, cut_ljsq, lj1, lj2, lj3, lj4, offset}; return tabs[k]; }
+ private:
+  std::vector<double> table_store;
+  std::vector<double *> table_rows;
 };
 
 // KSpace (kspace.h) as far as the glue touches it: the settings the handles read, and what a style's compute() fills -- energy,

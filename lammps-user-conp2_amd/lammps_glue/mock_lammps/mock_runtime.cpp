@@ -146,6 +146,35 @@ void *Pair::extract(const char *name, int &dim) {
   return nullptr;
 }
 void Pair::ev_tally(int, int, int, int, double, double, double, double, double, double) {}
+void Pair::ev_init(int eflag, int vflag) {          // Pair::ev_init / ev_setup: the flags, the accumulators cleared, eatom / vatom sized and cleared
+  evflag = (eflag || vflag) ? 1 : 0;
+  eflag_either = eflag; eflag_global = eflag & 1; eflag_atom = eflag & 2;
+  vflag_either = vflag; vflag_global = vflag & 3; vflag_atom = vflag & 12;
+  vflag_fdotr = (vflag_global == 2 && no_virial_fdotr == 0) ? 1 : 0;
+  eng_vdwl = eng_coul = 0.0;
+  for (double &v : virial) v = 0.0;
+  const size_t n = (size_t)std::max(std::max(atom->nmax, atom->nlocal + atom->nghost), 1);
+  if (eflag_atom) { eatom_store.assign(n, 0.0); eatom = eatom_store.data(); }
+  if (vflag_atom) {
+    vatom_store.assign(6 * n, 0.0);
+    vatom_rows.resize(n);
+    for (size_t i = 0; i < n; ++i) vatom_rows[i] = vatom_store.data() + 6 * i;
+    vatom = vatom_rows.data();
+  }
+}
+void *PairLJCutCoulLong::extract(const char *name, int &dim) {
+  dim = 0;
+  if (std::strcmp(name, "cut_coul") == 0) return &cut_coul;
+  return nullptr;
+}
+void PairLJCutCoulLong::mock_allocate(int ntypes) {
+  const size_t n = (size_t)ntypes + 1;
+  table_store.assign(7 * n * n, 0.0);
+  table_rows.resize(7 * n);
+  for (size_t k = 0; k < 7 * n; ++k) table_rows[k] = table_store.data() + k * n;
+  cutsq = table_rows.data(); cut_ljsq = table_rows.data() + n; lj1 = table_rows.data() + 2 * n; lj2 = table_rows.data() + 3 * n;
+  lj3 = table_rows.data() + 4 * n; lj4 = table_rows.data() + 5 * n; offset = table_rows.data() + 6 * n;
+}
 
 Pair *Force::pair_match(const std::string &word, int, int) { return word == "coul" ? pair : nullptr; }
 
