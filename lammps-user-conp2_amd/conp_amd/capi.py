@@ -522,34 +522,16 @@ class FixConp:
     def ewald_forces(self, at, energy=True, virial=True, eatom=False, f=None):
         """collective under decomposed ranks: reciprocal-space forces [nlocal][3] (added to `f`, zeros by default), energy, virial
         (xx, yy, zz, xy, xz, yz) and per-atom energies of the owned atoms -> (f, E, W, e); what was not asked for is None"""
-        f = np.zeros((at.nlocal, 3)) if f is None else f
-        assert f.dtype == np.float64 and f.flags.c_contiguous and f.shape == (at.nlocal, 3)
-        en = C.c_double() if energy else None
-        w = np.zeros(6) if virial else None
-        e = np.zeros(at.nlocal) if eatom else None
-        self._check(self.lib.conp_ewald_compute_forces(self.h, C.byref(self.atoms_view(at)), _dptr(f),
-                                                       C.byref(en) if energy else None, _dptr(w) if virial else None,
-                                                       _dptr(e) if eatom else None))
-        return f, (en.value if energy else None), w, e
+        return self._forces_vatom(self.lib.conp_ewald_compute_forces, at, energy, virial, eatom, f, True, vatom=False)[:4]
 
     def pppm_compute_forces(self, at, energy=True, virial=True, eatom=False, f=None, forces=True):
         """the mesh twin of ewald_forces (`pppm` handles; collective under decomposed ranks): PPPM reciprocal-space forces [nlocal][3]
         (added to `f`, zeros by default; forces=False: none), energy, virial (xx, yy, zz, xy, xz, yz) and per-atom energies of the owned
         atoms -> (f, E, W, e); what was not asked for is None"""
-        if forces:
-            f = np.zeros((at.nlocal, 3)) if f is None else f
-            assert f.dtype == np.float64 and f.flags.c_contiguous and f.shape == (at.nlocal, 3)
-        else:
-            f = None
-        en = C.c_double() if energy else None
-        w = np.zeros(6) if virial else None
-        e = np.zeros(at.nlocal) if eatom else None
-        self._check(self.lib.conp_pppm_compute_forces(self.h, C.byref(self.atoms_view(at)), _dptr(f) if forces else None,
-                                                      C.byref(en) if energy else None, _dptr(w) if virial else None,
-                                                      _dptr(e) if eatom else None))
-        return f, (en.value if energy else None), w, e
+        return self._forces_vatom(self.lib.conp_pppm_compute_forces, at, energy, virial, eatom, f, forces, vatom=False)[:4]
 
     def _forces_vatom(self, entry, at, energy, virial, eatom, f, forces, vatom):
+        """the output arrays of a host force entry and the call; `entry` with or without the trailing vatom parameter"""
         if forces:
             f = np.zeros((at.nlocal, 3)) if f is None else f
             assert f.dtype == np.float64 and f.flags.c_contiguous and f.shape == (at.nlocal, 3)
@@ -559,8 +541,9 @@ class FixConp:
         w = np.zeros(6) if virial else None
         e = np.zeros(at.nlocal) if eatom else None
         v = np.full((at.nlocal, 6), np.nan) if vatom else None        # (overwritten by the entry, zero-charge rows included)
-        self._check(entry(self.h, C.byref(self.atoms_view(at)), _dptr(f) if forces else None, C.byref(en) if energy else None,
-                          _dptr(w) if virial else None, _dptr(e) if eatom else None, _dptr(v) if vatom else None))
+        args = [_dptr(f) if forces else None, C.byref(en) if energy else None, _dptr(w) if virial else None, _dptr(e) if eatom else None,
+                _dptr(v) if vatom else None]
+        self._check(entry(self.h, C.byref(self.atoms_view(at)), *args[:len(entry.argtypes) - 2]))
         return f, (en.value if energy else None), w, e, v
 
     def ewald_forces_vatom(self, at, energy=True, virial=True, eatom=False, f=None, forces=True, vatom=True):
@@ -693,26 +676,25 @@ class FixConp:
     def pre_force_device(self, d_x: int, d_q: int, potdiff):
         self._check(self.lib.conp_fix_pre_force_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q), potdiff))
 
+    def _forces_device(self, entry, *ptrs):
+        self._check(entry(self.h, *[C.c_void_p(p) for p in ptrs]))
+
     def ewald_forces_device(self, d_x: int, d_q: int, d_f: int = 0, d_ev: int = 0, d_eatom: int = 0):
         """conp_ewald_compute_forces_device: raw device pointers (0 = NULL), enqueued on the handle's stream, no synchronisation;
         d_f [nlocal][3] is added to, d_ev [7] (energy, virial xx, yy, zz, xy, xz, yz) and d_eatom [nlocal] are overwritten"""
-        self._check(self.lib.conp_ewald_compute_forces_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q), C.c_void_p(d_f),
-                                                              C.c_void_p(d_ev), C.c_void_p(d_eatom)))
+        self._forces_device(self.lib.conp_ewald_compute_forces_device, d_x, d_q, d_f, d_ev, d_eatom)
 
     def pppm_forces_device(self, d_x: int, d_q: int, d_f: int = 0, d_ev: int = 0, d_eatom: int = 0):
         """conp_pppm_compute_forces_device: the mesh twin of ewald_forces_device (`pppm` handles)"""
-        self._check(self.lib.conp_pppm_compute_forces_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q), C.c_void_p(d_f),
-                                                             C.c_void_p(d_ev), C.c_void_p(d_eatom)))
+        self._forces_device(self.lib.conp_pppm_compute_forces_device, d_x, d_q, d_f, d_ev, d_eatom)
 
     def ewald_forces_vatom_device(self, d_x: int, d_q: int, d_f: int = 0, d_ev: int = 0, d_eatom: int = 0, d_vatom: int = 0):
         """conp_ewald_compute_forces_vatom_device: ewald_forces_device with d_vatom [nlocal][6] (xx, yy, zz, xy, xz, yz), overwritten"""
-        self._check(self.lib.conp_ewald_compute_forces_vatom_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q), C.c_void_p(d_f),
-                                                                    C.c_void_p(d_ev), C.c_void_p(d_eatom), C.c_void_p(d_vatom)))
+        self._forces_device(self.lib.conp_ewald_compute_forces_vatom_device, d_x, d_q, d_f, d_ev, d_eatom, d_vatom)
 
     def pppm_forces_vatom_device(self, d_x: int, d_q: int, d_f: int = 0, d_ev: int = 0, d_eatom: int = 0, d_vatom: int = 0):
         """conp_pppm_compute_forces_vatom_device: the mesh twin of ewald_forces_vatom_device (`pppm` handles)"""
-        self._check(self.lib.conp_pppm_compute_forces_vatom_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q), C.c_void_p(d_f),
-                                                                   C.c_void_p(d_ev), C.c_void_p(d_eatom), C.c_void_p(d_vatom)))
+        self._forces_device(self.lib.conp_pppm_compute_forces_vatom_device, d_x, d_q, d_f, d_ev, d_eatom, d_vatom)
 
     # -- pair forces of lj/cut/coul/long: set_params -> set_list -> compute / compute_device ----------------
     def pair_set_params(self, cutsq, cut_coul, lj=None, special_lj=(1.0, 1.0, 1.0, 1.0), special_coul=(1.0, 1.0, 1.0, 1.0)):

@@ -3290,6 +3290,7 @@ int64_t conp_host_pair_rows(int which, const conp_neighlist *l, const conp_atoms
 
 // ---- PPPM coupling beyond b, compute potential/atom --------------------------------------------------------------------------
 namespace {
+constexpr double MY_PI = 3.14159265358979323846, MY_PIS = 1.77245385090551602729;
 void need_pppm(conp_fix *f) {
   if (!f->args.pppm || f->dpppm.nfft <= 0)
     throw ConpError(CONP_ERR_STATE, "Compute requires a compatible KSpace provider like pppm/conp");   // compute_potential_atom.cpp:110
@@ -3415,12 +3416,210 @@ void ew_tables_at(conp_fix *f, const double *xb, int nb, int nb_pad) {
 }
 // ... of atoms [b0, b0 + nb) of the compact list d_ew_x
 void ew_tables(conp_fix *f, int b0, int nb, int nb_pad) { ew_tables_at(f, f->d_ew_x.p + 3 * (size_t)b0, nb, nb_pad); }
+
+// ---- the steps the k-space potential and force entries share (DESIGN.md sections 11-15) ----
+// (static: the unnamed namespace alone does not keep a name inside extern "C" out of the library's dynamic symbols)
+// split the atoms of a block over slices of G so that the launch keeps ~6 workgroups on every CU (the LDS limit of ew_sk_kernel;
+// each waits on its chunk loads) -- every split owns a slice: no atomics
+static int ew_nsplit(const conp_fix *f, int nb_pad) {
+  const KPlan &pl = f->plan;
+  const int wgs = std::max(1, pl.C_pad / 64 * pl.n_row_tiles);
+  int nsplit = std::max(1, std::min({6 * f->num_cus / wgs + 1, 32, nb_pad / 64}));
+  while (nsplit > 1 && (size_t)nsplit * pl.R_pad * pl.C_pad * sizeof(double) > EW_SLICES) --nsplit;
+  return nsplit;
+}
+// S of the n atoms at x (device, [n][3]) with the charges q (device, zeros behind n up to whole blocks) into d_ew_G: block by block
+// the phase tables and ew_sk_kernel into the slices, then the slices' sum.  After ew_reserve(f, nb_pad).
+static void ew_build_S(conp_fix *f, const double *x, const double *q, int n, int nb_pad) {
+  const size_t gsz = (size_t)f->plan.R_pad * f->plan.C_pad;
+  const int nsplit = ew_nsplit(f, nb_pad);
+  f->d_ew_Gp.reserve(gsz * nsplit); f->d_ew_G.reserve(gsz); f->d_ew_Gwf.reserve(gsz);
+  HIP_TRY(hipMemsetAsync(f->d_ew_Gp.p, 0, gsz * nsplit * sizeof(double), f->stream));
+  for (int b0 = 0; b0 < n; b0 += nb_pad) {
+    ew_tables_at(f, x + 3 * (size_t)b0, std::min(nb_pad, n - b0), nb_pad);
+    launch_ew_sk(f->stream, f->dplan, nb_pad, nsplit, f->d_ew_Rp.p, f->d_ew_Tz.p, q + b0, f->d_ew_Gp.p);
+  }
+  launch_ew_sk_sum(f->stream, f->dplan, nsplit, f->d_ew_Gp.p, f->d_ew_G.p);
+}
+// once per plan: (ug, kx, ky, kz) of the reference's k list into d_ew_kv; the tile lists of the projection into d_ew_tiles / d_ew_ctptr
+static void ew_kv_ready(conp_fix *f) {
+  if (f->ew_kv_gen != f->plan_gen) {
+    const KTables &kt = f->kt;
+    const int K = kt.kcount;
+    std::vector<double> kv((size_t)4 * K);
+    for (int k = 0; k < K; ++k) {
+      kv[k] = kt.ug[k];
+      kv[(size_t)K + k] = kt.unitk[0] * kt.kxvecs[k]; kv[2 * (size_t)K + k] = kt.unitk[1] * kt.kyvecs[k];
+      kv[3 * (size_t)K + k] = kt.unitk[2] * kt.kzvecs[k];
+    }
+    f->d_ew_kv.upload(kv, f->stream);
+    f->sync();                     // (kv goes out of scope)
+    f->ew_kv_gen = f->plan_gen;
+  }
+}
+static void ew_tiles_ready(conp_fix *f) {
+  if (f->ew_tiles_gen != f->plan_gen) {
+    f->d_ew_tiles.upload(f->tiles_h, f->stream); f->d_ew_ctptr.upload(f->ct_ptr_h, f->stream);
+    f->sync();
+    f->ew_tiles_gen = f->plan_gen;
+  }
+}
+// the seven sums (sum_k ug |S_k|^2, the six virial sums) of d_ew_G into d_ew_ev[0..6]
+static void ew_energy_virial(conp_fix *f) {
+  ew_kv_ready(f);
+  const int K = f->kt.kcount;
+  f->d_ew_ev.reserve((size_t)7 * (ew_energy_virial_workgroups(K) + 1));
+  launch_ew_energy_virial(f->stream, K, f->plan.C_pad, KPlan::PT, f->d_sf_row_a.p, f->d_sf_col_c.p, f->d_k_sign.p, f->d_ew_kv.p,
+                          f->env.g_ewald, f->d_ew_G.p, f->d_ew_ev.p + 7, f->d_ew_ev.p);
+}
+// x, q of the owned atoms idx, padded to whole blocks (padding atoms carry no charge), and idx itself into d_ew_x, d_ew_q, d_ew_idx.
+// The copies are asynchronous: they are staged in h, which the caller keeps until it has synchronised.
+struct EwStaged { std::vector<double> x, q; };
+static void ew_upload_compact(conp_fix *f, const conp_atoms *at, const std::vector<int> &idx, int nb_pad, EwStaged &h) {
+  const int n = (int)idx.size(), ntot = (n + nb_pad - 1) / nb_pad * nb_pad;
+  h.x.assign(3 * (size_t)ntot, 0.0); h.q.assign(ntot, 0.0);
+  for (int k = 0; k < n; ++k) {
+    const int i = idx[k];
+    for (int c = 0; c < 3; ++c) h.x[3 * (size_t)k + c] = at->x[3 * (size_t)i + c];
+    h.q[k] = at->q[i];
+  }
+  ew_reserve(f, nb_pad);
+  f->d_ew_x.upload(h.x, f->stream); f->d_ew_q.upload(h.q, f->stream); f->d_ew_idx.upload(idx, f->stream);
+}
+// The block loop of the force and per-atom virial kernels over n atoms at x (device) with the charges d_ew_q, from d_ew_Gwf / d_ew_G.
+// Host path: x = d_ew_x, idx = d_ew_idx (the outputs are indexed through it, o is complete), every block's tables are rebuilt.
+// Device path: x = the caller's array, idx = NULL (block b0 writes the atoms [b0, b0 + nb) of the caller's outputs; Q, M, M2 come
+// from d_kf_sums); one block: ew_build_S's tables are still there.  fo, eo, vo NULL: that output is not formed.
+static void ew_force_blocks(conp_fix *f, int n, int nb_pad, const double *x, const int *idx, const EwForceOut &o, double *fo, double *eo,
+                            double *vo) {
+  const KPlan &pl = f->plan;
+  const double *uk = f->kt.unitk, *q = f->d_ew_q.p;
+  f->d_ew_bk.reserve((size_t)16 * nb_pad);
+  if (vo) {
+    f->d_ew_Gwf2.reserve((size_t)pl.R_pad * pl.C_pad); f->d_ew_vk.reserve((size_t)24 * nb_pad);
+    launch_ew_gw2(f->stream, f->dplan, pl.kzt, uk[0], uk[1], uk[2], f->env.g_ewald, f->d_ew_G.p, f->d_ew_Gwf2.p);
+  }
+  for (int b0 = 0; b0 < n; b0 += nb_pad) {
+    const int nb = std::min(nb_pad, n - b0);
+    const double *xb = x + 3 * (size_t)b0;
+    if (idx || n > nb_pad) ew_tables_at(f, xb, nb, nb_pad);
+    launch_ew_force(f->stream, f->dplan, pl.kzt, uk[0], uk[1], uk[2], nb_pad, f->d_ew_ctptr.p, f->d_ew_tiles.p, f->d_ew_Gwf.p,
+                    f->d_ew_Rp.p, f->d_ew_Tz.p, f->d_ew_bk.p);
+    if (idx) launch_ew_force_out(f->stream, nb, nb_pad, f->d_ew_bk.p, idx + b0, q + b0, xb, o, fo, eo);
+    else if (fo || eo) launch_ew_force_out_device(f->stream, nb, nb_pad, f->d_ew_bk.p, q + b0, xb, o, f->d_kf_sums.p, b0, fo, eo);
+    if (!vo) continue;
+    launch_ew_vatom(f->stream, f->dplan, pl.kzt, uk[0], uk[1], uk[2], nb_pad, f->d_ew_ctptr.p, f->d_ew_tiles.p, f->d_ew_Gwf2.p,
+                    f->d_ew_Rp.p, f->d_ew_Tz.p, f->d_ew_vk.p);
+    if (idx) launch_ew_vatom_out(f->stream, nb, nb_pad, f->d_ew_bk.p, f->d_ew_vk.p, idx + b0, q + b0, f->env.qqrd2e, vo);
+    else launch_ew_vatom_out_device(f->stream, nb, nb_pad, f->d_ew_bk.p, f->d_ew_vk.p, q + b0, f->env.qqrd2e, b0, vo);
+  }
+}
+// Q, Q2, M, M2 of the n atoms of the device arrays into d_kf_sums[0..3]
+void kspace_four_sums(conp_fix *f, int n, const double *dx, const double *dq) {
+  f->d_kf_sums.reserve((size_t)4 * (kspace_four_sums_workgroups(n) + 1));
+  launch_kspace_four_sums(f->stream, n, dx, dq, f->d_kf_sums.p + 4, f->d_kf_sums.p);
+}
+KspaceFinish kspace_finish_args(const conp_fix *f, double V, double L) {
+  const double g = f->env.g_ewald;
+  KspaceFinish a{};
+  a.qs = f->env.qqrd2e; a.g_pis = g / MY_PIS; a.qcoef = 0.5 * MY_PI / (g * g * V);
+  a.slab = f->env.slabflag ? 1 : 0; a.slab_pref = 2.0 * MY_PI / V; a.L2_12 = L * L / 12.0;
+  return a;
+}
+// The parameter block of the force-output kernels.  four == NULL (the device entries): Q, M, M2 stay zero and ecoef lacks its
+// factor Q -- kspace_out_from_sums completes the block on the device.  The host entries hand in their four sums.
+EwForceOut kspace_out_args(const conp_fix *f, double V, double L, const double *four) {
+  const double g = f->env.g_ewald;
+  EwForceOut o{};
+  o.qs = f->env.qqrd2e; o.selfc = 2.0 * g / MY_PIS; o.ecoef = 0.5 * MY_PI / (g * g * V);
+  o.slab = f->env.slabflag ? 1 : 0;
+  o.fz_pref = -4.0 * MY_PI / V; o.e_pref = 2.0 * MY_PI / V; o.L2_12 = L * L / 12.0;
+  if (four) {
+    const double Q = four[0];
+    o.Q = Q; o.M = four[2]; o.M2 = four[3]; o.ecoef = 0.5 * MY_PI * Q / (g * g * V);
+  }
+  return o;
+}
+// the mesh's box: L = the slab-extended z period, V, the unit wave vectors
+struct PppmGeom { double L, V, uk[3]; };
+static PppmGeom pppm_geometry(const conp_fix *f) {
+  const double L = f->env.zprd * f->env.slab_volfactor;
+  return PppmGeom{L, f->env.xprd * f->env.yprd * L, {2.0 * MY_PI / f->env.xprd, 2.0 * MY_PI / f->env.yprd, 2.0 * MY_PI / L}};
+}
+// The mesh solve of the force entries, from the density brick in d_pp_re, in two halves (the device entry gathers the per-atom
+// virial between them).  pppm_mesh_spectra: forward transform; with vb, the six v_ab fields into d_pp_v[] and their pointers into
+// vb (rho^ is still in (re, im) then: the kspace launch overwrites it).  pppm_mesh_forces: pppm_kspace_kernel -- the seven sums
+// into d_pp_kpart[0..6]; d_ev: energy and virial from them (kspace_finish_kernel) -- then, with want_u, u and E_z back into
+// (d_pp_re, d_pp_im) and, with fields, E_x and E_y into (d_pp_ex, d_pp_ey).  The event brackets record under conp_fix_profile only.
+static void pppm_mesh_spectra(conp_fix *f, const PppmGeom &gm, bool fields, double **vb /*[6], or NULL: no per-atom virial*/) {
+  const size_t nf = (size_t)f->dpppm.nfft;
+  if (fields) { f->d_pp_ex.reserve(nf); f->d_pp_ey.reserve(nf); }
+  f->d_pp_kpart.reserve((size_t)7 * (pppm_kspace_workgroups(f->dpppm.nfft) + 1));
+  f->prof.begin("pppm_f_forward", f->stream);
+  launch_pppm_forward(f->stream, f->dpppm, f->d_pp_re.p, f->d_pp_im.p);
+  f->prof.end(f->stream);
+  if (!vb) return;
+  for (int c = 0; c < 6; ++c) { f->d_pp_v[c].reserve(nf); vb[c] = f->d_pp_v[c].p; }
+  launch_pppm_vatom_spectra(f->stream, f->dpppm, gm.uk, f->env.g_ewald, f->d_pp_re.p, f->d_pp_im.p, vb);
+  for (int c = 0; c < 6; c += 2) launch_pppm_backward(f->stream, f->dpppm, vb[c], vb[c + 1]);
+}
+static void pppm_mesh_forces(conp_fix *f, const PppmGeom &gm, bool fields, bool want_u, double *d_ev /*[7], or NULL*/) {
+  f->prof.begin("pppm_f_kspace", f->stream);
+  launch_pppm_kspace(f->stream, f->dpppm, gm.uk, f->env.g_ewald, gm.V, f->d_pp_re.p, f->d_pp_im.p, fields ? f->d_pp_ex.p : nullptr,
+                     fields ? f->d_pp_ey.p : nullptr, f->d_pp_kpart.p + 7, f->d_pp_kpart.p);
+  f->prof.end(f->stream);
+  f->pp_im_clean = false;
+  if (d_ev) launch_kspace_finish(f->stream, kspace_finish_args(f, gm.V, gm.L), f->d_pp_kpart.p, f->d_kf_sums.p, d_ev);
+  if (!want_u) return;
+  f->prof.begin("pppm_f_backward", f->stream);
+  launch_pppm_backward(f->stream, f->dpppm, f->d_pp_re.p, f->d_pp_im.p);
+  if (fields) launch_pppm_backward(f->stream, f->dpppm, f->d_pp_ex.p, f->d_pp_ey.p);
+  f->prof.end(f->stream);
+}
+// the owned atoms that carry charge into idx; Q, Q2, M, M2 of them (this rank's) into four
+static void charged_owned(const conp_atoms *at, std::vector<int> &idx, double four[4]) {
+  std::fill(four, four + 4, 0.0);
+  for (int i = 0; i < at->nlocal; ++i) {
+    const double q = at->q[i], z = at->x[3 * (size_t)i + 2];
+    if (q == 0) continue;
+    idx.push_back(i);
+    four[0] += q; four[1] += q * q; four[2] += q * z; four[3] += q * z * z;
+  }
+}
+// energy from the first of the seven k-space sums and the four sums: what kspace_finish_kernel evaluates for the device entries
+static double kspace_energy(const conp_fix *f, double s0, double Q, double Q2, double M, double M2, double V, double L) {
+  const double g = f->env.g_ewald;
+  double e = s0 - g * Q2 / MY_PIS - 0.5 * MY_PI * Q * Q / (g * g * V);
+  if (f->env.slabflag) e += 2.0 * MY_PI * (M * M - Q * M2 - Q * Q * L * L / 12.0) / V;
+  return f->env.qqrd2e * e;
+}
+// The per-atom outputs of a host entry: d_f [nlocal][3] is ADDED to fout, d_e and d_v overwrite eatom and vatom, at the n atoms idx.
+// A NULL device pointer: not formed, nothing copied; a NULL host pointer: not wanted.  Synchronises.
+static void download_scatter(conp_fix *f, int nlocal, const std::vector<int> &idx, int n, const double *d_f, const double *d_e,
+                             const double *d_v, double *fout, double *eatom, double *vatom) {
+  std::vector<double> hf, he, hv;
+  const auto download = [&](const double *d, size_t count, std::vector<double> &h) {
+    if (!d) return;
+    h.resize(count);
+    HIP_TRY(hipMemcpyAsync(h.data(), d, count * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+  };
+  download(d_v, 6 * (size_t)nlocal, hv); download(d_f, 3 * (size_t)nlocal, hf); download(d_e, nlocal, he);
+  HIP_TRY(hipGetLastError());
+  f->sync();
+  for (int k = 0; k < n; ++k) {
+    const int i = idx[k];
+    if (fout && d_f) for (int c = 0; c < 3; ++c) fout[3 * (size_t)i + c] += hf[3 * (size_t)i + c];
+    if (eatom && d_e) eatom[i] = he[i];
+    if (vatom && d_v) for (int c = 0; c < 6; ++c) vatom[6 * (size_t)i + c] = hv[6 * (size_t)i + c];
+  }
+}
+
 // w o G of every charged owned atom at the positions and charges of `at` (not the update's cached arrays) into d_ew_Gwf.
 // Decomposed ranks: each rank contracts its own atoms, G is summed through the host's all-reduce (km_ewald.cpp:784-785) --
 // COLLECTIVE.  Replicated-atom handles (several ranks without conp_fix_set_comm) hold every atom on every rank: no collective.
 void ewald_structure_factor(conp_fix *f, const conp_atoms *at) {
   if (at->nlocal + at->nghost != f->nall) throw ConpError(CONP_ERR_STATE, "atom count changed without post_neighbor");
-  const KPlan &pl = f->plan;
+  // (not ew_upload_compact: no atom at all still takes one block of padding here, and no index list is wanted)
   std::vector<double> xs, qs;
   for (int i = 0; i < at->nlocal; ++i) {
     if (at->q[i] == 0) continue;
@@ -3429,24 +3628,13 @@ void ewald_structure_factor(conp_fix *f, const conp_atoms *at) {
   }
   const int n = (int)qs.size();
   const int nb_pad = ew_block(f, n);
-  const size_t gsz = (size_t)pl.R_pad * pl.C_pad;
-  // split the atoms of a block over slices of G so that the launch keeps ~6 workgroups on every CU (the LDS limit of ew_sk_kernel;
-  // each waits on its chunk loads) -- every split owns a slice: no atomics
-  const int wgs = std::max(1, pl.C_pad / 64 * pl.n_row_tiles);
-  int nsplit = std::max(1, std::min({6 * f->num_cus / wgs + 1, 32, nb_pad / 64}));
-  while (nsplit > 1 && (size_t)nsplit * gsz * sizeof(double) > EW_SLICES) --nsplit;
   const int ntot = std::max(nb_pad, (n + nb_pad - 1) / nb_pad * nb_pad);
   xs.resize(3 * (size_t)ntot, 0.0); qs.resize(ntot, 0.0);     // padding atoms carry no charge
   ew_reserve(f, nb_pad);
   f->d_ew_x.upload(xs, f->stream); f->d_ew_q.upload(qs, f->stream);
-  f->d_ew_Gp.reserve(gsz * nsplit); f->d_ew_G.reserve(gsz); f->d_ew_Gwf.reserve(gsz);
-  HIP_TRY(hipMemsetAsync(f->d_ew_Gp.p, 0, gsz * nsplit * sizeof(double), f->stream));
-  for (int b0 = 0; b0 < n; b0 += nb_pad) {
-    ew_tables(f, b0, std::min(nb_pad, n - b0), nb_pad);
-    launch_ew_sk(f->stream, f->dplan, nb_pad, nsplit, f->d_ew_Rp.p, f->d_ew_Tz.p, f->d_ew_q.p + b0, f->d_ew_Gp.p);
-  }
-  launch_ew_sk_sum(f->stream, f->dplan, nsplit, f->d_ew_Gp.p, f->d_ew_G.p);
+  ew_build_S(f, f->d_ew_x.p, f->d_ew_q.p, n, nb_pad);
   if (f->decomposed) {
+    const size_t gsz = (size_t)f->plan.R_pad * f->plan.C_pad;
     std::vector<double> g(gsz);
     HIP_TRY(hipMemcpyAsync(g.data(), f->d_ew_G.p, gsz * sizeof(double), hipMemcpyDeviceToHost, f->stream));
     f->sync();
@@ -3465,19 +3653,12 @@ void ewald_project(conp_fix *f, const conp_atoms *at, const std::vector<int> &id
   const int n = (int)idx.size();
   if (n == 0) return;
   const int nb_pad = ew_block(f, n);
-  const int ntot = (n + nb_pad - 1) / nb_pad * nb_pad;
-  std::vector<double> xs(3 * (size_t)ntot, 0.0), qs(ntot, 0.0);
-  for (int k = 0; k < n; ++k) {
-    const int i = idx[k];
-    for (int c = 0; c < 3; ++c) xs[3 * (size_t)k + c] = at->x[3 * (size_t)i + c];
-    qs[k] = at->q[i];
-  }
-  ew_reserve(f, nb_pad);
-  f->d_ew_x.upload(xs, f->stream); f->d_ew_q.upload(qs, f->stream); f->d_ew_idx.upload(idx, f->stream);
-  f->d_ew_tiles.upload(f->tiles_h, f->stream); f->d_ew_ctptr.upload(f->ct_ptr_h, f->stream);
+  EwStaged staged;
+  ew_upload_compact(f, at, idx, nb_pad, staged);
+  ew_tiles_ready(f);
   f->d_ew_bk.reserve((size_t)4 * nb_pad);
   f->d_ew_g.reserve(at->nlocal); f->d_ew_u.reserve(at->nlocal);
-  const double selfc = 2.0 * f->env.g_ewald / 1.77245385090551602729;
+  const double selfc = 2.0 * f->env.g_ewald / MY_PIS;
   for (int b0 = 0; b0 < n; b0 += nb_pad) {
     const int nb = std::min(nb_pad, n - b0);
     ew_tables(f, b0, nb, nb_pad);
@@ -3495,124 +3676,47 @@ void ewald_project(conp_fix *f, const conp_atoms *at, const std::vector<int> &id
 // f_i += qqrd2e q_i grad g_i (+ slab) on every charged owned atom, from d_ew_Gwf at the atoms' positions in `at`: ewald_project's
 // blocking with ew_force_kernel in b_project_kernel's place; energy and virial from d_ew_G.  The sums of q, q^2, q z, q z^2 over the
 // owned atoms are all-reduced under decomposed ranks (COLLECTIVE there); S itself is the caller's business (ew_g_valid).
-void ewald_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy, double *virial, double *eatom,
-                  double *vatom = nullptr /*[nlocal][6], overwritten: the per-atom virial*/) {
-  const double MY_PI = 3.14159265358979323846, MY_PIS = 1.77245385090551602729;
-  const KTables &kt = f->kt;
-  const double g = f->env.g_ewald, qs = f->env.qqrd2e, V = kt.volume;
+// vatom: [nlocal][6], overwritten: the per-atom virial.
+void ewald_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy, double *virial, double *eatom, double *vatom) {
+  const double V = f->kt.volume, L = f->env.zprd * f->env.slab_volfactor;
   std::vector<int> idx;
-  double four[4] = {0.0, 0.0, 0.0, 0.0};              // Q, Q2, M, M2
-  for (int i = 0; i < at->nlocal; ++i) {
-    const double q = at->q[i], z = at->x[3 * (size_t)i + 2];
-    if (q == 0) continue;
-    idx.push_back(i);
-    four[0] += q; four[1] += q * q; four[2] += q * z; four[3] += q * z * z;
-  }
+  double four[4];                                     // Q, Q2, M, M2
+  charged_owned(at, idx, four);
   if (f->decomposed) f->rc.sum(four, 4);
-  const double Q = four[0], Q2 = four[1], M = four[2], M2 = four[3];
-  const double L = f->env.zprd * f->env.slab_volfactor;
   if (energy || virial) {
-    const int K = kt.kcount;
-    if (f->ew_kv_gen != f->plan_gen) {
-      std::vector<double> kv((size_t)4 * K);
-      for (int k = 0; k < K; ++k) {
-        kv[k] = kt.ug[k];
-        kv[(size_t)K + k] = kt.unitk[0] * kt.kxvecs[k]; kv[2 * (size_t)K + k] = kt.unitk[1] * kt.kyvecs[k];
-        kv[3 * (size_t)K + k] = kt.unitk[2] * kt.kzvecs[k];
-      }
-      f->d_ew_kv.upload(kv, f->stream);
-      f->sync();                     // (kv goes out of scope)
-      f->ew_kv_gen = f->plan_gen;
-    }
-    const int nwg = ew_energy_virial_workgroups(K);
-    f->d_ew_ev.reserve((size_t)7 * (nwg + 1));
-    launch_ew_energy_virial(f->stream, K, f->plan.C_pad, KPlan::PT, f->d_sf_row_a.p, f->d_sf_col_c.p, f->d_k_sign.p, f->d_ew_kv.p, g,
-                            f->d_ew_G.p, f->d_ew_ev.p + 7, f->d_ew_ev.p);
+    ew_energy_virial(f);
     double s7[7];
     HIP_TRY(hipMemcpyAsync(s7, f->d_ew_ev.p, 7 * sizeof(double), hipMemcpyDeviceToHost, f->stream));
     HIP_TRY(hipGetLastError());
     f->sync();
-    if (energy) {
-      double e = s7[0] - g * Q2 / MY_PIS - 0.5 * MY_PI * Q * Q / (g * g * V);
-      if (f->env.slabflag) e += 2.0 * MY_PI * (M * M - Q * M2 - Q * Q * L * L / 12.0) / V;
-      *energy = qs * e;
-    }
-    if (virial) for (int c = 0; c < 6; ++c) virial[c] = qs * s7[1 + c];
+    if (energy) *energy = kspace_energy(f, s7[0], four[0], four[1], four[2], four[3], V, L);
+    if (virial) for (int c = 0; c < 6; ++c) virial[c] = f->env.qqrd2e * s7[1 + c];
   }
   if (eatom) std::fill(eatom, eatom + at->nlocal, 0.0);
   if (vatom) std::fill(vatom, vatom + 6 * (size_t)at->nlocal, 0.0);
   const int n = (int)idx.size();
   if (n == 0 || (!fout && !eatom && !vatom)) return;
   const int nb_pad = ew_block(f, n);
-  const int ntot = (n + nb_pad - 1) / nb_pad * nb_pad;
-  std::vector<double> xs(3 * (size_t)ntot, 0.0), qv(ntot, 0.0);
-  for (int k = 0; k < n; ++k) {
-    const int i = idx[k];
-    for (int c = 0; c < 3; ++c) xs[3 * (size_t)k + c] = at->x[3 * (size_t)i + c];
-    qv[k] = at->q[i];
-  }
-  ew_reserve(f, nb_pad);
-  f->d_ew_x.upload(xs, f->stream); f->d_ew_q.upload(qv, f->stream); f->d_ew_idx.upload(idx, f->stream);
-  f->d_ew_tiles.upload(f->tiles_h, f->stream); f->d_ew_ctptr.upload(f->ct_ptr_h, f->stream);
-  f->d_ew_bk.reserve((size_t)16 * nb_pad);
+  EwStaged staged;
+  ew_upload_compact(f, at, idx, nb_pad, staged);
+  ew_tiles_ready(f);
   f->d_ew_f.reserve(3 * (size_t)at->nlocal); f->d_ew_e.reserve(at->nlocal);
-  if (vatom) {
-    f->d_ew_Gwf2.reserve((size_t)f->plan.R_pad * f->plan.C_pad); f->d_ew_vk.reserve((size_t)24 * nb_pad);
-    f->d_ew_v.reserve(6 * (size_t)at->nlocal);
-    launch_ew_gw2(f->stream, f->dplan, f->plan.kzt, kt.unitk[0], kt.unitk[1], kt.unitk[2], g, f->d_ew_G.p, f->d_ew_Gwf2.p);
-  }
-  EwForceOut o{};
-  o.qs = qs; o.selfc = 2.0 * g / MY_PIS; o.ecoef = 0.5 * MY_PI * Q / (g * g * V);
-  o.slab = f->env.slabflag ? 1 : 0;
-  o.fz_pref = -4.0 * MY_PI / V; o.e_pref = 2.0 * MY_PI / V; o.M = M; o.M2 = M2; o.Q = Q; o.L2_12 = L * L / 12.0;
-  for (int b0 = 0; b0 < n; b0 += nb_pad) {
-    const int nb = std::min(nb_pad, n - b0);
-    ew_tables(f, b0, nb, nb_pad);
-    launch_ew_force(f->stream, f->dplan, f->plan.kzt, kt.unitk[0], kt.unitk[1], kt.unitk[2], nb_pad, f->d_ew_ctptr.p, f->d_ew_tiles.p,
-                    f->d_ew_Gwf.p, f->d_ew_Rp.p, f->d_ew_Tz.p, f->d_ew_bk.p);
-    launch_ew_force_out(f->stream, nb, nb_pad, f->d_ew_bk.p, f->d_ew_idx.p + b0, f->d_ew_q.p + b0, f->d_ew_x.p + 3 * (size_t)b0, o,
-                        f->d_ew_f.p, f->d_ew_e.p);
-    if (vatom) {
-      launch_ew_vatom(f->stream, f->dplan, f->plan.kzt, kt.unitk[0], kt.unitk[1], kt.unitk[2], nb_pad, f->d_ew_ctptr.p, f->d_ew_tiles.p,
-                      f->d_ew_Gwf2.p, f->d_ew_Rp.p, f->d_ew_Tz.p, f->d_ew_vk.p);
-      launch_ew_vatom_out(f->stream, nb, nb_pad, f->d_ew_bk.p, f->d_ew_vk.p, f->d_ew_idx.p + b0, f->d_ew_q.p + b0, qs, f->d_ew_v.p);
-    }
-  }
-  std::vector<double> hv;
-  if (vatom) {
-    hv.resize(6 * (size_t)at->nlocal);
-    HIP_TRY(hipMemcpyAsync(hv.data(), f->d_ew_v.p, hv.size() * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-  }
-  std::vector<double> hf(3 * (size_t)at->nlocal), he(at->nlocal);
-  HIP_TRY(hipMemcpyAsync(hf.data(), f->d_ew_f.p, hf.size() * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-  HIP_TRY(hipMemcpyAsync(he.data(), f->d_ew_e.p, he.size() * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-  HIP_TRY(hipGetLastError());
-  f->sync();
-  for (int i : idx) {
-    if (fout) for (int c = 0; c < 3; ++c) fout[3 * (size_t)i + c] += hf[3 * (size_t)i + c];
-    if (eatom) eatom[i] = he[i];
-    if (vatom) for (int c = 0; c < 6; ++c) vatom[6 * (size_t)i + c] = hv[6 * (size_t)i + c];
-  }
+  if (vatom) f->d_ew_v.reserve(6 * (size_t)at->nlocal);
+  double *const d_v = vatom ? f->d_ew_v.p : nullptr;
+  ew_force_blocks(f, n, nb_pad, f->d_ew_x.p, f->d_ew_idx.p, kspace_out_args(f, V, L, four), f->d_ew_f.p, f->d_ew_e.p, d_v);
+  download_scatter(f, at->nlocal, idx, n, f->d_ew_f.p, f->d_ew_e.p, d_v, fout, eatom, vatom);
 }
 // ---- PPPM forces, energy, virial ----
 // PPPM::compute with ik differentiation on the handle's mesh, at the positions and charges of `at`: the brick of every charged atom is
 // spread afresh on every call (a kept electrolyte brick is that of the update's positions: never contracted with atoms that may have
 // moved), forward transform, pppm_kspace_kernel, two packed backward transforms, pppm_force_gather_kernel on the charged owned atoms.
 // COLLECTIVE under decomposed ranks like pppm_total_potential (one tagged gather, a replicated mesh) plus the four sums.  Leaves u in
-// d_pp_re (pp_u_valid), as conp_pppm_compute does.
-void pppm_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy, double *virial, double *eatom,
-                 double *vatom = nullptr /*[nlocal][6], overwritten: the per-atom virial*/) {
-  const double MY_PI = 3.14159265358979323846, MY_PIS = 1.77245385090551602729;
-  const double g = f->env.g_ewald, qs = f->env.qqrd2e;
-  const double L = f->env.zprd * f->env.slab_volfactor, V = f->env.xprd * f->env.yprd * L;
+// d_pp_re (pp_u_valid), as conp_pppm_compute does.  vatom: [nlocal][6], overwritten: the per-atom virial.
+void pppm_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy, double *virial, double *eatom, double *vatom) {
+  const PppmGeom gm = pppm_geometry(f);
   std::vector<int> idx;
-  double four[4] = {0.0, 0.0, 0.0, 0.0};              // Q, Q2, M, M2
-  for (int i = 0; i < at->nlocal; ++i) {
-    const double q = at->q[i], z = at->x[3 * (size_t)i + 2];
-    if (q == 0) continue;
-    idx.push_back(i);
-    four[0] += q; four[1] += q * q; four[2] += q * z; four[3] += q * z * z;
-  }
+  double four[4];                                     // Q, Q2, M, M2
+  charged_owned(at, idx, four);
   const int n = (int)idx.size();
   pppm_upload(f, at);
   f->d_pp_scratch.reserve(2048);
@@ -3630,64 +3734,29 @@ void pppm_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy
   }
   ++f->pp_elyte_spreads;
   f->pp_u_valid = false;
-  const double Q = four[0], Q2 = four[1], M = four[2], M2 = four[3];
-  const size_t nf = (size_t)f->dpppm.nfft;
-  const bool fields = fout != nullptr && n > 0;
-  if (fields) { f->d_pp_ex.reserve(nf); f->d_pp_ey.reserve(nf); }
-  const int nwg = pppm_kspace_workgroups(f->dpppm.nfft);
-  f->d_pp_kpart.reserve((size_t)7 * (nwg + 1));
-  const double uk[3] = {2.0 * MY_PI / f->env.xprd, 2.0 * MY_PI / f->env.yprd, 2.0 * MY_PI / L};
-  f->prof.begin("pppm_f_forward", f->stream);
-  launch_pppm_forward(f->stream, f->dpppm, f->d_pp_re.p, f->d_pp_im.p);
-  f->prof.end(f->stream);
-  const bool want_v = vatom != nullptr && n > 0;
-  double *vb[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (want_v) {                      // (rho^ is still in (re, im): the kspace launch below overwrites it)
-    for (int c = 0; c < 6; ++c) { f->d_pp_v[c].reserve(nf); vb[c] = f->d_pp_v[c].p; }
-    launch_pppm_vatom_spectra(f->stream, f->dpppm, uk, g, f->d_pp_re.p, f->d_pp_im.p, vb);
-    for (int c = 0; c < 6; c += 2) launch_pppm_backward(f->stream, f->dpppm, vb[c], vb[c + 1]);
-  }
-  f->prof.begin("pppm_f_kspace", f->stream);
-  launch_pppm_kspace(f->stream, f->dpppm, uk, g, V, f->d_pp_re.p, f->d_pp_im.p, fields ? f->d_pp_ex.p : nullptr,
-                     fields ? f->d_pp_ey.p : nullptr, f->d_pp_kpart.p + 7, f->d_pp_kpart.p);
-  f->prof.end(f->stream);
-  f->prof.begin("pppm_f_backward", f->stream);
-  launch_pppm_backward(f->stream, f->dpppm, f->d_pp_re.p, f->d_pp_im.p);
-  if (fields) launch_pppm_backward(f->stream, f->dpppm, f->d_pp_ex.p, f->d_pp_ey.p);
-  f->prof.end(f->stream);
-  f->pp_im_clean = false;
+  const bool fields = fout != nullptr && n > 0, want_v = vatom != nullptr && n > 0, per_atom = n > 0 && (fout || eatom);
+  double *vb[6];
+  pppm_mesh_spectra(f, gm, fields, want_v ? vb : nullptr);
+  pppm_mesh_forces(f, gm, fields, true, nullptr);
   double s7[7];
   HIP_TRY(hipMemcpyAsync(s7, f->d_pp_kpart.p, 7 * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-  const bool per_atom = n > 0 && (fout || eatom);
-  std::vector<double> hf, he, hv;
   if (want_v) {
     f->d_pp_vo.reserve(6 * (size_t)at->nlocal);
-    launch_pppm_vatom_gather(f->stream, f->dpppm, n, f->d_pp_fidx.p, f->d_x.p, f->d_q.p, vb, qs, f->d_pp_vo.p);
-    hv.resize(6 * (size_t)at->nlocal);
-    HIP_TRY(hipMemcpyAsync(hv.data(), f->d_pp_vo.p, hv.size() * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+    launch_pppm_vatom_gather(f->stream, f->dpppm, n, f->d_pp_fidx.p, f->d_x.p, f->d_q.p, vb, f->env.qqrd2e, f->d_pp_vo.p);
   }
   if (per_atom) {
     if (fout) f->d_pp_fo.reserve(3 * (size_t)at->nlocal);
     if (eatom) f->d_pp_eo.reserve(at->nlocal);
-    EwForceOut o{};
-    o.qs = qs; o.selfc = 2.0 * g / MY_PIS; o.ecoef = 0.5 * MY_PI * Q / (g * g * V);
-    o.slab = f->env.slabflag ? 1 : 0;
-    o.fz_pref = -4.0 * MY_PI / V; o.e_pref = 2.0 * MY_PI / V; o.M = M; o.M2 = M2; o.Q = Q; o.L2_12 = L * L / 12.0;
     f->prof.begin("pppm_f_gather", f->stream);
     launch_pppm_force_gather(f->stream, f->dpppm, n, f->d_pp_fidx.p, f->d_x.p, f->d_q.p, fout ? f->d_pp_ex.p : nullptr, f->d_pp_ey.p,
-                             f->d_pp_im.p, f->d_pp_re.p, o, fout ? f->d_pp_fo.p : nullptr, eatom ? f->d_pp_eo.p : nullptr);
+                             f->d_pp_im.p, f->d_pp_re.p, kspace_out_args(f, gm.V, gm.L, four), fout ? f->d_pp_fo.p : nullptr,
+                             eatom ? f->d_pp_eo.p : nullptr);
     f->prof.end(f->stream);
-    if (fout) {
-      hf.resize(3 * (size_t)at->nlocal);
-      HIP_TRY(hipMemcpyAsync(hf.data(), f->d_pp_fo.p, hf.size() * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-    }
-    if (eatom) {
-      he.resize(at->nlocal);
-      HIP_TRY(hipMemcpyAsync(he.data(), f->d_pp_eo.p, he.size() * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-    }
   }
-  HIP_TRY(hipGetLastError());
-  f->sync();
+  if (eatom) std::fill(eatom, eatom + at->nlocal, 0.0);
+  if (vatom) std::fill(vatom, vatom + 6 * (size_t)at->nlocal, 0.0);
+  download_scatter(f, at->nlocal, idx, n, per_atom && fout ? f->d_pp_fo.p : nullptr, per_atom && eatom ? f->d_pp_eo.p : nullptr,
+                   want_v ? f->d_pp_vo.p : nullptr, fout, eatom, vatom);
   f->pp_u_valid = true;
   if (f->decomposed) {
     // every rank spread the same atoms, but a mesh point's contributions arrive in no fixed order (atomic adds): the bricks agree to
@@ -3695,136 +3764,42 @@ void pppm_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy
     if (f->env.rank != 0) std::fill(s7, s7 + 7, 0.0);
     f->rc.sum(s7, 7);
   }
-  if (energy) {
-    double e = s7[0] - g * Q2 / MY_PIS - 0.5 * MY_PI * Q * Q / (g * g * V);
-    if (f->env.slabflag) e += 2.0 * MY_PI * (M * M - Q * M2 - Q * Q * L * L / 12.0) / V;
-    *energy = qs * e;
-  }
-  if (virial) for (int c = 0; c < 6; ++c) virial[c] = qs * s7[1 + c];
-  if (eatom) std::fill(eatom, eatom + at->nlocal, 0.0);
-  if (vatom) {
-    std::fill(vatom, vatom + 6 * (size_t)at->nlocal, 0.0);
-    if (want_v)
-      for (int k = 0; k < n; ++k)
-        for (int c = 0; c < 6; ++c) vatom[6 * (size_t)idx[k] + c] = hv[6 * (size_t)idx[k] + c];
-  }
-  if (!per_atom) return;
-  for (int k = 0; k < n; ++k) {
-    const int i = idx[k];
-    if (fout) for (int c = 0; c < 3; ++c) fout[3 * (size_t)i + c] += hf[3 * (size_t)i + c];
-    if (eatom) eatom[i] = he[i];
-  }
+  if (energy) *energy = kspace_energy(f, s7[0], four[0], four[1], four[2], four[3], gm.V, gm.L);
+  if (virial) for (int c = 0; c < 6; ++c) virial[c] = f->env.qqrd2e * s7[1 + c];
 }
 // ---- device-resident k-space forces ----
-// What the two entries share: the refusals, Q, Q2, M, M2 of the call's atoms into d_kf_sums[0..3], the parameter blocks.
-void kspace_device_check(conp_fix *f, const double *dx, const double *dq) {
-  if (f->decomposed) throw ConpError(CONP_ERR_STATE, "device-resident updates take replicated atoms (conp_env.rank / nranks); "
-                                                     "spatially decomposed runs use the host-buffer hooks");
-  if (!dx || !dq) throw ConpError(CONP_ERR_ARG, "null argument");
-}
-void kspace_four_sums(conp_fix *f, int n, const double *dx, const double *dq) {
-  f->d_kf_sums.reserve((size_t)4 * (kspace_four_sums_workgroups(n) + 1));
-  launch_kspace_four_sums(f->stream, n, dx, dq, f->d_kf_sums.p + 4, f->d_kf_sums.p);
-}
-KspaceFinish kspace_finish_args(const conp_fix *f, double V, double L) {
-  const double MY_PI = 3.14159265358979323846, MY_PIS = 1.77245385090551602729, g = f->env.g_ewald;
-  KspaceFinish a{};
-  a.qs = f->env.qqrd2e; a.g_pis = g / MY_PIS; a.qcoef = 0.5 * MY_PI / (g * g * V);
-  a.slab = f->env.slabflag ? 1 : 0; a.slab_pref = 2.0 * MY_PI / V; a.L2_12 = L * L / 12.0;
-  return a;
-}
-// (Q, M, M2 stay zero and ecoef lacks its factor Q: kspace_out_from_sums completes the block on the device)
-EwForceOut kspace_out_args(const conp_fix *f, double V, double L) {
-  const double MY_PI = 3.14159265358979323846, MY_PIS = 1.77245385090551602729, g = f->env.g_ewald;
-  EwForceOut o{};
-  o.qs = f->env.qqrd2e; o.selfc = 2.0 * g / MY_PIS; o.ecoef = 0.5 * MY_PI / (g * g * V);
-  o.slab = f->env.slabflag ? 1 : 0;
-  o.fz_pref = -4.0 * MY_PI / V; o.e_pref = 2.0 * MY_PI / V; o.L2_12 = L * L / 12.0;
-  return o;
-}
 // ewald_structure_factor + ewald_forces on the caller's device arrays, every owned atom a column and a target (a zero charge adds
 // zeros): nothing but launches, device-to-device copies and memsets on the handle's stream once the buffers have their sizes.
-void ewald_forces_device(conp_fix *f, const double *dx, const double *dq, double *df, double *dev, double *deatom,
-                         double *dvatom = nullptr /*[nlocal][6], overwritten*/) {
-  const KTables &kt = f->kt;
-  const KPlan &pl = f->plan;
-  const double L = f->env.zprd * f->env.slab_volfactor;
+// dvatom: [nlocal][6], overwritten.
+void ewald_forces_device(conp_fix *f, const double *dx, const double *dq, double *df, double *dev, double *deatom, double *dvatom) {
+  const double V = f->kt.volume, L = f->env.zprd * f->env.slab_volfactor;
   const int n = f->nlocal_cur;
   if (n <= 0) { if (dev) HIP_TRY(hipMemsetAsync(dev, 0, 7 * sizeof(double), f->stream)); return; }
   const int nb_pad = ew_block(f, n);
   const int ntot = (n + nb_pad - 1) / nb_pad * nb_pad;
-  const size_t gsz = (size_t)pl.R_pad * pl.C_pad;
-  const int wgs = std::max(1, pl.C_pad / 64 * pl.n_row_tiles);                   // (ewald_structure_factor's split of a block over slices)
-  int nsplit = std::max(1, std::min({6 * f->num_cus / wgs + 1, 32, nb_pad / 64}));
-  while (nsplit > 1 && (size_t)nsplit * gsz * sizeof(double) > EW_SLICES) --nsplit;
   ew_reserve(f, nb_pad);
   // q once into the padded buffer: the last block's padding columns carry no charge; x is read in place, block by block
   f->d_ew_q.reserve(ntot);
   HIP_TRY(hipMemcpyAsync(f->d_ew_q.p, dq, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, f->stream));
   if (ntot > n) HIP_TRY(hipMemsetAsync(f->d_ew_q.p + n, 0, (size_t)(ntot - n) * sizeof(double), f->stream));
-  f->d_ew_Gp.reserve(gsz * nsplit); f->d_ew_G.reserve(gsz); f->d_ew_Gwf.reserve(gsz);
-  HIP_TRY(hipMemsetAsync(f->d_ew_Gp.p, 0, gsz * nsplit * sizeof(double), f->stream));
   f->ew_g_valid = f->ew_u_valid = false;         // the host entries' scratch is overwritten from here on
-  for (int b0 = 0; b0 < n; b0 += nb_pad) {
-    ew_tables_at(f, dx + 3 * (size_t)b0, std::min(nb_pad, n - b0), nb_pad);
-    launch_ew_sk(f->stream, f->dplan, nb_pad, nsplit, f->d_ew_Rp.p, f->d_ew_Tz.p, f->d_ew_q.p + b0, f->d_ew_Gp.p);
-  }
-  launch_ew_sk_sum(f->stream, f->dplan, nsplit, f->d_ew_Gp.p, f->d_ew_G.p);
+  ew_build_S(f, dx, f->d_ew_q.p, n, nb_pad);
   launch_ew_gw(f->stream, f->dplan, f->d_ew_G.p, f->d_ew_Gwf.p);
   kspace_four_sums(f, n, dx, dq);
   if (dev) {
-    const int K = kt.kcount;
-    if (f->ew_kv_gen != f->plan_gen) {           // (once per plan, as in ewald_forces)
-      std::vector<double> kv((size_t)4 * K);
-      for (int k = 0; k < K; ++k) {
-        kv[k] = kt.ug[k];
-        kv[(size_t)K + k] = kt.unitk[0] * kt.kxvecs[k]; kv[2 * (size_t)K + k] = kt.unitk[1] * kt.kyvecs[k];
-        kv[3 * (size_t)K + k] = kt.unitk[2] * kt.kzvecs[k];
-      }
-      f->d_ew_kv.upload(kv, f->stream);
-      f->sync();                     // (kv goes out of scope)
-      f->ew_kv_gen = f->plan_gen;
-    }
-    f->d_ew_ev.reserve((size_t)7 * (ew_energy_virial_workgroups(K) + 1));
-    launch_ew_energy_virial(f->stream, K, pl.C_pad, KPlan::PT, f->d_sf_row_a.p, f->d_sf_col_c.p, f->d_k_sign.p, f->d_ew_kv.p, f->env.g_ewald,
-                            f->d_ew_G.p, f->d_ew_ev.p + 7, f->d_ew_ev.p);
-    launch_kspace_finish(f->stream, kspace_finish_args(f, kt.volume, L), f->d_ew_ev.p, f->d_kf_sums.p, dev);
+    ew_energy_virial(f);
+    launch_kspace_finish(f->stream, kspace_finish_args(f, V, L), f->d_ew_ev.p, f->d_kf_sums.p, dev);
   }
   if (df || deatom || dvatom) {
-    if (f->ew_tiles_gen != f->plan_gen) {        // the tile lists change with the plan only (the host entries upload the same bytes)
-      f->d_ew_tiles.upload(f->tiles_h, f->stream); f->d_ew_ctptr.upload(f->ct_ptr_h, f->stream);
-      f->sync();
-      f->ew_tiles_gen = f->plan_gen;
-    }
-    f->d_ew_bk.reserve((size_t)16 * nb_pad);
-    if (dvatom) {
-      f->d_ew_Gwf2.reserve(gsz); f->d_ew_vk.reserve((size_t)24 * nb_pad);
-      launch_ew_gw2(f->stream, f->dplan, pl.kzt, kt.unitk[0], kt.unitk[1], kt.unitk[2], f->env.g_ewald, f->d_ew_G.p, f->d_ew_Gwf2.p);
-    }
-    const EwForceOut o = kspace_out_args(f, kt.volume, L);
-    for (int b0 = 0; b0 < n; b0 += nb_pad) {
-      const int nb = std::min(nb_pad, n - b0);
-      if (ntot > nb_pad) ew_tables_at(f, dx + 3 * (size_t)b0, nb, nb_pad);       // (one block: its tables are still there)
-      launch_ew_force(f->stream, f->dplan, pl.kzt, kt.unitk[0], kt.unitk[1], kt.unitk[2], nb_pad, f->d_ew_ctptr.p, f->d_ew_tiles.p,
-                      f->d_ew_Gwf.p, f->d_ew_Rp.p, f->d_ew_Tz.p, f->d_ew_bk.p);
-      if (df || deatom)
-        launch_ew_force_out_device(f->stream, nb, nb_pad, f->d_ew_bk.p, f->d_ew_q.p + b0, dx + 3 * (size_t)b0, o, f->d_kf_sums.p, b0, df,
-                                   deatom);
-      if (dvatom) {
-        launch_ew_vatom(f->stream, f->dplan, pl.kzt, kt.unitk[0], kt.unitk[1], kt.unitk[2], nb_pad, f->d_ew_ctptr.p, f->d_ew_tiles.p,
-                        f->d_ew_Gwf2.p, f->d_ew_Rp.p, f->d_ew_Tz.p, f->d_ew_vk.p);
-        launch_ew_vatom_out_device(f->stream, nb, nb_pad, f->d_ew_bk.p, f->d_ew_vk.p, f->d_ew_q.p + b0, f->env.qqrd2e, b0, dvatom);
-      }
-    }
+    ew_tiles_ready(f);
+    ew_force_blocks(f, n, nb_pad, dx, nullptr, kspace_out_args(f, V, L, nullptr), df, deatom, dvatom);
   }
   HIP_TRY(hipGetLastError());
 }
 // pppm_forces on the caller's device arrays: the brick of every owned atom through the identity list, the mesh solve, the gather
-// on every owned atom; the seven sums stay on the device (kspace_finish_kernel reads them).
-void pppm_forces_device(conp_fix *f, const double *dx, const double *dq, double *df, double *dev, double *deatom,
-                        double *dvatom = nullptr /*[nlocal][6], overwritten*/) {
-  const double MY_PI = 3.14159265358979323846;
-  const double L = f->env.zprd * f->env.slab_volfactor, V = f->env.xprd * f->env.yprd * L;
+// on every owned atom; the seven sums stay on the device (kspace_finish_kernel reads them).  dvatom: [nlocal][6], overwritten.
+void pppm_forces_device(conp_fix *f, const double *dx, const double *dq, double *df, double *dev, double *deatom, double *dvatom) {
+  const PppmGeom gm = pppm_geometry(f);
   const int n = f->nlocal_cur;
   if (n <= 0) { if (dev) HIP_TRY(hipMemsetAsync(dev, 0, 7 * sizeof(double), f->stream)); return; }
   if (f->pp_iota_n < n) {
@@ -3839,29 +3814,14 @@ void pppm_forces_device(conp_fix *f, const double *dx, const double *dq, double 
   launch_pppm_density(f->stream, f->dpppm, n, f->d_pp_iota.p, dx, dq, f->d_pp_re.p, f->d_pp_scratch.p);
   ++f->pp_elyte_spreads;
   kspace_four_sums(f, n, dx, dq);
-  const size_t nf = (size_t)f->dpppm.nfft;
   const bool fields = df != nullptr, per_atom = df || deatom;
-  if (fields) { f->d_pp_ex.reserve(nf); f->d_pp_ey.reserve(nf); }
-  f->d_pp_kpart.reserve((size_t)7 * (pppm_kspace_workgroups(f->dpppm.nfft) + 1));
-  const double uk[3] = {2.0 * MY_PI / f->env.xprd, 2.0 * MY_PI / f->env.yprd, 2.0 * MY_PI / L};
-  launch_pppm_forward(f->stream, f->dpppm, f->d_pp_re.p, f->d_pp_im.p);
-  if (dvatom) {                      // (rho^ is still in (re, im): the kspace launch below overwrites it)
-    double *vb[6];
-    for (int c = 0; c < 6; ++c) { f->d_pp_v[c].reserve(nf); vb[c] = f->d_pp_v[c].p; }
-    launch_pppm_vatom_spectra(f->stream, f->dpppm, uk, f->env.g_ewald, f->d_pp_re.p, f->d_pp_im.p, vb);
-    for (int c = 0; c < 6; c += 2) launch_pppm_backward(f->stream, f->dpppm, vb[c], vb[c + 1]);
-    launch_pppm_vatom_gather(f->stream, f->dpppm, n, nullptr, dx, dq, vb, f->env.qqrd2e, dvatom);
-  }
-  launch_pppm_kspace(f->stream, f->dpppm, uk, f->env.g_ewald, V, f->d_pp_re.p, f->d_pp_im.p, fields ? f->d_pp_ex.p : nullptr,
-                     fields ? f->d_pp_ey.p : nullptr, f->d_pp_kpart.p + 7, f->d_pp_kpart.p);
-  f->pp_im_clean = false;
-  if (dev) launch_kspace_finish(f->stream, kspace_finish_args(f, V, L), f->d_pp_kpart.p, f->d_kf_sums.p, dev);
-  if (per_atom) {
-    launch_pppm_backward(f->stream, f->dpppm, f->d_pp_re.p, f->d_pp_im.p);
-    if (fields) launch_pppm_backward(f->stream, f->dpppm, f->d_pp_ex.p, f->d_pp_ey.p);
+  double *vb[6];
+  pppm_mesh_spectra(f, gm, fields, dvatom ? vb : nullptr);
+  if (dvatom) launch_pppm_vatom_gather(f->stream, f->dpppm, n, nullptr, dx, dq, vb, f->env.qqrd2e, dvatom);
+  pppm_mesh_forces(f, gm, fields, per_atom, dev);
+  if (per_atom)
     launch_pppm_force_gather_device(f->stream, f->dpppm, n, dx, dq, fields ? f->d_pp_ex.p : nullptr, f->d_pp_ey.p, f->d_pp_im.p,
-                                    f->d_pp_re.p, kspace_out_args(f, V, L), f->d_kf_sums.p, df, deatom);
-  }
+                                    f->d_pp_re.p, kspace_out_args(f, gm.V, gm.L, nullptr), f->d_kf_sums.p, df, deatom);
   HIP_TRY(hipGetLastError());
 }
 // the k-space tail of compute potential/atom (compute_potential_atom.cpp:165-175, slab correction :323-345) on the selected owned
@@ -3869,7 +3829,6 @@ void pppm_forces_device(conp_fix *f, const double *dx, const double *dq, double 
 // (the sums of q z and q over the owned atoms all-reduced, MPI_Allreduce :331, :337)
 void potential_atom_tail(conp_fix *f, const conp_atoms *at, const conp_potential_args *pa, const int *etasel, const std::vector<int> &idx,
                          const std::vector<double> &uk, std::vector<double> &pot) {
-  const double MY_PIS = 1.77245385090551602729;
   for (int i : idx) {
     pot[i] -= uk[i];
     if (pa->eta != 0.0 && etasel[i]) pot[i] += pa->eta * at->q[i] * std::sqrt(2.0) / MY_PIS;
@@ -4059,58 +4018,9 @@ int conp_ewald_compute_particle_potential(conp_fix *f, const conp_atoms *at, int
 }
 
 // Reciprocal-space forces, energy, virial and per-atom energy of all owned atoms at the charges of the call -- what a KSpace style's
-// compute() leaves in atom->f, energy, virial, eatom.  COLLECTIVE under decomposed ranks (S unless cached; always the four sums).
-int conp_ewald_compute_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy, double *virial, double *eatom) {
-  CONP_GUARD_BEGIN
-  if (!f || !at) throw ConpError(CONP_ERR_ARG, "null argument");
-  f->drop_graph();
-  need_ewald(f);
-  if (!f->ew_g_valid) ewald_structure_factor(f, at);
-  else if (at->nlocal + at->nghost != f->nall) throw ConpError(CONP_ERR_STATE, "atom count changed without post_neighbor");
-  ewald_forces(f, at, fout, energy, virial, eatom);
-  CONP_GUARD_END
-}
-
-// The mesh twin of conp_ewald_compute_forces: what PPPM::compute leaves in atom->f, energy, virial, eatom.  COLLECTIVE under
-// decomposed ranks.  Valid on a `pppm` handle only.
-int conp_pppm_compute_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy, double *virial, double *eatom) {
-  CONP_GUARD_BEGIN
-  if (!f || !at) throw ConpError(CONP_ERR_ARG, "null argument");
-  f->drop_graph();
-  if (!f->args.pppm)
-    throw ConpError(CONP_ERR_STATE, "conp_pppm_compute_forces: this handle's k-space provider is the Ewald sum -- use "
-                                    "conp_ewald_compute_forces");
-  need_pppm(f);
-  pppm_forces(f, at, fout, energy, virial, eatom);
-  CONP_GUARD_END
-}
-
-// The device-resident twins (DESIGN.md section 14): device pointers, everything enqueued on the handle's stream, no
-// synchronisation, S / the density brick formed from the arrays of the call; the host entries' caches are dropped.
-int conp_ewald_compute_forces_device(conp_fix *f, const double *d_x, const double *d_q, double *d_f, double *d_ev, double *d_eatom) {
-  CONP_GUARD_BEGIN
-  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
-  f->drop_graph();
-  need_ewald(f);
-  kspace_device_check(f, d_x, d_q);
-  if (!d_f && !d_ev && !d_eatom) return CONP_OK;
-  ewald_forces_device(f, d_x, d_q, d_f, d_ev, d_eatom);
-  CONP_GUARD_END
-}
-
-int conp_pppm_compute_forces_device(conp_fix *f, const double *d_x, const double *d_q, double *d_f, double *d_ev, double *d_eatom) {
-  CONP_GUARD_BEGIN
-  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
-  f->drop_graph();
-  need_pppm(f);
-  kspace_device_check(f, d_x, d_q);
-  if (!d_f && !d_ev && !d_eatom) return CONP_OK;
-  pppm_forces_device(f, d_x, d_q, d_f, d_ev, d_eatom);
-  CONP_GUARD_END
-}
-
-// The four force entries with the per-atom virial as one more output: S / the density brick and the forward
-// transform are formed once for all outputs.  vatom == NULL: the sibling, call for call.
+// compute() leaves in atom->f, energy, virial, eatom -- with the per-atom virial as one more output: S / the
+// density brick and the forward transform are formed once for all outputs.  COLLECTIVE under decomposed ranks (S unless cached;
+// always the four sums).  The entries without vatom are their _vatom siblings with vatom == NULL, call for call.
 int conp_ewald_compute_forces_vatom(conp_fix *f, const conp_atoms *at, double *fout, double *energy, double *virial, double *eatom,
                                     double *vatom) {
   CONP_GUARD_BEGIN
@@ -4123,41 +4033,71 @@ int conp_ewald_compute_forces_vatom(conp_fix *f, const conp_atoms *at, double *f
   CONP_GUARD_END
 }
 
-int conp_pppm_compute_forces_vatom(conp_fix *f, const conp_atoms *at, double *fout, double *energy, double *virial, double *eatom,
-                                   double *vatom) {
+int conp_ewald_compute_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy, double *virial, double *eatom) {
+  return conp_ewald_compute_forces_vatom(f, at, fout, energy, virial, eatom, nullptr);
+}
+
+// The mesh twins: what PPPM::compute leaves in atom->f, energy, virial, eatom (vatom).  COLLECTIVE under decomposed ranks.  Valid
+// on a `pppm` handle only; the refusal names the entry that was called (`entry`: conp_pppm_compute_forces[_vatom]).
+namespace {
+static int pppm_compute_forces_entry(const char *entry, conp_fix *f, const conp_atoms *at, double *fout, double *energy, double *virial,
+                                     double *eatom, double *vatom) {
   CONP_GUARD_BEGIN
   if (!f || !at) throw ConpError(CONP_ERR_ARG, "null argument");
   f->drop_graph();
   if (!f->args.pppm)
-    throw ConpError(CONP_ERR_STATE, "conp_pppm_compute_forces_vatom: this handle's k-space provider is the Ewald sum -- use "
-                                    "conp_ewald_compute_forces_vatom");
+    throw ConpError(CONP_ERR_STATE, std::string(entry) + ": this handle's k-space provider is the Ewald sum -- use conp_ewald" +
+                                        (entry + std::strlen("conp_pppm")));
   need_pppm(f);
   pppm_forces(f, at, fout, energy, virial, eatom, vatom);
   CONP_GUARD_END
 }
+// what the device entries refuse, in this order
+void kspace_device_check(conp_fix *f, void (*need)(conp_fix *), const double *dx, const double *dq) {
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->drop_graph();
+  need(f);
+  if (f->decomposed) throw ConpError(CONP_ERR_STATE, "device-resident updates take replicated atoms (conp_env.rank / nranks); "
+                                                     "spatially decomposed runs use the host-buffer hooks");
+  if (!dx || !dq) throw ConpError(CONP_ERR_ARG, "null argument");
+}
+}  // namespace
 
+int conp_pppm_compute_forces_vatom(conp_fix *f, const conp_atoms *at, double *fout, double *energy, double *virial, double *eatom,
+                                   double *vatom) {
+  return pppm_compute_forces_entry("conp_pppm_compute_forces_vatom", f, at, fout, energy, virial, eatom, vatom);
+}
+
+int conp_pppm_compute_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy, double *virial, double *eatom) {
+  return pppm_compute_forces_entry("conp_pppm_compute_forces", f, at, fout, energy, virial, eatom, nullptr);
+}
+
+// The device-resident twins (DESIGN.md section 14): device pointers, everything enqueued on the handle's stream, no
+// synchronisation, S / the density brick formed from the arrays of the call; the host entries' caches are dropped.
 int conp_ewald_compute_forces_vatom_device(conp_fix *f, const double *d_x, const double *d_q, double *d_f, double *d_ev, double *d_eatom,
                                            double *d_vatom) {
   CONP_GUARD_BEGIN
-  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
-  f->drop_graph();
-  need_ewald(f);
-  kspace_device_check(f, d_x, d_q);
+  kspace_device_check(f, need_ewald, d_x, d_q);
   if (!d_f && !d_ev && !d_eatom && !d_vatom) return CONP_OK;
   ewald_forces_device(f, d_x, d_q, d_f, d_ev, d_eatom, d_vatom);
   CONP_GUARD_END
 }
 
+int conp_ewald_compute_forces_device(conp_fix *f, const double *d_x, const double *d_q, double *d_f, double *d_ev, double *d_eatom) {
+  return conp_ewald_compute_forces_vatom_device(f, d_x, d_q, d_f, d_ev, d_eatom, nullptr);
+}
+
 int conp_pppm_compute_forces_vatom_device(conp_fix *f, const double *d_x, const double *d_q, double *d_f, double *d_ev, double *d_eatom,
                                           double *d_vatom) {
   CONP_GUARD_BEGIN
-  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
-  f->drop_graph();
-  need_pppm(f);
-  kspace_device_check(f, d_x, d_q);
+  kspace_device_check(f, need_pppm, d_x, d_q);
   if (!d_f && !d_ev && !d_eatom && !d_vatom) return CONP_OK;
   pppm_forces_device(f, d_x, d_q, d_f, d_ev, d_eatom, d_vatom);
   CONP_GUARD_END
+}
+
+int conp_pppm_compute_forces_device(conp_fix *f, const double *d_x, const double *d_q, double *d_f, double *d_ev, double *d_eatom) {
+  return conp_pppm_compute_forces_vatom_device(f, d_x, d_q, d_f, d_ev, d_eatom, nullptr);
 }
 
 // ---- pair forces of lj/cut/coul/long: set_params -> set_list -> compute / compute_device -------------------
