@@ -465,7 +465,8 @@ int conp_pppm_compute_forces_vatom_device(conp_fix *fix, const double *d_x, cons
  * once for i (if newton or i < nlocal) and once for j (if newton or j < nlocal).  Hence sum eatom = eng_vdwl + eng_coul and
  * sum vatom = virial; with newton on the ghost entries of f, eatom, vatom carry what LAMMPS' reverse communication would fold back,
  * with newton off ghost entries are not touched.
- * Order: conp_pair_set_params (once per run, or after pair_coeff changes) -> conp_pair_set_list (at every re-neighbour) ->
+ * Order: conp_pair_set_params (once per run, or after pair_coeff changes) -> conp_pair_set_list or conp_pair_build_list_device
+ * (at every re-neighbour) ->
  * conp_pair_compute / conp_pair_compute_device (every step).  Before set_params or set_list both compute entries return
  * CONP_ERR_STATE.  The list and nall are those of the last conp_pair_set_list; the tables and the list are copied (uploaded), the
  * caller's arrays need not stay.  conp_pair_set_list may synchronise and allocate; it checks that every index of the list is < nall, and a list it refuses (CONP_ERR_ARG) leaves the handle without one.
@@ -502,6 +503,52 @@ int conp_pair_compute(conp_fix *fix, const conp_atoms *atoms,
 int conp_pair_compute_device(conp_fix *fix, const double *d_x, const double *d_q,
                              double *d_f /* [nall][3] accumulated */, double *d_ev /* [8]: eng_vdwl, eng_coul, virial[6]; overwritten */,
                              double *d_eatom /* [nall] */, double *d_vatom /* [nall][6] */);
+
+/* ---- the pair style's half list built on the device ----------------------------------------------------
+ * conp_pair_build_list_device fills the list conp_pair_compute[_device] reads from d_x alone, in place of conp_pair_set_list: an
+ * engine whose coordinates live on the device re-neighbours without copying them back.  The list is LAMMPS' half/bin/newtoff
+ * (env.newton_pair == 0) or half/bin/newton list as a set, with the orientation of conp_amd/neighbor.py::_half_pairs:
+ *   owners i < nlocal, candidates j < nall, j != i;  del = x_i - x_j, rsq = delx^2 + dely^2 + delz^2 (products as written);
+ *   the pair is listed iff rsq < cutneigh^2 and
+ *     newton off, or j < nlocal:  j > i
+ *     newton on and j >= nlocal:  z_j > z_i, or z_j == z_i and y_j > y_i, or both equal and x_j > x_i   (the stored doubles)
+ *   One global cutneigh (per-type-pair list cutoffs and triclinic boxes: not supported); cutneigh^2 below the largest entry of the
+ *   cutsq table of conp_pair_set_params is refused.
+ * Special bonds (optional: d_tag, d_nspecial, d_special all non-NULL), LAMMPS' per-atom form, all DEVICE pointers: d_tag [nall],
+ * d_nspecial [nlocal][3] cumulative (1-2, 1-2 + 1-3, all), d_special [nlocal][maxspecial] tags.  For a listed pair `which` is the
+ * class (1, 2, 3) of the FIRST position of tag[j] in special[i][0 .. nspecial[i][2]), 0 if absent.  The entry is j | (which << 30)
+ * when which > 0, special_lj[which] and special_coul[which] of conp_pair_set_params are not both 1.0, and the pair passes LAMMPS'
+ * minimum_image_check: no dimension c with prd_half[c] > 0 has |del_c| > prd_half[c] (the image of a bonded partner more than half
+ * a box away is an ordinary neighbour); else plain j.  Nothing is dropped: with coul/long LAMMPS keeps excluded pairs for the
+ * k-space correction.  prd_half: half the box length per dimension, 0 for a non-periodic one.  Counts in d_nspecial outside
+ * [0, maxspecial] are clamped.
+ * Result: ilist = 0 .. nlocal-1; numneigh[i] and first[i] (the exclusive scan of numneigh) for i < nlocal, 0 for i >= nlocal; a row
+ * is ordered by the traversal of the cells around i (cell members in ascending atom index): the arrays are a pure function of the
+ * input, byte-identical from build to build.
+ * conp_pair_build_list_device replaces the handle's list as conp_pair_set_list does, and reserves what the compute entries need
+ * (their contract of no allocation, host copy or synchronisation holds after it); it may itself allocate and synchronise (the pair
+ * count reaches the host to size neigh).  Before conp_pair_set_params: CONP_ERR_STATE.  NULL d_x or a, nlocal > nall, a negative
+ * size, a too small cutneigh, some but not all of the three special pointers, a negative maxspecial or prd_half: CONP_ERR_ARG.  A
+ * coordinate of d_x[0 .. nall) that is not finite (it never becomes a cell index), or 2^31 pairs or more (`first` is int):
+ * CONP_ERR_NUMERIC.  A refused build leaves the handle without a list.  Works on Ewald and `pppm` handles; rank-local.
+ * conp_pair_list_moved_device is Neighbor::check_distance on the device: *d_flag (DEVICE memory, overwritten) = 1 if an owned atom
+ * has |x - x_build|^2 > trigger^2, x_build the owned coordinates the last build saw, else 0 (a coordinate that is not a number
+ * counts as moved).  LAMMPS passes skin / 2.  Enqueued on the handle's stream: no allocation, no synchronisation.  CONP_ERR_STATE
+ * when the handle's list did not come from a build; NULL d_x or d_flag, a negative trigger: CONP_ERR_ARG.
+ * conp_pair_get_list downloads the list the handle holds, built or uploaded (synchronous): the sizes, and with non-NULL arrays
+ * ilist [inum], numneigh [nall], first [nall], neigh [nneigh] -- the host copy conp_fix_init_list / conp_fix_post_neighbor take.
+ * Without a list: CONP_ERR_STATE. */
+typedef struct {
+  int nlocal, nall;
+  double cutneigh;
+  const int *d_tag, *d_nspecial, *d_special;  /* all three or none */
+  int maxspecial;
+  double prd_half[3];
+} conp_pair_build_args;
+int conp_pair_build_list_device(conp_fix *fix, const double *d_x, const conp_pair_build_args *a);
+int conp_pair_list_moved_device(conp_fix *fix, const double *d_x, double trigger, int *d_flag);
+int conp_pair_get_list(conp_fix *fix, int *inum, int *nall, int64_t *nneigh,
+                       int *ilist, int *numneigh, int *first, int *neigh);   /* arrays NULL: sizes only */
 
 /* per-kernel timing of the last N updates via HIP events on the library's stream (bench.py roofline leg).
  * enable: 0 off, 1 a pair of events around every kernel, 2 around every 4th launch of the dominant kernel (sk_gemm) only --

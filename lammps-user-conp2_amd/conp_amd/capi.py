@@ -75,6 +75,11 @@ class conp_pair_params(C.Structure):
                 ("special_lj", C.c_double * 4), ("special_coul", C.c_double * 4)]
 
 
+class conp_pair_build_args(C.Structure):
+    _fields_ = [("nlocal", C.c_int), ("nall", C.c_int), ("cutneigh", C.c_double), ("d_tag", C.c_void_p), ("d_nspecial", C.c_void_p),
+                ("d_special", C.c_void_p), ("maxspecial", C.c_int), ("prd_half", C.c_double * 3)]
+
+
 class conp_info(C.Structure):
     _fields_ = [("elenum", C.c_int), ("elenum_all", C.c_int), ("elytenum", C.c_int), ("maxtag_all", C.c_int),
                 ("runstage", C.c_int), ("kcount", C.c_int), ("kcount_flat", C.c_int), ("kcount_expand", C.c_int),
@@ -111,6 +116,7 @@ SYMBOLS = [
     "conp_ewald_compute_forces_vatom_device", "conp_pppm_compute_forces_vatom_device",
     "conp_compute_potential_atom",
     "conp_pair_set_params", "conp_pair_set_list", "conp_pair_compute", "conp_pair_compute_device",
+    "conp_pair_build_list_device", "conp_pair_list_moved_device", "conp_pair_get_list",
 ]
 
 
@@ -248,6 +254,10 @@ def load_library():
         lib.conp_pair_set_list.argtypes = [vp, C.POINTER(conp_neighlist), C.c_int]
         lib.conp_pair_compute.argtypes = [vp, C.POINTER(conp_atoms), dp, dp, dp, dp, dp]
         lib.conp_pair_compute_device.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "conp_pair_build_list_device"):
+        lib.conp_pair_build_list_device.argtypes = [vp, vp, C.POINTER(conp_pair_build_args)]
+        lib.conp_pair_list_moved_device.argtypes = [vp, vp, C.c_double, vp]
+        lib.conp_pair_get_list.argtypes = [vp, ip, ip, C.POINTER(C.c_int64), ip, ip, ip, ip]
     lib.conp_compute_potential_atom.argtypes = [vp, C.POINTER(conp_atoms), C.POINTER(conp_neighlist), ip, ip,
                                                 C.POINTER(conp_potential_args), dp]
     lib.conp_fix_set_comm.argtypes = [vp, C.POINTER(conp_comm)]
@@ -739,6 +749,34 @@ class FixConp:
         is added to, d_ev [8] (eng_vdwl, eng_coul, virial xx, yy, zz, xy, xz, yz), d_eatom [nall], d_vatom [nall][6] are overwritten"""
         self._check(self.lib.conp_pair_compute_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q), C.c_void_p(d_f), C.c_void_p(d_ev),
                                                       C.c_void_p(d_eatom), C.c_void_p(d_vatom)))
+
+    def pair_build_list_device(self, d_x: int, nlocal: int, nall: int, cutneigh: float, d_tag: int = 0, d_nspecial: int = 0,
+                               d_special: int = 0, maxspecial: int = 0, prd_half=(0.0, 0.0, 0.0)):
+        """conp_pair_build_list_device: the half list of d_x [nall][3] (raw device pointer) built on the device, in place of
+        pair_set_list; d_tag [nall], d_nspecial [nlocal][3], d_special [nlocal][maxspecial] (device pointers, all or none): special
+        bonds; prd_half: half the box lengths, 0 for a non-periodic dimension.  May allocate and synchronise"""
+        a = conp_pair_build_args(nlocal=int(nlocal), nall=int(nall), cutneigh=float(cutneigh), d_tag=d_tag or None,
+                                 d_nspecial=d_nspecial or None, d_special=d_special or None, maxspecial=int(maxspecial),
+                                 prd_half=(C.c_double * 3)(*[float(v) for v in prd_half]))
+        self._check(self.lib.conp_pair_build_list_device(self.h, C.c_void_p(d_x), C.byref(a)))
+
+    def pair_list_moved_device(self, d_x: int, trigger: float, d_flag: int):
+        """conp_pair_list_moved_device: *d_flag (a device int, overwritten) = an owned atom moved further than `trigger` since the
+        build; enqueued on the handle's stream, no synchronisation"""
+        self._check(self.lib.conp_pair_list_moved_device(self.h, C.c_void_p(d_x), float(trigger), C.c_void_p(d_flag)))
+
+    def pair_get_list(self):
+        """conp_pair_get_list: the list the handle holds, built or uploaded -> (neighbor.NeighList, nall); synchronous"""
+        from .neighbor import NeighList
+        inum, nall, nn = C.c_int(), C.c_int(), C.c_int64()
+        null = C.POINTER(C.c_int)()
+        self._check(self.lib.conp_pair_get_list(self.h, C.byref(inum), C.byref(nall), C.byref(nn), null, null, null, null))
+        ilist, neigh = np.zeros(max(inum.value, 1), np.int32), np.zeros(max(nn.value, 1), np.int32)
+        numneigh, first = np.zeros(max(nall.value, 1), np.int32), np.zeros(max(nall.value, 1), np.int32)
+        self._check(self.lib.conp_pair_get_list(self.h, C.byref(inum), C.byref(nall), C.byref(nn), _iptr(ilist), _iptr(numneigh),
+                                                _iptr(first), _iptr(neigh)))
+        return NeighList(inum=inum.value, ilist=ilist[:inum.value], numneigh=numneigh[:nall.value], first=first[:nall.value],
+                         neigh=neigh[:nn.value]), nall.value
 
     def profile(self, enable):
         """0 off, 1 events around every kernel, 2 around the dominant kernel only (conp_hip.h)"""

@@ -2539,6 +2539,15 @@ struct conp_fix {
   DevBuf<double4> d_pair_xq;
   DevBuf<int> d_pair_ilist, d_pair_numneigh, d_pair_first, d_pair_neigh, d_pair_type;
   std::vector<double> pair_out_h;
+  // the list built on the device (conp_neigh.hip): scratch of the build, and the owned coordinates it saw
+  bool pair_list_built = false;
+  int pair_build_nlocal = 0;
+  int64_t pair_nneigh = 0;
+  double pair_cutsq_max = 0.0;
+  DevBuf<double> d_nb_ext, d_nb_xbuild;
+  DevBuf<double4> d_nb_sorted;
+  DevBuf<int> d_nb_cell, d_nb_slot, d_nb_count, d_nb_start, d_nb_unsorted;
+  DevBuf<long long> d_nb_total;
 
   void pair_set_params(const conp_pair_params *p) {
     if (p->ntypes != env.ntypes) throw ConpError(CONP_ERR_ARG, "conp_pair_set_params: ntypes differs from the handle's");
@@ -2558,12 +2567,15 @@ struct conp_fix {
     sync();                                       // `tab` leaves scope
     pair_ntab = nt1 * nt1;
     pair_cut_coul = p->cut_coul;
+    pair_cutsq_max = 0.0;
+    for (int k = 0; k < nt1 * nt1; ++k) pair_cutsq_max = std::max(pair_cutsq_max, p->cutsq[k]);
     for (int k = 0; k < 4; ++k) { pair_special_lj[k] = p->special_lj[k]; pair_special_coul[k] = p->special_coul[k]; }
     pair_have_params = true;
   }
 
   void pair_set_list(const conp_neighlist *l, int nall_) {
     pair_have_list = false;                       // a list that is refused leaves the handle without one
+    pair_list_built = false;
     if (nall_ < 0 || l->inum < 0 || l->inum > nall_ || l->nneigh < 0) throw ConpError(CONP_ERR_ARG, "conp_pair_set_list: bad sizes");
     if (l->inum > 0 && (!l->ilist || !l->numneigh || !l->first)) throw ConpError(CONP_ERR_ARG, "conp_pair_set_list: null list array");
     if (l->nneigh > 0 && !l->neigh) throw ConpError(CONP_ERR_ARG, "conp_pair_set_list: null neighbour array");
@@ -2584,8 +2596,129 @@ struct conp_fix {
     d_pair_xq.reserve((size_t)std::max(nall_, 1));
     d_pair_ev.reserve(8);
     sync();                                       // the caller's arrays need not stay
-    pair_nall = nall_; pair_inum = l->inum;
+    pair_nall = nall_; pair_inum = l->inum; pair_nneigh = l->nneigh;
     pair_have_list = true;
+  }
+
+  // The cell grid of a build: cells at least cutneigh (1 + 2^-20) wide, so that the 27 cells around an atom's hold every atom
+  // within cutneigh of it whatever the rounding of the index arithmetic; at most 4 nall + 64 cells (a dilute or a very long box
+  // gets wider cells: the numbers of cells are halved, the largest first, until they fit).
+  static NeighGrid neigh_grid(const double ext[6], double cutneigh, int nall_) {
+    NeighGrid g;
+    const double w = cutneigh * (1.0 + 1.0 / 1048576.0);
+    for (int c = 0; c < 3; ++c) {
+      const double len = ext[3 + c] - ext[c];
+      g.lo[c] = ext[c];
+      g.n[c] = w > 0.0 && len > w ? (int)std::min(len / w, 1024.0) : 1;
+    }
+    const int64_t cap = 4 * (int64_t)nall_ + 64;
+    while ((int64_t)g.n[0] * g.n[1] * g.n[2] > cap) {
+      int c = 0;
+      if (g.n[1] > g.n[c]) c = 1;
+      if (g.n[2] > g.n[c]) c = 2;
+      g.n[c] = (g.n[c] + 1) / 2;
+    }
+    for (int c = 0; c < 3; ++c) {
+      const double len = ext[3 + c] - ext[c];
+      g.inv[c] = g.n[c] > 1 ? g.n[c] / len : 0.0;      // one cell: every atom gets index 0
+    }
+    return g;
+  }
+
+  void pair_build_list(const double *dx, const conp_pair_build_args *a) {
+    pair_have_list = false;                       // a build that is refused leaves the handle without a list
+    pair_list_built = false;
+    if (!pair_have_params) throw ConpError(CONP_ERR_STATE, "conp_pair_build_list_device before conp_pair_set_params");
+    if (!dx || !a) throw ConpError(CONP_ERR_ARG, "null argument");
+    if (a->nlocal < 0 || a->nall < 0 || a->nlocal > a->nall || a->nall > 0x3FFFFFFF)
+      throw ConpError(CONP_ERR_ARG, "conp_pair_build_list_device: bad sizes");
+    if (!(a->cutneigh * a->cutneigh >= pair_cutsq_max) || !(a->cutneigh > 0.0) || !std::isfinite(a->cutneigh))
+      throw ConpError(CONP_ERR_ARG, "conp_pair_build_list_device: cutneigh^2 is below the largest cutsq of conp_pair_set_params");
+    const int nsp = (a->d_tag != nullptr) + (a->d_nspecial != nullptr) + (a->d_special != nullptr);
+    if (nsp != 0 && nsp != 3) throw ConpError(CONP_ERR_ARG, "conp_pair_build_list_device: d_tag, d_nspecial, d_special: all three or none");
+    if (nsp == 3 && a->maxspecial < 0) throw ConpError(CONP_ERR_ARG, "conp_pair_build_list_device: negative maxspecial");
+    for (int c = 0; c < 3; ++c)
+      if (!(a->prd_half[c] >= 0.0)) throw ConpError(CONP_ERR_ARG, "conp_pair_build_list_device: prd_half is negative or not a number");
+    const int nl = a->nlocal, na = a->nall;
+    sync();                                       // no kernel may be reading the old list
+    d_pair_ilist.reserve((size_t)std::max(nl, 1));
+    d_pair_numneigh.reserve((size_t)std::max(na, 1));
+    d_pair_first.reserve((size_t)std::max(na, 1));
+    d_pair_part.reserve((size_t)std::max(nl, 1) * 8);
+    d_pair_xq.reserve((size_t)std::max(na, 1));
+    d_pair_ev.reserve(8);
+    d_nb_ext.reserve(8); d_nb_total.reserve(1);
+    d_nb_xbuild.reserve((size_t)std::max(nl, 1) * 3);
+    d_nb_cell.reserve((size_t)std::max(na, 1)); d_nb_slot.reserve((size_t)std::max(na, 1));
+    d_nb_unsorted.reserve((size_t)std::max(na, 1)); d_nb_sorted.reserve((size_t)std::max(na, 1));
+    long long total = 0;
+    if (na > 0) {
+      launch_neigh_extent(stream, na, dx, d_nb_ext.p);
+      double ext[7];
+      HIP_TRY(hipMemcpyAsync(ext, d_nb_ext.p, sizeof ext, hipMemcpyDeviceToHost, stream));
+      sync();
+      bool finite = ext[6] == 0.0;
+      for (int c = 0; c < 3; ++c) finite = finite && std::isfinite(ext[3 + c] - ext[c]);
+      if (!finite) throw ConpError(CONP_ERR_NUMERIC, "conp_pair_build_list_device: a coordinate is not finite");
+      const NeighGrid g = neigh_grid(ext, a->cutneigh, na);
+      const int ncell = g.n[0] * g.n[1] * g.n[2];
+      d_nb_count.reserve((size_t)ncell); d_nb_start.reserve((size_t)ncell + 1);
+      launch_neigh_bin(stream, na, dx, g, d_nb_cell.p, d_nb_slot.p, d_nb_count.p, d_nb_start.p, d_nb_total.p, d_nb_unsorted.p,
+                       d_nb_sorted.p);
+      NeighRowArgs r;
+      r.nlocal = nl; r.newton = env.newton_pair != 0; r.x = dx; r.cutneighsq = a->cutneigh * a->cutneigh; r.g = g;
+      r.cell = d_nb_cell.p; r.start = d_nb_start.p; r.sorted = d_nb_sorted.p;
+      r.tag = a->d_tag; r.nspecial = a->d_nspecial; r.special = a->d_special; r.maxspecial = a->maxspecial;
+      r.flagged[0] = 0;
+      for (int k = 1; k < 4; ++k) r.flagged[k] = !(pair_special_lj[k] == 1.0 && pair_special_coul[k] == 1.0);
+      for (int c = 0; c < 3; ++c) r.prd_half[c] = a->prd_half[c];
+      r.numneigh = d_pair_numneigh.p; r.first = d_pair_first.p; r.neigh = nullptr;
+      HIP_TRY(hipMemsetAsync(d_pair_numneigh.p, 0, (size_t)na * sizeof(int), stream));      // rows of i >= nlocal: 0
+      HIP_TRY(hipMemsetAsync(d_pair_first.p, 0, (size_t)na * sizeof(int), stream));
+      launch_neigh_rows(stream, r, false);
+      launch_neigh_scan(stream, nl, d_pair_numneigh.p, d_pair_first.p, d_nb_total.p);
+      HIP_TRY(hipMemcpyAsync(&total, d_nb_total.p, sizeof total, hipMemcpyDeviceToHost, stream));
+      sync();
+      if (total >= (1ll << 31)) throw ConpError(CONP_ERR_NUMERIC, "conp_pair_build_list_device: 2^31 pairs or more (first is int)");
+      d_pair_neigh.reserve((size_t)std::max<long long>(total, 1));
+      r.neigh = d_pair_neigh.p;
+      launch_neigh_rows(stream, r, true);
+      launch_neigh_iota(stream, nl, d_pair_ilist.p);
+      if (nl > 0) HIP_TRY(hipMemcpyAsync(d_nb_xbuild.p, dx, (size_t)nl * 3 * sizeof(double), hipMemcpyDeviceToDevice, stream));
+      HIP_TRY(hipGetLastError());
+      sync();
+    }
+    pair_nall = na; pair_inum = nl; pair_nneigh = total; pair_build_nlocal = nl;
+    pair_have_list = true;
+    pair_list_built = true;
+  }
+
+  void pair_list_moved(const double *dx, double trigger, int *dflag) {
+    if (!dx || !dflag) throw ConpError(CONP_ERR_ARG, "null argument");
+    if (!(trigger >= 0.0)) throw ConpError(CONP_ERR_ARG, "conp_pair_list_moved_device: trigger is negative or not a number");
+    if (!pair_have_list || !pair_list_built)
+      throw ConpError(CONP_ERR_STATE, "conp_pair_list_moved_device: the handle's list is not one of conp_pair_build_list_device");
+    launch_neigh_moved(stream, pair_build_nlocal, dx, d_nb_xbuild.p, trigger * trigger, dflag);
+    HIP_TRY(hipGetLastError());
+  }
+
+  void pair_get_list(int *inum, int *nall_, int64_t *nneigh, int *ilist, int *numneigh, int *first, int *neigh) {
+    if (!pair_have_list) throw ConpError(CONP_ERR_STATE, "conp_pair_get_list: the handle has no list");
+    if (inum) *inum = pair_inum;
+    if (nall_) *nall_ = pair_nall;
+    if (nneigh) *nneigh = pair_nneigh;
+    const bool rows = pair_inum > 0 && pair_nall > 0;      // (an uploaded list without owners has no per-atom arrays)
+    if (ilist && pair_inum > 0) HIP_TRY(hipMemcpyAsync(ilist, d_pair_ilist.p, (size_t)pair_inum * sizeof(int), hipMemcpyDeviceToHost, stream));
+    if (numneigh && pair_nall > 0) {
+      if (rows) HIP_TRY(hipMemcpyAsync(numneigh, d_pair_numneigh.p, (size_t)pair_nall * sizeof(int), hipMemcpyDeviceToHost, stream));
+      else std::memset(numneigh, 0, (size_t)pair_nall * sizeof(int));
+    }
+    if (first && pair_nall > 0) {
+      if (rows) HIP_TRY(hipMemcpyAsync(first, d_pair_first.p, (size_t)pair_nall * sizeof(int), hipMemcpyDeviceToHost, stream));
+      else std::memset(first, 0, (size_t)pair_nall * sizeof(int));
+    }
+    if (neigh && pair_nneigh > 0) HIP_TRY(hipMemcpyAsync(neigh, d_pair_neigh.p, (size_t)pair_nneigh * sizeof(int), hipMemcpyDeviceToHost, stream));
+    sync();
   }
 
   void pair_need_ready(const char *who) const {
@@ -4116,6 +4249,32 @@ int conp_pair_set_list(conp_fix *f, const conp_neighlist *l, int nall) {
   HIP_TRY(hipSetDevice(f->env.device));
   f->drop_graph();
   f->pair_set_list(l, nall);
+  CONP_GUARD_END
+}
+
+int conp_pair_build_list_device(conp_fix *f, const double *d_x, const conp_pair_build_args *a) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(f->env.device));
+  f->drop_graph();
+  f->pair_build_list(d_x, a);
+  CONP_GUARD_END
+}
+
+int conp_pair_list_moved_device(conp_fix *f, const double *d_x, double trigger, int *d_flag) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->drop_graph();
+  f->pair_list_moved(d_x, trigger, d_flag);
+  CONP_GUARD_END
+}
+
+int conp_pair_get_list(conp_fix *f, int *inum, int *nall, int64_t *nneigh, int *ilist, int *numneigh, int *first, int *neigh) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(f->env.device));
+  f->drop_graph();
+  f->pair_get_list(inum, nall, nneigh, ilist, numneigh, first, neigh);
   CONP_GUARD_END
 }
 

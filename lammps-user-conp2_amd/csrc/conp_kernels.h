@@ -352,6 +352,31 @@ struct PairArgs {
 void launch_pair_pack(hipStream_t s, int nall, const double *x, const double *q, double4 *xq);
 // ev [8] = eng_vdwl, eng_coul, virial xx, yy, zz, xy, xz, yz (overwritten, summed in a fixed order), or NULL
 void launch_pair_force(hipStream_t s, const PairArgs &a, double *ev);
+// ---- the pair style's half list built on the device (conp_neigh.hip) ----
+struct NeighGrid { double lo[3], inv[3]; int n[3]; };     // cell of v along c: clamp((v - lo[c]) * inv[c], 0, n[c] - 1); cells are >= cutneigh wide
+struct NeighRowArgs {
+  int nlocal, newton;
+  const double *x;                       // [nall][3]
+  double cutneighsq;
+  NeighGrid g;
+  const int *cell, *start;               // [nall] cell of an atom; [ncell + 1] first member of a cell in `sorted`
+  const double4 *sorted;                 // [nall] (x, y, z, atom index), cell by cell, ascending index inside a cell
+  const int *tag, *nspecial, *special;   // special bonds: [nall], [nlocal][3] cumulative, [nlocal][maxspecial] tags; tag NULL: none
+  int maxspecial;
+  int flagged[4];                        // class 1..3: its factors on the handle are not both 1.0 (the bits are stored)
+  double prd_half[3];                    // LAMMPS' minimum_image_check: 0 in a non-periodic dimension
+  int *numneigh;                         // [nall]: written by the count pass, read by the fill pass
+  const int *first;                      // [nall] (fill pass)
+  int *neigh;                            // (fill pass)
+};
+void launch_neigh_extent(hipStream_t s, int nall, const double *x, double *ext /*[7]: lo[3], hi[3], 1.0 if a coordinate is not finite*/);
+// cell / slot / unsorted [nall], count [ncell], start [ncell + 1], total: the member count (= nall)
+void launch_neigh_bin(hipStream_t s, int nall, const double *x, const NeighGrid &g, int *cell, int *slot, int *count, int *start,
+                      long long *total, int *unsorted, double4 *sorted);
+void launch_neigh_rows(hipStream_t s, const NeighRowArgs &a, bool fill);
+void launch_neigh_scan(hipStream_t s, int n, const int *in, int *out /*[n] exclusive*/, long long *total);
+void launch_neigh_iota(hipStream_t s, int n, int *out);
+void launch_neigh_moved(hipStream_t s, int nlocal, const double *x, const double *xb, double trigsq, int *flag);
 void launch_left_sum(hipStream_t s, int ne, const int *elecheck, const double *v, double *out);
 void launch_results_out(hipStream_t s, int ne, const int *elecheck, const double *v, double *scal, bool do_left, const double *qele,
                         double *host_q /*page-locked host memory*/, double *host_scal);
