@@ -321,6 +321,11 @@ typedef struct {
   int pppm_elyte_spreads;  /* `pppm`: how often the electrolyte atoms have been spread onto the mesh so far (b_cal, density and potential queries) */
   int zn_cols, zn_grid, zn_rows; /* the z-window form of the structure-factor contraction (conp_zn.hip) is in use: window columns (32 / 48), z grid points,
                               G rows this rank contracts; all 0: the full kernels */
+  int zn_ranges;           /* z-window: chunk ranges of this rank's item list (one projected piece per range and row tile), 0: the full kernels */
+  int hc_arithmetic;       /* 1: the sums over the projected pieces form the piece addresses themselves (no list look-ups) */
+  int zc_final;            /* planar electrodes: the finishing dot kernel completes b (0: it is not used) -- 1: electrode phases loaded per thread,
+                              2: their rows staged in LDS */
+  int zc_row_tiles;        /* row tiles (of 64 planar vectors) that kernel walks on this rank */
 } conp_info;
 int conp_fix_info(const conp_fix *fix, conp_info *out);
 /* integer tables; pass NULL for those not wanted.  Sizes: kcount / kcount_expand */
@@ -579,7 +584,8 @@ int conp_debug_check_guards(void);
 
 /* Test hooks (no reference counterpart): alternative code paths of the SAME computation, results inside the parity tolerances of
  * DESIGN.md section 2 -- what tests/ compares the default paths with (A/B inside one process).  Process-wide bit mask, read when a
- * handle is created (CONP_PATH_ROWS_HOST, CONP_PATH_PPPM_SPREAD_LAUNCH: at every call).  The first handle created with a
+ * handle is created (CONP_PATH_ROWS_HOST, CONP_PATH_PPPM_SPREAD_LAUNCH, CONP_PATH_ZC_PHASE_LOADS: at every call; CONP_PATH_HC_TABLES: at
+ * every list build).  The first handle created with a
  * non-zero mask says so on stderr.  conp_debug_set_sk_workgroups: workgroup count of the structure-factor launch (0 = the
  * library's choice), for the tests that cover heavily split tiles on a small deck.  conp_debug_set_ew_block: cap of the atom block of
  * the conp_ewald_* entries' phase tables (0 = the library's choice; else n rounded up to a multiple of 64), process-wide and read at
@@ -596,7 +602,9 @@ enum {
   CONP_PATH_TIME_SPLIT = 1 << 8,         /* host-buffer hooks: k-space and real-space halves of b_cal in launches of their own (timing log) */
   /* 1 << 9, 1 << 10, 1 << 11: retired (test paths of forms measured slower and removed); ignored when set */
   CONP_PATH_SK_CLASSIC = 1 << 12,        /* large planar systems: sk_gemm over all kz columns instead of the z-window contraction (conp_zn.hip) */
-  CONP_PATH_ZN_WIDE = 1 << 13            /* z-window: 48 window columns also where 32 would do (the second template form on medium boxes) */
+  CONP_PATH_ZN_WIDE = 1 << 13,           /* z-window: 48 window columns also where 32 would do (the second template form on medium boxes) */
+  CONP_PATH_ZC_PHASE_LOADS = 1 << 14,    /* planar electrodes: the finishing dot kernel loads its electrode phases per thread instead of staging the rows in LDS */
+  CONP_PATH_HC_TABLES = 1 << 15          /* z-window: the piece sums read their piece lists also where the addresses are arithmetic */
 };
 void conp_debug_set_paths(unsigned mask);
 void conp_debug_set_sk_workgroups(int n);

@@ -88,7 +88,8 @@ class conp_info(C.Structure):
                 ("volume", C.c_double), ("gsqmx", C.c_double), ("ug_tot", C.c_double), ("totsetq", C.c_double),
                 ("scalar_output", C.c_double), ("totinve", C.c_double), ("slabcorr", C.c_double),
                 ("n_blist_pairs", C.c_int64), ("n_alist_pairs", C.c_int64), ("n_elyte_charged", C.c_int64),
-                ("inverse_path", C.c_int), ("inverse_retries", C.c_int), ("pppm_elyte_spreads", C.c_int), ("zn_cols", C.c_int), ("zn_grid", C.c_int), ("zn_rows", C.c_int)]
+                ("inverse_path", C.c_int), ("inverse_retries", C.c_int), ("pppm_elyte_spreads", C.c_int), ("zn_cols", C.c_int), ("zn_grid", C.c_int), ("zn_rows", C.c_int),
+                ("zn_ranges", C.c_int), ("hc_arithmetic", C.c_int), ("zc_final", C.c_int), ("zc_row_tiles", C.c_int)]
 
 
 # every symbol include/conp_hip.h declares (checked by tests/test_capi_symbols.py without a GPU)
@@ -125,6 +126,8 @@ PATH_PARTIAL_TILES, PATH_A_GENERAL, PATH_INV_PIVOTED, PATH_CG_TWO_LAUNCH, PATH_G
 PATH_PHASE_LAUNCH, PATH_PPPM_SPREAD_LAUNCH, PATH_ROWS_HOST, PATH_TIME_SPLIT = 32, 64, 128, 256
 PATH_SK_CLASSIC = 4096      # (512, 1024, 2048: retired test paths, ignored by the library)
 PATH_ZN_WIDE = 8192         # z-window: 48 window columns also where 32 would do
+PATH_ZC_PHASE_LOADS = 16384     # finishing dot kernel: electrode phases loaded per thread, not staged in LDS
+PATH_HC_TABLES = 32768          # z-window: the piece sums read their piece lists, not arithmetic addresses
 
 
 class test_paths:

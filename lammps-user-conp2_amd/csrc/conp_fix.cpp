@@ -821,6 +821,8 @@ struct conp_fix {
   int zn_nrg = 0;                 // ranges of the current item list
   DevBuf<double2> d_zn_cs;
   int zn_nfrag = 0;
+  bool zn_frag_arith = false;     // the fragments' piece lists are arithmetic (hc_frag_lists_arithmetic): hc_sum reads no tables
+  int zc_final_form = 0;          // the last update's finishing dot kernel: 0 none, 1 phases loaded per thread, 2 rows staged in LDS
   std::vector<int> zn_ch_lo, zn_ch_hi;      // per chunk of the ordered list: lowest / highest first tap relative to zn_c_start
   int zn_c_start = 0;
   int *zn_flag_host = nullptr, *zn_flag_dev = nullptr;      // a page-locked word the window kernel stores 1 into when a tap leaves its window
@@ -958,6 +960,9 @@ struct conp_fix {
     std::vector<int2> fent;
     for (int g = 0; g < zn_nfrag; ++g) { fent.insert(fent.end(), of_frag[g].begin(), of_frag[g].end()); fptr[g + 1] = (int)fent.size(); }
     if (fent.empty()) fent.push_back(make_int2(0, 4));
+    // every fragment of every row tile with the same count, slot after slot (all row tiles owned, the launch order ascending in the
+    // range for a fixed tile): the sums form the addresses themselves; any other list keeps the tables
+    zn_frag_arith = hc_frag_lists_arithmetic(fptr.data(), fent.data(), zn_nfrag, nrg, sk_hc_stride());
     // rough electrodes: which (range, column) pairs hold grid point g, range after range
     zn_nrg = nrg;
     if (nzc == 0) {
@@ -2168,6 +2173,7 @@ struct conp_fix {
                       d_ele_z.p, d_slab_part.p, n_slab_part, 4.0 * 3.14159265358979323846 / kt.volume, d_b, d_scalars.p + 2);
       fin.breal = d_breal.p;
       use_fin = ride && nzc > 0 && zc_final_fits((int)own_rt_h.size(), nzc);
+      zc_final_form = !use_fin ? 0 : zc_final_phase_lds((int)own_rt_h.size(), nzc, plan.kxmax, plan.kymax) > 0 ? 2 : 1;
       const bool proj = sk_projects();
       if (zn_use() && !fuse_phase) {
         // the z-window form (conp_zn.hip): window matrix of the update, the contraction with 32 / 48 columns, the ranges' pieces
@@ -2181,7 +2187,7 @@ struct conp_fix {
         launch_project_zclass_pieces(stream, dplan, ne_pad, (int)own_rt_h.size(), d_own_rt.p, nzc, d_zn_pieces.p, d_hslot_ptr.p, d_hslot_idx.p,
                                      true, d_zn_frag_ptr.p, d_zn_frag_ents.p, zn_nfrag, d_Rp.p, d_Xe.p, d_Ye.p, d_own_pv.p, d_zclass.p, d_Hc.p,
                                      d_bk.p, use_fin ? &fin : nullptr, ride_hc ? &pairs_keep : nullptr, d_breal.p,
-                                     zn_nrg > 32 /*a piece per range: 32 threads per element*/);
+                                     zn_nrg > 32 /*a piece per range: 32 threads per element*/, zn_frag_arith ? zn_nrg : 0, sk_hc_stride());
         prof.end(stream);
       } else if (zn_gen_use() && !fuse_phase) {
         // rough electrodes: the ranges' windows -> the z grid -> G and w o G (what sk_reduce leaves), then the general projection
@@ -3204,6 +3210,8 @@ int conp_fix_info(const conp_fix *f, conp_info *o) {
   o->inverse_path = f->inverse_path; o->inverse_retries = f->inverse_retries; o->pppm_elyte_spreads = f->pp_elyte_spreads;
   const bool zn_on = f->zn_use() || f->zn_gen_use();
   o->zn_cols = zn_on ? 16 * f->zn_ncf : 0; o->zn_grid = zn_on ? f->zn_n : 0; o->zn_rows = zn_on ? 128 * (int)f->own_rt_h.size() : 0; o->n_alist_pairs = f->arows.npairs(); o->n_elyte_charged = f->nl;
+  o->zn_ranges = zn_on ? f->zn_nrg : 0; o->hc_arithmetic = f->zn_use() && f->zn_frag_arith ? 1 : 0;
+  o->zc_final = f->zc_final_form; o->zc_row_tiles = f->zc_final_form ? (int)f->own_rt_h.size() : 0;
   CONP_GUARD_END
 }
 

@@ -281,7 +281,14 @@ void launch_project_zclass_pieces(hipStream_t s, const DevPlan &pl, int ne_pad, 
                                   const double2 *Ye, const int *own_pv, const int *zclass, double *Hc, double *bk_part, const BRowArgs *fin,
                                   const BRowArgs *pairs = nullptr /*with breal_out: the pair sums ride in hc_sum's launch*/,
                                   double *breal_out = nullptr,
-                                  bool wide = false /*many pieces per fragment: 32 threads per element in the sum*/);
+                                  bool wide = false /*many pieces per fragment: 32 threads per element in the sum*/,
+                                  int arith_nrg = 0 /*> 0: fragment g's pieces are ((g >> 2) arith_nrg + j) arith_stride + 16 (g & 3),
+                                  rf = 4, j = 0 .. arith_nrg - 1 (hc_frag_lists_arithmetic): the sum forms the addresses itself*/,
+                                  int arith_stride = 0);
+// true when every row fragment's list is exactly that: the z-window form's pieces in slot order
+bool hc_frag_lists_arithmetic(const int *frag_ptr, const int2 *ents, int nfrag, int nrg, int stride);
+// dynamic LDS of the electrode phase rows b_zc_final_kernel stages behind its class table, 0: the per-thread loads are used
+size_t zc_final_phase_lds(int n_own, int nzc, int kxmax, int kymax);
 void launch_sk_reduce(hipStream_t s, const DevPlan &pl, const SkTile *tiles, int ntiles, int max_nsplit, double *part, double *G,
                       double *Gwf);
 void launch_sfac_gather(hipStream_t s, int kcount, int C_pad, int PT, const int *sf_row_a, const int *sf_col_c,

@@ -1265,7 +1265,7 @@ constexpr int HCS_MAXG = 16;                 // groups of eight pieces a thread 
 // four rows per block -- they depend on x, q only and may ride in any launch ahead of the dot kernel.
 __global__ __launch_bounds__(256) void hc_sum_kernel(const int *__restrict__ frag_ptr, const int2 *__restrict__ ents, int R_pad, int nzc,
                                                      const double *__restrict__ Hp, double *__restrict__ Hc4, int nfrag, BRowArgs ra,
-                                                     double *__restrict__ breal_out) {
+                                                     double *__restrict__ breal_out, int nrg, int pstride) {
   if ((int)blockIdx.y >= nfrag) {
     const int row = (((int)blockIdx.y - nfrag) * (int)gridDim.x + (int)blockIdx.x) * 4 + (int)(threadIdx.x >> 6);
     if (row < ra.ne) {
@@ -1275,7 +1275,8 @@ __global__ __launch_bounds__(256) void hc_sum_kernel(const int *__restrict__ fra
     return;
   }
   const int g = blockIdx.y;
-  const int s0 = frag_ptr[g], s1 = frag_ptr[g + 1];
+  // nrg > 0: the lists are arithmetic (hc_frag_lists_arithmetic), sidx is the piece's slot itself -- no look-up ahead of the pieces
+  const int s0 = nrg > 0 ? (g >> 2) * nrg : frag_ptr[g], s1 = nrg > 0 ? s0 + nrg : frag_ptr[g + 1];
   const int u = threadIdx.x & 7;
   const int e = blockIdx.x * 32 + (threadIdx.x >> 3);          // element of the fragment: (class, half, i)
   const bool live = e < 32 * nzc;
@@ -1289,8 +1290,11 @@ __global__ __launch_bounds__(256) void hc_sum_kernel(const int *__restrict__ fra
       const int sidx = s0 + 8 * (gb + k) + u;
       v[k] = 0.0;
       if (live && sidx < s1) {
-        const int2 en = ents[sidx];                  // x: offset of the fragment's first 'a' row in its piece, y: the band's rf
-        v[k] = Hp[(size_t)en.x + (size_t)(cls * 32 * en.y + half * 16 * en.y + i)];
+        if (nrg > 0) v[k] = Hp[(size_t)sidx * pstride + (size_t)(16 * (g & 3) + cls * 128 + half * 64 + i)];
+        else {
+          const int2 en = ents[sidx];                // x: offset of the fragment's first 'a' row in its piece, y: the band's rf
+          v[k] = Hp[(size_t)en.x + (size_t)(cls * 32 * en.y + half * 16 * en.y + i)];
+        }
       }
     }
 #pragma unroll
@@ -1366,14 +1370,23 @@ __global__ __launch_bounds__(1024) void b_zc_dot_kernel(int n_own, const int *__
 // LDS for ALL 128 rows of a tile; the 64 row lanes of an atom are added in a fixed order; then slab term and real-space sum
 // (already formed by elyte_phase's spare blocks): b is complete, no b_real_combine launch.  Used when the whole Hc table of
 // this rank fits in 64 KB of LDS (planar electrodes: 2-6 z classes).
+// STAGED (the default wherever it fits, zc_final_phase_lds): the workgroup's 16 atoms own only rows 0 .. kxmax + 1 of Xe and
+// 0 .. kymax of Ye, 256 B each -- about 10 KB at the headline size, of which the per-thread loads pulled 295 KB through the CU's L1
+// (every row sixteen times) behind the dependent own_pv word.  The rows are copied into LDS behind H, [row][16 atoms] (X rows first),
+// requested together with the own_pv words and the H staging, and taken from there behind the one barrier: nothing at the head of
+// the kernel depends on another load except own_rt -> Hc4.  Sixteen consecutive lanes read one row's 256 B.  Same products, same
+// order: the same bits as the loads, which remain (STAGED = false) for boxes whose rows do not fit and as a test path.
+template <bool STAGED>
 __global__ __launch_bounds__(1024) void b_zc_final_kernel(int n_own, const int *__restrict__ own_rt, int R_pad, int ne_pad, int nzc,
                                                           const double2 *__restrict__ Xe, const double2 *__restrict__ Ye,
                                                           const int *__restrict__ own_pv, const double *__restrict__ Hc4,
                                                           const int *__restrict__ zclass, BRowArgs ra, int nslot,
-                                                          const int *__restrict__ slot_ptr, const int *__restrict__ slot_idx) {
+                                                          const int *__restrict__ slot_ptr, const int *__restrict__ slot_idx,
+                                                          int nxr /*kxmax + 2*/, int nyr /*kymax + 1*/) {
 #pragma clang fp contract(off)
   extern __shared__ __attribute__((aligned(16))) char zf_smem[];
   double *H = reinterpret_cast<double *>(zf_smem);          // [n_own * 128][nzc]
+  double2 *PH = reinterpret_cast<double2 *>(zf_smem + (size_t)n_own * 128 * nzc * sizeof(double));      // STAGED: [nxr + nyr][16]
   __shared__ double red[64][17];
   const int a = threadIdx.x & 15, w = threadIdx.x >> 4;
   const int i = blockIdx.x * 16 + a;
@@ -1384,17 +1397,34 @@ __global__ __launch_bounds__(1024) void b_zc_final_kernel(int n_own, const int *
   // what the finishing threads add at the very end is requested now (it was one more dependent round trip behind the last barrier)
   double fin_z = 0.0, fin_r = 0.0;
   if (w == 0 && i < ra.ne) { if (ra.slab) fin_z = ra.ele_z[i]; fin_r = ra.breal[i]; }
-  // the first 8 row tiles' phases are requested BEFORE the Hc table is staged: the two latencies overlap instead of adding up --
-  // at the headline size that is everything this thread reads
+  // the first 8 row tiles' packed vectors and what the phases come from -- the workgroup's rows (STAGED) or the thread's own 16
+  // phases -- are requested BEFORE the Hc table is staged: the latencies overlap instead of adding up
   double2 xe0[8], ye0[8];
-  int sg0[8];
+  int pk0[8];
+  // the phases of planar vector pk for atom i; an absent tile gets a zero X phase: it adds 0 * H
+  auto fetch = [&](int pk, bool ok, double2 &X, double2 &Y) {
+    if (STAGED) {
+      X = ok ? PH[(pk & 4095) * 16 + a] : make_double2(0.0, 0.0);
+      Y = PH[(nxr + ((pk >> 12) & 4095)) * 16 + a];
+    } else {
+      X = ok ? Xe[(size_t)(pk & 4095) * ne_pad + i] : make_double2(0.0, 0.0);
+      Y = Ye[(size_t)((pk >> 12) & 4095) * ne_pad + i];
+    }
+  };
+  // element e of the workgroup's phase rows: (row e >> 4, atom e & 15), X rows first
+  auto row_elem = [&](int e) {
+    const int row = e >> 4;
+    const size_t col = (size_t)blockIdx.x * 16 + (e & 15);
+    return row < nxr ? Xe[(size_t)row * ne_pad + col] : Ye[(size_t)(row - nxr) * ne_pad + col];
+  };
+  const int nph = (nxr + nyr) * 16;
 #pragma unroll
-  for (int u = 0; u < 8; ++u) {
-    const bool ok = u < n_own;                   // an absent tile gets a zero X phase: it adds 0 * H
-    const int pk = own_pv[(ok ? u : 0) * 64 + w];      // |kx| | |ky| << 12 | (ky < 0) << 24
-    sg0[u] = (pk >> 24) & 1;
-    xe0[u] = ok ? Xe[(size_t)(pk & 4095) * ne_pad + i] : make_double2(0.0, 0.0);
-    ye0[u] = Ye[(size_t)((pk >> 12) & 4095) * ne_pad + i];
+  for (int u = 0; u < 8; ++u) pk0[u] = own_pv[(u < n_own ? u : 0) * 64 + w];      // |kx| | |ky| << 12 | (ky < 0) << 24
+  double2 ph0 = make_double2(0.0, 0.0);
+  if (STAGED) { if ((int)threadIdx.x < nph) ph0 = row_elem(threadIdx.x); }
+  else {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) fetch(pk0[u], u < n_own, xe0[u], ye0[u]);
   }
   const int nrow = n_own * 128;
   if (slot_ptr) {
@@ -1411,7 +1441,15 @@ __global__ __launch_bounds__(1024) void b_zc_final_kernel(int n_own, const int *
     const double h03 = (h[0] + h[hp]) + (h[2 * hp] + h[3 * hp]);       // slots = column slices of the reduction (4 or 8)
     H[rowl * nzc + cls] = nslot == 4 ? h03 : h03 + ((h[4 * hp] + h[5 * hp]) + (h[6 * hp] + h[7 * hp]));
   }
+  if (STAGED) {
+    if ((int)threadIdx.x < nph) PH[threadIdx.x] = ph0;
+    for (int e = threadIdx.x + 1024; e < nph; e += 1024) PH[e] = row_elem(e);      // (more than 64 rows: large boxes)
+  }
   __syncthreads();
+  if (STAGED) {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) fetch(pk0[u], u < n_own, xe0[u], ye0[u]);
+  }
   double sum = 0.0;
   // (cos, sin)(kx x +- ky y) of a planar vector for atom i: neg flips the sign of sin(ky y); padding vectors read the all-zero
   // row kxmax + 1 of Xe (like the electrolyte's X table) and come out as zero
@@ -1424,7 +1462,7 @@ __global__ __launch_bounds__(1024) void b_zc_final_kernel(int n_own, const int *
   for (int u = 0; u < 8; ++u) {                  // tiles 0..7 (absent tiles add 0 * H)
     const int kk = u < n_own ? u : 0;
     double pa, pb;
-    phase(xe0[u], ye0[u], sg0[u], pa, pb);
+    phase(xe0[u], ye0[u], (pk0[u] >> 24) & 1, pa, pb);
     sum += pa * H[(kk * 128 + w) * nzc + zc];
     sum += pb * H[(kk * 128 + w + 64) * nzc + zc];
   }
@@ -1436,8 +1474,7 @@ __global__ __launch_bounds__(1024) void b_zc_final_kernel(int n_own, const int *
       const bool ok = k0 + u < n_own;
       const int pk = own_pv[(ok ? k0 + u : k0) * 64 + w];
       sg[u] = (pk >> 24) & 1;
-      xe[u] = ok ? Xe[(size_t)(pk & 4095) * ne_pad + i] : make_double2(0.0, 0.0);
-      ye[u] = Ye[(size_t)((pk >> 12) & 4095) * ne_pad + i];
+      fetch(pk, ok, xe[u], ye[u]);
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -1471,7 +1508,7 @@ constexpr int HCW_MAXK = 4;                  // groups per octet and pass (16 or
 template <int NO /*octets per element: 4 or 8*/>
 __global__ __launch_bounds__(256) void hc_sum_wide_kernel(const int *__restrict__ frag_ptr, const int2 *__restrict__ ents, int R_pad, int nzc,
                                                           const double *__restrict__ Hp, double *__restrict__ Hc4, int nfrag, BRowArgs ra,
-                                                          double *__restrict__ breal_out) {
+                                                          double *__restrict__ breal_out, int nrg, int pstride) {
   if ((int)blockIdx.y >= nfrag) {
     const int row = (((int)blockIdx.y - nfrag) * (int)gridDim.x + (int)blockIdx.x) * 4 + (int)(threadIdx.x >> 6);
     if (row < ra.ne) {
@@ -1481,7 +1518,8 @@ __global__ __launch_bounds__(256) void hc_sum_wide_kernel(const int *__restrict_
     return;
   }
   const int g = blockIdx.y;
-  const int s0 = frag_ptr[g], s1 = frag_ptr[g + 1];
+  // nrg > 0: the lists are arithmetic (hc_frag_lists_arithmetic), sidx is the piece's slot itself -- no look-up ahead of the pieces
+  const int s0 = nrg > 0 ? (g >> 2) * nrg : frag_ptr[g], s1 = nrg > 0 ? s0 + nrg : frag_ptr[g + 1];
   const int u = threadIdx.x & 7, o = (threadIdx.x >> 3) & (NO - 1);
   const int e = blockIdx.x * (32 / NO) + threadIdx.x / (8 * NO);      // element of the fragment: (class, half, i)
   const bool live = e < 32 * nzc;
@@ -1496,8 +1534,11 @@ __global__ __launch_bounds__(256) void hc_sum_wide_kernel(const int *__restrict_
       const int sidx = s0 + 8 * (gb + NO * k + o) + u;
       double v = 0.0;
       if (live && sidx < s1) {
-        const int2 en = ents[sidx];                  // x: offset of the fragment's first 'a' row in its piece, y: the band's rf
-        v = Hp[(size_t)en.x + (size_t)(cls * 32 * en.y + half * 16 * en.y + i)];
+        if (nrg > 0) v = Hp[(size_t)sidx * pstride + (size_t)(16 * (g & 3) + cls * 128 + half * 64 + i)];
+        else {
+          const int2 en = ents[sidx];                // x: offset of the fragment's first 'a' row in its piece, y: the band's rf
+          v = Hp[(size_t)en.x + (size_t)(cls * 32 * en.y + half * 16 * en.y + i)];
+        }
       }
       t[k] = v;
     }
@@ -1528,15 +1569,31 @@ __global__ __launch_bounds__(256) void hc_sum_wide_kernel(const int *__restrict_
 //  at the headline size, 22 -> 33 us on il_onelayer: 64 late workgroups do serially what 4096 waves of their own launch do at once.)
 // true when b_zc_final_kernel can take the place of b_zc_dot + b_real_combine
 bool zc_final_fits(int n_own, int nzc) { return n_own > 0 && (size_t)n_own * 128 * nzc * sizeof(double) <= 64 * 1024; }
+// LDS of the electrode phase rows b_zc_final_kernel stages behind its class table ([kxmax + 2 + kymax + 1][16 atoms] double2), or 0:
+// table + rows exceed what a workgroup of gfx950 can be granted beside the kernel's static 8.5 KB (160 KB in all), or the test path
+// CONP_PATH_ZC_PHASE_LOADS asks for the per-thread loads
+constexpr size_t ZF_DYN_LDS_MAX = 160 * 1024 - 64 * 17 * sizeof(double);
+size_t zc_final_phase_lds(int n_own, int nzc, int kxmax, int kymax) {
+  const size_t rows = (size_t)(kxmax + 2 + kymax + 1) * 16 * sizeof(double2);
+  if (path_on(CONP_PATH_ZC_PHASE_LOADS) || (size_t)n_own * 128 * nzc * sizeof(double) + rows > ZF_DYN_LDS_MAX) return 0;
+  return rows;
+}
 
 static void launch_b_zc_final(hipStream_t s, const DevPlan &pl, int n_own, const int *own_rt, int ne_pad, int nzc, const double2 *Xe,
                               const double2 *Ye, const int *own_pv, const double *Hc, const int *zclass, const BRowArgs &fin, int nslot,
                               const int *slot_ptr = nullptr, const int *slot_idx = nullptr) {
-  const size_t lds = (size_t)n_own * 128 * nzc * sizeof(double);
-  static DynLdsCache granted{};
-  ensure_dyn_lds(b_zc_final_kernel, lds, granted);
-  hipLaunchKernelGGL(b_zc_final_kernel, dim3(ne_pad / 16), dim3(1024), lds, s, n_own, own_rt, pl.R_pad, ne_pad, nzc, Xe, Ye, own_pv, Hc,
-                     zclass, fin, nslot, slot_ptr, slot_idx);
+  const size_t rows = zc_final_phase_lds(n_own, nzc, pl.kxmax, pl.kymax);
+  const size_t lds = (size_t)n_own * 128 * nzc * sizeof(double) + rows;
+  static DynLdsCache granted{}, granted_s{};
+  if (rows) {
+    ensure_dyn_lds(b_zc_final_kernel<true>, lds, granted_s);
+    hipLaunchKernelGGL(b_zc_final_kernel<true>, dim3(ne_pad / 16), dim3(1024), lds, s, n_own, own_rt, pl.R_pad, ne_pad, nzc, Xe, Ye, own_pv,
+                       Hc, zclass, fin, nslot, slot_ptr, slot_idx, pl.kxmax + 2, pl.kymax + 1);
+  } else {
+    ensure_dyn_lds(b_zc_final_kernel<false>, lds, granted);
+    hipLaunchKernelGGL(b_zc_final_kernel<false>, dim3(ne_pad / 16), dim3(1024), lds, s, n_own, own_rt, pl.R_pad, ne_pad, nzc, Xe, Ye, own_pv,
+                       Hc, zclass, fin, nslot, slot_ptr, slot_idx, pl.kxmax + 2, pl.kymax + 1);
+  }
 }
 
 static void launch_b_zc_dot(hipStream_t s, int n_own, const int *own_rt, int R_pad, int ne_pad, int nzc, const double *Rp,
@@ -1648,11 +1705,23 @@ void launch_b_project_zclass(hipStream_t s, const DevPlan &pl, int ne_pad, const
 // planar electrodes, sk_gemm in projecting mode: Hp = the segments' pieces; slot lists per owned row tile.  fin: the dot kernel
 // adds the pieces itself (presum: hc_sum first -- many pieces per tile, every block of the dot kernel would re-add them all);
 // otherwise hc_sum -> slot 0 of Hc -> b_zc_dot.
+bool hc_frag_lists_arithmetic(const int *frag_ptr, const int2 *ents, int nfrag, int nrg, int stride) {
+  if (nrg <= 0 || nfrag <= 0 || path_on(CONP_PATH_HC_TABLES)) return false;
+  for (int g = 0; g < nfrag; ++g) {
+    if (frag_ptr[g] != g * nrg || frag_ptr[g + 1] != (g + 1) * nrg) return false;
+    for (int j = 0; j < nrg; ++j) {
+      const int2 en = ents[g * nrg + j];
+      if (en.y != 4 || (long long)en.x != ((long long)(g >> 2) * nrg + j) * stride + 16 * (g & 3)) return false;
+    }
+  }
+  return true;
+}
+
 void launch_project_zclass_pieces(hipStream_t s, const DevPlan &pl, int ne_pad, int n_own, const int *own_rt, int nzc, const double *Hp,
                                   const int *slot_ptr, const int *slot_idx, bool presum, const int *frag_ptr, const int2 *frag_ents, int nfrag,
                                   const double *Rp, const double2 *Xe,
                                   const double2 *Ye, const int *own_pv, const int *zclass, double *Hc, double *bk_part, const BRowArgs *fin,
-                                  const BRowArgs *pairs, double *breal_out, bool wide) {
+                                  const BRowArgs *pairs, double *breal_out, bool wide, int arith_nrg, int arith_stride) {
   if (n_own <= 0) return;
   if (fin && !presum) { launch_b_zc_final(s, pl, n_own, own_rt, ne_pad, nzc, Xe, Ye, own_pv, Hp, zclass, *fin, 0, slot_ptr, slot_idx); return; }
   if (nfrag > 0) {
@@ -1663,10 +1732,11 @@ void launch_project_zclass_pieces(hipStream_t s, const DevPlan &pl, int ne_pad, 
       constexpr int NO = 4;
       const int extra = pairs ? ((ra.ne + 3) / 4 + NO * nzc - 1) / (NO * nzc) : 0;
       hipLaunchKernelGGL(hc_sum_wide_kernel<NO>, dim3(NO * nzc, nfrag + extra), dim3(256), 0, s, frag_ptr, frag_ents, pl.R_pad, nzc, Hp, Hc, nfrag, ra,
-                         breal_out);
+                         breal_out, arith_nrg, arith_stride);
     } else {
       const int extra = pairs ? ((ra.ne + 3) / 4 + nzc - 1) / nzc : 0;
-      hipLaunchKernelGGL(hc_sum_kernel, dim3(nzc, nfrag + extra), dim3(256), 0, s, frag_ptr, frag_ents, pl.R_pad, nzc, Hp, Hc, nfrag, ra, breal_out);
+      hipLaunchKernelGGL(hc_sum_kernel, dim3(nzc, nfrag + extra), dim3(256), 0, s, frag_ptr, frag_ents, pl.R_pad, nzc, Hp, Hc, nfrag, ra, breal_out, arith_nrg,
+                         arith_stride);
     }
   }
   if (fin) launch_b_zc_final(s, pl, n_own, own_rt, ne_pad, nzc, Xe, Ye, own_pv, Hc, zclass, *fin, 1);
@@ -1898,10 +1968,18 @@ __device__ __forceinline__ double wave_sum16_transposed(double (&p)[16], unsigne
 // (two passes of 16 rows per wavefront, the second pass's loads requested when the first pass's values have been used: ~110
 //  registers, four workgroups per CU -- all 528 tiles of the headline size resident at once.  With all 32 rows of a wavefront in flight
 //  the kernel needs 204 registers: two workgroups per CU, 512 slots for 528 tiles, a second round for sixteen of them.)
+#ifdef SYM_TIMELINE
+// diagnostic build only (tools/sym_timeline.py): wall-clock stamps (100 MHz) of every workgroup's start and end + where it ran
+__device__ unsigned long long sym_tl[4096 * 3];
+#define SYM_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x < 4096) sym_tl[blockIdx.x * 3 + (k)] = wall_clock64(); } while (0)
+#else
+#define SYM_STAMP(k) do { } while (0)
+#endif
 __global__ __launch_bounds__(256, 4) void sym_gemv_kernel(int ne, int ne_pad, const double *__restrict__ Spk, const double *__restrict__ b,
                                                           double *__restrict__ yp /*[nb][ne_pad]*/) {
   __shared__ double bi_s[SG_T], bj_s[SG_T];
   __shared__ double tr[4][SG_T];
+  SYM_STAMP(0);
   int t = blockIdx.x, bi = 0;
   while ((bi + 1) * (bi + 2) / 2 <= t) ++bi;
   const int bj = t - bi * (bi + 1) / 2;
@@ -1948,6 +2026,16 @@ __global__ __launch_bounds__(256, 4) void sym_gemv_kernel(int ne, int ne_pad, co
     __syncthreads();
     if (tid < SG_T) yp[(size_t)bi * ne_pad + bj * SG_T + tid] = (tr[0][tid] + tr[1][tid]) + (tr[2][tid] + tr[3][tid]);
   }
+#ifdef SYM_TIMELINE
+  __syncthreads();
+  SYM_STAMP(1);
+  if (threadIdx.x == 0 && blockIdx.x < 4096) {
+    unsigned hw, xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+    sym_tl[blockIdx.x * 3 + 2] = ((unsigned long long)xcc << 32) | hw;
+  }
+#endif
 }
 
 // y[row] = sum of the row's nb slots (fixed order), q = y + dV setq (+ qinit); then the charge write of gemv_finish_kernel's tail:
@@ -1998,6 +2086,11 @@ __global__ __launch_bounds__(4 * SF_R) void sym_finish_kernel(int n, int ne_pad,
   for (int k = k0 + (int)threadIdx.x; k < k1; k += 4 * SF_R) q_atoms[atoms_of[k]] = vq[atoms_row[k] - row0];
 }
 
+#ifdef SYM_TIMELINE
+extern "C" int conp_debug_sym_timeline(unsigned long long *out, int nblocks) {
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(sym_tl), sizeof(unsigned long long) * 3 * (size_t)nblocks);
+}
+#endif
 size_t sym_packed_doubles(int ne_pad) { const size_t nb = ne_pad / SG_T; return nb * (nb + 1) / 2 * SG_T * SG_T; }
 void launch_sym_pack(hipStream_t s, int ne, int ne_pad, const double *S, double *Spk, unsigned long long *stat) {
   const int nb = ne_pad / SG_T;
