@@ -555,6 +555,60 @@ int conp_pair_list_moved_device(conp_fix *fix, const double *d_x, double trigger
 int conp_pair_get_list(conp_fix *fix, int *inum, int *nall, int64_t *nneigh,
                        int *ilist, int *numneigh, int *first, int *neigh);   /* arrays NULL: sizes only */
 
+/* ---- ghost atoms built, updated and folded back on the device ---------------------------------------------
+ * Comm::borders, Comm::forward_comm and Comm::reverse_comm of LAMMPS for ONE rank in a periodic orthogonal box, and the remap into
+ * the box that precedes a ghost build: what keeps the ghost part of d_x, d_q and d_f (nlocal owned atoms, then nghost periodic
+ * images) without a host round trip.  All d_ pointers are ordinary device memory; everything runs on the handle's stream
+ * (conp_fix_set_stream).  The entries work on Ewald and `pppm` handles; they are rank-local, never collective (ghosts owned by
+ * other ranks and triclinic boxes: not supported).  This state is separate from conp_env.ghost_images of the host-array hooks.
+ *
+ * The build rule (conp_amd/neighbor.py::make_ghosts, bit for bit).  On the host, in double: prd_c = boxhi_c - boxlo_c,
+ * lo_c = boxlo_c - cutghost, hi_c = boxhi_c + cutghost; m_c = ceil(cutghost / prd_c) in a periodic dimension, 0 in another.  Shifts
+ * are the triples (sx, sy, sz), s_c in -m_c .. m_c, enumerated with sx slowest and sz fastest, each ascending, without (0, 0, 0).
+ * For owner o and shift s:  xi_c = x[o][c] + ((double)s_c * prd_c) -- the product first, then the sum, no contraction, also for
+ * s_c = 0: the arithmetic of Comm::pack_comm.  The image is a ghost iff lo_c <= xi_c < hi_c in all three dimensions.  Ghosts are
+ * ordered by shift in that enumeration and, within a shift, by ascending owner: the map is a pure function of the input,
+ * byte-identical from build to build.  Owned atoms outside the box are not an error (the rule is applied as written); a coordinate
+ * that is not a number or infinite fails every comparison: that atom has no images.
+ *
+ * conp_ghost_build_device keeps owner[g] and img[g][3] of every ghost and, per owner, the list of its ghosts in ascending ghost
+ * index; *nghost reaches the host, so the build may allocate and synchronise (like conp_pair_build_list_device), and it reserves
+ * whatever fill and fold need.  CONP_ERR_ARG: NULL a or nghost, NULL d_x with nlocal > 0, negative nlocal, cutghost negative or not
+ * a number, a box bound that is not finite, boxhi_c <= boxlo_c in a periodic dimension, more than 4096 shifts.  CONP_ERR_NUMERIC:
+ * nlocal + nghost >= 2^30 (neighbour entries keep 30 bits; counted before anything is allocated for the ghosts).  A refused build
+ * leaves the handle without ghosts.
+ * conp_ghost_fill_device: for every ghost x[nlocal + g] = x[owner] + img * prd (the arithmetic above, the prd of the build) and
+ * q[nlocal + g] = q[owner]; NULL d_q: coordinates only.  conp_ghost_fill_int_device copies `width` (1 .. 8) ints per ghost from the
+ * owner's row: tag, type, mask.  conp_ghost_fold_device: for every owner and component v[o] = (((v[o] + v[g1]) + v[g2]) + ...) over
+ * its ghosts in ascending ghost index, summed by one thread in that order without atomics -- a pure function of the input; ghost
+ * rows are left as they are (as LAMMPS does: the caller clears f each step); width 1 (eatom), 3 (f) or 6 (vatom), any other:
+ * CONP_ERR_ARG.  These three make no allocation, no copy to the host and no synchronisation (the contract of DESIGN.md section 14).
+ * conp_ghost_get downloads the map (synchronous); NULL arrays: the sizes only.
+ * Fill, fill_int, fold and get before a successful build: CONP_ERR_STATE.  A NULL array that is required (nlocal + nghost > 0):
+ * CONP_ERR_ARG.  Without ghosts (nlocal 0, no periodic dimension, cutghost 0) fill and fold are no-ops returning CONP_OK.
+ * conp_atoms_wrap_device is Domain::remap for owned atoms, per periodic dimension c:  if x < boxlo_c: x += prd_c, image_c -= 1;
+ * then if x >= boxhi_c: x -= prd_c, x = max(x, boxlo_c), image_c += 1.  One pass: atoms must have moved less than a box length.
+ * d_image: optional plain int counters [nlocal][3].  Enqueued only, no allocation; needs no earlier ghost build.  CONP_ERR_ARG: NULL
+ * d_x with nlocal > 0, NULL boxlo / boxhi / periodic, negative nlocal, boxhi_c <= boxlo_c in a periodic dimension.
+ *
+ * Intended order, all on one stream.  At a re-neighbour: conp_pair_list_moved_device (the decision) -> conp_atoms_wrap_device ->
+ * conp_ghost_build_device -> conp_ghost_fill_device and conp_ghost_fill_int_device for tag -> conp_pair_build_list_device.  At
+ * every step: conp_ghost_fill_device -> conp_fix_pre_force_device, the k-space force entry and conp_pair_compute_device ->
+ * conp_ghost_fold_device on d_f, and on d_eatom / d_vatom when they are tallied.  conp_fix_post_neighbor still takes host arrays. */
+typedef struct {
+  int nlocal;
+  double boxlo[3], boxhi[3];
+  int periodic[3];
+  double cutghost;
+} conp_ghost_build_args;
+int conp_ghost_build_device(conp_fix *fix, const double *d_x /*[nlocal][3]*/, const conp_ghost_build_args *a, int *nghost);
+int conp_ghost_fill_device(conp_fix *fix, double *d_x /*[nall][3]*/, double *d_q /*[nall] or NULL*/);
+int conp_ghost_fill_int_device(conp_fix *fix, int *d_v /*[nall][width]*/, int width);
+int conp_ghost_fold_device(conp_fix *fix, double *d_v /*[nall][width]*/, int width);
+int conp_ghost_get(conp_fix *fix, int *nlocal, int *nghost, int *owner /*[nghost] or NULL*/, int *img /*[nghost][3] or NULL*/);
+int conp_atoms_wrap_device(conp_fix *fix, double *d_x /*[nlocal][3]*/, int nlocal, const double boxlo[3], const double boxhi[3],
+                           const int periodic[3], int *d_image /*[nlocal][3] or NULL*/);
+
 /* per-kernel timing of the last N updates via HIP events on the library's stream (bench.py roofline leg).
  * enable: 0 off, 1 a pair of events around every kernel, 2 around every 4th launch of the dominant kernel (sk_gemm) only --
  * cheap enough to stay on inside a timed region (an event pair drains the queue around the kernel it brackets). */

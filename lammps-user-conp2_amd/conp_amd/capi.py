@@ -80,6 +80,11 @@ class conp_pair_build_args(C.Structure):
                 ("d_special", C.c_void_p), ("maxspecial", C.c_int), ("prd_half", C.c_double * 3)]
 
 
+class conp_ghost_build_args(C.Structure):
+    _fields_ = [("nlocal", C.c_int), ("boxlo", C.c_double * 3), ("boxhi", C.c_double * 3), ("periodic", C.c_int * 3),
+                ("cutghost", C.c_double)]
+
+
 class conp_info(C.Structure):
     _fields_ = [("elenum", C.c_int), ("elenum_all", C.c_int), ("elytenum", C.c_int), ("maxtag_all", C.c_int),
                 ("runstage", C.c_int), ("kcount", C.c_int), ("kcount_flat", C.c_int), ("kcount_expand", C.c_int),
@@ -118,6 +123,8 @@ SYMBOLS = [
     "conp_compute_potential_atom",
     "conp_pair_set_params", "conp_pair_set_list", "conp_pair_compute", "conp_pair_compute_device",
     "conp_pair_build_list_device", "conp_pair_list_moved_device", "conp_pair_get_list",
+    "conp_ghost_build_device", "conp_ghost_fill_device", "conp_ghost_fill_int_device", "conp_ghost_fold_device", "conp_ghost_get",
+    "conp_atoms_wrap_device",
 ]
 
 
@@ -261,6 +268,13 @@ def load_library():
         lib.conp_pair_build_list_device.argtypes = [vp, vp, C.POINTER(conp_pair_build_args)]
         lib.conp_pair_list_moved_device.argtypes = [vp, vp, C.c_double, vp]
         lib.conp_pair_get_list.argtypes = [vp, ip, ip, C.POINTER(C.c_int64), ip, ip, ip, ip]
+    if hasattr(lib, "conp_ghost_build_device"):                # (comparison builds loaded through CONP_LIB lack these)
+        lib.conp_ghost_build_device.argtypes = [vp, vp, C.POINTER(conp_ghost_build_args), ip]
+        lib.conp_ghost_fill_device.argtypes = [vp, vp, vp]
+        lib.conp_ghost_fill_int_device.argtypes = [vp, vp, C.c_int]
+        lib.conp_ghost_fold_device.argtypes = [vp, vp, C.c_int]
+        lib.conp_ghost_get.argtypes = [vp, ip, ip, ip, ip]
+        lib.conp_atoms_wrap_device.argtypes = [vp, vp, C.c_int, dp, dp, ip, vp]
     lib.conp_compute_potential_atom.argtypes = [vp, C.POINTER(conp_atoms), C.POINTER(conp_neighlist), ip, ip,
                                                 C.POINTER(conp_potential_args), dp]
     lib.conp_fix_set_comm.argtypes = [vp, C.POINTER(conp_comm)]
@@ -780,6 +794,47 @@ class FixConp:
                                                 _iptr(first), _iptr(neigh)))
         return NeighList(inum=inum.value, ilist=ilist[:inum.value], numneigh=numneigh[:nall.value], first=first[:nall.value],
                          neigh=neigh[:nn.value]), nall.value
+
+    # -- ghost atoms on the device: wrap -> build -> fill / fill_int -> .. -> fold ----------------
+    def ghost_build_device(self, d_x: int, nlocal: int, boxlo, boxhi, periodic, cutghost: float) -> int:
+        """conp_ghost_build_device: the ghosts of the owned atoms d_x [nlocal][3] (raw device pointer) by the rule of
+        neighbor.make_ghosts -> nghost.  May allocate and synchronise"""
+        a = conp_ghost_build_args(nlocal=int(nlocal), boxlo=(C.c_double * 3)(*[float(v) for v in boxlo]),
+                                  boxhi=(C.c_double * 3)(*[float(v) for v in boxhi]),
+                                  periodic=(C.c_int * 3)(*[int(bool(v)) for v in periodic]), cutghost=float(cutghost))
+        n = C.c_int(-1)
+        self._check(self.lib.conp_ghost_build_device(self.h, C.c_void_p(d_x), C.byref(a), C.byref(n)))
+        return n.value
+
+    def ghost_fill_device(self, d_x: int, d_q: int = 0):
+        """conp_ghost_fill_device: ghost rows of d_x [nall][3] (and d_q [nall], 0 = NULL) from their owners; enqueued, no synchronisation"""
+        self._check(self.lib.conp_ghost_fill_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q)))
+
+    def ghost_fill_int_device(self, d_v: int, width: int = 1):
+        """conp_ghost_fill_int_device: ghost rows of the int array d_v [nall][width] (tag, type, mask) from their owners; enqueued"""
+        self._check(self.lib.conp_ghost_fill_int_device(self.h, C.c_void_p(d_v), int(width)))
+
+    def ghost_fold_device(self, d_v: int, width: int):
+        """conp_ghost_fold_device: ghost rows of d_v [nall][width] (1 eatom, 3 f, 6 vatom) added onto their owners in ascending ghost
+        index; ghost rows stay; enqueued, no synchronisation"""
+        self._check(self.lib.conp_ghost_fold_device(self.h, C.c_void_p(d_v), int(width)))
+
+    def ghost_get(self):
+        """conp_ghost_get -> (nlocal, nghost, owner [nghost], img [nghost][3]); synchronous"""
+        nl, ng = C.c_int(), C.c_int()
+        null = C.POINTER(C.c_int)()
+        self._check(self.lib.conp_ghost_get(self.h, C.byref(nl), C.byref(ng), null, null))
+        owner, img = np.zeros(max(ng.value, 1), np.int32), np.zeros((max(ng.value, 1), 3), np.int32)
+        self._check(self.lib.conp_ghost_get(self.h, C.byref(nl), C.byref(ng), _iptr(owner), _iptr(img)))
+        return nl.value, ng.value, owner[:ng.value], img[:ng.value]
+
+    def atoms_wrap_device(self, d_x: int, nlocal: int, boxlo, boxhi, periodic, d_image: int = 0):
+        """conp_atoms_wrap_device: owned atoms d_x [nlocal][3] remapped into the box, d_image [nlocal][3] int counters (0 = NULL);
+        enqueued, no synchronisation"""
+        lo, hi = np.ascontiguousarray(boxlo, dtype=np.float64), np.ascontiguousarray(boxhi, dtype=np.float64)
+        per = np.ascontiguousarray([int(bool(v)) for v in periodic], dtype=np.int32)
+        self._check(self.lib.conp_atoms_wrap_device(self.h, C.c_void_p(d_x), int(nlocal), _dptr(lo), _dptr(hi), _iptr(per),
+                                                    C.c_void_p(d_image)))
 
     def profile(self, enable):
         """0 off, 1 events around every kernel, 2 around the dominant kernel only (conp_hip.h)"""

@@ -2727,6 +2727,135 @@ struct conp_fix {
     sync();
   }
 
+  // ---- ghost atoms on the device (conp_ghost.hip): Comm::borders / forward_comm / reverse_comm of one rank --
+  // The build keeps owner and image of every ghost and, per owner, the ascending list of its ghosts; fill, fill_int and fold only
+  // enqueue.  Separate from map_ghosts / ghost_mode of the host-array path (conp_env.ghost_images).
+  bool ghost_built = false;
+  int ghost_nlocal = 0, ghost_n = 0;
+  double ghost_prd[3] = {0.0, 0.0, 0.0};
+  DevBuf<int> d_gh_shift, d_gh_count, d_gh_start, d_gh_nimg, d_gh_ofirst, d_gh_owner, d_gh_img, d_gh_list;
+  DevBuf<long long> d_gh_total;
+  static constexpr int GHOST_MAX_SHIFTS = 4096;
+
+  void ghost_build(const double *dx, const conp_ghost_build_args *a, int *nghost_out) {
+    ghost_built = false;                          // a build that is refused leaves the handle without ghosts
+    if (!a || !nghost_out) throw ConpError(CONP_ERR_ARG, "null argument");
+    if (a->nlocal < 0) throw ConpError(CONP_ERR_ARG, "conp_ghost_build_device: negative nlocal");
+    if (!dx && a->nlocal > 0) throw ConpError(CONP_ERR_ARG, "conp_ghost_build_device: d_x is NULL");
+    if (!(a->cutghost >= 0.0)) throw ConpError(CONP_ERR_ARG, "conp_ghost_build_device: cutghost is negative or not a number");
+    GhostBuildArgs g;
+    double nshift_d = 1.0;
+    int m[3];
+    for (int c = 0; c < 3; ++c) {
+      if (!std::isfinite(a->boxlo[c]) || !std::isfinite(a->boxhi[c]))
+        throw ConpError(CONP_ERR_ARG, "conp_ghost_build_device: a box bound is not finite");
+      if (a->periodic[c] && !(a->boxhi[c] > a->boxlo[c]))
+        throw ConpError(CONP_ERR_ARG, "conp_ghost_build_device: boxhi <= boxlo in a periodic dimension");
+      g.prd[c] = a->boxhi[c] - a->boxlo[c];
+      g.lo[c] = a->boxlo[c] - a->cutghost;
+      g.hi[c] = a->boxhi[c] + a->cutghost;
+      const double mc = a->periodic[c] ? std::ceil(a->cutghost / g.prd[c]) : 0.0;
+      nshift_d *= 2.0 * mc + 1.0;
+      if (!(nshift_d - 1.0 <= (double)GHOST_MAX_SHIFTS)) throw ConpError(CONP_ERR_ARG, "conp_ghost_build_device: more than 4096 shifts");
+      m[c] = (int)mc;
+    }
+    if (a->nlocal >= (1 << 30)) throw ConpError(CONP_ERR_NUMERIC, "conp_ghost_build_device: 2^30 atoms or more (neighbour entries keep 30 bits)");
+    std::vector<int> shifts;
+    for (int sx = -m[0]; sx <= m[0]; ++sx)
+      for (int sy = -m[1]; sy <= m[1]; ++sy)
+        for (int sz = -m[2]; sz <= m[2]; ++sz)
+          if (sx || sy || sz) { shifts.push_back(sx); shifts.push_back(sy); shifts.push_back(sz); }
+    const int nl = a->nlocal, nshift = (int)(shifts.size() / 3), nblock = (nl + 63) / 64;
+    const size_t ncount = (size_t)nshift * nblock;
+    if (ncount >= (1ull << 31))                   // (the scan takes an int length; 2^37 image tests would be behind this)
+      throw ConpError(CONP_ERR_NUMERIC, "conp_ghost_build_device: shifts times blocks of 64 owners reach 2^31");
+    sync();                                      // no kernel may be reading the old map
+    long long total = 0;
+    if (ncount > 0) {
+      d_gh_shift.upload(shifts, stream);
+      d_gh_count.reserve(ncount); d_gh_start.reserve(ncount);
+      d_gh_nimg.reserve((size_t)nl); d_gh_ofirst.reserve((size_t)nl);
+      d_gh_total.reserve(1);
+      g.nlocal = nl; g.nblock = nblock; g.nshift = nshift; g.x = dx; g.shift = d_gh_shift.p;
+      g.count = d_gh_count.p; g.nimg = d_gh_nimg.p; g.start = nullptr; g.ofirst = nullptr;
+      g.nghost = 0; g.owner = nullptr; g.img = nullptr; g.list = nullptr;
+      launch_ghost_images(stream, g, false);
+      launch_neigh_scan(stream, nl, d_gh_nimg.p, d_gh_ofirst.p, d_gh_total.p);
+      launch_neigh_scan(stream, (int)ncount, d_gh_count.p, d_gh_start.p, d_gh_total.p);
+      HIP_TRY(hipMemcpyAsync(&total, d_gh_total.p, sizeof total, hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipGetLastError());
+      sync();
+      if ((long long)nl + total >= (1ll << 30))
+        throw ConpError(CONP_ERR_NUMERIC, "conp_ghost_build_device: nlocal + nghost reaches 2^30 (neighbour entries keep 30 bits)");
+      if (total > 0) {
+        d_gh_owner.reserve((size_t)total); d_gh_img.reserve((size_t)total * 3); d_gh_list.reserve((size_t)total);
+        g.start = d_gh_start.p; g.ofirst = d_gh_ofirst.p; g.nghost = (int)total;
+        g.owner = d_gh_owner.p; g.img = d_gh_img.p; g.list = d_gh_list.p;
+        launch_ghost_images(stream, g, true);
+        HIP_TRY(hipGetLastError());
+        sync();
+      }
+    }
+    ghost_nlocal = nl; ghost_n = (int)total;
+    for (int c = 0; c < 3; ++c) ghost_prd[c] = g.prd[c];
+    ghost_built = true;
+    *nghost_out = ghost_n;
+  }
+
+  void ghost_need_built(const char *who) const {
+    if (!ghost_built) throw ConpError(CONP_ERR_STATE, std::string(who) + " before a successful conp_ghost_build_device");
+  }
+
+  void ghost_fill(double *dx, double *dq) {
+    ghost_need_built("conp_ghost_fill_device");
+    if (!dx && ghost_nlocal + ghost_n > 0) throw ConpError(CONP_ERR_ARG, "conp_ghost_fill_device: d_x is NULL");
+    if (ghost_n <= 0) return;
+    launch_ghost_fill_xq(stream, ghost_nlocal, ghost_n, d_gh_owner.p, d_gh_img.p, ghost_prd[0], ghost_prd[1], ghost_prd[2], dx, dq);
+    HIP_TRY(hipGetLastError());
+  }
+
+  void ghost_fill_int(int *dv, int width) {
+    ghost_need_built("conp_ghost_fill_int_device");
+    if (width < 1 || width > 8) throw ConpError(CONP_ERR_ARG, "conp_ghost_fill_int_device: width outside 1 .. 8");
+    if (!dv && ghost_nlocal + ghost_n > 0) throw ConpError(CONP_ERR_ARG, "conp_ghost_fill_int_device: d_v is NULL");
+    if (ghost_n <= 0) return;
+    launch_ghost_fill_int(stream, ghost_nlocal, ghost_n, width, d_gh_owner.p, dv);
+    HIP_TRY(hipGetLastError());
+  }
+
+  void ghost_fold(double *dv, int width) {
+    ghost_need_built("conp_ghost_fold_device");
+    if (width != 1 && width != 3 && width != 6) throw ConpError(CONP_ERR_ARG, "conp_ghost_fold_device: width is not 1, 3 or 6");
+    if (!dv && ghost_nlocal + ghost_n > 0) throw ConpError(CONP_ERR_ARG, "conp_ghost_fold_device: d_v is NULL");
+    if (ghost_n <= 0) return;
+    launch_ghost_fold(stream, ghost_nlocal, width, d_gh_ofirst.p, d_gh_nimg.p, d_gh_list.p, dv);
+    HIP_TRY(hipGetLastError());
+  }
+
+  void ghost_get(int *nlocal_out, int *nghost_out, int *owner, int *img) {
+    ghost_need_built("conp_ghost_get");
+    if (nlocal_out) *nlocal_out = ghost_nlocal;
+    if (nghost_out) *nghost_out = ghost_n;
+    if (owner && ghost_n > 0) HIP_TRY(hipMemcpyAsync(owner, d_gh_owner.p, (size_t)ghost_n * sizeof(int), hipMemcpyDeviceToHost, stream));
+    if (img && ghost_n > 0) HIP_TRY(hipMemcpyAsync(img, d_gh_img.p, (size_t)ghost_n * 3 * sizeof(int), hipMemcpyDeviceToHost, stream));
+    sync();
+  }
+
+  void atoms_wrap(double *dx, int nlocal_, const double *boxlo, const double *boxhi, const int *periodic, int *dimage) {
+    if (!boxlo || !boxhi || !periodic) throw ConpError(CONP_ERR_ARG, "null argument");
+    if (nlocal_ < 0) throw ConpError(CONP_ERR_ARG, "conp_atoms_wrap_device: negative nlocal");
+    if (!dx && nlocal_ > 0) throw ConpError(CONP_ERR_ARG, "conp_atoms_wrap_device: d_x is NULL");
+    AtomsWrapArgs w;
+    w.nlocal = nlocal_;
+    for (int c = 0; c < 3; ++c) {
+      w.periodic[c] = periodic[c] != 0;
+      if (w.periodic[c] && !(boxhi[c] > boxlo[c])) throw ConpError(CONP_ERR_ARG, "conp_atoms_wrap_device: boxhi <= boxlo in a periodic dimension");
+      w.lo[c] = boxlo[c]; w.hi[c] = boxhi[c]; w.prd[c] = boxhi[c] - boxlo[c];
+    }
+    launch_atoms_wrap(stream, w, dx, dimage);
+    HIP_TRY(hipGetLastError());
+  }
+
   void pair_need_ready(const char *who) const {
     if (!pair_have_params) throw ConpError(CONP_ERR_STATE, std::string(who) + " before conp_pair_set_params");
     if (!pair_have_list) throw ConpError(CONP_ERR_STATE, std::string(who) + " before conp_pair_set_list");
@@ -4283,6 +4412,58 @@ int conp_pair_get_list(conp_fix *f, int *inum, int *nall, int64_t *nneigh, int *
   HIP_TRY(hipSetDevice(f->env.device));
   f->drop_graph();
   f->pair_get_list(inum, nall, nneigh, ilist, numneigh, first, neigh);
+  CONP_GUARD_END
+}
+
+// ---- ghost atoms on the device: wrap -> build -> fill / fill_int -> .. -> fold ------------------------------
+int conp_ghost_build_device(conp_fix *f, const double *d_x, const conp_ghost_build_args *a, int *nghost) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(f->env.device));
+  f->drop_graph();
+  f->ghost_build(d_x, a, nghost);
+  CONP_GUARD_END
+}
+
+int conp_ghost_fill_device(conp_fix *f, double *d_x, double *d_q) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->drop_graph();
+  f->ghost_fill(d_x, d_q);
+  CONP_GUARD_END
+}
+
+int conp_ghost_fill_int_device(conp_fix *f, int *d_v, int width) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->drop_graph();
+  f->ghost_fill_int(d_v, width);
+  CONP_GUARD_END
+}
+
+int conp_ghost_fold_device(conp_fix *f, double *d_v, int width) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->drop_graph();
+  f->ghost_fold(d_v, width);
+  CONP_GUARD_END
+}
+
+int conp_ghost_get(conp_fix *f, int *nlocal, int *nghost, int *owner, int *img) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(f->env.device));
+  f->drop_graph();
+  f->ghost_get(nlocal, nghost, owner, img);
+  CONP_GUARD_END
+}
+
+int conp_atoms_wrap_device(conp_fix *f, double *d_x, int nlocal, const double boxlo[3], const double boxhi[3], const int periodic[3],
+                           int *d_image) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->drop_graph();
+  f->atoms_wrap(d_x, nlocal, boxlo, boxhi, periodic, d_image);
   CONP_GUARD_END
 }
 

@@ -384,6 +384,25 @@ void launch_neigh_rows(hipStream_t s, const NeighRowArgs &a, bool fill);
 void launch_neigh_scan(hipStream_t s, int n, const int *in, int *out /*[n] exclusive*/, long long *total);
 void launch_neigh_iota(hipStream_t s, int n, int *out);
 void launch_neigh_moved(hipStream_t s, int nlocal, const double *x, const double *xb, double trigsq, int *flag);
+// ---- ghost atoms built, updated and folded back on the device (conp_ghost.hip) ----
+struct GhostBuildArgs {
+  int nlocal, nblock, nshift;            // owners, blocks of 64 owners, shifts
+  const double *x;                       // [nlocal][3]
+  const int *shift;                      // [nshift][3], sx slowest, sz fastest, without (0, 0, 0)
+  double prd[3], lo[3], hi[3];           // box lengths; box bounds widened by cutghost
+  int *count;                            // [nshift][nblock] images kept (count pass)
+  int *nimg;                             // [nlocal] images per owner: written by the count pass, read by the fill pass
+  const int *start, *ofirst;             // exclusive scans of count and nimg (fill pass)
+  int nghost;                            // (fill pass)
+  int *owner, *img, *list;               // [nghost], [nghost][3], [nghost]: an owner's ghosts at list[ofirst[o] .. + nimg[o]), ascending
+};
+void launch_ghost_images(hipStream_t s, const GhostBuildArgs &a, bool fill);
+void launch_ghost_fill_xq(hipStream_t s, int nlocal, int nghost, const int *owner, const int *img, double px, double py, double pz, double *x,
+                          double *q /*[nall] or NULL*/);
+void launch_ghost_fill_int(hipStream_t s, int nlocal, int nghost, int width, const int *owner, int *v /*[nlocal + nghost][width]*/);
+void launch_ghost_fold(hipStream_t s, int nlocal, int width, const int *ofirst, const int *nimg, const int *list, double *v /*[nlocal + nghost][width]*/);
+struct AtomsWrapArgs { int nlocal, periodic[3]; double lo[3], hi[3], prd[3]; };
+void launch_atoms_wrap(hipStream_t s, const AtomsWrapArgs &a, double *x /*[nlocal][3]*/, int *image /*[nlocal][3] or NULL*/);
 void launch_left_sum(hipStream_t s, int ne, const int *elecheck, const double *v, double *out);
 void launch_results_out(hipStream_t s, int ne, const int *elecheck, const double *v, double *scal, bool do_left, const double *qele,
                         double *host_q /*page-locked host memory*/, double *host_scal);

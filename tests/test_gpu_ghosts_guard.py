@@ -1,0 +1,48 @@
+"""-m gpu: the ghost entries under CONP_GUARD=1 in a fresh child process (as tests/test_gpu_pair_build_guard.py): every device buffer of
+the library sits between two zones of a known byte pattern, and no kernel of conp_ghost.hip -- nor the list build and the pair kernels
+reading the ghosts it made -- stores outside its buffers.  (The caller's arrays carry sentinel rows of their own in the tests run.)"""
+import os
+import subprocess
+import sys
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+CHILD = r'''
+import sys
+sys.path[:0] = [{tests!r}, {pkg!r}, {oracle!r}, {root!r}]
+import torch
+torch.cuda.init()
+import test_gpu_ghosts as tg
+from conp_amd import capi
+lib = capi.load_library()
+lib.conp_debug_check_guards.restype = int
+assert lib.conp_debug_check_guards() == 0, "guard zones are off"
+def clean(what):
+    bad = lib.conp_debug_check_guards()
+    assert bad == 0, (what, bad, lib.conp_last_error().decode())
+for kind in tg.KINDS:
+    tg.test_build_equals_the_reference(kind)
+    clean("build " + kind)
+for kind in ("small", "sparse"):
+    tg.test_fill_after_a_move(kind)
+    clean("fill " + kind)
+for width in (1, 3, 6):
+    tg.test_fold(width)
+    clean("fold %d" % width)
+tg.test_composition_with_the_list_build_and_the_pair_forces("small")
+clean("composition")
+print("GUARD_OK")
+'''
+
+
+def test_no_store_outside_the_buffers(tmp_path):
+    script = tmp_path / "guard_child.py"
+    script.write_text(CHILD.format(tests=os.path.join(ROOT, "tests"), pkg=os.path.join(ROOT, "lammps-user-conp2_amd"),
+                                   oracle=os.path.join(ROOT, "oracle"), root=ROOT))
+    env = dict(os.environ, CONP_GUARD="1")
+    p = subprocess.run([sys.executable, str(script)], env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    assert "GUARD_OK" in p.stdout
