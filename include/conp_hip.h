@@ -133,6 +133,8 @@ int conp_fix_setup_post_neighbor(conp_fix *fix, const conp_atoms *atoms); /* fix
 int conp_fix_setup_pre_force(conp_fix *fix, const conp_atoms *atoms, int64_t ntimestep, double potdiff); /* :387-391 */
 int conp_fix_post_neighbor(conp_fix *fix, const conp_atoms *atoms);       /* :468-539 */
 int conp_fix_pre_force(conp_fix *fix, const conp_atoms *atoms, int64_t ntimestep, double potdiff); /* :543-573 */
+/* The fix scalar of the LAST update, whichever entry made it: the host-buffer hooks bring it over themselves, after a
+ * device-resident update (conp_fix_pre_force_device, conp_fix_scatter_device) this call forms what is missing and fetches it. */
 double conp_fix_compute_scalar(const conp_fix *fix);                      /* :592-595 */
 /* FixConp::post_force -> force_cal (fix_conp.cpp:577-580, 1163-1201) + blist_coul_cal_post_force (:1368-1444), ETA pair mode:
  * adds the real-space Gaussian-correction forces to f[nall][3] (host, accumulated like atom->f) and returns what the reference

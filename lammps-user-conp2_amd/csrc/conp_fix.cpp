@@ -351,6 +351,7 @@ struct conp_fix {
       d_elecheck, d_zclass, d_nb_act, d_rt_mine, d_own_rt, d_own_pv, d_ele_pairs, d_a_chunk_group, d_ct_ptr, d_seg_ptr, d_seg_idx, d_hslot_ptr, d_hslot_idx, d_b_rowptr, d_b_ele, d_b_oth, d_a_rowptr, d_a_ele, d_a_oth, d_a_col, d_bl_ilist, d_bl_numneigh, d_bl_first, d_bl_neigh, d_pp_egrid, d_ipiv, d_info, d_cg_done, d_iota, d_ele_csr_ptr, d_ele_csr_of, d_ele_csr_row;
   bool left_stale = false;          // the fused GEMV + charge write leaves the fix scalar's group-1 sum to refresh_scalar()
   double left_potdiff = 0.0;
+  bool scalars_unfetched = false;   // conp_fix_scatter_device left this update's scalars on the device: compute_scalar brings them over
   DevBuf<unsigned char> d_mask;
   DevBuf<SkItem> d_items;
   DevBuf<SkWItem> d_witems;
@@ -2460,6 +2461,8 @@ struct conp_fix {
     }
     if (labelled) prof.end(stream);
     HIP_TRY(hipGetLastError());
+    // the group-1 sum (conq, cond: the potential difference) of THIS update is in d_scalars; the host copy is fetched on demand
+    left_stale = false; scalars_unfetched = true; left_potdiff = potdiff;
   }
 
   void finish_scalar(double potdiff) {
@@ -2469,6 +2472,7 @@ struct conp_fix {
     sync();
     scalar_output = (args.conq || args.cond) ? h[3] : potdiff * totsetq + h[1];   // fix_conp.cpp:1159 / fix_conq.cpp:78-80 / fix_cond.cpp:116
     slabcorr = h[2];
+    scalars_unfetched = false;
   }
 
   // fix_conp.cpp:1120-1161 update_charge (host-buffer flavour)
@@ -2485,7 +2489,7 @@ struct conp_fix {
     // no copy-engine transfer at the end of the update
     double *h = qe + ne_pad;
     launch_results_out(stream, ne, d_elecheck.p, d_eleallq, d_scalars.p, left_stale, d_qele.p, qe, h);
-    left_stale = false;
+    left_stale = false; scalars_unfetched = false;
     sync();
     scalar_output = (args.conq || args.cond) ? h[3] : potdiff * totsetq + h[1];
     slabcorr = h[2];
@@ -3220,7 +3224,7 @@ int conp_fix_pre_force(conp_fix *f, const conp_atoms *at, int64_t ntimestep, dou
 
 double conp_fix_compute_scalar(const conp_fix *cf) {
   conp_fix *f = const_cast<conp_fix *>(cf);
-  if (f->left_stale) {          // device-resident updates do not bring the scalar over every step: form and fetch it now
+  if (f->left_stale || f->scalars_unfetched) {   // device-resident updates do not bring the scalar over every step: form and fetch it now
     try { (void)hipSetDevice(f->env.device); f->finish_scalar(f->left_potdiff); } catch (...) {}
   }
   return f->scalar_output;
