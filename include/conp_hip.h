@@ -388,8 +388,8 @@ int64_t conp_host_pair_rows(int which, const conp_neighlist *list, const conp_at
  * device-resident entries do not synchronise, so an atom that left its window is seen one call later: that call returns
  * CONP_ERR_NUMERIC (the charges of the updates since the list build are invalid; call conp_fix_post_neighbor and repeat), and the
  * handle uses the full kernels until the next list build.  This holds for replayed graphs (CONP_GRAPH=1) too.  When the next call
- * is conp_fix_post_neighbor, it completes the list build at the new positions and then returns CONP_ERR_NUMERIC (the handle is
- * ready; repeat the update).  conp_fix_pre_force (host arrays) repeats the update by itself. */
+ * is conp_fix_post_neighbor (or conp_fix_post_neighbor_device), it completes the list build at the new positions and then returns
+ * CONP_ERR_NUMERIC (the handle is ready; repeat the update).  conp_fix_pre_force (host arrays) repeats the update by itself. */
 int conp_fix_set_stream(conp_fix *fix, void *hip_stream);
 int conp_fix_bind_device_buffers(conp_fix *fix, double *d_b /*[Ne]*/, double *d_q /*[Ne]*/);
 /* this rank's electrode rows: blocks of ceil(Ne / nranks) rows, so that rank r's rows start at r * ceil(Ne / nranks) */
@@ -596,7 +596,8 @@ int conp_pair_get_list(conp_fix *fix, int *inum, int *nall, int64_t *nneigh,
  * Intended order, all on one stream.  At a re-neighbour: conp_pair_list_moved_device (the decision) -> conp_atoms_wrap_device ->
  * conp_ghost_build_device -> conp_ghost_fill_device and conp_ghost_fill_int_device for tag -> conp_pair_build_list_device.  At
  * every step: conp_ghost_fill_device -> conp_fix_pre_force_device, the k-space force entry and conp_pair_compute_device ->
- * conp_ghost_fold_device on d_f, and on d_eatom / d_vatom when they are tallied.  conp_fix_post_neighbor still takes host arrays. */
+ * conp_ghost_fold_device on d_f, and on d_eatom / d_vatom when they are tallied.  The fix itself is re-neighboured from the same
+ * arrays by conp_fix_post_neighbor_device (below), right behind conp_pair_build_list_device. */
 typedef struct {
   int nlocal;
   double boxlo[3], boxhi[3];
@@ -610,6 +611,63 @@ int conp_ghost_fold_device(conp_fix *fix, double *d_v /*[nall][width]*/, int wid
 int conp_ghost_get(conp_fix *fix, int *nlocal, int *nghost, int *owner /*[nghost] or NULL*/, int *img /*[nghost][3] or NULL*/);
 int conp_atoms_wrap_device(conp_fix *fix, double *d_x /*[nlocal][3]*/, int nlocal, const double boxlo[3], const double boxhi[3],
                            const int periodic[3], int *d_image /*[nlocal][3] or NULL*/);
+
+/* ---- the fix re-neighboured on the device -----------------------------------------------------------------
+ * conp_fix_post_neighbor_device is FixConp::post_neighbor for an engine whose atoms live on the device: it rebuilds everything
+ * conp_fix_post_neighbor leaves on the device for the update and for post_force, from the handle's own half list
+ * (conp_pair_build_list_device), its own ghost map (conp_ghost_build_device) and the d_x [nall][3], d_q [nall] of the call -- of
+ * which only the owned rows are read (ghost rows must already be filled: the updates that follow read them).  No per-atom and no
+ * per-pair data crosses PCIe.  The re-neighbour sequence of a device-resident engine is
+ *   conp_atoms_wrap_device -> conp_ghost_build_device -> conp_ghost_fill_device (+ conp_ghost_fill_int_device for tag) ->
+ *   conp_pair_build_list_device -> conp_fix_post_neighbor_device,
+ * and the run needs host arrays once, at setup.
+ * Preconditions (one that fails: CONP_ERR_STATE, a NULL d_x or d_q: CONP_ERR_ARG; a refused call leaves the handle exactly as it was):
+ *   - conp_fix_setup_post_neighbor and conp_fix_linalg_setup / conp_fix_setup_pre_force have run with host arrays (the electrode
+ *     numbering, the A matrix and its inverse stay host-side work, once per run);
+ *   - the handle is not decomposed (no conp_fix_set_comm; replicated-atom rank handles are allowed);
+ *   - a successful conp_pair_build_list_device and a successful conp_ghost_build_device exist, both for the nlocal of the last host
+ *     (setup_)post_neighbor; the list's nall is nlocal + nghost of the ghost map; the list's cutneigh is at least env.cut_coul (its
+ *     newton setting is env.newton_pair by construction);
+ *   - the owned atoms keep the local order and the identity (tag, type, electrode membership) they had at that host call.  This one
+ *     cannot be checked: an engine that sorts or exchanges atoms calls conp_fix_post_neighbor with host arrays.
+ * What it rebuilds, each piece in the form and order of the host route (the kernels behind it are the same):
+ *   1. the per-atom tables for the new nall: owned rows stay, the ghost rows of type and of the atom -> electrode-row table are copied
+ *      from their owners;
+ *   2. the charge scatter list: the (atom, row) pairs of owned and ghost electrode atoms in ascending atom index, and its CSR by
+ *      electrode row -- per row the owned atom, then its ghosts in ascending ghost index;
+ *   3. the fix's half list: device-to-device COPIES of the pair style's buffers, then the electrode rows of the real-space b regrouped
+ *      from them.  Lifetime: the copies belong to the fix.  A later conp_pair_build_list_device (or conp_pair_set_list) replaces the
+ *      pair style's list only; conp_fix_pre_force_device and conp_fix_post_force keep working with the list, the ghosts and the nall
+ *      of THIS call until the next conp_fix_post_neighbor[_device] -- as after a host conp_fix_post_neighbor;
+ *   4. the electrolyte list: owned atoms with no electrode row and q != 0, ascending.  (Owned atoms keep their identity, and every
+ *      owned electrode atom of a handle that is not decomposed has a row: "no row" is the host's electrode_check == 0.);
+ *   5. the z-window order, when the handle takes that path (conp_info.zn_cols): with n grid cells, gscale = n / lz and the owned z of
+ *      the call, in double without contraction:  u = z gscale;  u -= n floor(u (1 / n));  c = (int)u, and c >= n: c = n - 1,
+ *      u = nextafter(n, 0).  From the occupancy of the cells the start cell c0 behind the longest run of empty cells -- the ring is
+ *      walked twice from cell 0, the first of several equally long runs wins, a box without an empty cell starts at 0.  The list is
+ *      sorted by (c - c0) mod n with a STABLE counting sort: atoms of one cell keep ascending atom index.  Per chunk of 16 sorted
+ *      atoms the lowest and highest  i0 = (int)ceil(ur - 7.5),  ur = u - c0 (+ n if negative).  The occupancy and the chunk bounds go
+ *      to the host, which cuts the ranges and window origins from them exactly as conp_fix_post_neighbor does;
+ *   6. a z-window flag that an earlier device-resident update raised is taken as conp_fix_post_neighbor takes it: the build is
+ *      completed, then the call returns CONP_ERR_NUMERIC once (the handle is ready; repeat the update).
+ * Contract: at most four stream synchronisations (the flag of the earlier updates; the two list lengths with the cell occupancy; the
+ * chunk bounds, on the z-window path only; the closing one) and host traffic of O(grid cells + nl / 16 + schedule items) -- nothing
+ * of the size of nall or of the pair count; device allocations only when something grew; a pure function of its input: two calls on
+ * the same input leave byte-identical tables.
+ * Host mirrors: the host copies of the lists (electrolyte list, scatter list, the fix's half list and its rows) are NOT refreshed.
+ * Until the next conp_fix_post_neighbor with host arrays these entries return CONP_ERR_STATE, with a message that says so, instead of
+ * computing with stale indices: conp_fix_pre_force, conp_fix_setup_pre_force, conp_fix_b_cal, conp_km_b_cal, conp_fix_update_charge,
+ * conp_fix_post_force, conp_fix_post_force_step.  Entries that upload the atoms they are given and read no mirror keep working
+ * (conp_pair_compute, the conp_ewald_* / conp_pppm_* entries, conp_compute_potential_atom, conp_fix_a_cal), and so does every device
+ * entry: conp_fix_pre_force_device, conp_fix_b_cal_device / _solve_device / _scatter_device, the _device force entries,
+ * conp_fix_compute_scalar, conp_fix_get_vectors.
+ * conp_fix_get_step_tables downloads what (2) - (5) left on the device, after either route (synchronous; for tests).  sizes[8] =
+ * {nl, electrode atoms in the scatter list, Ne, b-row pairs, chunk origins (nl padded to 32, / 16; 0 when the list is not z-ordered),
+ * 1 if the list is z-ordered, nall, start cell}.  Arrays may be NULL: elyte_idx [nl], ele_pairs [2 sizes[1]], csr_ptr [Ne + 1],
+ * csr_of / csr_row [sizes[1]], b_rowptr [Ne + 1], b_ele / b_oth [sizes[3]], g0c [sizes[4]] the window origin of every chunk. */
+int conp_fix_post_neighbor_device(conp_fix *fix, const double *d_x /*[nall][3]*/, const double *d_q /*[nall]*/);
+int conp_fix_get_step_tables(conp_fix *fix, int64_t *sizes /*[8] or NULL*/, int *elyte_idx, int *ele_pairs, int *csr_ptr, int *csr_of,
+                             int *csr_row, int *b_rowptr, int *b_ele, int *b_oth, int *g0c);
 
 /* per-kernel timing of the last N updates via HIP events on the library's stream (bench.py roofline leg).
  * enable: 0 off, 1 a pair of events around every kernel, 2 around every 4th launch of the dominant kernel (sk_gemm) only --

@@ -125,6 +125,7 @@ SYMBOLS = [
     "conp_pair_build_list_device", "conp_pair_list_moved_device", "conp_pair_get_list",
     "conp_ghost_build_device", "conp_ghost_fill_device", "conp_ghost_fill_int_device", "conp_ghost_fold_device", "conp_ghost_get",
     "conp_atoms_wrap_device",
+    "conp_fix_post_neighbor_device", "conp_fix_get_step_tables",
 ]
 
 
@@ -275,6 +276,9 @@ def load_library():
         lib.conp_ghost_fold_device.argtypes = [vp, vp, C.c_int]
         lib.conp_ghost_get.argtypes = [vp, ip, ip, ip, ip]
         lib.conp_atoms_wrap_device.argtypes = [vp, vp, C.c_int, dp, dp, ip, vp]
+    if hasattr(lib, "conp_fix_post_neighbor_device"):          # (comparison builds loaded through CONP_LIB lack these)
+        lib.conp_fix_post_neighbor_device.argtypes = [vp, vp, vp]
+        lib.conp_fix_get_step_tables.argtypes = [vp, C.POINTER(C.c_int64)] + [ip] * 9
     lib.conp_compute_potential_atom.argtypes = [vp, C.POINTER(conp_atoms), C.POINTER(conp_neighlist), ip, ip,
                                                 C.POINTER(conp_potential_args), dp]
     lib.conp_fix_set_comm.argtypes = [vp, C.POINTER(conp_comm)]
@@ -835,6 +839,31 @@ class FixConp:
         per = np.ascontiguousarray([int(bool(v)) for v in periodic], dtype=np.int32)
         self._check(self.lib.conp_atoms_wrap_device(self.h, C.c_void_p(d_x), int(nlocal), _dptr(lo), _dptr(hi), _iptr(per),
                                                     C.c_void_p(d_image)))
+
+    # -- the fix re-neighboured on the device ------------------------------------------------------
+    def post_neighbor_device(self, d_x: int, d_q: int):
+        """conp_fix_post_neighbor_device: the fix's tables rebuilt from the handle's own list and ghost map and the owned rows of
+        d_x [nall][3], d_q [nall] (raw device pointers); synchronous"""
+        self._check(self.lib.conp_fix_post_neighbor_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q)))
+
+    STEP_TABLES = ("elyte_idx", "ele_pairs", "csr_ptr", "csr_of", "csr_row", "b_rowptr", "b_ele", "b_oth", "g0c")
+
+    def step_tables(self):
+        """conp_fix_get_step_tables -> dict of the sizes (nl, n_ele_atoms, ne, n_b_pairs, n_chunks, zn_listed, nall, c_start) and the
+        arrays of STEP_TABLES, after a host or a device post_neighbor; synchronous"""
+        sizes = np.zeros(8, np.int64)
+        sp = sizes.ctypes.data_as(C.POINTER(C.c_int64))
+        null = C.POINTER(C.c_int)()
+        self._check(self.lib.conp_fix_get_step_tables(self.h, sp, *([null] * 9)))
+        nl, nea, ne, nbp, nch = (int(v) for v in sizes[:5])
+        lens = dict(elyte_idx=nl, ele_pairs=2 * nea, csr_ptr=ne + 1, csr_of=nea, csr_row=nea, b_rowptr=ne + 1, b_ele=nbp, b_oth=nbp, g0c=nch)
+        arr = {k: np.full(max(lens[k], 1), -7, np.int32) for k in self.STEP_TABLES}
+        self._check(self.lib.conp_fix_get_step_tables(self.h, sp, *[_iptr(arr[k]) for k in self.STEP_TABLES]))
+        out = {k: arr[k][:lens[k]] for k in self.STEP_TABLES}
+        out["ele_pairs"] = out["ele_pairs"].reshape(-1, 2)
+        out.update(nl=nl, n_ele_atoms=nea, ne=ne, n_b_pairs=nbp, n_chunks=nch, zn_listed=int(sizes[5]), nall=int(sizes[6]),
+                   c_start=int(sizes[7]))
+        return out
 
     def profile(self, enable):
         """0 off, 1 events around every kernel, 2 around the dominant kernel only (conp_hip.h)"""

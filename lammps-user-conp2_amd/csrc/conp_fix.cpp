@@ -692,9 +692,9 @@ struct conp_fix {
   int64_t n_b_pairs = 0;
   unsigned *h_np = nullptr;            // page-locked word the regrouping's pair count lands in
   bool np_pending = false;
-  void build_b_rows_device(const conp_atoms *at) {
+  void build_b_rows_device(const conp_atoms *at /*NULL: the device route, which has no host list to regroup*/, int nlocal_) {
     const int ne = idx.elenum_all;
-    const bool on_host = path_on(CONP_PATH_ROWS_HOST);      // read per call: the A/B test flips it between two handles
+    const bool on_host = at && path_on(CONP_PATH_ROWS_HOST);      // read per call: the A/B test flips it between two handles
     np_pending = false;
     if (on_host) {
       build_b_rows(blist, at->nlocal, at->tag, at->echeck, idx, env.newton_pair != 0, brows);
@@ -707,7 +707,7 @@ struct conp_fix {
     d_b_rowptr.reserve((size_t)ne + 1); d_b_ele.reserve(std::max<size_t>(bl_nneigh, 1)); d_b_oth.reserve(std::max<size_t>(bl_nneigh, 1));
     if (!h_np) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&h_np), 64, hipHostMallocDefault));
     launch_build_b_rows(stream, bl_inum, bl_nneigh, d_bl_ilist.p, d_bl_numneigh.p, d_bl_first.p, d_bl_neigh.p, d_atom2eleall.p,
-                        at->nlocal, env.newton_pair != 0, ne, d_rows_scratch.p, sb, d_b_rowptr.p, d_b_ele.p, d_b_oth.p, h_np);
+                        nlocal_, env.newton_pair != 0, ne, d_rows_scratch.p, sb, d_b_rowptr.p, d_b_ele.p, d_b_oth.p, h_np);
     np_pending = true;                 // the count is read after post_neighbor's closing sync()
     HIP_TRY(hipGetLastError());
   }
@@ -784,9 +784,10 @@ struct conp_fix {
     mark("ghost map");
     build_elyte_list(at, true);
     mark("electrolyte list + schedule");
-    build_b_rows_device(at);
+    build_b_rows_device(at, at->nlocal);
     mark("b rows (device)");
     nlocal_cur = at->nlocal;
+    mirrors_stale = false;
     sync();
     if (np_pending) { n_b_pairs = *h_np; np_pending = false; }
     mark("sync");
@@ -832,18 +833,32 @@ struct conp_fix {
   // rough electrodes (no z classes; one rank): the same contraction, the ranges' raw windows -> rows on the z grid -> G (conp_zn.hip)
   bool zn_gen_use() const { return zn_listed && !zn_off && zn_eligible() && !sk_projects() && nzc == 0 && env.nranks <= 1 && zn_nrg > 0; }
   double zn_lz() const { return kt.slabflag ? env.zprd * env.slab_volfactor : env.zprd; }
+  // the z grid of the list order and of the windows (both re-neighbouring routes): the smallest multiple of 16 with an oversampling
+  // ratio n / (2 nz) >= 1.9 (15 taps: 2e-13 of the largest entry there, tools/proto/zn_proto.py); the window's shape parameter
+  // follows the ratio
+  int zn_grid_setup() {
+    const int n = std::max(64, (38 * plan.nz / 10 + 15) / 16 * 16);       // any integer does (no FFT anywhere): a multiple of 16
+    zn_n = n;
+    zn_beta = 0.97 * 3.14159265358979323846 * ZN_W * (1.0 - (double)plan.nz / n);      // gamma pi W (1 - 1 / (2 sigma))
+    zn_gscale = (double)n / zn_lz();
+    return n;
+  }
+  // the cell behind the longest run of empty cells (the first of several equally long ones; the ring is walked twice so that a run
+  // across cell 0 counts whole), 0 for a box without an empty cell -- from the occupancy, whichever route counted it
+  static int zn_start_cell(const int *occ, int n) {
+    int best_len = 0, best_end = 0, run = 0;
+    for (int c = 0; c < 2 * n; ++c) {
+      if (occ[c % n] == 0) { if (++run > best_len && run <= n) { best_len = run; best_end = c % n; } }
+      else run = 0;
+    }
+    return best_len > 0 ? (best_end + 1) % n : 0;
+  }
   // z-order the list (stable: atoms of one cell keep their list order) and cut it into ranges with a window origin each
   void zn_order_list(const conp_atoms *at) {
     zn_listed = false; zn_off = false;
     if (getenv("CONP_TIME_REN")) std::fprintf(stderr, "  z-window: eligible %d (decomposed %d pppm %d nl %d) plan.nz %d\n", (int)zn_eligible(), (int)decomposed, args.pppm, nl, plan.nz);
     if (!zn_eligible() || plan.nz <= 0) return;
-    // grid: the smallest multiple of 16 with an oversampling ratio n / (2 nz) >= 1.9 (15 taps: 2e-13 of the largest entry there,
-    // tools/proto/zn_proto.py); the window's shape parameter follows the ratio
-    int n = std::max(64, (38 * plan.nz / 10 + 15) / 16 * 16);       // any integer does (no FFT anywhere): a multiple of 16
-    zn_n = n;
-    zn_beta = 0.97 * 3.14159265358979323846 * ZN_W * (1.0 - (double)plan.nz / n);      // gamma pi W (1 - 1 / (2 sigma))
-    const double lz = zn_lz();
-    zn_gscale = (double)n / lz;
+    const int n = zn_grid_setup();
     const int nlist = (int)elyte_idx_h.size();
     std::vector<int> cell(nlist), occ(n, 0), cnt(n + 1, 0);
     std::vector<double> uw(nlist);                       // grid coordinate of every listed atom, wrapped into [0, n)
@@ -858,12 +873,7 @@ struct conp_fix {
     // the list starts behind the longest run of empty cells (the vacuum / the electrodes of a slab cell), so that no chunk of 16
     // consecutive atoms straddles it; a box without a gap starts at cell 0 and the windows wrap (positions are taken relative to
     // a range's origin, modulo the grid)
-    int best_len = 0, best_end = 0, run = 0;
-    for (int c = 0; c < 2 * n; ++c) {
-      if (occ[c % n] == 0) { if (++run > best_len && run <= n) { best_len = run; best_end = c % n; } }
-      else run = 0;
-    }
-    const int c_start = best_len > 0 ? (best_end + 1) % n : 0;
+    const int c_start = zn_start_cell(occ.data(), n);
     for (int k = 0; k < nlist; ++k) { int c = cell[k] - c_start; if (c < 0) c += n; cell[k] = c; ++cnt[c + 1]; }
     for (int c = 0; c < n; ++c) cnt[c + 1] += cnt[c];
     elyte_dev_h.assign(nlist, 0);
@@ -885,7 +895,7 @@ struct conp_fix {
     // from build_items (table_c0 .. table_c1)
     zn_listed = true;
   }
-  void zn_build_items(const conp_atoms *at) {
+  void zn_build_items() {
     if (!zn_listed) return;
     const int n = zn_n;
     const int nchunks = nl_pad / 16;
@@ -1091,10 +1101,14 @@ struct conp_fix {
     zn_order_list(at);
     lap("z order");
     ren_upload(d_elyte_idx, zn_listed ? elyte_dev_h : elyte_idx_h);
+    finish_elyte_list();
+    lap("schedule + z-window items");
+  }
+  // what follows the ordered list on the device, whichever route put it there: the sk_gemm schedule, the z-window items (from the
+  // chunk bounds zn_ch_lo / zn_ch_hi) and the buffers that scale with the list
+  void finish_elyte_list() {
     build_items();
-    lap("sk_gemm schedule");
-    zn_build_items(at);
-    lap("z-window items");
+    zn_build_items();
     d_Xt.reserve((size_t)(plan.kxmax + 2) * nl_pad); d_Yt.reserve((size_t)(plan.kymax + 1) * nl_pad);
     d_Zt.reserve((size_t)(1 + plan.n_col_tiles * 32) * nl_pad); d_Zt.zero(stream);   // unit step + a seed every 5th kz
     d_qc.reserve(nl_pad); d_slab_part.reserve((nl_pad + 31) / 32 + 1025);      // (one per z block of the phase kernel: up to four per 128 atoms)
@@ -1801,7 +1815,7 @@ struct conp_fix {
     try { idx.renumber_from_tags(tags, at->nlocal, at->tag, at->echeck, &rc); }
     catch (const std::exception &e) { throw ConpError(CONP_ERR_IO, e.what()); }
     upload_atoms_static(at);                                   // atom2eleall follows the new numbering
-    build_b_rows_device(at);                                   // rows follow the new numbering (the list is on the device)
+    build_b_rows_device(at, at->nlocal);                                   // rows follow the new numbering (the list is on the device)
     ++s_generation;
     HIP_TRY(hipMemcpyAsync(d_A.p, a.data(), a.size() * sizeof(double), hipMemcpyHostToDevice, stream));
     km_a_read(at);                                             // kspmod->a_read(): electrode phase tables (:772)
@@ -2552,6 +2566,7 @@ struct conp_fix {
   // the list built on the device (conp_neigh.hip): scratch of the build, and the owned coordinates it saw
   bool pair_list_built = false;
   int pair_build_nlocal = 0;
+  double pair_build_cutneigh = 0.0;
   int64_t pair_nneigh = 0;
   double pair_cutsq_max = 0.0;
   DevBuf<double> d_nb_ext, d_nb_xbuild;
@@ -2698,7 +2713,7 @@ struct conp_fix {
       HIP_TRY(hipGetLastError());
       sync();
     }
-    pair_nall = na; pair_inum = nl; pair_nneigh = total; pair_build_nlocal = nl;
+    pair_nall = na; pair_inum = nl; pair_nneigh = total; pair_build_nlocal = nl; pair_build_cutneigh = a->cutneigh;
     pair_have_list = true;
     pair_list_built = true;
   }
@@ -2858,6 +2873,188 @@ struct conp_fix {
     }
     launch_atoms_wrap(stream, w, dx, dimage);
     HIP_TRY(hipGetLastError());
+  }
+
+  // ---- the fix's re-neighbouring on the device (conp_reneigh.hip): Fix::post_neighbor without host arrays ------
+  // Everything post_neighbor leaves on the device for the update and for post_force, rebuilt from the handle's half list (section
+  // 17), its ghost map (section 18) and the d_x, d_q of the call.  The host keeps what it kept: the electrode numbering (idx), the
+  // schedules (build_items, zn_build_items).  What the host route forms from `atoms` -- elyte_idx_h, ele_pairs_h, blist, brows -- is
+  // NOT refreshed: mirrors_stale bars the host-array entries that read them until the next host post_neighbor.
+  bool mirrors_stale = false;
+  DevBuf<int> d_ren_cnt, d_ren_start, d_ren_out, d_ren_elyte, d_ren_own, d_ren_cell, d_ren_i0, d_ren_ch;
+  DevBuf<double> d_ren_uw;
+  std::vector<int> ren_host;
+  void need_mirrors(const char *who) const {
+    if (mirrors_stale)
+      throw ConpError(CONP_ERR_STATE, std::string(who) + ": the last re-neighbouring was conp_fix_post_neighbor_device, which leaves the host "
+                                      "copies of the lists as they were at the re-neighbouring before it; call conp_fix_post_neighbor with "
+                                      "the host arrays of the current neighbouring first (the _device entries need none)");
+  }
+  // d.n >= count with the first `keep` entries preserved (DevBuf::reserve alone drops the content when it re-allocates)
+  void grow_keep(DevBuf<int> &d, size_t count, size_t keep) {
+    if (count <= d.n) return;
+    DevBuf<int> t;
+    t.reserve(count + count / 4);
+    keep = std::min(keep, d.n);
+    if (keep) HIP_TRY(hipMemcpyAsync(t.p, d.p, keep * sizeof(int), hipMemcpyDeviceToDevice, stream));
+    sync();
+    std::swap(d.p, t.p); std::swap(d.n, t.n);
+  }
+  // the preconditions of include/conp_hip.h, every one checked before anything of the handle changes
+  void post_neighbor_device_check(const double *dx, const double *dq) const {
+    const char *w = "conp_fix_post_neighbor_device: ";
+    if (!dx || !dq) throw ConpError(CONP_ERR_ARG, std::string(w) + "null argument");
+    if (decomposed) throw ConpError(CONP_ERR_STATE, std::string(w) + "the handle is spatially decomposed (conp_fix_set_comm): the host hook re-neighbours it");
+    if (!idx.initialised || nlocal_cur <= 0 || nall <= 0)
+      throw ConpError(CONP_ERR_STATE, std::string(w) + "before conp_fix_setup_post_neighbor (host arrays, once per run)");
+    if (runstage < 2) throw ConpError(CONP_ERR_STATE, std::string(w) + "before conp_fix_linalg_setup / conp_fix_setup_pre_force");
+    if (!pair_have_list || !pair_list_built) throw ConpError(CONP_ERR_STATE, std::string(w) + "no list of conp_pair_build_list_device");
+    if (!ghost_built) throw ConpError(CONP_ERR_STATE, std::string(w) + "no ghost map of conp_ghost_build_device");
+    if (pair_build_nlocal != nlocal_cur || ghost_nlocal != nlocal_cur)
+      throw ConpError(CONP_ERR_STATE, std::string(w) + "the list or the ghost map was built for another nlocal than the last host (setup_)post_neighbor saw");
+    if (pair_nall != ghost_nlocal + ghost_n) throw ConpError(CONP_ERR_STATE, std::string(w) + "the list's nall is not nlocal + nghost of the ghost map");
+    // (the list's newton setting is env.newton_pair by construction: conp_pair_build_list_device reads it from the handle)
+    if (!(pair_build_cutneigh >= env.cut_coul)) throw ConpError(CONP_ERR_STATE, std::string(w) + "the list's cutneigh is below env.cut_coul");
+    if (d_type.n < (size_t)nlocal_cur || d_atom2eleall.n < (size_t)nlocal_cur)
+      throw ConpError(CONP_ERR_STATE, std::string(w) + "the per-atom tables of the last host post_neighbor are missing");
+    const int n = std::max(64, (38 * plan.nz / 10 + 15) / 16 * 16);
+    if ((long long)n * ((idx.elytenum + 255) / 256 + 1) >= (1ll << 31))
+      throw ConpError(CONP_ERR_NUMERIC, std::string(w) + "z cells times blocks of 256 listed atoms reach 2^31");
+  }
+  // Synchronisations: the flag of the updates before (zn_take_flag_before_rebuild, only once a z-window has been used), (1) the two
+  // list lengths and the cell occupancy, (2) the chunk bounds -- only when the z-window is eligible --, (3) the closing one (the
+  // b-row pair count; the small uploads have left the arena).  Host traffic: 4 + n ints, 2 ceil(nl / 16) ints, the schedules.
+  void post_neighbor_device(const double *dx, const double *dq) {
+    post_neighbor_device_check(dx, dq);
+    resident_step = -1;
+    pp_elyte_valid = pp_u_valid = false;
+    ew_g_valid = ew_u_valid = false;
+    const int nloc = nlocal_cur, ng = ghost_n, na = nloc + ng, ne = idx.elenum_all;
+    sync();                                       // no kernel may be reading the tables that are replaced
+    ren_begin(sizeof(int) * (8 * (size_t)std::max(ne, 64) + (size_t)idx.elytenum / 4 + 65536) + 64 * 32);
+    // (1) per-atom tables: the owned rows stay, the ghost rows follow their owners
+    grow_keep(d_type, (size_t)na, (size_t)nloc);
+    grow_keep(d_atom2eleall, (size_t)na, (size_t)nloc);
+    launch_ren_ghost_rows(stream, nloc, ng, d_gh_owner.p, d_type.p, d_atom2eleall.p);
+    nall = na;
+    ghost_mode = false;                           // (the host-array path's own ghost map described the old ghosts)
+    d_x.reserve((size_t)na * 3); d_q.reserve(na);
+    // (2) + (4), count passes: the electrode atoms among all atoms, the charged electrolyte atoms among the owned ones.  Owned atoms
+    // keep their identity, so atom2eleall < 0 is the host's electrode_check == 0 (upload_atoms_static gives every owned electrode
+    // atom of a handle that is not decomposed its row: every tag of the group is in tag2eleall)
+    const int nb_all = (na + 63) / 64, nb_own = (nloc + 63) / 64;
+    const bool zn_static = !args.pppm && !path_on(CONP_PATH_SK_CLASSIC) && plan.nz > 0;
+    const int zn = zn_static ? std::max(64, (38 * plan.nz / 10 + 15) / 16 * 16) : 0;
+    // (scratch of every count -> scan -> fill below, sized once: blocks of 64 atoms, electrode rows, (z cell, block of 256) counts)
+    const size_t nscr = std::max<size_t>((size_t)std::max(nb_all, ne + 1), (size_t)zn * ((idx.elytenum + 255) / 256));
+    d_ren_cnt.reserve(nscr); d_ren_start.reserve(nscr);
+    d_ren_out.reserve(4 + (size_t)zn);
+    long long *d_tot_ele = reinterpret_cast<long long *>(d_ren_out.p), *d_tot_nl = d_tot_ele + 1;
+    d_ren_elyte.reserve((size_t)std::max(idx.elytenum, 1));
+    HIP_TRY(hipMemsetAsync(d_ren_out.p, 0, (4 + (size_t)zn) * sizeof(int), stream));
+    launch_ren_compact(stream, 1, false, nloc, d_atom2eleall.p, dq, d_ren_cnt.p, nullptr, 0, nullptr);
+    launch_neigh_scan(stream, nb_own, d_ren_cnt.p, d_ren_start.p, d_tot_nl);
+    launch_ren_compact(stream, 1, true, nloc, d_atom2eleall.p, dq, nullptr, d_ren_start.p, idx.elytenum, d_ren_elyte.p);
+    ZnOrderArgs za{};
+    if (zn_static) {
+      zn_grid_setup();
+      za.n = zn_n; za.w = ZN_W; za.gscale = zn_gscale; za.rn = 1.0 / zn_n; za.n_below = std::nextafter((double)zn_n, 0.0);
+      d_ren_cell.reserve((size_t)std::max(idx.elytenum, 1)); d_ren_uw.reserve((size_t)std::max(idx.elytenum, 1));
+      launch_ren_zcell(stream, za, idx.elytenum, d_tot_nl, d_ren_elyte.p, dx, d_ren_cell.p, d_ren_uw.p, d_ren_out.p + 4);
+    }
+    launch_ren_compact(stream, 0, false, na, d_atom2eleall.p, nullptr, d_ren_cnt.p, nullptr, 0, nullptr);
+    launch_neigh_scan(stream, nb_all, d_ren_cnt.p, d_ren_start.p, d_tot_ele);
+    ren_host.resize(4 + (size_t)zn);
+    HIP_TRY(hipMemcpyAsync(ren_host.data(), d_ren_out.p, ren_host.size() * sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipGetLastError());
+    sync();
+    long long tot[2];
+    std::memcpy(tot, ren_host.data(), sizeof tot);
+    n_ele_atoms = (int)tot[0];
+    nl_local = nl = (int)tot[1];
+    nl_pad = std::max(32, (nl + 31) / 32 * 32);
+    // (2) the scatter lists: the pairs in ascending atom index, the CSR by electrode row
+    d_ele_pairs.reserve(2 * (size_t)std::max(n_ele_atoms, 1));
+    if (n_ele_atoms == 0) HIP_TRY(hipMemsetAsync(d_ele_pairs.p, 0, 2 * sizeof(int), stream));
+    launch_ren_compact(stream, 0, true, na, d_atom2eleall.p, nullptr, nullptr, d_ren_start.p, n_ele_atoms, d_ele_pairs.p);
+    d_ele_csr_ptr.reserve((size_t)ne + 1); d_ele_csr_of.reserve((size_t)std::max(n_ele_atoms, 1)); d_ele_csr_row.reserve((size_t)std::max(n_ele_atoms, 1));
+    d_ren_own.reserve((size_t)std::max(ne, 1));
+    HIP_TRY(hipMemsetAsync(d_ren_cnt.p, 0, ((size_t)ne + 1) * sizeof(int), stream));
+    HIP_TRY(hipMemsetAsync(d_ren_own.p, 0, (size_t)std::max(ne, 1) * sizeof(int), stream));
+    if (n_ele_atoms == 0) {
+      HIP_TRY(hipMemsetAsync(d_ele_csr_of.p, 0, sizeof(int), stream));
+      HIP_TRY(hipMemsetAsync(d_ele_csr_row.p, 0, sizeof(int), stream));
+    }
+    const bool with_ghosts = ng > 0;
+    launch_ren_csr_count(stream, nloc, ne, d_atom2eleall.p, with_ghosts ? d_gh_nimg.p : nullptr, d_ren_own.p, d_ren_cnt.p);
+    launch_neigh_scan(stream, ne + 1, d_ren_cnt.p, d_ele_csr_ptr.p, d_tot_ele);
+    launch_ren_csr_fill(stream, nloc, ne, n_ele_atoms, d_ren_own.p, d_ele_csr_ptr.p, with_ghosts ? d_gh_ofirst.p : nullptr,
+                        with_ghosts ? d_gh_nimg.p : nullptr, with_ghosts ? d_gh_list.p : nullptr, d_ele_csr_of.p, d_ele_csr_row.p);
+    // (3) the fix's list: copies of the pair style's buffers -- a later conp_pair_build_list_device replaces THOSE, and the post-force
+    // kernel and the b rows keep the list of this re-neighbouring until the next (host or device) post_neighbor
+    bl_inum = pair_inum; bl_nneigh = (size_t)pair_nneigh;
+    d_bl_neigh.reserve(std::max<size_t>(bl_nneigh, 1)); d_bl_ilist.reserve((size_t)std::max(bl_inum, 1));
+    d_bl_numneigh.reserve((size_t)std::max(nloc, 1)); d_bl_first.reserve((size_t)std::max(nloc, 1));
+    if (bl_nneigh) HIP_TRY(hipMemcpyAsync(d_bl_neigh.p, d_pair_neigh.p, bl_nneigh * sizeof(int), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_bl_ilist.p, d_pair_ilist.p, (size_t)bl_inum * sizeof(int), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_bl_numneigh.p, d_pair_numneigh.p, (size_t)nloc * sizeof(int), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_bl_first.p, d_pair_first.p, (size_t)nloc * sizeof(int), hipMemcpyDeviceToDevice, stream));
+    build_b_rows_device(nullptr, nloc);
+    // (5) the z-window order: start cell on the host from the occupancy, the stable sort and the chunk bounds on the device
+    zn_listed = false; zn_off = false;
+    d_elyte_idx.reserve((size_t)std::max(nl, 1));
+    if (zn_static && zn_eligible()) {
+      const int n = zn_n, nblock = (nl + 255) / 256, nch = (nl + 15) / 16;
+      const int c_start = zn_start_cell(ren_host.data() + 4, n);
+      const size_t ncount = (size_t)n * nblock;
+      d_ren_i0.reserve((size_t)nl); d_ren_ch.reserve(2 * (size_t)nch);
+      HIP_TRY(hipMemsetAsync(d_ren_cnt.p, 0, ncount * sizeof(int), stream));
+      launch_ren_zsort(stream, za, false, nl, c_start, d_ren_elyte.p, d_ren_cell.p, d_ren_uw.p, d_ren_cnt.p, nullptr, nullptr, nullptr);
+      launch_neigh_scan(stream, (int)ncount, d_ren_cnt.p, d_ren_start.p, d_tot_nl);
+      launch_ren_zsort(stream, za, true, nl, c_start, d_ren_elyte.p, d_ren_cell.p, d_ren_uw.p, nullptr, d_ren_start.p, d_elyte_idx.p, d_ren_i0.p);
+      launch_ren_chunk_bounds(stream, nl, d_ren_i0.p, d_ren_ch.p, d_ren_ch.p + nch);
+      zn_c_start = c_start;
+      zn_ch_lo.assign(nch, 0); zn_ch_hi.assign(nch, 0);
+      HIP_TRY(hipMemcpyAsync(zn_ch_lo.data(), d_ren_ch.p, (size_t)nch * sizeof(int), hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipMemcpyAsync(zn_ch_hi.data(), d_ren_ch.p + nch, (size_t)nch * sizeof(int), hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipGetLastError());
+      sync();
+      zn_listed = true;
+    } else if (nl > 0) {
+      HIP_TRY(hipMemcpyAsync(d_elyte_idx.p, d_ren_elyte.p, (size_t)nl * sizeof(int), hipMemcpyDeviceToDevice, stream));
+    }
+    finish_elyte_list();
+    mirrors_stale = true;
+    HIP_TRY(hipGetLastError());
+    sync();
+    if (np_pending) { n_b_pairs = *h_np; np_pending = false; }
+  }
+
+  // what (2) - (5) left on the device, for the tests: sizes, then the arrays a caller asks for
+  void get_step_tables(int64_t *sizes, int *elyte, int *pairs, int *cptr, int *cof, int *crow, int *brp, int *bele, int *both, int *g0c) {
+    if (!idx.initialised || nlocal_cur <= 0) throw ConpError(CONP_ERR_STATE, "conp_fix_get_step_tables before a post_neighbor");
+    sync();
+    if (np_pending) { n_b_pairs = *h_np; np_pending = false; }
+    const int ne = idx.elenum_all, nchunks = zn_listed ? nl_pad / 16 : 0;
+    if (sizes) {
+      sizes[0] = nl; sizes[1] = n_ele_atoms; sizes[2] = ne; sizes[3] = n_b_pairs; sizes[4] = nchunks; sizes[5] = zn_listed ? 1 : 0;
+      sizes[6] = nall; sizes[7] = zn_listed ? zn_c_start : 0;
+    }
+    auto get = [&](int *h, const DevBuf<int> &d, size_t n) {
+      if (!h || !n) return;
+      if (d.n < n) throw ConpError(CONP_ERR_STATE, "conp_fix_get_step_tables: a table is shorter than its size says");
+      HIP_TRY(hipMemcpyAsync(h, d.p, n * sizeof(int), hipMemcpyDeviceToHost, stream));
+    };
+    get(elyte, d_elyte_idx, (size_t)nl);
+    get(pairs, d_ele_pairs, 2 * (size_t)n_ele_atoms);
+    get(cptr, d_ele_csr_ptr, (size_t)ne + 1);
+    get(cof, d_ele_csr_of, (size_t)n_ele_atoms);
+    get(crow, d_ele_csr_row, (size_t)n_ele_atoms);
+    get(brp, d_b_rowptr, (size_t)ne + 1);
+    get(bele, d_b_ele, (size_t)n_b_pairs);
+    get(both, d_b_oth, (size_t)n_b_pairs);
+    get(g0c, d_zn_g0c, (size_t)nchunks);
+    sync();
   }
 
   void pair_need_ready(const char *who) const {
@@ -3200,6 +3397,30 @@ int conp_fix_post_neighbor(conp_fix *f, const conp_atoms *at) {
   CONP_GUARD_END
 }
 
+int conp_fix_post_neighbor_device(conp_fix *f, const double *d_x, const double *d_q) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  (void)hipSetDevice(f->env.device);
+  f->post_neighbor_device_check(d_x, d_q);        // a refused call leaves the handle as it was: its graph and flag included
+  f->drop_graph();
+  const bool overflowed = f->zn_take_flag_before_rebuild();
+  f->post_neighbor_device(d_x, d_q);
+  if (overflowed)
+    throw ConpError(CONP_ERR_NUMERIC, "a device-resident update's z-window overflowed before this re-neighbouring (an electrolyte atom drifted "
+                                      "more than 2.5 A in z): the charges of the updates since the previous list build are invalid; the list "
+                                      "is rebuilt at the new positions");
+  CONP_GUARD_END
+}
+
+int conp_fix_get_step_tables(conp_fix *f, int64_t *sizes, int *elyte_idx, int *ele_pairs, int *csr_ptr, int *csr_of, int *csr_row,
+                             int *b_rowptr, int *b_ele, int *b_oth, int *g0c) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  (void)hipSetDevice(f->env.device);
+  f->get_step_tables(sizes, elyte_idx, ele_pairs, csr_ptr, csr_of, csr_row, b_rowptr, b_ele, b_oth, g0c);
+  CONP_GUARD_END
+}
+
 int conp_fix_linalg_setup(conp_fix *f, const conp_atoms *at) {
   CONP_GUARD_BEGIN
   f->drop_graph();
@@ -3209,6 +3430,7 @@ int conp_fix_linalg_setup(conp_fix *f, const conp_atoms *at) {
 
 int conp_fix_setup_pre_force(conp_fix *f, const conp_atoms *at, int64_t ntimestep, double potdiff) {
   CONP_GUARD_BEGIN
+  f->need_mirrors("conp_fix_setup_pre_force");
   f->drop_graph();
   f->linalg_setup(at);
   f->pre_force(at, ntimestep, potdiff);
@@ -3217,6 +3439,7 @@ int conp_fix_setup_pre_force(conp_fix *f, const conp_atoms *at, int64_t ntimeste
 
 int conp_fix_pre_force(conp_fix *f, const conp_atoms *at, int64_t ntimestep, double potdiff) {
   CONP_GUARD_BEGIN
+  f->need_mirrors("conp_fix_pre_force");
   f->drop_graph();
   f->pre_force(at, ntimestep, potdiff);
   CONP_GUARD_END
@@ -3243,6 +3466,7 @@ int conp_fix_modify_param(conp_fix *f, int narg, const char *const *arg, int *co
 
 int conp_fix_post_force(conp_fix *f, const conp_atoms *at, double *fo, double *ek, double *ec, double *vir) {
   CONP_GUARD_BEGIN
+  f->need_mirrors("conp_fix_post_force");
   f->drop_graph();
   if (f->runstage < 2) throw ConpError(CONP_ERR_STATE, "post_force before setup");
   f->post_force(at, fo, ek, ec, vir);
@@ -3251,6 +3475,7 @@ int conp_fix_post_force(conp_fix *f, const conp_atoms *at, double *fo, double *e
 
 int conp_fix_post_force_step(conp_fix *f, const conp_atoms *at, int64_t ntimestep, double *fo, double *ek, double *ec, double *vir) {
   CONP_GUARD_BEGIN
+  f->need_mirrors("conp_fix_post_force_step");
   f->drop_graph();
   if (f->runstage < 2) throw ConpError(CONP_ERR_STATE, "post_force before setup");
   f->post_force(at, fo, ek, ec, vir, ntimestep);
@@ -3266,6 +3491,7 @@ int conp_fix_a_cal(conp_fix *f, const conp_atoms *at) {
 
 int conp_fix_b_cal(conp_fix *f, const conp_atoms *at) {
   CONP_GUARD_BEGIN
+  f->need_mirrors("conp_fix_b_cal");
   f->drop_graph();
   f->b_cal(at);
   f->sync();
@@ -3281,6 +3507,7 @@ int conp_fix_equation_solve(conp_fix *f) {
 
 int conp_fix_update_charge(conp_fix *f, const conp_atoms *at, double potdiff) {
   CONP_GUARD_BEGIN
+  f->need_mirrors("conp_fix_update_charge");
   f->drop_graph();
   f->update_charge(at, potdiff);
   CONP_GUARD_END
@@ -3311,6 +3538,7 @@ int conp_km_a_cal(conp_fix *f, const conp_atoms *at, double *aaa) {
 
 int conp_km_b_cal(conp_fix *f, const conp_atoms *at, double *bbb) {
   CONP_GUARD_BEGIN
+  f->need_mirrors("conp_km_b_cal");
   f->drop_graph();
   if (!f->tables_current) f->km_a_read(at);
   if (at->nlocal + at->nghost != f->nall) throw ConpError(CONP_ERR_STATE, "atom count changed without post_neighbor");

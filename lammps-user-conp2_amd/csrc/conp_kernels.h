@@ -403,6 +403,24 @@ void launch_ghost_fill_int(hipStream_t s, int nlocal, int nghost, int width, con
 void launch_ghost_fold(hipStream_t s, int nlocal, int width, const int *ofirst, const int *nimg, const int *list, double *v /*[nlocal + nghost][width]*/);
 struct AtomsWrapArgs { int nlocal, periodic[3]; double lo[3], hi[3], prd[3]; };
 void launch_atoms_wrap(hipStream_t s, const AtomsWrapArgs &a, double *x /*[nlocal][3]*/, int *image /*[nlocal][3] or NULL*/);
+// ---- the fix's re-neighbouring on the device (conp_reneigh.hip) ----
+void launch_ren_ghost_rows(hipStream_t s, int nlocal, int nghost, const int *owner, int *type /*[nall]*/, int *atom2eleall /*[nall]*/);
+// pred 0: atoms i < n with atom2eleall[i] >= 0 -> out[k] = (i, atom2eleall[i]); pred 1: atom2eleall[i] < 0 and q[i] != 0 -> out[k] = i.
+// count / start: one entry per block of 64 atoms; the fill pass stores at most `cap` entries
+void launch_ren_compact(hipStream_t s, int pred, bool fill, int n, const int *atom2eleall, const double *q, int *count, const int *start,
+                        int cap, int *out);
+void launch_ren_csr_count(hipStream_t s, int nlocal, int ne, const int *atom2eleall, const int *nimg /*[nlocal] or NULL: no ghosts*/,
+                          int *own_of /*[ne]*/, int *cnt /*[ne + 1], zeroed by the caller*/);
+void launch_ren_csr_fill(hipStream_t s, int nlocal, int ne, int cap, const int *own_of, const int *ptr /*[ne + 1]*/, const int *ofirst,
+                         const int *nimg, const int *list, int *of /*[cap]*/, int *rowof /*[cap]*/);
+// the z grid of Fix::zn_order_list: n cells, window width w, gscale = n / lz, rn = 1 / n, n_below = nextafter(n, 0)
+struct ZnOrderArgs { int n, w; double gscale, rn, n_below; };
+void launch_ren_zcell(hipStream_t s, const ZnOrderArgs &a, int nl_max, const long long *nl_dev, const int *list, const double *x,
+                      int *cell /*[nl]*/, double *uw /*[nl]*/, int *occ /*[n], zeroed by the caller*/);
+// count / start: [n][ceil(nl / 256)], key-major; the count pass needs `count` zeroed
+void launch_ren_zsort(hipStream_t s, const ZnOrderArgs &a, bool fill, int nl, int c_start, const int *list, const int *cell, const double *uw,
+                      int *count, const int *start, int *sorted /*[nl]*/, int *i0s /*[nl]*/);
+void launch_ren_chunk_bounds(hipStream_t s, int nl, const int *i0s, int *lo /*[ceil(nl / 16)]*/, int *hi);
 void launch_left_sum(hipStream_t s, int ne, const int *elecheck, const double *v, double *out);
 void launch_results_out(hipStream_t s, int ne, const int *elecheck, const double *v, double *scal, bool do_left, const double *qele,
                         double *host_q /*page-locked host memory*/, double *host_scal);
