@@ -637,7 +637,7 @@ int conp_atoms_wrap_device(conp_fix *fix, double *d_x /*[nlocal][3]*/, int nloca
  *      electrode row -- per row the owned atom, then its ghosts in ascending ghost index;
  *   3. the fix's half list: device-to-device COPIES of the pair style's buffers, then the electrode rows of the real-space b regrouped
  *      from them.  Lifetime: the copies belong to the fix.  A later conp_pair_build_list_device (or conp_pair_set_list) replaces the
- *      pair style's list only; conp_fix_pre_force_device and conp_fix_post_force keep working with the list, the ghosts and the nall
+ *      pair style's list only; conp_fix_pre_force_device and conp_fix_post_force[_device] keep working with the list, the ghosts and the nall
  *      of THIS call until the next conp_fix_post_neighbor[_device] -- as after a host conp_fix_post_neighbor;
  *   4. the electrolyte list: owned atoms with no electrode row and q != 0, ascending.  (Owned atoms keep their identity, and every
  *      owned electrode atom of a handle that is not decomposed has a row: "no row" is the host's electrode_check == 0.);
@@ -660,7 +660,7 @@ int conp_atoms_wrap_device(conp_fix *fix, double *d_x /*[nlocal][3]*/, int nloca
  * conp_fix_post_force, conp_fix_post_force_step.  Entries that upload the atoms they are given and read no mirror keep working
  * (conp_pair_compute, the conp_ewald_* / conp_pppm_* entries, conp_compute_potential_atom, conp_fix_a_cal), and so does every device
  * entry: conp_fix_pre_force_device, conp_fix_b_cal_device / _solve_device / _scatter_device, the _device force entries,
- * conp_fix_compute_scalar, conp_fix_get_vectors.
+ * conp_fix_post_force_device (below), conp_fix_compute_scalar, conp_fix_get_vectors.
  * conp_fix_get_step_tables downloads what (2) - (5) left on the device, after either route (synchronous; for tests).  sizes[8] =
  * {nl, electrode atoms in the scatter list, Ne, b-row pairs, chunk origins (nl padded to 32, / 16; 0 when the list is not z-ordered),
  * 1 if the list is z-ordered, nall, start cell}.  Arrays may be NULL: elyte_idx [nl], ele_pairs [2 sizes[1]], csr_ptr [Ne + 1],
@@ -668,6 +668,37 @@ int conp_atoms_wrap_device(conp_fix *fix, double *d_x /*[nlocal][3]*/, int nloca
 int conp_fix_post_neighbor_device(conp_fix *fix, const double *d_x /*[nall][3]*/, const double *d_q /*[nall]*/);
 int conp_fix_get_step_tables(conp_fix *fix, int64_t *sizes /*[8] or NULL*/, int *elyte_idx, int *ele_pairs, int *csr_ptr, int *csr_of,
                              int *csr_row, int *b_rowptr, int *b_ele, int *b_oth, int *g0c);
+
+/* ---- the Gaussian correction on the device -----------------------------------------------------------------
+ * conp_fix_post_force_device is conp_fix_post_force for an engine whose atoms live on the device: the last hook of a step that
+ * needed host arrays.  All pointers are device pointers laid out as for conp_pair_compute_device: owned atoms first, then ghosts;
+ * the ghost rows of d_x and d_q must be filled (conp_ghost_fill_device); nall and nlocal are those of the last
+ * conp_fix_post_neighbor[_device].  d_f [nall][3] is ADDED to -- there is no staging array, no flag and no read-back; with newton on
+ * the term lands on ghost electrolyte atoms too, and the caller folds d_f with conp_ghost_fold_device.  d_out [9] is OVERWRITTEN:
+ *   d_out[0]     what the reference adds to force->kspace->energy:  qqrd2e eta sum q^2 / (sqrt 2 sqrt pi) over the owned electrode
+ *                atoms, with active EHGO  qqrd2e sum u0_type q^2  -- conp_fix_post_force's two expressions, same operations;
+ *   d_out[1]     eng_coul_add;
+ *   d_out[2..7]  the virial xx, yy, zz, xy, xz, yz;
+ *   d_out[8]     the number of contributing pairs (inside the eta^2 r^2 < 5.8 gate), as a double: whether the term acted.
+ * Either output may be NULL; with both NULL the call returns CONP_OK and does nothing.
+ * The pair set and the arithmetic are conp_fix_post_force's: every listed pair of the FIX's half list with exactly one electrode
+ * member (no newton / ghost filter on membership), `del*forcecoul`, the 5.8 gate on the fix's eta, the EHGO branch, the force on the
+ * j side under newton or j < nlocal, the energy weights 1 / 0.5 / 0.5, no contraction.
+ * It reads device tables only (the fix's list, the atom -> electrode-row table, the types, the real-space parameters), so it works
+ * after a host conp_fix_post_neighbor and after conp_fix_post_neighbor_device alike (the stale host mirrors of section 19 do not
+ * concern it), and a later conp_pair_build_list_device does not change what it walks (the lifetime rule above).
+ * Order guarantee: energy, virial and the pair count meet no atomic -- every lane adds its pairs in list order, waves, workgroups and
+ * the rows they store are added in a fixed order -- so d_out is byte-identical from call to call on the same input, and d_out[0] is
+ * byte-identical to conp_fix_post_force's kspace_energy_add for the same charges.  Forces are added with atomics (contributions are
+ * rare, and one atom can be several pairs' j): they reproduce to the rounding of those adds.
+ * Contract: everything is enqueued on the handle's stream; after the first call at a given list size a call makes no device
+ * allocation, no copy to the host and no synchronisation.  CONP_ERR_ARG: NULL d_x or d_q.  CONP_ERR_STATE: before setup; a decomposed
+ * handle (conp_fix_set_comm: sum q^2 needs an all-reduce; replicated-atom rank handles compute locally).  A refused call changes
+ * nothing.  The entry shares no state with conp_fix_post_force[_step], which behave as before.
+ * A device step: conp_fix_pre_force_device -> conp_*_compute_forces_device -> conp_pair_compute_device ->
+ * conp_fix_post_force_device -> conp_ghost_fold_device. */
+int conp_fix_post_force_device(conp_fix *fix, const double *d_x /*[nall][3]*/, const double *d_q /*[nall]*/,
+                               double *d_f /*[nall][3], added to; NULL: none*/, double *d_out /*[9], overwritten; NULL: none*/);
 
 /* per-kernel timing of the last N updates via HIP events on the library's stream (bench.py roofline leg).
  * enable: 0 off, 1 a pair of events around every kernel, 2 around every 4th launch of the dominant kernel (sk_gemm) only --

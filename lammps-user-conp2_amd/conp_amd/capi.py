@@ -126,6 +126,7 @@ SYMBOLS = [
     "conp_ghost_build_device", "conp_ghost_fill_device", "conp_ghost_fill_int_device", "conp_ghost_fold_device", "conp_ghost_get",
     "conp_atoms_wrap_device",
     "conp_fix_post_neighbor_device", "conp_fix_get_step_tables",
+    "conp_fix_post_force_device",
 ]
 
 
@@ -279,6 +280,8 @@ def load_library():
     if hasattr(lib, "conp_fix_post_neighbor_device"):          # (comparison builds loaded through CONP_LIB lack these)
         lib.conp_fix_post_neighbor_device.argtypes = [vp, vp, vp]
         lib.conp_fix_get_step_tables.argtypes = [vp, C.POINTER(C.c_int64)] + [ip] * 9
+    if hasattr(lib, "conp_fix_post_force_device"):
+        lib.conp_fix_post_force_device.argtypes = [vp, vp, vp, vp, vp]
     lib.conp_compute_potential_atom.argtypes = [vp, C.POINTER(conp_atoms), C.POINTER(conp_neighlist), ip, ip,
                                                 C.POINTER(conp_potential_args), dp]
     lib.conp_fix_set_comm.argtypes = [vp, C.POINTER(conp_comm)]
@@ -845,6 +848,12 @@ class FixConp:
         """conp_fix_post_neighbor_device: the fix's tables rebuilt from the handle's own list and ghost map and the owned rows of
         d_x [nall][3], d_q [nall] (raw device pointers); synchronous"""
         self._check(self.lib.conp_fix_post_neighbor_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q)))
+
+    # -- the Gaussian correction on the device (DESIGN.md section 20) ------------------------------------------------------
+    def post_force_device(self, d_x: int, d_q: int, d_f: int = 0, d_out: int = 0):
+        """conp_fix_post_force_device: raw device pointers (0 = NULL), enqueued on the handle's stream, no synchronisation; d_f [nall][3]
+        is added to, d_out [9] (self energy, eng_coul, virial xx, yy, zz, xy, xz, yz, contributing pairs) is overwritten"""
+        self._check(self.lib.conp_fix_post_force_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q), C.c_void_p(d_f), C.c_void_p(d_out)))
 
     STEP_TABLES = ("elyte_idx", "ele_pairs", "csr_ptr", "csr_of", "csr_row", "b_rowptr", "b_ele", "b_oth", "g0c")
 

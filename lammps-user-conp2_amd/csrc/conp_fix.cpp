@@ -2552,6 +2552,28 @@ struct conp_fix {
     if (vir) for (int k = 0; k < 6; ++k) vir[k] = acc[1 + k];
   }
 
+  // The same term for an engine whose atoms live on the device: added straight into the caller's d_f, the
+  // nine results left in the caller's d_out.  Reads device tables only (the fix's list, atom2eleall, type, the real-space block), so
+  // mirrors_stale does not bar it; enqueued only.  It shares nothing with the host entry: d_f, d_pfacc, pf_f_dirty and
+  // resident_step are not touched.  d_pfd_part: one row per workgroup of the pair kernel, grown with the list only.
+  DevBuf<double> d_pfd_part;
+  void post_force_device(const double *dx, const double *dq, double *df, double *dout) {
+    if (!dx || !dq) throw ConpError(CONP_ERR_ARG, "null argument");
+    if (decomposed) throw ConpError(CONP_ERR_STATE, "device-resident updates take replicated atoms (conp_env.rank / nranks); "
+                                                    "spatially decomposed runs use the host-buffer hooks");
+    if (runstage < 2 || !idx.initialised || nlocal_cur <= 0 || nall <= 0) throw ConpError(CONP_ERR_STATE, "post_force before setup");
+    drop_graph();
+    if (!df && !dout) return;
+    if (dout) d_pfd_part.reserve(8 * (size_t)std::max((bl_inum + 3) / 4, 1));
+    const double k_self = ehgo_active ? env.qqrd2e * 1.0 : env.qqrd2e * 1.0 * args.eta;                       // :1198, :1180
+    const double k_div = std::sqrt(2.0) * 1.77245385090551602729;
+    prof.begin("post_force_device", stream);
+    launch_post_force_device(stream, bl_inum, d_bl_ilist.p, d_bl_numneigh.p, d_bl_first.p, d_bl_neigh.p, nlocal_cur, env.newton_pair != 0,
+                             dx, dq, d_type.p, d_atom2eleall.p, real_params(), env.qqrd2e, k_self, k_div, df, d_pfd_part.p, dout);
+    prof.end(stream);
+    HIP_TRY(hipGetLastError());
+  }
+
   // ---- pair forces of lj/cut/coul/long over the pair style's own half list (conp_pair.hip) ----------------
   // set_params copies the per-type-pair tables (one 8-double record per pair), set_list uploads the list and sizes every buffer a
   // compute call needs: the device entry then allocates nothing.
@@ -3479,6 +3501,14 @@ int conp_fix_post_force_step(conp_fix *f, const conp_atoms *at, int64_t ntimeste
   f->drop_graph();
   if (f->runstage < 2) throw ConpError(CONP_ERR_STATE, "post_force before setup");
   f->post_force(at, fo, ek, ec, vir, ntimestep);
+  CONP_GUARD_END
+}
+
+int conp_fix_post_force_device(conp_fix *f, const double *d_x, const double *d_q, double *d_f, double *d_out) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  (void)hipSetDevice(f->env.device);
+  f->post_force_device(d_x, d_q, d_f, d_out);     // (checks, then drop_graph(): a refused call leaves the handle as it was)
   CONP_GUARD_END
 }
 

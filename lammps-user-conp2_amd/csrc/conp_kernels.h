@@ -339,6 +339,11 @@ void launch_post_force(hipStream_t s, int inum, const int *ilist, const int *num
                        int nall, int newton, const double *x,
                        const double *q, const int *type, const int *atom2eleall, RealParams rp, double qqrd2e, double *f,
                        double *acc /*[9]: eng_coul, virial[6], sum q^2 of owned electrode atoms, contributing pairs*/, bool clear_f);
+// the device entry: forces added into f (NULL: none), out[9] = self energy, eng_coul, virial[6], contributing
+// pairs (NULL: none); part: one row of 8 doubles per workgroup of four owners, (inum + 3) / 4 rows, every one written before it is read
+void launch_post_force_device(hipStream_t s, int inum, const int *ilist, const int *numneigh, const int *first, const int *neigh,
+                              int nlocal, int newton, const double *x, const double *q, const int *type, const int *atom2eleall,
+                              RealParams rp, double qqrd2e, double k_self, double k_div, double *f, double *part, double *out);
 // ---- pair forces of lj/cut/coul/long over the pair style's half list (conp_pair.hip) ----
 constexpr int PAIR_TAB_W = 8;            // doubles per type pair: cutsq, cut_ljsq, lj1, lj2, lj3, lj4, offset, (pad)
 constexpr int PAIR_LDS_ENTRIES = 256;    // type pairs, (ntypes + 1)^2, the LDS form of the table holds (16 KB); more: read from global

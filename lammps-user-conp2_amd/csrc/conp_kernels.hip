@@ -2286,18 +2286,34 @@ __global__ __launch_bounds__(256) void post_force_kernel(int inum, const int *__
   for (int jj = threadIdx.x & 63; jj < jn; jj += 64) post_force_pair(i, jl[jj] & 0x3FFFFFFF, ei, nlocal, newton, x, q, type, atom2eleall, rp, qqrd2e, f, acc);
 }
 
-// Gaussian self energy sum over owned electrode atoms of q^2 (fix_conp.cpp:1167-1181), one workgroup, fixed tree
+// Gaussian self energy sum over owned electrode atoms of q^2 (fix_conp.cpp:1167-1181) by one workgroup of 1024, fixed tree; thread 0
+// returns it.  One definition for ele_qsq_kernel and post_force_finish_kernel: the two form the sum with the same operations in the
+// same order, so the host entry and the device entry report the same bits.
+__device__ __forceinline__ double ele_qsq_block(int nlocal, const int *__restrict__ atom2eleall, const double *__restrict__ q,
+                                                const int *__restrict__ type, const double *__restrict__ u0_i, double *red /*[16]*/) {
+  double s = 0.0;
+  // (the row and the charge are loaded before the test: the loads of several iterations are in flight at once, where a charge read
+  // under the test waited for the row first -- 36 such round trips per thread at the headline size.  The additions keep their order.)
+#pragma unroll 8
+  for (int i = threadIdx.x; i < nlocal; i += 1024) {
+    const int a = atom2eleall[i];
+    const double qi = q[i];
+    if (a >= 0) s += u0_i ? u0_i[type[i]] * qi * qi : qi * qi;                             // EHGO weights by u0 of the type (:1189)
+  }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  double t = 0.0;
+  if (threadIdx.x == 0) for (int k = 0; k < 16; ++k) t += red[k];
+  return t;
+}
+
 __global__ __launch_bounds__(1024) void ele_qsq_kernel(int nlocal, const int *__restrict__ atom2eleall, const double *__restrict__ q,
                                                        const int *__restrict__ type, const double *__restrict__ u0_i,
                                                        double *__restrict__ out) {
   __shared__ double red[16];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < nlocal; i += 1024)
-    if (atom2eleall[i] >= 0) s += u0_i ? u0_i[type[i]] * q[i] * q[i] : q[i] * q[i];       // EHGO weights by u0 of the type (:1189)
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) { double t = 0.0; for (int k = 0; k < 16; ++k) t += red[k]; *out = t; }
+  const double t = ele_qsq_block(nlocal, atom2eleall, q, type, u0_i, red);
+  if (threadIdx.x == 0) *out = t;
 }
 
 void launch_post_force(hipStream_t s, int inum, const int *ilist, const int *numneigh, const int *first, const int *neigh, int nlocal,
@@ -2310,6 +2326,134 @@ void launch_post_force(hipStream_t s, int inum, const int *ilist, const int *num
     hipLaunchKernelGGL(post_force_kernel, dim3((inum + 3) / 4), dim3(256), 0, s, inum, ilist, numneigh, first, neigh, nlocal, newton,
                        x, q, type, atom2eleall, rp, qqrd2e, f, acc);
   hipLaunchKernelGGL(ele_qsq_kernel, dim3(1), dim3(1024), 0, s, nlocal, atom2eleall, q, type, rp.ehgo ? rp.u0_i : nullptr, acc + 7);
+}
+
+// ---- the device entry's pair of kernels (conp_fix_post_force_device) ----------------------------------------
+// post_force_kernel's walk and post_force_pair's arithmetic, operation for operation, with two differences: forces go straight into
+// the caller's f (F), and the seven sums and the pair count (EV) never meet an atomic.  Every lane adds its pairs in jj order, the
+// wave and then the four waves of the workgroup are added in a fixed order, and EVERY workgroup stores its row part[blockIdx.x][8]
+// = (eng_coul, virial[6], contributing pairs) -- a workgroup without a pair stores zeros, so nothing has to be cleared.
+template <bool F, bool EV>
+__global__ __launch_bounds__(256) void post_force_device_kernel(int inum, const int *__restrict__ ilist, const int *__restrict__ numneigh,
+                                                                const int *__restrict__ first, const int *__restrict__ neigh,
+                                                                int nlocal, int newton, const double *__restrict__ x,
+                                                                const double *__restrict__ q, const int *__restrict__ type,
+                                                                const int *__restrict__ atom2eleall, RealParams rp, double qqrd2e,
+                                                                double *__restrict__ f, double *__restrict__ part) {
+#pragma clang fp contract(off)
+  __shared__ double red[4][8];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int ii = blockIdx.x * 4 + wave;
+  double s[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (ii < inum) {                                                   // (no early return: the workgroup meets at the barrier below)
+    const int i = ilist[ii];
+    const int *jl = neigh + first[i];
+    const int jn = numneigh[i];
+    const bool ei = atom2eleall[i] >= 0;
+    const int nt1 = rp.ntypes + 1;
+    for (int jj = lane; jj < jn; jj += 64) {
+      const int j = jl[jj] & 0x3FFFFFFF;
+      if (ei == (atom2eleall[j] >= 0)) continue;                     // exactly one electrode member: nearly every pair ends here
+      const size_t i3 = 3 * (size_t)i, j3 = 3 * (size_t)j;
+      const double delx = x[i3] - x[j3], dely = x[i3 + 1] - x[j3 + 1], delz = x[i3 + 2] - x[j3 + 2];
+      const double rsq = delx * delx + dely * dely + delz * delz;
+      const int tij = type[i] * nt1 + type[j];
+      if (!(rsq < rp.cutsq[tij])) continue;
+      const double etarij2 = rp.eta * rp.eta * rsq;
+      if (!(etarij2 < 5.8)) continue;                                // :1419 (ERFC_MAX, not its square -- kept as written)
+      const double prefactor = qqrd2e * q[i] * q[j];
+      double fterm;
+      if (rp.ehgo) {                                                 // ehgo_force :1568-1573
+        const double etaij = rp.eta_ij[tij], foij = rp.fo_ij[tij];
+        const double e2 = etaij * etaij * rsq;
+        fterm = e2 * foij * exp(-0.5 * e2) - ferfcr_sqrt_dev(e2) * etaij;
+      } else fterm = -ferfcr_sqrt_dev(etarij2) * rp.eta;            // eta_force :1477-1480
+      const double forcecoul = prefactor * fterm;
+      if (F) {
+        if (!ei) {
+          atomicAdd(&f[i3], delx * forcecoul); atomicAdd(&f[i3 + 1], dely * forcecoul); atomicAdd(&f[i3 + 2], delz * forcecoul);
+        } else if (newton || j < nlocal) {
+          atomicAdd(&f[j3], -(delx * forcecoul)); atomicAdd(&f[j3 + 1], -(dely * forcecoul)); atomicAdd(&f[j3 + 2], -(delz * forcecoul));
+        }
+      }
+      if (EV) {
+        const double fpair = forcecoul / rsq;
+        const double ecoul = prefactor * pair_potential_dev(rp, rsq, type[i], type[j], false);
+        double w = 0.0;
+        if (newton) w = 1.0;
+        else { if (i < nlocal) w += 0.5; if (j < nlocal) w += 0.5; }
+        s[0] += w * ecoul;
+        s[1] += w * (delx * delx * fpair); s[2] += w * (dely * dely * fpair); s[3] += w * (delz * delz * fpair);
+        s[4] += w * (delx * dely * fpair); s[5] += w * (delx * delz * fpair); s[6] += w * (dely * delz * fpair);
+        s[7] += 1.0;
+      }
+    }
+  }
+  if (EV) {
+    // (a wave without a contributing pair -- nearly every one -- holds +0.0 in every lane, and so would its sums: the 48 shuffles are
+    // skipped, the bits are the same)
+    if (__ballot(s[7] != 0.0) != 0) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) s[k] = wave_sum(s[k]);
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) red[wave][k] = s[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < 8) part[8 * (size_t)blockIdx.x + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+  }
+}
+
+// out[1..8] = the sum over the rows of part, every thread adding its rows in ascending order, then one fixed tree (the scheme of
+// pair_finish_kernel); out[0] = the Gaussian self energy (force_cal :1180 / :1198) from ele_qsq_kernel's sum and the two constants
+// the host formed once: k_self = qqrd2e * 1.0 * eta and k_div = sqrt(2) * sqrt(pi) (ETA), k_self = qqrd2e * 1.0 (EHGO, u0_i != NULL)
+__global__ __launch_bounds__(1024) void post_force_finish_kernel(int nrows, const double *__restrict__ part, int nlocal,
+                                                                 const int *__restrict__ atom2eleall, const double *__restrict__ q,
+                                                                 const int *__restrict__ type, const double *__restrict__ u0_i,
+                                                                 double k_self, double k_div, double *__restrict__ out) {
+#pragma clang fp contract(off)
+  __shared__ double red[16][8];
+  __shared__ double redq[16];
+  double s[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll 4                                  // (several rows' loads in flight; the additions keep their order)
+  for (int r = threadIdx.x; r < nrows; r += 1024) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s[k] += part[8 * (size_t)r + k];
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) s[k] = wave_sum(s[k]);
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) red[threadIdx.x >> 6][k] = s[k];
+  }
+  const double qsq = ele_qsq_block(nlocal, atom2eleall, q, type, u0_i, redq);       // (its barrier also publishes red)
+  if (threadIdx.x < 8) {
+    double t = 0.0;
+    for (int w = 0; w < 16; ++w) t += red[w][threadIdx.x];
+    out[1 + threadIdx.x] = t;
+  }
+  if (threadIdx.x == 0) out[0] = u0_i ? k_self * qsq : k_self * qsq / k_div;
+}
+
+void launch_post_force_device(hipStream_t s, int inum, const int *ilist, const int *numneigh, const int *first, const int *neigh,
+                              int nlocal, int newton, const double *x, const double *q, const int *type, const int *atom2eleall,
+                              RealParams rp, double qqrd2e, double k_self, double k_div, double *f, double *part, double *out) {
+  const dim3 grid((inum + 3) / 4), block(256);
+  if (inum > 0) {
+    if (f && out)
+      hipLaunchKernelGGL((post_force_device_kernel<true, true>), grid, block, 0, s, inum, ilist, numneigh, first, neigh, nlocal, newton,
+                         x, q, type, atom2eleall, rp, qqrd2e, f, part);
+    else if (f)
+      hipLaunchKernelGGL((post_force_device_kernel<true, false>), grid, block, 0, s, inum, ilist, numneigh, first, neigh, nlocal, newton,
+                         x, q, type, atom2eleall, rp, qqrd2e, f, part);
+    else if (out)
+      hipLaunchKernelGGL((post_force_device_kernel<false, true>), grid, block, 0, s, inum, ilist, numneigh, first, neigh, nlocal, newton,
+                         x, q, type, atom2eleall, rp, qqrd2e, f, part);
+  }
+  if (out)
+    hipLaunchKernelGGL(post_force_finish_kernel, dim3(1), dim3(1024), 0, s, inum > 0 ? (inum + 3) / 4 : 0, part, nlocal, atom2eleall, q,
+                       type, rp.ehgo ? rp.u0_i : nullptr, k_self, k_div, out);
 }
 
 // sum of v over the group-1 ("left") electrode atoms (totsetq :1098-1104); one workgroup
