@@ -14,169 +14,18 @@
 #include <cstring>
 #include <map>
 #include <memory>
-#include <mutex>
-#include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "../../include/conp_hip.h"
 #include "conp_host.hpp"
 #include "conp_kernels.h"
+#include "conp_dev.hpp"
+#include "conp_ghostmap.hpp"
+#include "conp_pairstyle.hpp"
 
+using namespace conp::dev;
 namespace {
-
-thread_local std::string g_last_error;
-
-struct ConpError : std::runtime_error {
-  int code;
-  ConpError(int c, const std::string &m) : std::runtime_error(m), code(c) {}
-};
-
-#define HIP_TRY(expr)                                                                                     \
-  do {                                                                                                    \
-    hipError_t e_ = (expr);                                                                               \
-    if (e_ != hipSuccess)                                                                                 \
-      throw ConpError(CONP_ERR_NO_DEVICE, std::string("HIP error: ") + hipGetErrorString(e_) + " at " #expr); \
-  } while (0)
-
-// CONP_GUARD=1 (diagnostic; tests/test_gpu_guard.py): every device buffer of the library is allocated with a 4-KB zone of a
-// known byte pattern before and after it, and conp_debug_check_guards() reads all zones back -- an out-of-range STORE of any kernel
-// shows up as a damaged zone with the buffer's size, instead of as silent corruption of a neighbouring allocation or as an abort
-// of the HIP runtime somewhere else (round 3 had one abort whose message was lost).  Off: no cost.
-struct GuardZones {
-  static constexpr size_t G = 4096;
-  static constexpr int PATTERN = 0xA5;
-  std::mutex m;
-  std::map<const void *, size_t> live;       // raw allocation -> payload bytes
-  static bool on() { static const bool v = getenv("CONP_GUARD") != nullptr; return v; }
-  static GuardZones &get() { static GuardZones g; return g; }
-  int bad_freed = 0;                         // damaged zones found when a buffer was released (checked then: the zones go with it)
-  std::string what_freed;
-  void add(const void *raw, size_t bytes) { std::lock_guard<std::mutex> l(m); live[raw] = bytes; }
-  void drop(const void *raw) {
-    std::lock_guard<std::mutex> l(m);
-    auto it = live.find(raw);
-    if (it == live.end()) return;
-    (void)hipDeviceSynchronize();
-    bad_freed += check_one(static_cast<const char *>(raw), it->second, what_freed, bad_freed);
-    live.erase(it);
-  }
-  static int check_one(const char *raw, size_t bytes, std::string &what, int already) {
-    std::vector<unsigned char> h(2 * G);
-    if (hipMemcpy(h.data(), raw, G, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(h.data() + G, raw + G + bytes, G, hipMemcpyDeviceToHost) != hipSuccess) { what += " [unreadable zone]"; return 1; }
-    int bad = 0;
-    for (int side = 0; side < 2; ++side) {
-      size_t first = G;
-      for (size_t i = 0; i < G; ++i) if (h[side * G + i] != PATTERN) { first = i; break; }
-      if (first == G) continue;
-      ++bad;
-      if (already + bad <= 4) {
-        char line[160];
-        std::snprintf(line, sizeof line, " [buffer of %zu bytes: zone %s it damaged from byte %zu]", bytes, side ? "behind" : "before", first);
-        what += line;
-      }
-    }
-    return bad;
-  }
-  // number of damaged zones, of live buffers and of buffers released since the process started; `what` names the first few
-  int check(std::string &what) {
-    std::lock_guard<std::mutex> l(m);
-    (void)hipDeviceSynchronize();
-    int bad = bad_freed;
-    what = what_freed;
-    for (const auto &kv : live) bad += check_one(static_cast<const char *>(kv.first), kv.second, what, bad);
-    return bad;
-  }
-};
-
-template <typename T>
-struct DevBuf {
-  T *p = nullptr;
-  size_t n = 0;
-  void free_() {
-    if (!p) return;
-    if (GuardZones::on()) {
-      char *raw = reinterpret_cast<char *>(p) - GuardZones::G;
-      GuardZones::get().drop(raw);
-      (void)hipFree(raw);
-    } else (void)hipFree(p);
-    p = nullptr;
-  }
-  ~DevBuf() { free_(); }
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  void reserve(size_t count) {
-    if (count <= n) return;
-    free_();
-    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-    if (GuardZones::on()) {
-      constexpr size_t G = GuardZones::G;
-      const size_t padded = (bytes + 15) / 16 * 16;
-      char *raw = nullptr;
-      HIP_TRY(hipMalloc(reinterpret_cast<void **>(&raw), padded + 2 * G));
-      HIP_TRY(hipMemset(raw, GuardZones::PATTERN, G));
-      HIP_TRY(hipMemset(raw + G + padded, GuardZones::PATTERN, G));
-      GuardZones::get().add(raw, padded);
-      p = reinterpret_cast<T *>(raw + G);
-    } else HIP_TRY(hipMalloc(reinterpret_cast<void **>(&p), bytes));
-    n = count;
-  }
-  void upload(const T *h, size_t count, hipStream_t s) {
-    reserve(count);
-    if (count) HIP_TRY(hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, s));
-  }
-  void upload(const std::vector<T> &v, hipStream_t s) { upload(v.data(), v.size(), s); }
-  void zero(hipStream_t s) { if (n) HIP_TRY(hipMemsetAsync(p, 0, n * sizeof(T), s)); }
-  void release() { free_(); n = 0; }
-};
-
-// per-kernel timing with HIP events on the library's stream (bench.py's roofline leg)
-struct Profiler {
-  bool on = false;
-  bool dominant_only = false;      // mode 2: events around sk_gemm only (cheap enough to ride inside a timed region)
-  bool skipped = false;            // the begin() that belongs to the next end() recorded nothing
-  unsigned n_dominant = 0;
-  struct Rec { std::string name; hipEvent_t a, b; };
-  std::vector<Rec> pending;
-  std::vector<hipEvent_t> pool;    // events are reused: creating a pair per kernel per update costs host time
-  std::vector<std::string> order;
-  std::map<std::string, std::pair<double, int>> acc;
-  std::vector<std::string> names_keep;
-  hipEvent_t get() {
-    hipEvent_t e = nullptr;
-    if (!pool.empty()) { e = pool.back(); pool.pop_back(); }
-    else (void)hipEventCreate(&e);
-    return e;
-  }
-  void begin(const char *name, hipStream_t s) {
-    if (!on) return;
-    skipped = dominant_only && std::strcmp(name, "sk_gemm") != 0 && std::strcmp(name, "zn_gemm") != 0;
-    // (an event pair drains the queue on both sides of the kernel: ~5 us per update when every launch carries one, measured
-    //  0.3057 -> 0.3110 ms at the headline size; every 4th launch keeps the timed region within 0.4 % of an uninstrumented run)
-    if (!skipped && dominant_only && (n_dominant++ & 3) != 0) skipped = true;
-    if (skipped) return;
-    if (pending.size() >= 4096) collect();        // a host that leaves profiling on for a long run must not grow this forever
-    Rec r; r.name = name;
-    r.a = get(); r.b = get();
-    (void)hipEventRecord(r.a, s);
-    pending.push_back(r);
-  }
-  void end(hipStream_t s) { if (on && !skipped && !pending.empty()) (void)hipEventRecord(pending.back().b, s); }
-  void collect() {
-    for (auto &r : pending) {
-      (void)hipEventSynchronize(r.b);
-      float ms = 0; (void)hipEventElapsedTime(&ms, r.a, r.b);
-      if (!acc.count(r.name)) order.push_back(r.name);
-      auto &e = acc[r.name]; e.first += ms; e.second += 1;
-      pool.push_back(r.a); pool.push_back(r.b);
-    }
-    pending.clear();
-  }
-  void reset() { collect(); acc.clear(); order.clear(); n_dominant = 0; }
-  ~Profiler() { for (auto e : pool) (void)hipEventDestroy(e); }
-};
 
 // ---- ranks: the host's conp_comm callbacks behind the RankOps interface of conp_host.hpp ----------------------------------
 struct RankComm : conp::RankOps {
@@ -249,7 +98,7 @@ Rccl g_rccl;   // plain pointers, no destructor: nothing of it runs at exit
 
 using namespace conp;
 
-struct conp_fix {
+struct conp_fix : DevCtx {
   conp_fix_args args{};
   conp_env env{};
   std::vector<double> cutsq_h;
@@ -288,7 +137,6 @@ struct conp_fix {
   // CONP_TIME_HOST=1: where a host-buffer update spends its host time (printed to stderr when the handle is closed)
   const bool time_host = getenv("CONP_TIME_HOST") != nullptr;
   double th[6] = {0, 0, 0, 0, 0, 0};    // list check, staging copies, enqueue, wait, scatter, updates
-  static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
   bool pp_im_clean = false;      // the mesh's imaginary brick is all zero (left so by the b path's last backward pass)
   // PPPMCONP's per-step caches (pppm_conp.cpp: elyte_density_brick + elyte_mapped, u_brick): pp_keep -- a host that overrides
   // PPPM::make_rho asked for the electrolyte brick of every b_cal (conp_pppm_keep_density); pp_elyte_valid -- d_pp_elyte holds the
@@ -340,7 +188,6 @@ struct conp_fix {
   DevBuf<char> d_rows_scratch;
   int nlocal_cur = 0;
   // device state
-  hipStream_t stream = nullptr;
   bool own_stream = false;
   DevBuf<double> d_x, d_q, d_qc, d_slab_part, d_Gpart, d_G, d_Gw, d_wfull, d_Rp, d_Tz, d_ele_z, d_bk, d_breal, d_b_own,
       d_eleallq_own, d_qele, d_elesetq, d_eleinitq, d_A, d_cutsq, d_scalars, d_ainve, d_sfr, d_sfi, d_cg_res, d_cg_p, d_Srows, d_xg, d_qg, d_pp_ele, d_pp_scratch,
@@ -377,7 +224,6 @@ struct conp_fix {
   int max_nsplit = 0;              // most output slots any tile of the plan has (chooses sk_reduce's one- or two-level sum)
   int n_slots = 0;                 // output slots of sk_gemm: one per (segment, row tile of the plan its band touches)
   DevPlan dplan{};
-  Profiler prof;
 
   ~conp_fix() {
     if (time_host && th[5] > 0)
@@ -405,20 +251,6 @@ struct conp_fix {
     rp.cut_coulsq = cut_coulsq; rp.ntypes = env.ntypes; rp.cutsq = d_cutsq.p;
     rp.ehgo = ehgo_active ? 1 : 0; rp.eta_ij = d_eta_ij.p; rp.fo_ij = d_fo_ij.p; rp.u0_i = d_u0_i.p;
     return rp;
-  }
-
-  // The wait at the end of a host-buffer update: the runtime's blocking synchronisation wakes the thread tens of microseconds after
-  // the stream drained; polling the stream for the first two milliseconds (an update takes 0.03 - 20 ms) returns within a few.
-  // Longer waits (setup, large systems) fall back to the blocking call: no core is burnt for them.
-  void sync() {
-    const double t0 = now_s();
-    for (;;) {
-      const hipError_t e = hipStreamQuery(stream);
-      if (e == hipSuccess) return;
-      if (e != hipErrorNotReady) HIP_TRY(e);
-      if (now_s() - t0 > 2e-3) break;
-    }
-    HIP_TRY(hipStreamSynchronize(stream));
   }
 
   // ---------------------------------------------------------------------------------------------
@@ -2574,328 +2406,10 @@ struct conp_fix {
     HIP_TRY(hipGetLastError());
   }
 
-  // ---- pair forces of lj/cut/coul/long over the pair style's own half list (conp_pair.hip) ----------------
-  // set_params copies the per-type-pair tables (one 8-double record per pair), set_list uploads the list and sizes every buffer a
-  // compute call needs: the device entry then allocates nothing.
-  bool pair_have_params = false, pair_have_list = false;
+  // ---- the pair style with its half list (conp_pairstyle.cpp, DESIGN.md sections 16, 17) and the ghost map (conp_ghostmap.cpp, 18) ----
+  PairStyle pair{*this};
+  GhostMap ghost{*this};
   bool types_in_range = false;                   // every atoms->type of the last (setup_)post_neighbor lies in [0, ntypes]
-  int pair_nall = 0, pair_inum = 0, pair_ntab = 0;
-  double pair_cut_coul = 0.0, pair_special_lj[4] = {1, 1, 1, 1}, pair_special_coul[4] = {1, 1, 1, 1};
-  DevBuf<double> d_pair_tab, d_pair_part, d_pair_x, d_pair_q, d_pair_f, d_pair_ev, d_pair_ea, d_pair_va;
-  DevBuf<double4> d_pair_xq;
-  DevBuf<int> d_pair_ilist, d_pair_numneigh, d_pair_first, d_pair_neigh, d_pair_type;
-  std::vector<double> pair_out_h;
-  // the list built on the device (conp_neigh.hip): scratch of the build, and the owned coordinates it saw
-  bool pair_list_built = false;
-  int pair_build_nlocal = 0;
-  double pair_build_cutneigh = 0.0;
-  int64_t pair_nneigh = 0;
-  double pair_cutsq_max = 0.0;
-  DevBuf<double> d_nb_ext, d_nb_xbuild;
-  DevBuf<double4> d_nb_sorted;
-  DevBuf<int> d_nb_cell, d_nb_slot, d_nb_count, d_nb_start, d_nb_unsorted;
-  DevBuf<long long> d_nb_total;
-
-  void pair_set_params(const conp_pair_params *p) {
-    if (p->ntypes != env.ntypes) throw ConpError(CONP_ERR_ARG, "conp_pair_set_params: ntypes differs from the handle's");
-    if (!p->cutsq) throw ConpError(CONP_ERR_ARG, "conp_pair_set_params: cutsq is NULL");
-    if (p->cut_ljsq && (!p->lj1 || !p->lj2 || !p->lj3 || !p->lj4 || !p->offset))
-      throw ConpError(CONP_ERR_ARG, "conp_pair_set_params: cut_ljsq without lj1..lj4 and offset");
-    const int nt1 = env.ntypes + 1;
-    std::vector<double> tab((size_t)nt1 * nt1 * PAIR_TAB_W, 0.0);
-    for (int k = 0; k < nt1 * nt1; ++k) {
-      double *t = &tab[(size_t)k * PAIR_TAB_W];
-      t[0] = p->cutsq[k];
-      if (p->cut_ljsq) { t[1] = p->cut_ljsq[k]; t[2] = p->lj1[k]; t[3] = p->lj2[k]; t[4] = p->lj3[k]; t[5] = p->lj4[k]; t[6] = p->offset[k]; }
-      // (no LJ part: cut_ljsq stays 0, and rsq < 0 never holds)
-    }
-    sync();                                       // no kernel may be reading the old table
-    d_pair_tab.upload(tab, stream);
-    sync();                                       // `tab` leaves scope
-    pair_ntab = nt1 * nt1;
-    pair_cut_coul = p->cut_coul;
-    pair_cutsq_max = 0.0;
-    for (int k = 0; k < nt1 * nt1; ++k) pair_cutsq_max = std::max(pair_cutsq_max, p->cutsq[k]);
-    for (int k = 0; k < 4; ++k) { pair_special_lj[k] = p->special_lj[k]; pair_special_coul[k] = p->special_coul[k]; }
-    pair_have_params = true;
-  }
-
-  void pair_set_list(const conp_neighlist *l, int nall_) {
-    pair_have_list = false;                       // a list that is refused leaves the handle without one
-    pair_list_built = false;
-    if (nall_ < 0 || l->inum < 0 || l->inum > nall_ || l->nneigh < 0) throw ConpError(CONP_ERR_ARG, "conp_pair_set_list: bad sizes");
-    if (l->inum > 0 && (!l->ilist || !l->numneigh || !l->first)) throw ConpError(CONP_ERR_ARG, "conp_pair_set_list: null list array");
-    if (l->nneigh > 0 && !l->neigh) throw ConpError(CONP_ERR_ARG, "conp_pair_set_list: null neighbour array");
-    for (int ii = 0; ii < l->inum; ++ii) {        // every index a kernel will use is checked here, once per list
-      const int i = l->ilist[ii];
-      if (i < 0 || i >= nall_) throw ConpError(CONP_ERR_ARG, "conp_pair_set_list: list owner outside [0, nall)");
-      const int64_t a = l->first[i], n = l->numneigh[i];
-      if (a < 0 || n < 0 || a + n > l->nneigh) throw ConpError(CONP_ERR_ARG, "conp_pair_set_list: a row leaves the neighbour array");
-      for (int64_t k = a; k < a + n; ++k)
-        if ((l->neigh[k] & 0x3FFFFFFF) >= nall_) throw ConpError(CONP_ERR_ARG, "conp_pair_set_list: neighbour index outside [0, nall)");
-    }
-    sync();
-    d_pair_ilist.upload(l->ilist, (size_t)l->inum, stream);
-    d_pair_numneigh.upload(l->numneigh, (size_t)(l->inum > 0 ? nall_ : 0), stream);
-    d_pair_first.upload(l->first, (size_t)(l->inum > 0 ? nall_ : 0), stream);
-    d_pair_neigh.upload(l->neigh, (size_t)l->nneigh, stream);
-    d_pair_part.reserve((size_t)std::max(l->inum, 1) * 8);
-    d_pair_xq.reserve((size_t)std::max(nall_, 1));
-    d_pair_ev.reserve(8);
-    sync();                                       // the caller's arrays need not stay
-    pair_nall = nall_; pair_inum = l->inum; pair_nneigh = l->nneigh;
-    pair_have_list = true;
-  }
-
-  // The cell grid of a build: cells at least cutneigh (1 + 2^-20) wide, so that the 27 cells around an atom's hold every atom
-  // within cutneigh of it whatever the rounding of the index arithmetic; at most 4 nall + 64 cells (a dilute or a very long box
-  // gets wider cells: the numbers of cells are halved, the largest first, until they fit).
-  static NeighGrid neigh_grid(const double ext[6], double cutneigh, int nall_) {
-    NeighGrid g;
-    const double w = cutneigh * (1.0 + 1.0 / 1048576.0);
-    for (int c = 0; c < 3; ++c) {
-      const double len = ext[3 + c] - ext[c];
-      g.lo[c] = ext[c];
-      g.n[c] = w > 0.0 && len > w ? (int)std::min(len / w, 1024.0) : 1;
-    }
-    const int64_t cap = 4 * (int64_t)nall_ + 64;
-    while ((int64_t)g.n[0] * g.n[1] * g.n[2] > cap) {
-      int c = 0;
-      if (g.n[1] > g.n[c]) c = 1;
-      if (g.n[2] > g.n[c]) c = 2;
-      g.n[c] = (g.n[c] + 1) / 2;
-    }
-    for (int c = 0; c < 3; ++c) {
-      const double len = ext[3 + c] - ext[c];
-      g.inv[c] = g.n[c] > 1 ? g.n[c] / len : 0.0;      // one cell: every atom gets index 0
-    }
-    return g;
-  }
-
-  void pair_build_list(const double *dx, const conp_pair_build_args *a) {
-    pair_have_list = false;                       // a build that is refused leaves the handle without a list
-    pair_list_built = false;
-    if (!pair_have_params) throw ConpError(CONP_ERR_STATE, "conp_pair_build_list_device before conp_pair_set_params");
-    if (!dx || !a) throw ConpError(CONP_ERR_ARG, "null argument");
-    if (a->nlocal < 0 || a->nall < 0 || a->nlocal > a->nall || a->nall > 0x3FFFFFFF)
-      throw ConpError(CONP_ERR_ARG, "conp_pair_build_list_device: bad sizes");
-    if (!(a->cutneigh * a->cutneigh >= pair_cutsq_max) || !(a->cutneigh > 0.0) || !std::isfinite(a->cutneigh))
-      throw ConpError(CONP_ERR_ARG, "conp_pair_build_list_device: cutneigh^2 is below the largest cutsq of conp_pair_set_params");
-    const int nsp = (a->d_tag != nullptr) + (a->d_nspecial != nullptr) + (a->d_special != nullptr);
-    if (nsp != 0 && nsp != 3) throw ConpError(CONP_ERR_ARG, "conp_pair_build_list_device: d_tag, d_nspecial, d_special: all three or none");
-    if (nsp == 3 && a->maxspecial < 0) throw ConpError(CONP_ERR_ARG, "conp_pair_build_list_device: negative maxspecial");
-    for (int c = 0; c < 3; ++c)
-      if (!(a->prd_half[c] >= 0.0)) throw ConpError(CONP_ERR_ARG, "conp_pair_build_list_device: prd_half is negative or not a number");
-    const int nl = a->nlocal, na = a->nall;
-    sync();                                       // no kernel may be reading the old list
-    d_pair_ilist.reserve((size_t)std::max(nl, 1));
-    d_pair_numneigh.reserve((size_t)std::max(na, 1));
-    d_pair_first.reserve((size_t)std::max(na, 1));
-    d_pair_part.reserve((size_t)std::max(nl, 1) * 8);
-    d_pair_xq.reserve((size_t)std::max(na, 1));
-    d_pair_ev.reserve(8);
-    d_nb_ext.reserve(8); d_nb_total.reserve(1);
-    d_nb_xbuild.reserve((size_t)std::max(nl, 1) * 3);
-    d_nb_cell.reserve((size_t)std::max(na, 1)); d_nb_slot.reserve((size_t)std::max(na, 1));
-    d_nb_unsorted.reserve((size_t)std::max(na, 1)); d_nb_sorted.reserve((size_t)std::max(na, 1));
-    long long total = 0;
-    if (na > 0) {
-      launch_neigh_extent(stream, na, dx, d_nb_ext.p);
-      double ext[7];
-      HIP_TRY(hipMemcpyAsync(ext, d_nb_ext.p, sizeof ext, hipMemcpyDeviceToHost, stream));
-      sync();
-      bool finite = ext[6] == 0.0;
-      for (int c = 0; c < 3; ++c) finite = finite && std::isfinite(ext[3 + c] - ext[c]);
-      if (!finite) throw ConpError(CONP_ERR_NUMERIC, "conp_pair_build_list_device: a coordinate is not finite");
-      const NeighGrid g = neigh_grid(ext, a->cutneigh, na);
-      const int ncell = g.n[0] * g.n[1] * g.n[2];
-      d_nb_count.reserve((size_t)ncell); d_nb_start.reserve((size_t)ncell + 1);
-      launch_neigh_bin(stream, na, dx, g, d_nb_cell.p, d_nb_slot.p, d_nb_count.p, d_nb_start.p, d_nb_total.p, d_nb_unsorted.p,
-                       d_nb_sorted.p);
-      NeighRowArgs r;
-      r.nlocal = nl; r.newton = env.newton_pair != 0; r.x = dx; r.cutneighsq = a->cutneigh * a->cutneigh; r.g = g;
-      r.cell = d_nb_cell.p; r.start = d_nb_start.p; r.sorted = d_nb_sorted.p;
-      r.tag = a->d_tag; r.nspecial = a->d_nspecial; r.special = a->d_special; r.maxspecial = a->maxspecial;
-      r.flagged[0] = 0;
-      for (int k = 1; k < 4; ++k) r.flagged[k] = !(pair_special_lj[k] == 1.0 && pair_special_coul[k] == 1.0);
-      for (int c = 0; c < 3; ++c) r.prd_half[c] = a->prd_half[c];
-      r.numneigh = d_pair_numneigh.p; r.first = d_pair_first.p; r.neigh = nullptr;
-      HIP_TRY(hipMemsetAsync(d_pair_numneigh.p, 0, (size_t)na * sizeof(int), stream));      // rows of i >= nlocal: 0
-      HIP_TRY(hipMemsetAsync(d_pair_first.p, 0, (size_t)na * sizeof(int), stream));
-      launch_neigh_rows(stream, r, false);
-      launch_neigh_scan(stream, nl, d_pair_numneigh.p, d_pair_first.p, d_nb_total.p);
-      HIP_TRY(hipMemcpyAsync(&total, d_nb_total.p, sizeof total, hipMemcpyDeviceToHost, stream));
-      sync();
-      if (total >= (1ll << 31)) throw ConpError(CONP_ERR_NUMERIC, "conp_pair_build_list_device: 2^31 pairs or more (first is int)");
-      d_pair_neigh.reserve((size_t)std::max<long long>(total, 1));
-      r.neigh = d_pair_neigh.p;
-      launch_neigh_rows(stream, r, true);
-      launch_neigh_iota(stream, nl, d_pair_ilist.p);
-      if (nl > 0) HIP_TRY(hipMemcpyAsync(d_nb_xbuild.p, dx, (size_t)nl * 3 * sizeof(double), hipMemcpyDeviceToDevice, stream));
-      HIP_TRY(hipGetLastError());
-      sync();
-    }
-    pair_nall = na; pair_inum = nl; pair_nneigh = total; pair_build_nlocal = nl; pair_build_cutneigh = a->cutneigh;
-    pair_have_list = true;
-    pair_list_built = true;
-  }
-
-  void pair_list_moved(const double *dx, double trigger, int *dflag) {
-    if (!dx || !dflag) throw ConpError(CONP_ERR_ARG, "null argument");
-    if (!(trigger >= 0.0)) throw ConpError(CONP_ERR_ARG, "conp_pair_list_moved_device: trigger is negative or not a number");
-    if (!pair_have_list || !pair_list_built)
-      throw ConpError(CONP_ERR_STATE, "conp_pair_list_moved_device: the handle's list is not one of conp_pair_build_list_device");
-    launch_neigh_moved(stream, pair_build_nlocal, dx, d_nb_xbuild.p, trigger * trigger, dflag);
-    HIP_TRY(hipGetLastError());
-  }
-
-  void pair_get_list(int *inum, int *nall_, int64_t *nneigh, int *ilist, int *numneigh, int *first, int *neigh) {
-    if (!pair_have_list) throw ConpError(CONP_ERR_STATE, "conp_pair_get_list: the handle has no list");
-    if (inum) *inum = pair_inum;
-    if (nall_) *nall_ = pair_nall;
-    if (nneigh) *nneigh = pair_nneigh;
-    const bool rows = pair_inum > 0 && pair_nall > 0;      // (an uploaded list without owners has no per-atom arrays)
-    if (ilist && pair_inum > 0) HIP_TRY(hipMemcpyAsync(ilist, d_pair_ilist.p, (size_t)pair_inum * sizeof(int), hipMemcpyDeviceToHost, stream));
-    if (numneigh && pair_nall > 0) {
-      if (rows) HIP_TRY(hipMemcpyAsync(numneigh, d_pair_numneigh.p, (size_t)pair_nall * sizeof(int), hipMemcpyDeviceToHost, stream));
-      else std::memset(numneigh, 0, (size_t)pair_nall * sizeof(int));
-    }
-    if (first && pair_nall > 0) {
-      if (rows) HIP_TRY(hipMemcpyAsync(first, d_pair_first.p, (size_t)pair_nall * sizeof(int), hipMemcpyDeviceToHost, stream));
-      else std::memset(first, 0, (size_t)pair_nall * sizeof(int));
-    }
-    if (neigh && pair_nneigh > 0) HIP_TRY(hipMemcpyAsync(neigh, d_pair_neigh.p, (size_t)pair_nneigh * sizeof(int), hipMemcpyDeviceToHost, stream));
-    sync();
-  }
-
-  // ---- ghost atoms on the device (conp_ghost.hip): Comm::borders / forward_comm / reverse_comm of one rank --
-  // The build keeps owner and image of every ghost and, per owner, the ascending list of its ghosts; fill, fill_int and fold only
-  // enqueue.  Separate from map_ghosts / ghost_mode of the host-array path (conp_env.ghost_images).
-  bool ghost_built = false;
-  int ghost_nlocal = 0, ghost_n = 0;
-  double ghost_prd[3] = {0.0, 0.0, 0.0};
-  DevBuf<int> d_gh_shift, d_gh_count, d_gh_start, d_gh_nimg, d_gh_ofirst, d_gh_owner, d_gh_img, d_gh_list;
-  DevBuf<long long> d_gh_total;
-  static constexpr int GHOST_MAX_SHIFTS = 4096;
-
-  void ghost_build(const double *dx, const conp_ghost_build_args *a, int *nghost_out) {
-    ghost_built = false;                          // a build that is refused leaves the handle without ghosts
-    if (!a || !nghost_out) throw ConpError(CONP_ERR_ARG, "null argument");
-    if (a->nlocal < 0) throw ConpError(CONP_ERR_ARG, "conp_ghost_build_device: negative nlocal");
-    if (!dx && a->nlocal > 0) throw ConpError(CONP_ERR_ARG, "conp_ghost_build_device: d_x is NULL");
-    if (!(a->cutghost >= 0.0)) throw ConpError(CONP_ERR_ARG, "conp_ghost_build_device: cutghost is negative or not a number");
-    GhostBuildArgs g;
-    double nshift_d = 1.0;
-    int m[3];
-    for (int c = 0; c < 3; ++c) {
-      if (!std::isfinite(a->boxlo[c]) || !std::isfinite(a->boxhi[c]))
-        throw ConpError(CONP_ERR_ARG, "conp_ghost_build_device: a box bound is not finite");
-      if (a->periodic[c] && !(a->boxhi[c] > a->boxlo[c]))
-        throw ConpError(CONP_ERR_ARG, "conp_ghost_build_device: boxhi <= boxlo in a periodic dimension");
-      g.prd[c] = a->boxhi[c] - a->boxlo[c];
-      g.lo[c] = a->boxlo[c] - a->cutghost;
-      g.hi[c] = a->boxhi[c] + a->cutghost;
-      const double mc = a->periodic[c] ? std::ceil(a->cutghost / g.prd[c]) : 0.0;
-      nshift_d *= 2.0 * mc + 1.0;
-      if (!(nshift_d - 1.0 <= (double)GHOST_MAX_SHIFTS)) throw ConpError(CONP_ERR_ARG, "conp_ghost_build_device: more than 4096 shifts");
-      m[c] = (int)mc;
-    }
-    if (a->nlocal >= (1 << 30)) throw ConpError(CONP_ERR_NUMERIC, "conp_ghost_build_device: 2^30 atoms or more (neighbour entries keep 30 bits)");
-    std::vector<int> shifts;
-    for (int sx = -m[0]; sx <= m[0]; ++sx)
-      for (int sy = -m[1]; sy <= m[1]; ++sy)
-        for (int sz = -m[2]; sz <= m[2]; ++sz)
-          if (sx || sy || sz) { shifts.push_back(sx); shifts.push_back(sy); shifts.push_back(sz); }
-    const int nl = a->nlocal, nshift = (int)(shifts.size() / 3), nblock = (nl + 63) / 64;
-    const size_t ncount = (size_t)nshift * nblock;
-    if (ncount >= (1ull << 31))                   // (the scan takes an int length; 2^37 image tests would be behind this)
-      throw ConpError(CONP_ERR_NUMERIC, "conp_ghost_build_device: shifts times blocks of 64 owners reach 2^31");
-    sync();                                      // no kernel may be reading the old map
-    long long total = 0;
-    if (ncount > 0) {
-      d_gh_shift.upload(shifts, stream);
-      d_gh_count.reserve(ncount); d_gh_start.reserve(ncount);
-      d_gh_nimg.reserve((size_t)nl); d_gh_ofirst.reserve((size_t)nl);
-      d_gh_total.reserve(1);
-      g.nlocal = nl; g.nblock = nblock; g.nshift = nshift; g.x = dx; g.shift = d_gh_shift.p;
-      g.count = d_gh_count.p; g.nimg = d_gh_nimg.p; g.start = nullptr; g.ofirst = nullptr;
-      g.nghost = 0; g.owner = nullptr; g.img = nullptr; g.list = nullptr;
-      launch_ghost_images(stream, g, false);
-      launch_neigh_scan(stream, nl, d_gh_nimg.p, d_gh_ofirst.p, d_gh_total.p);
-      launch_neigh_scan(stream, (int)ncount, d_gh_count.p, d_gh_start.p, d_gh_total.p);
-      HIP_TRY(hipMemcpyAsync(&total, d_gh_total.p, sizeof total, hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipGetLastError());
-      sync();
-      if ((long long)nl + total >= (1ll << 30))
-        throw ConpError(CONP_ERR_NUMERIC, "conp_ghost_build_device: nlocal + nghost reaches 2^30 (neighbour entries keep 30 bits)");
-      if (total > 0) {
-        d_gh_owner.reserve((size_t)total); d_gh_img.reserve((size_t)total * 3); d_gh_list.reserve((size_t)total);
-        g.start = d_gh_start.p; g.ofirst = d_gh_ofirst.p; g.nghost = (int)total;
-        g.owner = d_gh_owner.p; g.img = d_gh_img.p; g.list = d_gh_list.p;
-        launch_ghost_images(stream, g, true);
-        HIP_TRY(hipGetLastError());
-        sync();
-      }
-    }
-    ghost_nlocal = nl; ghost_n = (int)total;
-    for (int c = 0; c < 3; ++c) ghost_prd[c] = g.prd[c];
-    ghost_built = true;
-    *nghost_out = ghost_n;
-  }
-
-  void ghost_need_built(const char *who) const {
-    if (!ghost_built) throw ConpError(CONP_ERR_STATE, std::string(who) + " before a successful conp_ghost_build_device");
-  }
-
-  void ghost_fill(double *dx, double *dq) {
-    ghost_need_built("conp_ghost_fill_device");
-    if (!dx && ghost_nlocal + ghost_n > 0) throw ConpError(CONP_ERR_ARG, "conp_ghost_fill_device: d_x is NULL");
-    if (ghost_n <= 0) return;
-    launch_ghost_fill_xq(stream, ghost_nlocal, ghost_n, d_gh_owner.p, d_gh_img.p, ghost_prd[0], ghost_prd[1], ghost_prd[2], dx, dq);
-    HIP_TRY(hipGetLastError());
-  }
-
-  void ghost_fill_int(int *dv, int width) {
-    ghost_need_built("conp_ghost_fill_int_device");
-    if (width < 1 || width > 8) throw ConpError(CONP_ERR_ARG, "conp_ghost_fill_int_device: width outside 1 .. 8");
-    if (!dv && ghost_nlocal + ghost_n > 0) throw ConpError(CONP_ERR_ARG, "conp_ghost_fill_int_device: d_v is NULL");
-    if (ghost_n <= 0) return;
-    launch_ghost_fill_int(stream, ghost_nlocal, ghost_n, width, d_gh_owner.p, dv);
-    HIP_TRY(hipGetLastError());
-  }
-
-  void ghost_fold(double *dv, int width) {
-    ghost_need_built("conp_ghost_fold_device");
-    if (width != 1 && width != 3 && width != 6) throw ConpError(CONP_ERR_ARG, "conp_ghost_fold_device: width is not 1, 3 or 6");
-    if (!dv && ghost_nlocal + ghost_n > 0) throw ConpError(CONP_ERR_ARG, "conp_ghost_fold_device: d_v is NULL");
-    if (ghost_n <= 0) return;
-    launch_ghost_fold(stream, ghost_nlocal, width, d_gh_ofirst.p, d_gh_nimg.p, d_gh_list.p, dv);
-    HIP_TRY(hipGetLastError());
-  }
-
-  void ghost_get(int *nlocal_out, int *nghost_out, int *owner, int *img) {
-    ghost_need_built("conp_ghost_get");
-    if (nlocal_out) *nlocal_out = ghost_nlocal;
-    if (nghost_out) *nghost_out = ghost_n;
-    if (owner && ghost_n > 0) HIP_TRY(hipMemcpyAsync(owner, d_gh_owner.p, (size_t)ghost_n * sizeof(int), hipMemcpyDeviceToHost, stream));
-    if (img && ghost_n > 0) HIP_TRY(hipMemcpyAsync(img, d_gh_img.p, (size_t)ghost_n * 3 * sizeof(int), hipMemcpyDeviceToHost, stream));
-    sync();
-  }
-
-  void atoms_wrap(double *dx, int nlocal_, const double *boxlo, const double *boxhi, const int *periodic, int *dimage) {
-    if (!boxlo || !boxhi || !periodic) throw ConpError(CONP_ERR_ARG, "null argument");
-    if (nlocal_ < 0) throw ConpError(CONP_ERR_ARG, "conp_atoms_wrap_device: negative nlocal");
-    if (!dx && nlocal_ > 0) throw ConpError(CONP_ERR_ARG, "conp_atoms_wrap_device: d_x is NULL");
-    AtomsWrapArgs w;
-    w.nlocal = nlocal_;
-    for (int c = 0; c < 3; ++c) {
-      w.periodic[c] = periodic[c] != 0;
-      if (w.periodic[c] && !(boxhi[c] > boxlo[c])) throw ConpError(CONP_ERR_ARG, "conp_atoms_wrap_device: boxhi <= boxlo in a periodic dimension");
-      w.lo[c] = boxlo[c]; w.hi[c] = boxhi[c]; w.prd[c] = boxhi[c] - boxlo[c];
-    }
-    launch_atoms_wrap(stream, w, dx, dimage);
-    HIP_TRY(hipGetLastError());
-  }
 
   // ---- the fix's re-neighbouring on the device (conp_reneigh.hip): Fix::post_neighbor without host arrays ------
   // Everything post_neighbor leaves on the device for the update and for post_force, rebuilt from the handle's half list (section
@@ -2930,13 +2444,13 @@ struct conp_fix {
     if (!idx.initialised || nlocal_cur <= 0 || nall <= 0)
       throw ConpError(CONP_ERR_STATE, std::string(w) + "before conp_fix_setup_post_neighbor (host arrays, once per run)");
     if (runstage < 2) throw ConpError(CONP_ERR_STATE, std::string(w) + "before conp_fix_linalg_setup / conp_fix_setup_pre_force");
-    if (!pair_have_list || !pair_list_built) throw ConpError(CONP_ERR_STATE, std::string(w) + "no list of conp_pair_build_list_device");
-    if (!ghost_built) throw ConpError(CONP_ERR_STATE, std::string(w) + "no ghost map of conp_ghost_build_device");
-    if (pair_build_nlocal != nlocal_cur || ghost_nlocal != nlocal_cur)
+    if (!pair.have_list || !pair.list_built) throw ConpError(CONP_ERR_STATE, std::string(w) + "no list of conp_pair_build_list_device");
+    if (!ghost.built) throw ConpError(CONP_ERR_STATE, std::string(w) + "no ghost map of conp_ghost_build_device");
+    if (pair.build_nlocal != nlocal_cur || ghost.nlocal != nlocal_cur)
       throw ConpError(CONP_ERR_STATE, std::string(w) + "the list or the ghost map was built for another nlocal than the last host (setup_)post_neighbor saw");
-    if (pair_nall != ghost_nlocal + ghost_n) throw ConpError(CONP_ERR_STATE, std::string(w) + "the list's nall is not nlocal + nghost of the ghost map");
+    if (pair.nall != ghost.nlocal + ghost.nghost) throw ConpError(CONP_ERR_STATE, std::string(w) + "the list's nall is not nlocal + nghost of the ghost map");
     // (the list's newton setting is env.newton_pair by construction: conp_pair_build_list_device reads it from the handle)
-    if (!(pair_build_cutneigh >= env.cut_coul)) throw ConpError(CONP_ERR_STATE, std::string(w) + "the list's cutneigh is below env.cut_coul");
+    if (!(pair.build_cutneigh >= env.cut_coul)) throw ConpError(CONP_ERR_STATE, std::string(w) + "the list's cutneigh is below env.cut_coul");
     if (d_type.n < (size_t)nlocal_cur || d_atom2eleall.n < (size_t)nlocal_cur)
       throw ConpError(CONP_ERR_STATE, std::string(w) + "the per-atom tables of the last host post_neighbor are missing");
     const int n = std::max(64, (38 * plan.nz / 10 + 15) / 16 * 16);
@@ -2951,13 +2465,13 @@ struct conp_fix {
     resident_step = -1;
     pp_elyte_valid = pp_u_valid = false;
     ew_g_valid = ew_u_valid = false;
-    const int nloc = nlocal_cur, ng = ghost_n, na = nloc + ng, ne = idx.elenum_all;
+    const int nloc = nlocal_cur, ng = ghost.nghost, na = nloc + ng, ne = idx.elenum_all;
     sync();                                       // no kernel may be reading the tables that are replaced
     ren_begin(sizeof(int) * (8 * (size_t)std::max(ne, 64) + (size_t)idx.elytenum / 4 + 65536) + 64 * 32);
     // (1) per-atom tables: the owned rows stay, the ghost rows follow their owners
     grow_keep(d_type, (size_t)na, (size_t)nloc);
     grow_keep(d_atom2eleall, (size_t)na, (size_t)nloc);
-    launch_ren_ghost_rows(stream, nloc, ng, d_gh_owner.p, d_type.p, d_atom2eleall.p);
+    launch_ren_ghost_rows(stream, nloc, ng, ghost.d_owner.p, d_type.p, d_atom2eleall.p);
     nall = na;
     ghost_mode = false;                           // (the host-array path's own ghost map described the old ghosts)
     d_x.reserve((size_t)na * 3); d_q.reserve(na);
@@ -3008,19 +2522,19 @@ struct conp_fix {
       HIP_TRY(hipMemsetAsync(d_ele_csr_row.p, 0, sizeof(int), stream));
     }
     const bool with_ghosts = ng > 0;
-    launch_ren_csr_count(stream, nloc, ne, d_atom2eleall.p, with_ghosts ? d_gh_nimg.p : nullptr, d_ren_own.p, d_ren_cnt.p);
+    launch_ren_csr_count(stream, nloc, ne, d_atom2eleall.p, with_ghosts ? ghost.d_nimg.p : nullptr, d_ren_own.p, d_ren_cnt.p);
     launch_neigh_scan(stream, ne + 1, d_ren_cnt.p, d_ele_csr_ptr.p, d_tot_ele);
-    launch_ren_csr_fill(stream, nloc, ne, n_ele_atoms, d_ren_own.p, d_ele_csr_ptr.p, with_ghosts ? d_gh_ofirst.p : nullptr,
-                        with_ghosts ? d_gh_nimg.p : nullptr, with_ghosts ? d_gh_list.p : nullptr, d_ele_csr_of.p, d_ele_csr_row.p);
+    launch_ren_csr_fill(stream, nloc, ne, n_ele_atoms, d_ren_own.p, d_ele_csr_ptr.p, with_ghosts ? ghost.d_ofirst.p : nullptr,
+                        with_ghosts ? ghost.d_nimg.p : nullptr, with_ghosts ? ghost.d_list.p : nullptr, d_ele_csr_of.p, d_ele_csr_row.p);
     // (3) the fix's list: copies of the pair style's buffers -- a later conp_pair_build_list_device replaces THOSE, and the post-force
     // kernel and the b rows keep the list of this re-neighbouring until the next (host or device) post_neighbor
-    bl_inum = pair_inum; bl_nneigh = (size_t)pair_nneigh;
+    bl_inum = pair.inum; bl_nneigh = (size_t)pair.nneigh;
     d_bl_neigh.reserve(std::max<size_t>(bl_nneigh, 1)); d_bl_ilist.reserve((size_t)std::max(bl_inum, 1));
     d_bl_numneigh.reserve((size_t)std::max(nloc, 1)); d_bl_first.reserve((size_t)std::max(nloc, 1));
-    if (bl_nneigh) HIP_TRY(hipMemcpyAsync(d_bl_neigh.p, d_pair_neigh.p, bl_nneigh * sizeof(int), hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_bl_ilist.p, d_pair_ilist.p, (size_t)bl_inum * sizeof(int), hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_bl_numneigh.p, d_pair_numneigh.p, (size_t)nloc * sizeof(int), hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_bl_first.p, d_pair_first.p, (size_t)nloc * sizeof(int), hipMemcpyDeviceToDevice, stream));
+    if (bl_nneigh) HIP_TRY(hipMemcpyAsync(d_bl_neigh.p, pair.d_neigh.p, bl_nneigh * sizeof(int), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_bl_ilist.p, pair.d_ilist.p, (size_t)bl_inum * sizeof(int), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_bl_numneigh.p, pair.d_numneigh.p, (size_t)nloc * sizeof(int), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_bl_first.p, pair.d_first.p, (size_t)nloc * sizeof(int), hipMemcpyDeviceToDevice, stream));
     build_b_rows_device(nullptr, nloc);
     // (5) the z-window order: start cell on the host from the occupancy, the stable sort and the chunk bounds on the device
     zn_listed = false; zn_off = false;
@@ -3079,81 +2593,34 @@ struct conp_fix {
     sync();
   }
 
-  void pair_need_ready(const char *who) const {
-    if (!pair_have_params) throw ConpError(CONP_ERR_STATE, std::string(who) + " before conp_pair_set_params");
-    if (!pair_have_list) throw ConpError(CONP_ERR_STATE, std::string(who) + " before conp_pair_set_list");
-  }
-
-  // pack + force kernel (+ finish) on the stream; eatom / vatom are overwritten: zeroed first, then accumulated
-  void pair_enqueue(const double *dx, const double *dq, const int *dtype, int nlocal_, double *df, double *dev, double *dea, double *dva) {
-    PairArgs a;
-    a.inum = pair_inum; a.ilist = d_pair_ilist.p; a.numneigh = d_pair_numneigh.p; a.first = d_pair_first.p; a.neigh = d_pair_neigh.p;
-    a.nlocal = nlocal_; a.newton = env.newton_pair != 0;
-    a.xq = d_pair_xq.p; a.type = dtype; a.nt1 = env.ntypes + 1; a.ntab = pair_ntab; a.tab = d_pair_tab.p;
-    a.cut_coulsq = pair_cut_coul * pair_cut_coul; a.g_ewald = env.g_ewald; a.qqrd2e = env.qqrd2e;
-    for (int k = 0; k < 4; ++k) { a.special_lj[k] = pair_special_lj[k]; a.special_coul[k] = pair_special_coul[k]; }
-    a.f = df; a.eatom = dea; a.vatom = dva; a.part = d_pair_part.p;
-    if (dea && pair_nall > 0) HIP_TRY(hipMemsetAsync(dea, 0, (size_t)pair_nall * sizeof(double), stream));
-    if (dva && pair_nall > 0) HIP_TRY(hipMemsetAsync(dva, 0, (size_t)pair_nall * 6 * sizeof(double), stream));
-    prof.begin("pair_force", stream);
-    launch_pair_pack(stream, pair_nall, dx, dq, d_pair_xq.p);
-    launch_pair_force(stream, a, dev);
-    prof.end(stream);
-    HIP_TRY(hipGetLastError());
-  }
-
   void pair_compute_host(const conp_atoms *at, double *f, double *eng, double *vir, double *eatom, double *vatom) {
-    pair_need_ready("conp_pair_compute");
+    pair.need_ready("conp_pair_compute");
     const int n = at->nlocal + at->nghost;
-    if (at->nlocal < 0 || at->nghost < 0 || n != pair_nall)
+    if (at->nlocal < 0 || at->nghost < 0 || n != pair.nall)
       throw ConpError(CONP_ERR_ARG, "conp_pair_compute: nlocal + nghost differs from the nall of conp_pair_set_list");
     if (!f && !eng && !vir && !eatom && !vatom) return;
     if (n > 0 && (!at->x || !at->q || !at->type)) throw ConpError(CONP_ERR_ARG, "conp_pair_compute: null atom array");
     for (int i = 0; i < n; ++i)
       if (at->type[i] < 0 || at->type[i] > env.ntypes) throw ConpError(CONP_ERR_ARG, "conp_pair_compute: atom type outside [0, ntypes]");
-    const double *dx, *dq;
+    const double *dx = nullptr, *dq = nullptr;              // NULL: the pair style stages at->x, at->q itself
     if (n == nall && n > 0 && at->nlocal == nlocal_cur && d_x.n >= (size_t)n * 3) {   // the atoms of the last post_neighbor: the handle's upload path (ghost_images)
       upload_xq(at);
       resident_step = -1;
       dx = d_x.p; dq = d_q.p;
-    } else {
-      sync();
-      d_pair_x.upload(at->x, (size_t)n * 3, stream); d_pair_q.upload(at->q, (size_t)n, stream);
-      dx = d_pair_x.p; dq = d_pair_q.p;
     }
-    d_pair_type.upload(at->type, (size_t)n, stream);
-    const size_t nf = f ? (size_t)n * 3 : 0, ne = eatom ? (size_t)n : 0, nv = vatom ? (size_t)n * 6 : 0;
-    const bool ev = eng || vir;
-    if (f) { d_pair_f.reserve(std::max<size_t>(nf, 1)); if (nf) HIP_TRY(hipMemsetAsync(d_pair_f.p, 0, nf * sizeof(double), stream)); }
-    if (eatom) d_pair_ea.reserve(std::max<size_t>(ne, 1));
-    if (vatom) d_pair_va.reserve(std::max<size_t>(nv, 1));
-    pair_enqueue(dx, dq, d_pair_type.p, at->nlocal, f ? d_pair_f.p : nullptr, ev ? d_pair_ev.p : nullptr, eatom ? d_pair_ea.p : nullptr,
-                 vatom ? d_pair_va.p : nullptr);
-    pair_out_h.resize(nf + ne + nv + 8);
-    double *h = pair_out_h.data();
-    if (nf) HIP_TRY(hipMemcpyAsync(h, d_pair_f.p, nf * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (ne) HIP_TRY(hipMemcpyAsync(h + nf, d_pair_ea.p, ne * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (nv) HIP_TRY(hipMemcpyAsync(h + nf + ne, d_pair_va.p, nv * sizeof(double), hipMemcpyDeviceToHost, stream));
-    if (ev) HIP_TRY(hipMemcpyAsync(h + nf + ne + nv, d_pair_ev.p, 8 * sizeof(double), hipMemcpyDeviceToHost, stream));
-    sync();
-    for (size_t k = 0; k < nf; ++k) f[k] += h[k];
-    if (ne) std::memcpy(eatom, h + nf, ne * sizeof(double));
-    if (nv) std::memcpy(vatom, h + nf + ne, nv * sizeof(double));
-    const double *e8 = h + nf + ne + nv;
-    if (eng) { eng[0] = e8[0]; eng[1] = e8[1]; }
-    if (vir) for (int k = 0; k < 6; ++k) vir[k] = e8[2 + k];
+    pair.compute_host(at, dx, dq, f, eng, vir, eatom, vatom);
   }
 
   void pair_compute_device(const double *dx, const double *dq, double *df, double *dev, double *dea, double *dva) {
     if (!dx || !dq) throw ConpError(CONP_ERR_ARG, "null argument");
-    pair_need_ready("conp_pair_compute_device");
-    if (nall <= 0 || pair_nall != nall || d_type.n < (size_t)nall)
+    pair.need_ready("conp_pair_compute_device");
+    if (nall <= 0 || pair.nall != nall || d_type.n < (size_t)nall)
       throw ConpError(CONP_ERR_STATE, "conp_pair_compute_device: the nall of conp_pair_set_list is not the atom count of the last "
                                       "post_neighbor (whose type array the entry reads)");
     if (!types_in_range)
       throw ConpError(CONP_ERR_ARG, "conp_pair_compute_device: an atom type of the last post_neighbor lies outside [0, ntypes]");
     if (!df && !dev && !dea && !dva) return;
-    pair_enqueue(dx, dq, d_type.p, nlocal_cur, df, dev, dea, dva);
+    pair.enqueue(dx, dq, d_type.p, nlocal_cur, df, dev, dea, dva);
   }
 
   // fix_conp.cpp:677-695 b_cal / update_bk
@@ -3277,13 +2744,13 @@ struct conp_fix {
 #define CONP_GUARD_BEGIN try {
 #define CONP_GUARD_END                                                   \
   }                                                                      \
-  catch (const ConpError &e) { g_last_error = e.what(); return e.code; } \
-  catch (const std::exception &e) { g_last_error = e.what(); return CONP_ERR_STATE; } \
+  catch (const ConpError &e) { last_error() = e.what(); return e.code; } \
+  catch (const std::exception &e) { last_error() = e.what(); return CONP_ERR_STATE; } \
   return CONP_OK;
 
 extern "C" {
 
-const char *conp_last_error(void) { return g_last_error.c_str(); }
+const char *conp_last_error(void) { return last_error().c_str(); }
 int conp_abi_version(void) { return CONP_ABI_VERSION; }
 
 // fix_conp.cpp:79-176.  arg[0..2] = ID group1 conp ; arg[3] Nevery ; arg[4] group2 ; arg[5] eta ; arg[6] DV ; arg[7] log
@@ -3372,6 +2839,7 @@ int conp_fix_create(const conp_fix_args *args, const conp_env *env, conp_fix **o
   std::unique_ptr<conp_fix> f(new conp_fix());
   f->args = *args;
   f->env = *env;
+  f->pair.env = {env->ntypes, env->newton_pair, env->g_ewald, env->qqrd2e};
   const size_t nc = (size_t)(env->ntypes + 1) * (env->ntypes + 1);
   f->cutsq_h.assign(env->cutsq, env->cutsq + nc);
   f->env.cutsq = nullptr;
@@ -3817,7 +3285,7 @@ int64_t conp_host_pair_rows(int which, const conp_neighlist *l, const conp_atoms
     else build_a_rows(v, at->nlocal, at->tag, at->echeck, x, newton != 0, r);
     cp(row_ptr, r.row_ptr); cp(ele_atom, r.ele_atom); cp(oth_atom, r.oth_atom); cp(col, r.col);
     return r.npairs();
-  } catch (const std::exception &e) { g_last_error = e.what(); return -1; }
+  } catch (const std::exception &e) { last_error() = e.what(); return -1; }
 }
 
 // ---- PPPM coupling beyond b, compute potential/atom --------------------------------------------------------------------------
@@ -4638,7 +4106,7 @@ int conp_pair_set_params(conp_fix *f, const conp_pair_params *p) {
   if (!f || !p) throw ConpError(CONP_ERR_ARG, "null argument");
   HIP_TRY(hipSetDevice(f->env.device));
   f->drop_graph();
-  f->pair_set_params(p);
+  f->pair.set_params(p);
   CONP_GUARD_END
 }
 
@@ -4647,7 +4115,7 @@ int conp_pair_set_list(conp_fix *f, const conp_neighlist *l, int nall) {
   if (!f || !l) throw ConpError(CONP_ERR_ARG, "null argument");
   HIP_TRY(hipSetDevice(f->env.device));
   f->drop_graph();
-  f->pair_set_list(l, nall);
+  f->pair.set_list(l, nall);
   CONP_GUARD_END
 }
 
@@ -4656,7 +4124,7 @@ int conp_pair_build_list_device(conp_fix *f, const double *d_x, const conp_pair_
   if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
   HIP_TRY(hipSetDevice(f->env.device));
   f->drop_graph();
-  f->pair_build_list(d_x, a);
+  f->pair.build_list(d_x, a);
   CONP_GUARD_END
 }
 
@@ -4664,7 +4132,7 @@ int conp_pair_list_moved_device(conp_fix *f, const double *d_x, double trigger, 
   CONP_GUARD_BEGIN
   if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
   f->drop_graph();
-  f->pair_list_moved(d_x, trigger, d_flag);
+  f->pair.list_moved(d_x, trigger, d_flag);
   CONP_GUARD_END
 }
 
@@ -4673,7 +4141,7 @@ int conp_pair_get_list(conp_fix *f, int *inum, int *nall, int64_t *nneigh, int *
   if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
   HIP_TRY(hipSetDevice(f->env.device));
   f->drop_graph();
-  f->pair_get_list(inum, nall, nneigh, ilist, numneigh, first, neigh);
+  f->pair.get_list(inum, nall, nneigh, ilist, numneigh, first, neigh);
   CONP_GUARD_END
 }
 
@@ -4683,7 +4151,7 @@ int conp_ghost_build_device(conp_fix *f, const double *d_x, const conp_ghost_bui
   if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
   HIP_TRY(hipSetDevice(f->env.device));
   f->drop_graph();
-  f->ghost_build(d_x, a, nghost);
+  f->ghost.build(d_x, a, nghost);
   CONP_GUARD_END
 }
 
@@ -4691,7 +4159,7 @@ int conp_ghost_fill_device(conp_fix *f, double *d_x, double *d_q) {
   CONP_GUARD_BEGIN
   if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
   f->drop_graph();
-  f->ghost_fill(d_x, d_q);
+  f->ghost.fill(d_x, d_q);
   CONP_GUARD_END
 }
 
@@ -4699,7 +4167,7 @@ int conp_ghost_fill_int_device(conp_fix *f, int *d_v, int width) {
   CONP_GUARD_BEGIN
   if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
   f->drop_graph();
-  f->ghost_fill_int(d_v, width);
+  f->ghost.fill_int(d_v, width);
   CONP_GUARD_END
 }
 
@@ -4707,7 +4175,7 @@ int conp_ghost_fold_device(conp_fix *f, double *d_v, int width) {
   CONP_GUARD_BEGIN
   if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
   f->drop_graph();
-  f->ghost_fold(d_v, width);
+  f->ghost.fold(d_v, width);
   CONP_GUARD_END
 }
 
@@ -4716,7 +4184,7 @@ int conp_ghost_get(conp_fix *f, int *nlocal, int *nghost, int *owner, int *img) 
   if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
   HIP_TRY(hipSetDevice(f->env.device));
   f->drop_graph();
-  f->ghost_get(nlocal, nghost, owner, img);
+  f->ghost.get(nlocal, nghost, owner, img);
   CONP_GUARD_END
 }
 
@@ -4725,7 +4193,7 @@ int conp_atoms_wrap_device(conp_fix *f, double *d_x, int nlocal, const double bo
   CONP_GUARD_BEGIN
   if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
   f->drop_graph();
-  f->atoms_wrap(d_x, nlocal, boxlo, boxhi, periodic, d_image);
+  atoms_wrap(*f, d_x, nlocal, boxlo, boxhi, periodic, d_image);
   CONP_GUARD_END
 }
 
@@ -4986,7 +4454,7 @@ int conp_debug_check_guards(void) {
   if (!GuardZones::on()) return -1;
   std::string what;
   const int bad = GuardZones::get().check(what);
-  if (bad) g_last_error = "guard zones damaged:" + what;
+  if (bad) last_error() = "guard zones damaged:" + what;
   return bad;
 }
 

@@ -1,0 +1,42 @@
+// struct PairStyle: lj/cut/coul/long pair forces over the pair style's own half list (conp_pairstyle.cpp, DESIGN.md sections 16, 17).
+#pragma once
+#include "conp_dev.hpp"
+#include "conp_kernels.h"
+
+namespace conp {
+
+struct PairStyle {
+  dev::DevCtx &ctx;                                                     // the handle's stream, wait and profiler
+  struct Env { int ntypes, newton_pair; double g_ewald, qqrd2e; } env{};      // what the pair style reads of conp_env
+  bool have_params = false, have_list = false;
+  int nall = 0, inum = 0, ntab = 0;
+  double cut_coul = 0.0, special_lj[4] = {1, 1, 1, 1}, special_coul[4] = {1, 1, 1, 1};
+  dev::DevBuf<double> d_tab, d_part, d_x, d_q, d_f, d_ev, d_ea, d_va;
+  dev::DevBuf<double4> d_xq;
+  dev::DevBuf<int> d_ilist, d_numneigh, d_first, d_neigh, d_type;
+  std::vector<double> out_h;
+  // the list built on the device (conp_neigh.hip): scratch of the build, and the owned coordinates it saw
+  bool list_built = false;
+  int build_nlocal = 0;
+  int64_t nneigh = 0;
+  double build_cutneigh = 0.0, cutsq_max = 0.0;
+  dev::DevBuf<double> d_nb_ext, d_nb_xbuild;
+  dev::DevBuf<double4> d_nb_sorted;
+  dev::DevBuf<int> d_nb_cell, d_nb_slot, d_nb_count, d_nb_start, d_nb_unsorted;
+  dev::DevBuf<long long> d_nb_total;
+
+  void set_params(const conp_pair_params *p);
+  void set_list(const conp_neighlist *l, int nall_);
+  void build_list(const double *dx, const conp_pair_build_args *a);
+  void list_moved(const double *dx, double trigger, int *dflag);
+  void get_list(int *inum_, int *nall_, int64_t *nneigh_, int *ilist, int *numneigh, int *first, int *neigh);
+  void need_ready(const char *who) const {
+    if (!have_params) throw dev::ConpError(CONP_ERR_STATE, std::string(who) + " before conp_pair_set_params");
+    if (!have_list) throw dev::ConpError(CONP_ERR_STATE, std::string(who) + " before conp_pair_set_list");
+  }
+  void enqueue(const double *dx, const double *dq, const int *dtype, int nlocal_, double *df, double *dev, double *dea, double *dva);
+  // dx, dq: device arrays of the call's atoms, or NULL (at->x, at->q are staged); downloads and adds into f, overwrites the rest
+  void compute_host(const conp_atoms *at, const double *dx, const double *dq, double *f, double *eng, double *vir, double *eatom, double *vatom);
+};
+
+}  // namespace conp

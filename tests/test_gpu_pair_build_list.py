@@ -243,7 +243,7 @@ def test_refusals():
     fx = FixConp(s)
     with pytest.raises(ConpError) as e:                                          # before conp_pair_set_params
         fx.pair_build_list_device(d_x.data_ptr(), at.nlocal, at.nall, inp.cutneigh)
-    assert e.value.code == -2 and "conp_pair_set_params" in str(e.value)
+    assert e.value.code == -2 and "conp_pair_build_list_device before conp_pair_set_params" in str(e.value)
     fx.close()
     fx, p = _handle(s, True)
     ok = lambda: fx.pair_build_list_device(d_x.data_ptr(), at.nlocal, at.nall, inp.cutneigh)
