@@ -4,6 +4,7 @@ re-neighbour with re-ordered atoms, and the electrode-row regrouping of LAMMPS h
 import numpy as np
 import pytest
 
+import ewald_shape_cases
 import oracle_py
 from conp_amd import capi, neighbor, systems
 
@@ -15,6 +16,9 @@ CASES = {
     "il_twolayer_noslab_zneutr": lambda: systems.deck("il_twolayer", "noslab_zneutr"),
     "headline": lambda: systems.synthetic_fast(),
 }
+# the boxes of tests/test_gpu_ewald_shapes.py: their k lists are pinned to the oracle's too
+CASES.update({f"ewald_shape_{name}_{mode}": (lambda name=name, mode=mode: ewald_shape_cases.system(name, mode))
+              for name, (make, modes) in ewald_shape_cases.BOXES.items() for mode in modes})
 
 
 @pytest.mark.parametrize("case", list(CASES))
