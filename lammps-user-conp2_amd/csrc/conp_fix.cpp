@@ -23,6 +23,7 @@
 #include "conp_dev.hpp"
 #include "conp_ghostmap.hpp"
 #include "conp_pairstyle.hpp"
+#include "conp_ewaldquery.hpp"
 
 using namespace conp::dev;
 namespace {
@@ -48,7 +49,7 @@ struct RankComm : conp::RankOps {
     for (int r = 0; r < nranks_; ++r) { cb[r] = (int64_t)counts[r] * sizeof(int); db[r] = (int64_t)displs[r] * sizeof(int); }
     check(c.allgatherv(c.ctx, send, (int64_t)n * sizeof(int), recv, cb.data(), db.data()), "allgatherv");
   }
-  void sum(double *b, int64_t n) { if (active() && n > 0) check(c.allreduce_sum(c.ctx, b, n), "allreduce_sum"); }
+  void sum(double *b, int64_t n) override { if (active() && n > 0) check(c.allreduce_sum(c.ctx, b, n), "allreduce_sum"); }
   // rank r contributes counts[r] doubles (w values per item); recv holds them rank-major
   void gatherv(const double *send, const std::vector<int> &items, int w, double *recv) {
     if (!active()) { std::memcpy(recv, send, (size_t)items[0] * w * sizeof(double)); return; }
@@ -147,28 +148,12 @@ struct conp_fix : DevCtx {
   DevBuf<double> d_pp_elyte, d_pp_xg, d_pp_qg;
   DevBuf<double> d_pp_ex, d_pp_ey, d_pp_kpart, d_pp_fo, d_pp_eo;      // conp_pppm_compute_forces: E_x, E_y bricks, the seven sums, outputs
   DevBuf<double> d_pp_v[6], d_pp_vo;           // ..._vatom: the six v_ab bricks (xx, yy, zz, xy, xz, yz), the per-atom virial (section 15)
-  DevBuf<double> d_ew_Gwf2, d_ew_vk, d_ew_v;   // conp_ewald_compute_forces_vatom: (c o w) o G, ew_vatom_kernel's parts, the per-atom virial
   DevBuf<int> d_pp_fidx;
   DevBuf<int> d_pp_iota;
-  // Ewald per-atom potential (conp_ewald_*, conp_compute_potential_atom on an Ewald handle; conp_potential.hip): the structure factor
-  // of every charged owned atom (all ranks' under decomposition) in buffers of its own -- the update's schedule, tables and G are
-  // not touched.  ew_g_valid: d_ew_Gwf holds w o G of the atoms a collective entry last saw; ew_u_valid: ew_u_h holds u_i of every
-  // owned atom (the per-atom entry's cache).  Both are dropped by every update, re-neighbour, set_matrix and k-table setup.
-  bool ew_g_valid = false, ew_u_valid = false;
-  int ew_tables_nb = 0;             // block width and plan the phase-table buffers were zeroed for (padding entries stay zero)
-  long ew_tables_gen = -1;
-  std::vector<double> ew_u_h;
-  DevBuf<double> d_ew_G, d_ew_Gp, d_ew_Gwf, d_ew_x, d_ew_q, d_ew_seeds, d_ew_Rp, d_ew_Tz, d_ew_bk, d_ew_g, d_ew_u;
-  DevBuf<double> d_ew_kv, d_ew_ev, d_ew_f, d_ew_e;      // conp_ewald_compute_forces: (ug, k) per listed k, the seven sums, outputs
-  long ew_kv_gen = -1;
-  DevBuf<double2> d_ew_Xe, d_ew_Ye;
-  DevBuf<int> d_ew_idx, d_ew_ctptr;
-  DevBuf<SkTile> d_ew_tiles;
-  // the device-resident force entries (conp_*_compute_forces_device): Q, Q2, M, M2 of the call's atoms with the
-  // workgroups' partial rows behind them; the plan whose tile lists d_ew_tiles / d_ew_ctptr hold; how many leading entries of
-  // d_pp_iota are the identity list 0, 1, 2, ... (pppm_gather_all, the only other writer, resets it)
+  // the device-resident PPPM force entry (conp_pppm_compute_forces_device): Q, Q2, M, M2 of the call's atoms
+  // with the workgroups' partial rows behind them; how many leading entries of d_pp_iota are the identity list 0, 1, 2, ...
+  // (pppm_gather_all, the only other writer, resets it)
   DevBuf<double> d_kf_sums;
-  long ew_tiles_gen = -1;
   int pp_iota_n = 0;
   double Btime = 0., Ctime = 0., Ktime = 0.;      // accumulated like :549-552 (seconds)
   hipEvent_t ev_b[3] = {nullptr, nullptr, nullptr};
@@ -253,6 +238,8 @@ struct conp_fix : DevCtx {
     return rp;
   }
 
+  // what the k-space steps shared with EwaldQuery (conp_kspace_common.hpp) read of env
+  KspaceEnv kspace_env() const { return {env.g_ewald, env.qqrd2e, env.slabflag, env.zprd, env.slab_volfactor}; }
   // ---------------------------------------------------------------------------------------------
   void init_device() {
     int ndev = 0;
@@ -351,6 +338,7 @@ struct conp_fix : DevCtx {
              env.qqrd2e, env.dielectric);
     plan.build(kt);
     ++plan_gen;
+    ew.replan();
     // padding planar rows point at the all-zero X row kxmax+1 (they then contribute nothing)
     // (96 more than the plan's row tiles hold: a band of sk_gemm may run up to five row fragments past the last planar vector)
     std::vector<int> ikx(plan.n_row_tiles * 64 + 96, plan.kxmax + 1), iky(plan.n_row_tiles * 64 + 96, 0), sgn(plan.n_row_tiles * 64 + 96, 1);
@@ -408,7 +396,6 @@ struct conp_fix : DevCtx {
     d_ct_ptr.upload(ct_ptr_h, stream);
     sync();
     kspace_ready = true;
-    ew_g_valid = ew_u_valid = false;
     // the electrode tables, the z-class tables and sk_gemm's projection block (d_skproj: raw pointers into d_wfull / d_TzcT, the
     // plan's C_pad) belong to the plan that was just replaced: whoever needs them next rebuilds them (km_a_read)
     tables_current = false;
@@ -550,7 +537,7 @@ struct conp_fix : DevCtx {
     if (!have_blist) throw ConpError(CONP_ERR_STATE, "post_neighbor: no neighbor list (init_list not called)");
     resident_step = -1;
     pp_elyte_valid = pp_u_valid = false;
-    ew_g_valid = ew_u_valid = false;
+    ew.invalidate();
     static const bool tren = getenv("CONP_TIME_REN") != nullptr;
     auto tm0 = std::chrono::steady_clock::now();
     auto mark = [&](const char *what) {
@@ -1934,7 +1921,7 @@ struct conp_fix : DevCtx {
   void b_cal_device(const double *dx, const double *dq, bool coulyes, bool timed = false) {
     const int ne = idx.elenum_all;
     pp_elyte_valid = pp_u_valid = false;          // positions / charges may have changed: the mesh caches are this update's or nobody's
-    ew_g_valid = ew_u_valid = false;              // (so are the Ewald per-atom potentials)
+    ew.invalidate();                              // (so are the Ewald per-atom potentials)
     const double *ex = decomposed ? d_xg.p : dx, *eq = decomposed ? d_qg.p : dq;
     const int *eidx = decomposed ? d_iota.p : d_elyte_idx.p;
     if (!kspace_ready || !tables_current || d_b == nullptr)
@@ -2406,9 +2393,11 @@ struct conp_fix : DevCtx {
     HIP_TRY(hipGetLastError());
   }
 
-  // ---- the pair style with its half list (conp_pairstyle.cpp, DESIGN.md sections 16, 17) and the ghost map (conp_ghostmap.cpp, 18) ----
+  // ---- the pair style with its half list (conp_pairstyle.cpp, DESIGN.md sections 16, 17), the ghost map (conp_ghostmap.cpp, 18) and
+  // the exact-Ewald query entries (conp_ewaldquery.cpp, sections 11, 12, 14, 15) ----
   PairStyle pair{*this};
   GhostMap ghost{*this};
+  EwaldQuery ew{*this, kt, plan, dplan, tiles_h, ct_ptr_h, d_sf_row_a, d_sf_col_c, d_k_sign};
   bool types_in_range = false;                   // every atoms->type of the last (setup_)post_neighbor lies in [0, ntypes]
 
   // ---- the fix's re-neighbouring on the device (conp_reneigh.hip): Fix::post_neighbor without host arrays ------
@@ -2464,7 +2453,7 @@ struct conp_fix : DevCtx {
     post_neighbor_device_check(dx, dq);
     resident_step = -1;
     pp_elyte_valid = pp_u_valid = false;
-    ew_g_valid = ew_u_valid = false;
+    ew.invalidate();
     const int nloc = nlocal_cur, ng = ghost.nghost, na = nloc + ng, ne = idx.elenum_all;
     sync();                                       // no kernel may be reading the tables that are replaced
     ren_begin(sizeof(int) * (8 * (size_t)std::max(ne, 64) + (size_t)idx.elytenum / 4 + 65536) + 64 * 32);
@@ -2840,10 +2829,12 @@ int conp_fix_create(const conp_fix_args *args, const conp_env *env, conp_fix **o
   f->args = *args;
   f->env = *env;
   f->pair.env = {env->ntypes, env->newton_pair, env->g_ewald, env->qqrd2e};
+  f->ew.env = f->kspace_env();
   const size_t nc = (size_t)(env->ntypes + 1) * (env->ntypes + 1);
   f->cutsq_h.assign(env->cutsq, env->cutsq + nc);
   f->env.cutsq = nullptr;
   f->init_device();
+  f->ew.num_cus = f->num_cus;
   // `himem` (fix_conp.cpp:168 -> lowmemflag = false) makes KSpaceModuleEwald keep pre-scaled csk / snk[Ne][K] tables instead of
   // expanding them per atom (km_ewald.cpp:263-268, 498-506): a memory / time trade of the CPU provider.  This provider has ONE
   // formulation (phases regenerated on the matrix cores, nothing of size Ne x K stored), so the keyword selects nothing -- said
@@ -3117,7 +3108,7 @@ int conp_fix_set_matrix(conp_fix *f, const double *aaa, int runstage) {
   HIP_TRY(hipMemcpyAsync(f->d_A.p, aaa, ne * ne * sizeof(double), hipMemcpyHostToDevice, f->stream));
   f->sync();
   f->runstage = runstage;
-  f->ew_g_valid = f->ew_u_valid = false;
+  f->ew.invalidate();
   CONP_GUARD_END
 }
 
@@ -3290,7 +3281,6 @@ int64_t conp_host_pair_rows(int which, const conp_neighlist *l, const conp_atoms
 
 // ---- PPPM coupling beyond b, compute potential/atom --------------------------------------------------------------------------
 namespace {
-constexpr double MY_PI = 3.14159265358979323846, MY_PIS = 1.77245385090551602729;
 void need_pppm(conp_fix *f) {
   if (!f->args.pppm || f->dpppm.nfft <= 0)
     throw ConpError(CONP_ERR_STATE, "Compute requires a compatible KSpace provider like pppm/conp");   // compute_potential_atom.cpp:110
@@ -3382,163 +3372,11 @@ void need_ewald(conp_fix *f) {
                                     "conp_pppm_compute_group_potential / conp_pppm_compute_particle_potential");
   if (!f->kspace_ready) throw ConpError(CONP_ERR_STATE, "conp_ewald_*: no k-space tables yet (setup_post_neighbor or conp_km_conp_setup)");
 }
-// Atoms per block of phase tables: Rp, Tz, seeds and axis tables of a block stay within EW_TABLES (the 16384 / 262144 box takes
-// blocks of a few hundred atoms instead of a 2-GB table over all of them); the split slices of G within EW_SLICES.  With G and
-// w o G (R_pad C_pad doubles each: 5 MB at the headline size) that bounds the scratch of these entries.
-constexpr size_t EW_TABLES = (size_t)80 << 20, EW_SLICES = (size_t)40 << 20;
-int ew_block(const conp_fix *f, int n) {
-  const KPlan &pl = f->plan;
-  const size_t per_atom = ((size_t)pl.R_pad + pl.C_pad + 6 + 2 * ((size_t)pl.kxmax + 2) + 2 * ((size_t)pl.kymax + 1)) * sizeof(double);
-  int cap = (int)std::max<size_t>(64, std::min<size_t>(8192, EW_TABLES / per_atom / 64 * 64));
-  if (debug_ew_block() > 0) cap = debug_ew_block();      // test hook (conp_debug_set_ew_block): several blocks on a deck
-  return std::min(cap, std::max(64, (n + 63) / 64 * 64));
-}
-void ew_reserve(conp_fix *f, int nb_pad) {
-  const KPlan &pl = f->plan;
-  const size_t nrp = (size_t)pl.R_pad * nb_pad, ntz = (size_t)pl.C_pad * nb_pad;
-  const size_t nxe = (size_t)(pl.kxmax + 2) * nb_pad, nye = (size_t)(pl.kymax + 1) * nb_pad;
-  const bool grew = nrp > f->d_ew_Rp.n || ntz > f->d_ew_Tz.n || nxe > f->d_ew_Xe.n || nye > f->d_ew_Ye.n;
-  f->d_ew_Rp.reserve(nrp); f->d_ew_Tz.reserve(ntz); f->d_ew_Xe.reserve(nxe); f->d_ew_Ye.reserve(nye);
-  f->d_ew_seeds.reserve((size_t)6 * nb_pad);
-  // padding rows / columns (planar vectors past np, the kz = 0 sin column, columns past nz) are never written: zero them once per
-  // layout (block width, plan); afterwards every block overwrites the same entries
-  if (!grew && f->ew_tables_nb == nb_pad && f->ew_tables_gen == f->plan_gen) return;
-  HIP_TRY(hipMemsetAsync(f->d_ew_Rp.p, 0, nrp * sizeof(double), f->stream));
-  HIP_TRY(hipMemsetAsync(f->d_ew_Tz.p, 0, ntz * sizeof(double), f->stream));
-  HIP_TRY(hipMemsetAsync(f->d_ew_Xe.p, 0, nxe * sizeof(double2), f->stream));
-  HIP_TRY(hipMemsetAsync(f->d_ew_Ye.p, 0, nye * sizeof(double2), f->stream));
-  f->ew_tables_nb = nb_pad; f->ew_tables_gen = f->plan_gen;
-}
-// phase tables of the nb atoms at xb (device, [nb][3]), nb_pad columns (stale columns >= nb of an earlier block stay finite)
-void ew_tables_at(conp_fix *f, const double *xb, int nb, int nb_pad) {
-  launch_ew_seeds(f->stream, nb, xb, f->kt.unitk[0], f->kt.unitk[1], f->kt.unitk[2], f->d_ew_seeds.p);
-  launch_ele_tables(f->stream, f->dplan, f->plan.kzt, nb, nb_pad, f->d_ew_seeds.p, f->d_ew_Xe.p, f->d_ew_Ye.p, f->d_ew_Tz.p, f->d_ew_Rp.p);
-}
-// ... of atoms [b0, b0 + nb) of the compact list d_ew_x
-void ew_tables(conp_fix *f, int b0, int nb, int nb_pad) { ew_tables_at(f, f->d_ew_x.p + 3 * (size_t)b0, nb, nb_pad); }
-
-// ---- the steps the k-space potential and force entries share (DESIGN.md sections 11-15) ----
+// the handle's check -- before anything is uploaded -- then w o G of the atoms of `at` (EwaldQuery::structure_factor)
 // (static: the unnamed namespace alone does not keep a name inside extern "C" out of the library's dynamic symbols)
-// split the atoms of a block over slices of G so that the launch keeps ~6 workgroups on every CU (the LDS limit of ew_sk_kernel;
-// each waits on its chunk loads) -- every split owns a slice: no atomics
-static int ew_nsplit(const conp_fix *f, int nb_pad) {
-  const KPlan &pl = f->plan;
-  const int wgs = std::max(1, pl.C_pad / 64 * pl.n_row_tiles);
-  int nsplit = std::max(1, std::min({6 * f->num_cus / wgs + 1, 32, nb_pad / 64}));
-  while (nsplit > 1 && (size_t)nsplit * pl.R_pad * pl.C_pad * sizeof(double) > EW_SLICES) --nsplit;
-  return nsplit;
-}
-// S of the n atoms at x (device, [n][3]) with the charges q (device, zeros behind n up to whole blocks) into d_ew_G: block by block
-// the phase tables and ew_sk_kernel into the slices, then the slices' sum.  After ew_reserve(f, nb_pad).
-static void ew_build_S(conp_fix *f, const double *x, const double *q, int n, int nb_pad) {
-  const size_t gsz = (size_t)f->plan.R_pad * f->plan.C_pad;
-  const int nsplit = ew_nsplit(f, nb_pad);
-  f->d_ew_Gp.reserve(gsz * nsplit); f->d_ew_G.reserve(gsz); f->d_ew_Gwf.reserve(gsz);
-  HIP_TRY(hipMemsetAsync(f->d_ew_Gp.p, 0, gsz * nsplit * sizeof(double), f->stream));
-  for (int b0 = 0; b0 < n; b0 += nb_pad) {
-    ew_tables_at(f, x + 3 * (size_t)b0, std::min(nb_pad, n - b0), nb_pad);
-    launch_ew_sk(f->stream, f->dplan, nb_pad, nsplit, f->d_ew_Rp.p, f->d_ew_Tz.p, q + b0, f->d_ew_Gp.p);
-  }
-  launch_ew_sk_sum(f->stream, f->dplan, nsplit, f->d_ew_Gp.p, f->d_ew_G.p);
-}
-// once per plan: (ug, kx, ky, kz) of the reference's k list into d_ew_kv; the tile lists of the projection into d_ew_tiles / d_ew_ctptr
-static void ew_kv_ready(conp_fix *f) {
-  if (f->ew_kv_gen != f->plan_gen) {
-    const KTables &kt = f->kt;
-    const int K = kt.kcount;
-    std::vector<double> kv((size_t)4 * K);
-    for (int k = 0; k < K; ++k) {
-      kv[k] = kt.ug[k];
-      kv[(size_t)K + k] = kt.unitk[0] * kt.kxvecs[k]; kv[2 * (size_t)K + k] = kt.unitk[1] * kt.kyvecs[k];
-      kv[3 * (size_t)K + k] = kt.unitk[2] * kt.kzvecs[k];
-    }
-    f->d_ew_kv.upload(kv, f->stream);
-    f->sync();                     // (kv goes out of scope)
-    f->ew_kv_gen = f->plan_gen;
-  }
-}
-static void ew_tiles_ready(conp_fix *f) {
-  if (f->ew_tiles_gen != f->plan_gen) {
-    f->d_ew_tiles.upload(f->tiles_h, f->stream); f->d_ew_ctptr.upload(f->ct_ptr_h, f->stream);
-    f->sync();
-    f->ew_tiles_gen = f->plan_gen;
-  }
-}
-// the seven sums (sum_k ug |S_k|^2, the six virial sums) of d_ew_G into d_ew_ev[0..6]
-static void ew_energy_virial(conp_fix *f) {
-  ew_kv_ready(f);
-  const int K = f->kt.kcount;
-  f->d_ew_ev.reserve((size_t)7 * (ew_energy_virial_workgroups(K) + 1));
-  launch_ew_energy_virial(f->stream, K, f->plan.C_pad, KPlan::PT, f->d_sf_row_a.p, f->d_sf_col_c.p, f->d_k_sign.p, f->d_ew_kv.p,
-                          f->env.g_ewald, f->d_ew_G.p, f->d_ew_ev.p + 7, f->d_ew_ev.p);
-}
-// x, q of the owned atoms idx, padded to whole blocks (padding atoms carry no charge), and idx itself into d_ew_x, d_ew_q, d_ew_idx.
-// The copies are asynchronous: they are staged in h, which the caller keeps until it has synchronised.
-struct EwStaged { std::vector<double> x, q; };
-static void ew_upload_compact(conp_fix *f, const conp_atoms *at, const std::vector<int> &idx, int nb_pad, EwStaged &h) {
-  const int n = (int)idx.size(), ntot = (n + nb_pad - 1) / nb_pad * nb_pad;
-  h.x.assign(3 * (size_t)ntot, 0.0); h.q.assign(ntot, 0.0);
-  for (int k = 0; k < n; ++k) {
-    const int i = idx[k];
-    for (int c = 0; c < 3; ++c) h.x[3 * (size_t)k + c] = at->x[3 * (size_t)i + c];
-    h.q[k] = at->q[i];
-  }
-  ew_reserve(f, nb_pad);
-  f->d_ew_x.upload(h.x, f->stream); f->d_ew_q.upload(h.q, f->stream); f->d_ew_idx.upload(idx, f->stream);
-}
-// The block loop of the force and per-atom virial kernels over n atoms at x (device) with the charges d_ew_q, from d_ew_Gwf / d_ew_G.
-// Host path: x = d_ew_x, idx = d_ew_idx (the outputs are indexed through it, o is complete), every block's tables are rebuilt.
-// Device path: x = the caller's array, idx = NULL (block b0 writes the atoms [b0, b0 + nb) of the caller's outputs; Q, M, M2 come
-// from d_kf_sums); one block: ew_build_S's tables are still there.  fo, eo, vo NULL: that output is not formed.
-static void ew_force_blocks(conp_fix *f, int n, int nb_pad, const double *x, const int *idx, const EwForceOut &o, double *fo, double *eo,
-                            double *vo) {
-  const KPlan &pl = f->plan;
-  const double *uk = f->kt.unitk, *q = f->d_ew_q.p;
-  f->d_ew_bk.reserve((size_t)16 * nb_pad);
-  if (vo) {
-    f->d_ew_Gwf2.reserve((size_t)pl.R_pad * pl.C_pad); f->d_ew_vk.reserve((size_t)24 * nb_pad);
-    launch_ew_gw2(f->stream, f->dplan, pl.kzt, uk[0], uk[1], uk[2], f->env.g_ewald, f->d_ew_G.p, f->d_ew_Gwf2.p);
-  }
-  for (int b0 = 0; b0 < n; b0 += nb_pad) {
-    const int nb = std::min(nb_pad, n - b0);
-    const double *xb = x + 3 * (size_t)b0;
-    if (idx || n > nb_pad) ew_tables_at(f, xb, nb, nb_pad);
-    launch_ew_force(f->stream, f->dplan, pl.kzt, uk[0], uk[1], uk[2], nb_pad, f->d_ew_ctptr.p, f->d_ew_tiles.p, f->d_ew_Gwf.p,
-                    f->d_ew_Rp.p, f->d_ew_Tz.p, f->d_ew_bk.p);
-    if (idx) launch_ew_force_out(f->stream, nb, nb_pad, f->d_ew_bk.p, idx + b0, q + b0, xb, o, fo, eo);
-    else if (fo || eo) launch_ew_force_out_device(f->stream, nb, nb_pad, f->d_ew_bk.p, q + b0, xb, o, f->d_kf_sums.p, b0, fo, eo);
-    if (!vo) continue;
-    launch_ew_vatom(f->stream, f->dplan, pl.kzt, uk[0], uk[1], uk[2], nb_pad, f->d_ew_ctptr.p, f->d_ew_tiles.p, f->d_ew_Gwf2.p,
-                    f->d_ew_Rp.p, f->d_ew_Tz.p, f->d_ew_vk.p);
-    if (idx) launch_ew_vatom_out(f->stream, nb, nb_pad, f->d_ew_bk.p, f->d_ew_vk.p, idx + b0, q + b0, f->env.qqrd2e, vo);
-    else launch_ew_vatom_out_device(f->stream, nb, nb_pad, f->d_ew_bk.p, f->d_ew_vk.p, q + b0, f->env.qqrd2e, b0, vo);
-  }
-}
-// Q, Q2, M, M2 of the n atoms of the device arrays into d_kf_sums[0..3]
-void kspace_four_sums(conp_fix *f, int n, const double *dx, const double *dq) {
-  f->d_kf_sums.reserve((size_t)4 * (kspace_four_sums_workgroups(n) + 1));
-  launch_kspace_four_sums(f->stream, n, dx, dq, f->d_kf_sums.p + 4, f->d_kf_sums.p);
-}
-KspaceFinish kspace_finish_args(const conp_fix *f, double V, double L) {
-  const double g = f->env.g_ewald;
-  KspaceFinish a{};
-  a.qs = f->env.qqrd2e; a.g_pis = g / MY_PIS; a.qcoef = 0.5 * MY_PI / (g * g * V);
-  a.slab = f->env.slabflag ? 1 : 0; a.slab_pref = 2.0 * MY_PI / V; a.L2_12 = L * L / 12.0;
-  return a;
-}
-// The parameter block of the force-output kernels.  four == NULL (the device entries): Q, M, M2 stay zero and ecoef lacks its
-// factor Q -- kspace_out_from_sums completes the block on the device.  The host entries hand in their four sums.
-EwForceOut kspace_out_args(const conp_fix *f, double V, double L, const double *four) {
-  const double g = f->env.g_ewald;
-  EwForceOut o{};
-  o.qs = f->env.qqrd2e; o.selfc = 2.0 * g / MY_PIS; o.ecoef = 0.5 * MY_PI / (g * g * V);
-  o.slab = f->env.slabflag ? 1 : 0;
-  o.fz_pref = -4.0 * MY_PI / V; o.e_pref = 2.0 * MY_PI / V; o.L2_12 = L * L / 12.0;
-  if (four) {
-    const double Q = four[0];
-    o.Q = Q; o.M = four[2]; o.M2 = four[3]; o.ecoef = 0.5 * MY_PI * Q / (g * g * V);
-  }
-  return o;
+static void ewald_structure_factor(conp_fix *f, const conp_atoms *at) {
+  if (at->nlocal + at->nghost != f->nall) throw ConpError(CONP_ERR_STATE, "atom count changed without post_neighbor");
+  f->ew.structure_factor(at);
 }
 // the mesh's box: L = the slab-extended z period, V, the unit wave vectors
 struct PppmGeom { double L, V, uk[3]; };
@@ -3569,155 +3407,12 @@ static void pppm_mesh_forces(conp_fix *f, const PppmGeom &gm, bool fields, bool 
                      fields ? f->d_pp_ey.p : nullptr, f->d_pp_kpart.p + 7, f->d_pp_kpart.p);
   f->prof.end(f->stream);
   f->pp_im_clean = false;
-  if (d_ev) launch_kspace_finish(f->stream, kspace_finish_args(f, gm.V, gm.L), f->d_pp_kpart.p, f->d_kf_sums.p, d_ev);
+  if (d_ev) launch_kspace_finish(f->stream, kspace_finish_args(f->kspace_env(), gm.V, gm.L), f->d_pp_kpart.p, f->d_kf_sums.p, d_ev);
   if (!want_u) return;
   f->prof.begin("pppm_f_backward", f->stream);
   launch_pppm_backward(f->stream, f->dpppm, f->d_pp_re.p, f->d_pp_im.p);
   if (fields) launch_pppm_backward(f->stream, f->dpppm, f->d_pp_ex.p, f->d_pp_ey.p);
   f->prof.end(f->stream);
-}
-// A running sum that keeps its rounding errors (Neumaier).  The host entries add the atoms one by one: 66 000 sites that share four
-// charge values lose 1e-8 of Q in a plain loop (the partial sum climbs to 1e4 and every addition rounds the same way), which the
-// Q L^2 / 12 and Q z^2 slab terms carry into the energy and the per-atom potential; the device entries' tree sums do not.
-struct CompSum {
-  double s = 0.0, c = 0.0;
-  void add(double v) {
-    const double t = s + v;
-    c += std::fabs(s) >= std::fabs(v) ? (s - t) + v : (v - t) + s;
-    s = t;
-  }
-  double value() const { return s + c; }
-};
-// the owned atoms that carry charge into idx; Q, Q2, M, M2 of them (this rank's) into four
-static void charged_owned(const conp_atoms *at, std::vector<int> &idx, double four[4]) {
-  CompSum acc[4];
-  for (int i = 0; i < at->nlocal; ++i) {
-    const double q = at->q[i], z = at->x[3 * (size_t)i + 2];
-    if (q == 0) continue;
-    idx.push_back(i);
-    acc[0].add(q); acc[1].add(q * q); acc[2].add(q * z); acc[3].add(q * z * z);
-  }
-  for (int c = 0; c < 4; ++c) four[c] = acc[c].value();
-}
-// energy from the first of the seven k-space sums and the four sums: what kspace_finish_kernel evaluates for the device entries
-static double kspace_energy(const conp_fix *f, double s0, double Q, double Q2, double M, double M2, double V, double L) {
-  const double g = f->env.g_ewald;
-  double e = s0 - g * Q2 / MY_PIS - 0.5 * MY_PI * Q * Q / (g * g * V);
-  if (f->env.slabflag) e += 2.0 * MY_PI * (M * M - Q * M2 - Q * Q * L * L / 12.0) / V;
-  return f->env.qqrd2e * e;
-}
-// The per-atom outputs of a host entry: d_f [nlocal][3] is ADDED to fout, d_e and d_v overwrite eatom and vatom, at the n atoms idx.
-// A NULL device pointer: not formed, nothing copied; a NULL host pointer: not wanted.  Synchronises.
-static void download_scatter(conp_fix *f, int nlocal, const std::vector<int> &idx, int n, const double *d_f, const double *d_e,
-                             const double *d_v, double *fout, double *eatom, double *vatom) {
-  std::vector<double> hf, he, hv;
-  const auto download = [&](const double *d, size_t count, std::vector<double> &h) {
-    if (!d) return;
-    h.resize(count);
-    HIP_TRY(hipMemcpyAsync(h.data(), d, count * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-  };
-  download(d_v, 6 * (size_t)nlocal, hv); download(d_f, 3 * (size_t)nlocal, hf); download(d_e, nlocal, he);
-  HIP_TRY(hipGetLastError());
-  f->sync();
-  for (int k = 0; k < n; ++k) {
-    const int i = idx[k];
-    if (fout && d_f) for (int c = 0; c < 3; ++c) fout[3 * (size_t)i + c] += hf[3 * (size_t)i + c];
-    if (eatom && d_e) eatom[i] = he[i];
-    if (vatom && d_v) for (int c = 0; c < 6; ++c) vatom[6 * (size_t)i + c] = hv[6 * (size_t)i + c];
-  }
-}
-
-// w o G of every charged owned atom at the positions and charges of `at` (not the update's cached arrays) into d_ew_Gwf.
-// Decomposed ranks: each rank contracts its own atoms, G is summed through the host's all-reduce (km_ewald.cpp:784-785) --
-// COLLECTIVE.  Replicated-atom handles (several ranks without conp_fix_set_comm) hold every atom on every rank: no collective.
-void ewald_structure_factor(conp_fix *f, const conp_atoms *at) {
-  if (at->nlocal + at->nghost != f->nall) throw ConpError(CONP_ERR_STATE, "atom count changed without post_neighbor");
-  // (not ew_upload_compact: no atom at all still takes one block of padding here, and no index list is wanted)
-  std::vector<double> xs, qs;
-  for (int i = 0; i < at->nlocal; ++i) {
-    if (at->q[i] == 0) continue;
-    xs.insert(xs.end(), at->x + 3 * (size_t)i, at->x + 3 * (size_t)i + 3);
-    qs.push_back(at->q[i]);
-  }
-  const int n = (int)qs.size();
-  const int nb_pad = ew_block(f, n);
-  const int ntot = std::max(nb_pad, (n + nb_pad - 1) / nb_pad * nb_pad);
-  xs.resize(3 * (size_t)ntot, 0.0); qs.resize(ntot, 0.0);     // padding atoms carry no charge
-  ew_reserve(f, nb_pad);
-  f->d_ew_x.upload(xs, f->stream); f->d_ew_q.upload(qs, f->stream);
-  ew_build_S(f, f->d_ew_x.p, f->d_ew_q.p, n, nb_pad);
-  if (f->decomposed) {
-    const size_t gsz = (size_t)f->plan.R_pad * f->plan.C_pad;
-    std::vector<double> g(gsz);
-    HIP_TRY(hipMemcpyAsync(g.data(), f->d_ew_G.p, gsz * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-    f->sync();
-    f->rc.sum(g.data(), (int64_t)gsz);
-    HIP_TRY(hipMemcpyAsync(f->d_ew_G.p, g.data(), gsz * sizeof(double), hipMemcpyHostToDevice, f->stream));
-    f->sync();
-  }
-  launch_ew_gw(f->stream, f->dplan, f->d_ew_G.p, f->d_ew_Gwf.p);
-  HIP_TRY(hipGetLastError());
-  f->sync();                       // (the host vectors go out of scope)
-  f->ew_g_valid = true; f->ew_u_valid = false;
-}
-// g_i and u_i = g_i + 2 g_ewald q_i / sqrt(pi) of the owned atoms idx (local indices), at their positions in `at`, from d_ew_Gwf:
-// block by block, the block's phase tables, b_project_kernel, ew_out_kernel.  Rank-local.  g, u: [nlocal], only idx written.
-void ewald_project(conp_fix *f, const conp_atoms *at, const std::vector<int> &idx, double *g, double *u) {
-  const int n = (int)idx.size();
-  if (n == 0) return;
-  const int nb_pad = ew_block(f, n);
-  EwStaged staged;
-  ew_upload_compact(f, at, idx, nb_pad, staged);
-  ew_tiles_ready(f);
-  f->d_ew_bk.reserve((size_t)4 * nb_pad);
-  f->d_ew_g.reserve(at->nlocal); f->d_ew_u.reserve(at->nlocal);
-  const double selfc = 2.0 * f->env.g_ewald / MY_PIS;
-  for (int b0 = 0; b0 < n; b0 += nb_pad) {
-    const int nb = std::min(nb_pad, n - b0);
-    ew_tables(f, b0, nb, nb_pad);
-    launch_b_project(f->stream, f->dplan, nb_pad, f->d_ew_ctptr.p, f->d_ew_tiles.p, f->d_ew_Gwf.p, f->d_ew_Rp.p, f->d_ew_Tz.p, f->d_ew_bk.p);
-    launch_ew_out(f->stream, nb, nb_pad, f->d_ew_bk.p, f->d_ew_idx.p + b0, f->d_ew_q.p + b0, selfc, f->d_ew_g.p, f->d_ew_u.p);
-  }
-  std::vector<double> hg(at->nlocal), hu(at->nlocal);
-  HIP_TRY(hipMemcpyAsync(hg.data(), f->d_ew_g.p, (size_t)at->nlocal * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-  HIP_TRY(hipMemcpyAsync(hu.data(), f->d_ew_u.p, (size_t)at->nlocal * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-  HIP_TRY(hipGetLastError());
-  f->sync();
-  for (int i : idx) { if (g) g[i] = hg[i]; if (u) u[i] = hu[i]; }
-}
-// ---- exact Ewald forces, energy, virial ----
-// f_i += qqrd2e q_i grad g_i (+ slab) on every charged owned atom, from d_ew_Gwf at the atoms' positions in `at`: ewald_project's
-// blocking with ew_force_kernel in b_project_kernel's place; energy and virial from d_ew_G.  The sums of q, q^2, q z, q z^2 over the
-// owned atoms are all-reduced under decomposed ranks (COLLECTIVE there); S itself is the caller's business (ew_g_valid).
-// vatom: [nlocal][6], overwritten: the per-atom virial.
-void ewald_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy, double *virial, double *eatom, double *vatom) {
-  const double V = f->kt.volume, L = f->env.zprd * f->env.slab_volfactor;
-  std::vector<int> idx;
-  double four[4];                                     // Q, Q2, M, M2
-  charged_owned(at, idx, four);
-  if (f->decomposed) f->rc.sum(four, 4);
-  if (energy || virial) {
-    ew_energy_virial(f);
-    double s7[7];
-    HIP_TRY(hipMemcpyAsync(s7, f->d_ew_ev.p, 7 * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-    HIP_TRY(hipGetLastError());
-    f->sync();
-    if (energy) *energy = kspace_energy(f, s7[0], four[0], four[1], four[2], four[3], V, L);
-    if (virial) for (int c = 0; c < 6; ++c) virial[c] = f->env.qqrd2e * s7[1 + c];
-  }
-  if (eatom) std::fill(eatom, eatom + at->nlocal, 0.0);
-  if (vatom) std::fill(vatom, vatom + 6 * (size_t)at->nlocal, 0.0);
-  const int n = (int)idx.size();
-  if (n == 0 || (!fout && !eatom && !vatom)) return;
-  const int nb_pad = ew_block(f, n);
-  EwStaged staged;
-  ew_upload_compact(f, at, idx, nb_pad, staged);
-  ew_tiles_ready(f);
-  f->d_ew_f.reserve(3 * (size_t)at->nlocal); f->d_ew_e.reserve(at->nlocal);
-  if (vatom) f->d_ew_v.reserve(6 * (size_t)at->nlocal);
-  double *const d_v = vatom ? f->d_ew_v.p : nullptr;
-  ew_force_blocks(f, n, nb_pad, f->d_ew_x.p, f->d_ew_idx.p, kspace_out_args(f, V, L, four), f->d_ew_f.p, f->d_ew_e.p, d_v);
-  download_scatter(f, at->nlocal, idx, n, f->d_ew_f.p, f->d_ew_e.p, d_v, fout, eatom, vatom);
 }
 // ---- PPPM forces, energy, virial ----
 // PPPM::compute with ik differentiation on the handle's mesh, at the positions and charges of `at`: the brick of every charged atom is
@@ -3762,13 +3457,13 @@ void pppm_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy
     if (eatom) f->d_pp_eo.reserve(at->nlocal);
     f->prof.begin("pppm_f_gather", f->stream);
     launch_pppm_force_gather(f->stream, f->dpppm, n, f->d_pp_fidx.p, f->d_x.p, f->d_q.p, fout ? f->d_pp_ex.p : nullptr, f->d_pp_ey.p,
-                             f->d_pp_im.p, f->d_pp_re.p, kspace_out_args(f, gm.V, gm.L, four), fout ? f->d_pp_fo.p : nullptr,
+                             f->d_pp_im.p, f->d_pp_re.p, kspace_out_args(f->kspace_env(), gm.V, gm.L, four), fout ? f->d_pp_fo.p : nullptr,
                              eatom ? f->d_pp_eo.p : nullptr);
     f->prof.end(f->stream);
   }
   if (eatom) std::fill(eatom, eatom + at->nlocal, 0.0);
   if (vatom) std::fill(vatom, vatom + 6 * (size_t)at->nlocal, 0.0);
-  download_scatter(f, at->nlocal, idx, n, per_atom && fout ? f->d_pp_fo.p : nullptr, per_atom && eatom ? f->d_pp_eo.p : nullptr,
+  download_scatter(*f, at->nlocal, idx, n, per_atom && fout ? f->d_pp_fo.p : nullptr, per_atom && eatom ? f->d_pp_eo.p : nullptr,
                    want_v ? f->d_pp_vo.p : nullptr, fout, eatom, vatom);
   f->pp_u_valid = true;
   if (f->decomposed) {
@@ -3777,38 +3472,10 @@ void pppm_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy
     if (f->env.rank != 0) std::fill(s7, s7 + 7, 0.0);
     f->rc.sum(s7, 7);
   }
-  if (energy) *energy = kspace_energy(f, s7[0], four[0], four[1], four[2], four[3], gm.V, gm.L);
+  if (energy) *energy = kspace_energy(f->kspace_env(), s7[0], four[0], four[1], four[2], four[3], gm.V, gm.L);
   if (virial) for (int c = 0; c < 6; ++c) virial[c] = f->env.qqrd2e * s7[1 + c];
 }
 // ---- device-resident k-space forces ----
-// ewald_structure_factor + ewald_forces on the caller's device arrays, every owned atom a column and a target (a zero charge adds
-// zeros): nothing but launches, device-to-device copies and memsets on the handle's stream once the buffers have their sizes.
-// dvatom: [nlocal][6], overwritten.
-void ewald_forces_device(conp_fix *f, const double *dx, const double *dq, double *df, double *dev, double *deatom, double *dvatom) {
-  const double V = f->kt.volume, L = f->env.zprd * f->env.slab_volfactor;
-  const int n = f->nlocal_cur;
-  if (n <= 0) { if (dev) HIP_TRY(hipMemsetAsync(dev, 0, 7 * sizeof(double), f->stream)); return; }
-  const int nb_pad = ew_block(f, n);
-  const int ntot = (n + nb_pad - 1) / nb_pad * nb_pad;
-  ew_reserve(f, nb_pad);
-  // q once into the padded buffer: the last block's padding columns carry no charge; x is read in place, block by block
-  f->d_ew_q.reserve(ntot);
-  HIP_TRY(hipMemcpyAsync(f->d_ew_q.p, dq, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, f->stream));
-  if (ntot > n) HIP_TRY(hipMemsetAsync(f->d_ew_q.p + n, 0, (size_t)(ntot - n) * sizeof(double), f->stream));
-  f->ew_g_valid = f->ew_u_valid = false;         // the host entries' scratch is overwritten from here on
-  ew_build_S(f, dx, f->d_ew_q.p, n, nb_pad);
-  launch_ew_gw(f->stream, f->dplan, f->d_ew_G.p, f->d_ew_Gwf.p);
-  kspace_four_sums(f, n, dx, dq);
-  if (dev) {
-    ew_energy_virial(f);
-    launch_kspace_finish(f->stream, kspace_finish_args(f, V, L), f->d_ew_ev.p, f->d_kf_sums.p, dev);
-  }
-  if (df || deatom || dvatom) {
-    ew_tiles_ready(f);
-    ew_force_blocks(f, n, nb_pad, dx, nullptr, kspace_out_args(f, V, L, nullptr), df, deatom, dvatom);
-  }
-  HIP_TRY(hipGetLastError());
-}
 // pppm_forces on the caller's device arrays: the brick of every owned atom through the identity list, the mesh solve, the gather
 // on every owned atom; the seven sums stay on the device (kspace_finish_kernel reads them).  dvatom: [nlocal][6], overwritten.
 void pppm_forces_device(conp_fix *f, const double *dx, const double *dq, double *df, double *dev, double *deatom, double *dvatom) {
@@ -3826,7 +3493,7 @@ void pppm_forces_device(conp_fix *f, const double *dx, const double *dq, double 
   f->pp_u_valid = false;             // d_pp_re is overwritten from here on
   launch_pppm_density(f->stream, f->dpppm, n, f->d_pp_iota.p, dx, dq, f->d_pp_re.p, f->d_pp_scratch.p);
   ++f->pp_elyte_spreads;
-  kspace_four_sums(f, n, dx, dq);
+  kspace_four_sums(*f, f->d_kf_sums, n, dx, dq);
   const bool fields = df != nullptr, per_atom = df || deatom;
   double *vb[6];
   pppm_mesh_spectra(f, gm, fields, dvatom ? vb : nullptr);
@@ -3834,7 +3501,7 @@ void pppm_forces_device(conp_fix *f, const double *dx, const double *dq, double 
   pppm_mesh_forces(f, gm, fields, per_atom, dev);
   if (per_atom)
     launch_pppm_force_gather_device(f->stream, f->dpppm, n, dx, dq, fields ? f->d_pp_ex.p : nullptr, f->d_pp_ey.p, f->d_pp_im.p,
-                                    f->d_pp_re.p, kspace_out_args(f, gm.V, gm.L, nullptr), f->d_kf_sums.p, df, deatom);
+                                    f->d_pp_re.p, kspace_out_args(f->kspace_env(), gm.V, gm.L, nullptr), f->d_kf_sums.p, df, deatom);
   HIP_TRY(hipGetLastError());
 }
 // the k-space tail of compute potential/atom (compute_potential_atom.cpp:165-175, slab correction :323-345) on the selected owned
@@ -3998,10 +3665,10 @@ int conp_ewald_compute_group_potential(conp_fix *f, const conp_atoms *at, const 
   need_ewald(f);
   // (collective: every rank, whatever it selected) -- unless a collective entry formed it since the last update, re-neighbouring or
   // set_matrix: those drop the cache on every rank alike, so every rank takes the same branch
-  if (!f->ew_g_valid) ewald_structure_factor(f, at);
+  if (!f->ew.g_valid) ewald_structure_factor(f, at);
   std::vector<int> idx;
   for (int i = 0; i < at->nlocal; ++i) if (sel[i]) idx.push_back(i);
-  ewald_project(f, at, idx, recv, nullptr);
+  f->ew.project(at, idx, recv, nullptr);
   CONP_GUARD_END
 }
 
@@ -4014,8 +3681,8 @@ int conp_ewald_compute_particle_potential(conp_fix *f, const conp_atoms *at, int
   f->drop_graph();
   need_ewald(f);
   if (i < 0 || i >= at->nlocal) throw ConpError(CONP_ERR_ARG, "atom index out of range");
-  if (!f->ew_u_valid || (int)f->ew_u_h.size() != at->nlocal) {
-    if (!f->ew_g_valid) {
+  if (!f->ew.u_valid || (int)f->ew.u_h.size() != at->nlocal) {
+    if (!f->ew.g_valid) {
       if (f->decomposed || f->env.nranks > 1)
         throw ConpError(CONP_ERR_STATE, "conp_ewald_compute_particle_potential is rank-local -- under several MPI ranks the structure "
                                         "factor has to be formed by a collective call first (conp_ewald_compute / compute_group_potential)");
@@ -4023,11 +3690,11 @@ int conp_ewald_compute_particle_potential(conp_fix *f, const conp_atoms *at, int
     }
     std::vector<int> all(at->nlocal);
     for (int k = 0; k < at->nlocal; ++k) all[k] = k;
-    f->ew_u_h.assign(at->nlocal, 0.0);
-    ewald_project(f, at, all, nullptr, f->ew_u_h.data());
-    f->ew_u_valid = true;
+    f->ew.u_h.assign(at->nlocal, 0.0);
+    f->ew.project(at, all, nullptr, f->ew.u_h.data());
+    f->ew.u_valid = true;
   }
-  *u = f->ew_u_h[i];
+  *u = f->ew.u_h[i];
   CONP_GUARD_END
 }
 
@@ -4041,9 +3708,9 @@ int conp_ewald_compute_forces_vatom(conp_fix *f, const conp_atoms *at, double *f
   if (!f || !at) throw ConpError(CONP_ERR_ARG, "null argument");
   f->drop_graph();
   need_ewald(f);
-  if (!f->ew_g_valid) ewald_structure_factor(f, at);
+  if (!f->ew.g_valid) ewald_structure_factor(f, at);
   else if (at->nlocal + at->nghost != f->nall) throw ConpError(CONP_ERR_STATE, "atom count changed without post_neighbor");
-  ewald_forces(f, at, fout, energy, virial, eatom, vatom);
+  f->ew.forces(at, fout, energy, virial, eatom, vatom);
   CONP_GUARD_END
 }
 
@@ -4093,7 +3760,7 @@ int conp_ewald_compute_forces_vatom_device(conp_fix *f, const double *d_x, const
   CONP_GUARD_BEGIN
   kspace_device_check(f, need_ewald, d_x, d_q);
   if (!d_f && !d_ev && !d_eatom && !d_vatom) return CONP_OK;
-  ewald_forces_device(f, d_x, d_q, d_f, d_ev, d_eatom, d_vatom);
+  f->ew.forces_device(f->nlocal_cur, d_x, d_q, d_f, d_ev, d_eatom, d_vatom);
   CONP_GUARD_END
 }
 
@@ -4260,7 +3927,7 @@ int conp_compute_potential_atom(conp_fix *f, const conp_atoms *at, const conp_ne
     std::vector<int> idx;
     for (int i = 0; i < at->nlocal; ++i) if (sel[i]) idx.push_back(i);
     ewald_structure_factor(f, at);
-    ewald_project(f, at, idx, nullptr, uk.data());
+    f->ew.project(at, idx, nullptr, uk.data());
     HIP_TRY(hipMemcpyAsync(pot.data(), d_pot.p, (size_t)nall * sizeof(double), hipMemcpyDeviceToHost, f->stream));
     f->sync();
     potential_atom_tail(f, at, pa, etasel, idx, uk, pot);
@@ -4311,6 +3978,7 @@ int conp_fix_set_comm(conp_fix *f, const conp_comm *comm) {
   f->rc.c = *comm; f->rc.have = true; f->rc.rank_ = comm->rank; f->rc.nranks_ = comm->nranks;
   f->env.rank = comm->rank; f->env.nranks = comm->nranks;
   f->decomposed = true;
+  f->ew.ranks = &f->rc;
   CONP_GUARD_END
 }
 

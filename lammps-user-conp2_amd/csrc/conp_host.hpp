@@ -115,6 +115,7 @@ struct RankOps {
   virtual void allgatherv_int(const int *send, int n, int *recv, const int * /*counts*/, const int * /*displs*/) {
     for (int i = 0; i < n; ++i) recv[i] = send[i];
   }
+  virtual void sum(double *, int64_t) {}
 };
 
 // ------------------------------------------------------------------------------------------------

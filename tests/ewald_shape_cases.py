@@ -6,9 +6,9 @@ Restated rules:
   KPlan::build (conp_host.cpp):  nz = kzmax + 1, n_col_tiles = ceil(ceil(nz / 16) / 10), kzt = ceil(ceil(nz / n_col_tiles) / 8) * 8;
       np = the distinct planar vectors (kx, +-ky) of the k list, origin included; n_row_tiles = ceil(np / 64),
       R_pad = 128 n_row_tiles, C_pad = 320 n_col_tiles.
-  ew_block (conp_fix.cpp):  min(cap, max(64, 64 ceil(n / 64))), cap = max(64, min(8192, 64 floor(80 MiB / per_atom / 64))) or the
+  EwaldQuery::block (conp_ewaldquery.cpp):  min(cap, max(64, 64 ceil(n / 64))), cap = max(64, min(8192, 64 floor(80 MiB / per_atom / 64))) or the
       width of conp_debug_set_ew_block, per_atom = 8 (R_pad + C_pad + 6 + 2 (kxmax + 2) + 2 (kymax + 1)) bytes.
-  ew_nsplit (conp_fix.cpp):  max(1, min(6 CUs / workgroups + 1, 32, nb_pad / 64)), workgroups = C_pad / 64 * n_row_tiles, lowered
+  EwaldQuery::nsplit (conp_ewaldquery.cpp):  max(1, min(6 CUs / workgroups + 1, 32, nb_pad / 64)), workgroups = C_pad / 64 * n_row_tiles, lowered
       while nsplit slices of R_pad C_pad doubles exceed 40 MiB.
   launch_ew_sk (conp_potential.hip):  per_split = 16 ceil(ceil(nb_pad / nsplit) / 16); split z takes the columns
       [z per_split, min(nb_pad, (z + 1) per_split)) of the block, an empty range returns at once.
@@ -91,6 +91,11 @@ C_CASES = {
 D_BOX = ("uneven", "slab")
 F_BOXES = (("tiny", "ffield"), ("half2", "slab"))           # case (f): a net charge of 1 e
 G_BOX = ("half2", "slab")                                   # case (g): 160 owned atoms, blocks of 64 and 128 differ
+# case (i): a live handle re-planned between calls.  The k list follows sum q^2 through the accuracy estimate alone (KTables::build:
+# the axis cut-offs are integers, nothing else reads it), so a twentieth of the box's own sum is a smaller plan of the same box:
+# K 83 -> 5, planar rows 7 -> 3, kz columns 8 -> 2, kxmax = kymax 2 -> 1, inside the same padded sizes (one row tile, one column tile)
+I_BOX = ("tiny", "slab")
+I_QSQ_FACTOR = 0.05
 
 
 def situation(t):
@@ -106,6 +111,11 @@ def system(name, mode):
     make, modes = BOXES[name]
     assert mode in modes, (name, mode)
     return make(mode)
+
+
+def with_qsqsum_factor(s, factor):
+    """the box with every charge scaled so that sum q^2 is `factor` times its own"""
+    return dataclasses.replace(s, name=f"{s.name}*{factor}", q=s.q * np.sqrt(factor))
 
 
 def plan_shape(kxvecs, kyvecs, kzvecs, kcount_dims, unitk=None):

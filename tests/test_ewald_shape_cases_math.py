@@ -90,6 +90,16 @@ def test_case_e_tier():
     assert 5e7 <= s.natoms * sh["K"] <= 2e8                       # the reference's one O(N K) structure factor
 
 
+def test_case_i_second_plan_is_smaller_in_rows_and_columns():
+    s = sc.system(*sc.I_BOX)
+    a, b = sc.host_shape(s), sc.host_shape(sc.with_qsqsum_factor(s, sc.I_QSQ_FACTOR))
+    print(a, b)
+    assert b["K"] < a["K"] and b["np"] < a["np"] and b["nz"] < a["nz"] and b["kxmax"] < a["kxmax"] and b["kymax"] < a["kymax"]
+    assert (b["R_pad"], b["C_pad"]) == (a["R_pad"], a["C_pad"])  # the smaller plan lies inside the larger one's buffers
+    for f in (sc.I_QSQ_FACTOR / 2, sc.I_QSQ_FACTOR * 1.5):        # (and the choice is not at a step of the accuracy estimate)
+        assert sc.host_shape(sc.with_qsqsum_factor(s, f)) == b
+
+
 # ---- the references carry the Q terms (case (f)) --------------------------------------------------------------------------
 @pytest.mark.parametrize("name,mode", sc.F_BOXES)
 def test_references_carry_the_net_charge_terms(name, mode):

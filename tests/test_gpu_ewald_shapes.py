@@ -10,7 +10,8 @@ claims, and prints it.
     charged atoms;  (c) blocks of 64, 128, 192 with a full last block, a last block of one atom, one block for everything, 1, 2 and
     3 splits, all five entries;  (d) uneven splits: 2112 columns over 32 splits of 80, the 27th partial, five empty;  (e) `bigN`:
     66 256 atoms in nine blocks of 8192, kspace_four_sums saturated, a net charge in slab mode;  (f) a net charge of 1 e;
-    (g) results do not depend on the calls before them, byte for byte;  (h) guard zones around (b), (c), (d).
+    (g) results do not depend on the calls before them, byte for byte;  (h) guard zones around (b), (c), (d);  (i) a live handle
+    re-planned to a smaller plan and back (conp_km_conp_setup) gives what handles set up with either plan give, byte for byte.
 
 References: tests/ewald_force_ref.py, tests/kspace_vatom_ref.py and _brute_g of tests/test_gpu_ewald_potential.py, on ALL owned
 atoms (bigN: S over all atoms, per-atom quantities on 512 seeded atoms and the probes).  Bounds, those of the sibling tests and no
@@ -38,11 +39,12 @@ potential, particle potential and potential/atom.  No bound is exceeded, so no f
                                   716), nsplit 32, per_split 256, four sums saturated
     (f) tiny/ffield Q = +1                                                               4.8e-5  4.8e-6  3.7e-4  7.8e-5  1.6e-5  3.3e-5  8.2e-3
     (f) half2/slab Q = +1                                                                2.0e-4  1.4e-5  8.8e-5  5.4e-5  7.8e-5  4.9e-5  1.1e-2
-    (g) byte-identical to fresh handles; (h) no guard zone damaged.  The 26 tests take 17 s.
+    (g) byte-identical to fresh handles; (h) no guard zone damaged; (i) byte-identical to handles set up with either plan (tiny/slab,
+    K 83 -> 5 -> 83).  The 27 tests take 20 s.
 The finding of (e): with the host entries' four sums and the potential/atom tail added in plain loops, bigN's host entries stood at
 0.84 (potential/atom), 0.11 (energy), 0.059 (force) and 0.028 (eatom) of their bounds -- 66 000 sites sharing four charge values lose
-1e-8 of Q in a running sum -- where the device entries' tree sums gave 3e-4 and less.  conp_fix.cpp now adds them with a compensated
-sum (CompSum); the row above is measured with it."""
+1e-8 of Q in a running sum -- where the device entries' tree sums gave 3e-4 and less.  The library now adds them with a compensated
+sum (CompSum, conp_kspace_common.hpp); the row above is measured with it."""
 import functools
 import os
 import subprocess
@@ -373,6 +375,53 @@ def test_results_do_not_depend_on_the_calls_before_them():
     for name, a, b in zip(("f", "ev", "eatom"), out6, out6_fresh):
         assert a.tobytes() == b.tobytes(), (name, np.abs(a - b).max())
     for h in (fx, fa, fb):
+        h.close()
+
+
+# ---- (i) re-planning a live handle -----------------------------------------------------------------------------------------
+def test_replanned_handle_gives_what_a_fresh_handle_of_that_plan_gives():
+    """The smaller plan inside buffers sized and zeroed for the larger one: stale padding rows of the phase tables, a stale k list
+    or stale tile lists would show.  Byte identity with handles that never had another plan is the contract."""
+    c = case(*sc.I_BOX)
+    at, n, s = c.at, c.n, c.s
+    sB = sc.with_qsqsum_factor(s, sc.I_QSQ_FACTOR)
+    qsq_A, qsq_B = s.qsqsum, sB.qsqsum
+
+    def four_calls(fx):
+        fx.ewald_compute(at)
+        g = fx.ewald_group_potential(at, np.ones(n, np.int32))
+        f, E, W, e = fx.ewald_forces(at, eatom=True)
+        return (g, f, np.float64(E), W, e) + tuple(_vcall(fx.ewald_forces_vatom_device, c.d_x, c.d_q, n))
+
+    def plan(fx):
+        sh, kt = sc.handle_shape(fx), fx.ktables()
+        assert sh["K"] == fx.info().kcount
+        return sh, np.stack([kt["kxvecs"], kt["kyvecs"], kt["kzvecs"]]).tobytes() + kt["ug"].tobytes()
+
+    H = _handle(s)[3]
+    pA = plan(H)
+    four_calls(H)                                                                 # first round, plan A
+    H.km_conp_setup(qsq_B, s.natoms)
+    pB = plan(H)
+    a, b = pA[0], pB[0]
+    print(f"{c.tag}: plan A {a}\n{c.tag}: plan B {b}")
+    assert b["K"] < a["K"] and b["np"] < a["np"] and b["nz"] < a["nz"] and b["kxmax"] < a["kxmax"] and b["kymax"] < a["kymax"]
+    assert (b["R_pad"], b["C_pad"]) == (a["R_pad"], a["C_pad"])                   # B lies inside A's buffers
+    second = four_calls(H)
+    H.km_conp_setup(qsq_A, s.natoms)
+    assert plan(H) == pA
+    third = four_calls(H)
+    # the fresh handles: set up with the atoms whose sum q^2 gives the plan (no update: the entries read the charges of the call)
+    FB, FA = _handle(sB, update=False)[3], _handle(s, update=False)[3]
+    assert plan(FB) == pB and plan(FA) == pA
+    names = ("group potential", "f", "E", "W", "eatom", "device f", "device ev", "device eatom", "device vatom")
+    for label, got, fresh in (("second round against plan B", second, four_calls(FB)), ("third round against plan A", third, four_calls(FA))):
+        assert len(got) == len(fresh) == len(names)
+        for name, x, y in zip(names, got, fresh):
+            assert np.abs(y).max() > 0 and x.tobytes() == y.tobytes(), (label, name, np.abs(x - y).max())
+    assert any(x.tobytes() != y.tobytes() for x, y in zip(second, third))          # (the two plans do give different numbers)
+    _compare(c.tag, "group potential after the re-plans", third[0], c.g, 1e-11 * np.abs(c.g).max())      # (and plan A's are right)
+    for h in (H, FB, FA):
         h.close()
 
 

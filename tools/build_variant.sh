@@ -8,4 +8,4 @@ for f in conp_zn conp_kernels; do
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -pthread -o $C/../conp_amd/libconp_hip_$1.so $C/conp_kernels_var_$1.o $C/conp_inverse.o $C/conp_pppm.o \
   $C/conp_rows.o $C/conp_tables.o $C/conp_zn_var_$1.o $C/conp_potential.o $C/conp_pair.o $C/conp_neigh.o $C/conp_ghost.o $C/conp_reneigh.o \
-  $C/conp_fix.o $C/conp_dev.o $C/conp_pairstyle.o $C/conp_ghostmap.o $C/conp_host.o
+  $C/conp_fix.o $C/conp_dev.o $C/conp_pairstyle.o $C/conp_ghostmap.o $C/conp_ewaldquery.o $C/conp_host.o
