@@ -700,6 +700,80 @@ int conp_fix_get_step_tables(conp_fix *fix, int64_t *sizes /*[8] or NULL*/, int 
 int conp_fix_post_force_device(conp_fix *fix, const double *d_x /*[nall][3]*/, const double *d_q /*[nall]*/,
                                double *d_f /*[nall][3], added to; NULL: none*/, double *d_out /*[9], overwritten; NULL: none*/);
 
+/* ---- bonded forces: `bond_style harmonic` and `angle_style harmonic` on the device -------------------------
+ * The bond and angle loops of LAMMPS' bond_harmonic.cpp and angle_harmonic.cpp @ 27May2021 with Bond::ev_tally's and
+ * Angle::ev_tally's energy, virial and per-atom tallies.  All arithmetic is double, in the order written, no contraction.
+ * newton = newton_bond of conp_bonded_set_params; nlocal, nall, prd those of conp_bonded_set_lists.
+ * Closest image of x_b seen from x_a, per dimension c with prd[c] > 0:  d = x_a[c] - x_b[c];  s = +1 if d > prd[c] / 2, s = -1 if
+ * d < -prd[c] / 2, else s = 0;  x_b'[c] = x_b[c] + ((double)s * prd[c])  -- the product first, then the sum, also for s = 0: the ghost
+ * arithmetic of conp_ghost_fill_device, so an image has the bits a ghost would have.  One pass: partners more than 1.5 box lengths
+ * apart are the caller's error.  With prd[c] = 0: x_b'[c] = x_b[c].
+ * Bond (i1, i2, t), x2' the closest image of x2 from x1:
+ *   del = x1 - x2';  rsq = delx^2 + dely^2 + delz^2;  r = sqrt(rsq);  dr = r - r0[t];  rk = k[t] dr
+ *   fbond = (r > 0) ? -2 rk / r : 0;  ebond = rk dr
+ *   f[i1] += del fbond  if newton or i1 < nlocal;   f[i2] -= del fbond  if newton or i2 < nlocal
+ *   v = fbond (delx^2, dely^2, delz^2, delx dely, delx delz, dely delz)
+ *   Tally: with newton ebond and v are counted whole, else ebond / 2 and v / 2 once per owned member.  eatom gets ebond / 2 and vatom
+ *   v / 2, for i1 and for i2, each under the force's condition.
+ * Angle (i1, i2, i3, t), i2 the centre, x1' and x3' the closest images from x2:
+ *   del1 = x1' - x2;  del2 = x3' - x2;  rsq1 = |del1|^2;  rsq2 = |del2|^2;  r1 = sqrt(rsq1);  r2 = sqrt(rsq2)
+ *   c = (del1 . del2) / (r1 r2), clamped to [-1, 1];  s = sqrt(1 - c c);  if s < 0.001: s = 0.001;  s = 1 / s
+ *   dtheta = acos(c) - theta0[t];  tk = k[t] dtheta;  eangle = tk dtheta
+ *   a = -2 tk s;  a11 = a c / rsq1;  a12 = -a / (r1 r2);  a22 = a c / rsq2
+ *   f1 = a11 del1 + a12 del2;  f3 = a22 del2 + a12 del1
+ *   f[i1] += f1;  f[i2] -= f1 + f3;  f[i3] += f3,  each if newton or i < nlocal
+ *   v = (delx1 f1x + delx2 f3x, dely1 f1y + dely2 f3y, delz1 f1z + delz2 f3z,
+ *        delx1 f1y + delx2 f3y, delx1 f1z + delx2 f3z, dely1 f1z + dely2 f3z)
+ *   Tally: whole with newton, else (1.0 / 3.0) eangle and (1.0 / 3.0) v once per owned member.  eatom gets eangle (1.0 / 3.0) and
+ *   vatom v (1.0 / 3.0) per member, under the force's condition.
+ * Hence with newton sum eatom = ebond + eangle and sum vatom = virial.
+ * The two ways to hand over lists:
+ *   - a LAMMPS-like host passes neighbor->bondlist / anglelist with ghost indices and prd = {0, 0, 0} at every re-neighbour; the ghost
+ *     rows of f, eatom, vatom then carry what the reverse communication (conp_ghost_fold_device) folds back;
+ *   - a device-resident engine passes owned indices and the box lengths ONCE: nothing lands on a ghost row, no fold is needed, and
+ *     the lists survive every device re-neighbour for as long as the owned atoms keep their local order and identity -- the
+ *     precondition conp_fix_post_neighbor_device already has.
+ * Order and reproducibility: no output meets an atomic.  conp_bonded_set_lists builds a per-atom table of the (term, role) slots an
+ * atom takes part in, bonds first in list order, then angles in list order; an atom's contributions to f, eatom and vatom are summed
+ * from 0.0 by one thread in that order and added to f once; energy and virial are added over terms in a fixed order.  Every output
+ * is a pure function of the input: byte-identical from call to call and between the host and the device entry.  Rows of atoms in
+ * no term (or, with newton off, of ghosts): f is untouched bit for bit, eatom / vatom are exactly 0.0.
+ * Order: conp_bonded_set_params (once per run, or after bond_coeff / angle_coeff changes) -> conp_bonded_set_lists -> the compute
+ * entries.  CONP_ERR_STATE: a compute entry before set_params or set_lists; set_lists before set_params.  conp_bonded_set_params
+ * after conp_bonded_set_lists DROPS the lists (they were checked against the old tables): set them again.
+ * CONP_ERR_ARG: a NULL struct; a NULL array with a positive count; a negative count; nlocal > nall; an index outside [0, nall); a
+ * type outside [1, ntypes]; a negative or non-finite prd; NULL d_x / atoms; atoms->nlocal + nghost != nall.  A refused
+ * conp_bonded_set_lists leaves the handle without lists.  All outputs NULL: CONP_OK, nothing done.  Empty lists: the outputs are
+ * zeroed, f is untouched.
+ * The entries need nothing of the fix but its stream: they work from conp_fix_create on, on Ewald and `pppm` handles, and they are
+ * rank-local, never collective (decomposed handles are allowed).
+ * Device entry: everything is enqueued on the handle's stream; conp_bonded_set_lists reserves all scratch, so a compute call makes
+ * no device allocation, no copy to the host and no synchronisation.  A device step: conp_ghost_fill_device ->
+ * conp_fix_pre_force_device -> conp_*_compute_forces_device -> conp_pair_compute_device -> conp_bonded_compute_device ->
+ * conp_fix_post_force_device -> conp_ghost_fold_device.
+ * Host entry: stages atoms->x (only x is read), is synchronous and adds into f. */
+typedef struct {
+  int nbondtypes, nangletypes;          /* either may be 0 */
+  const double *bond_k, *bond_r0;       /* [nbondtypes + 1], entry 0 unused (bond_coeff K r0) */
+  const double *angle_k, *angle_theta0; /* [nangletypes + 1], theta0 in RADIANS (LAMMPS converts at angle_coeff) */
+  int newton_bond;                      /* force->newton_bond */
+} conp_bonded_params;
+
+typedef struct {
+  int nlocal, nall;                     /* every index below is < nall; i < nlocal is an owned atom */
+  int nbond;  const int *bond;          /* [nbond][3]  i1, i2, type      -- neighbor->bondlist */
+  int nangle; const int *angle;         /* [nangle][4] i1, i2, i3, type  -- neighbor->anglelist, i2 the centre */
+  double prd[3];                        /* > 0: closest image in that dimension (above); 0: coordinates as they are */
+} conp_bonded_lists;
+
+int conp_bonded_set_params(conp_fix *fix, const conp_bonded_params *p);   /* copied */
+int conp_bonded_set_lists(conp_fix *fix, const conp_bonded_lists *l);     /* host arrays, copied and uploaded; may allocate and synchronise */
+int conp_bonded_compute(conp_fix *fix, const conp_atoms *atoms, double *f /*[nall][3] accumulated*/, double *eng /*[2] ebond, eangle*/,
+                        double *virial /*[6]*/, double *eatom /*[nall] overwritten*/, double *vatom /*[nall][6] overwritten*/);
+int conp_bonded_compute_device(conp_fix *fix, const double *d_x /*[nall][3]*/, double *d_f /*[nall][3] accumulated*/,
+                               double *d_ev /*[8] ebond, eangle, virial xx,yy,zz,xy,xz,yz; overwritten*/,
+                               double *d_eatom /*[nall]*/, double *d_vatom /*[nall][6]*/);
+
 /* per-kernel timing of the last N updates via HIP events on the library's stream (bench.py roofline leg).
  * enable: 0 off, 1 a pair of events around every kernel, 2 around every 4th launch of the dominant kernel (sk_gemm) only --
  * cheap enough to stay on inside a timed region (an event pair drains the queue around the kernel it brackets). */

@@ -85,6 +85,16 @@ class conp_ghost_build_args(C.Structure):
                 ("cutghost", C.c_double)]
 
 
+class conp_bonded_params(C.Structure):
+    _fields_ = [("nbondtypes", C.c_int), ("nangletypes", C.c_int), ("bond_k", C.POINTER(C.c_double)), ("bond_r0", C.POINTER(C.c_double)),
+                ("angle_k", C.POINTER(C.c_double)), ("angle_theta0", C.POINTER(C.c_double)), ("newton_bond", C.c_int)]
+
+
+class conp_bonded_lists(C.Structure):
+    _fields_ = [("nlocal", C.c_int), ("nall", C.c_int), ("nbond", C.c_int), ("bond", C.POINTER(C.c_int)), ("nangle", C.c_int),
+                ("angle", C.POINTER(C.c_int)), ("prd", C.c_double * 3)]
+
+
 class conp_info(C.Structure):
     _fields_ = [("elenum", C.c_int), ("elenum_all", C.c_int), ("elytenum", C.c_int), ("maxtag_all", C.c_int),
                 ("runstage", C.c_int), ("kcount", C.c_int), ("kcount_flat", C.c_int), ("kcount_expand", C.c_int),
@@ -127,6 +137,7 @@ SYMBOLS = [
     "conp_atoms_wrap_device",
     "conp_fix_post_neighbor_device", "conp_fix_get_step_tables",
     "conp_fix_post_force_device",
+    "conp_bonded_set_params", "conp_bonded_set_lists", "conp_bonded_compute", "conp_bonded_compute_device",
 ]
 
 
@@ -282,6 +293,11 @@ def load_library():
         lib.conp_fix_get_step_tables.argtypes = [vp, C.POINTER(C.c_int64)] + [ip] * 9
     if hasattr(lib, "conp_fix_post_force_device"):
         lib.conp_fix_post_force_device.argtypes = [vp, vp, vp, vp, vp]
+    if hasattr(lib, "conp_bonded_compute"):                    # (comparison builds loaded through CONP_LIB lack these)
+        lib.conp_bonded_set_params.argtypes = [vp, C.POINTER(conp_bonded_params)]
+        lib.conp_bonded_set_lists.argtypes = [vp, C.POINTER(conp_bonded_lists)]
+        lib.conp_bonded_compute.argtypes = [vp, C.POINTER(conp_atoms), dp, dp, dp, dp, dp]
+        lib.conp_bonded_compute_device.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.conp_compute_potential_atom.argtypes = [vp, C.POINTER(conp_atoms), C.POINTER(conp_neighlist), ip, ip,
                                                 C.POINTER(conp_potential_args), dp]
     lib.conp_fix_set_comm.argtypes = [vp, C.POINTER(conp_comm)]
@@ -856,6 +872,49 @@ class FixConp:
         self._check(self.lib.conp_fix_post_force_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q), C.c_void_p(d_f), C.c_void_p(d_out)))
 
     STEP_TABLES = ("elyte_idx", "ele_pairs", "csr_ptr", "csr_of", "csr_row", "b_rowptr", "b_ele", "b_oth", "g0c")
+
+    # -- harmonic bonds and angles: set_params -> set_lists -> compute / compute_device ----------
+    def bonded_set_params(self, bond_k=(), bond_r0=(), angle_k=(), angle_theta0=(), newton_bond=True):
+        """conp_bonded_set_params: per-type coefficients WITHOUT the unused entry 0 (bond type t reads bond_k[t - 1]); theta0 in
+        radians; copied by the library.  Drops the handle's bonded lists"""
+        tab = lambda a: np.ascontiguousarray(np.concatenate([[0.0], np.asarray(a, dtype=np.float64).reshape(-1)]))
+        bk, br, ak, a0 = tab(bond_k), tab(bond_r0), tab(angle_k), tab(angle_theta0)
+        assert bk.size == br.size and ak.size == a0.size
+        p = conp_bonded_params(nbondtypes=bk.size - 1, nangletypes=ak.size - 1, bond_k=_dptr(bk), bond_r0=_dptr(br),
+                               angle_k=_dptr(ak), angle_theta0=_dptr(a0), newton_bond=int(newton_bond))
+        self._check(self.lib.conp_bonded_set_params(self.h, C.byref(p)))
+
+    def bonded_set_lists(self, nlocal, nall, bonds=None, angles=None, prd=(0.0, 0.0, 0.0)):
+        """conp_bonded_set_lists: bonds [nbond][3] (i1, i2, type), angles [nangle][4] (i1, i2, i3, type; i2 the centre), local
+        indices below nall; prd > 0: closest image along that dimension.  Copied and uploaded; may allocate and synchronise"""
+        b = np.ascontiguousarray(np.zeros((0, 3)) if bonds is None else bonds, dtype=np.int32).reshape(-1, 3)
+        a = np.ascontiguousarray(np.zeros((0, 4)) if angles is None else angles, dtype=np.int32).reshape(-1, 4)
+        l = conp_bonded_lists(nlocal=int(nlocal), nall=int(nall), nbond=b.shape[0], bond=_iptr(b) if b.size else None,
+                              nangle=a.shape[0], angle=_iptr(a) if a.size else None, prd=(C.c_double * 3)(*prd))
+        self._check(self.lib.conp_bonded_set_lists(self.h, C.byref(l)))
+
+    def bonded_compute(self, at, forces=True, eng=True, virial=True, eatom=True, vatom=True, f=None):
+        """conp_bonded_compute on host arrays (only at.x is read) -> (f [nall][3] (added to `f`, zeros by default), eng [2] = ebond,
+        eangle, W [6], eatom [nall], vatom [nall][6]); what was not asked for is None"""
+        n = at.nlocal + at.nghost
+        if forces:
+            f = np.zeros((n, 3)) if f is None else f
+            assert f.dtype == np.float64 and f.flags.c_contiguous and f.shape == (n, 3)
+        else:
+            f = None
+        e2 = np.full(2, np.nan) if eng else None
+        w = np.full(6, np.nan) if virial else None
+        ea = np.full(n, np.nan) if eatom else None
+        va = np.full((n, 6), np.nan) if vatom else None
+        ptr = lambda a: _dptr(a) if a is not None else None
+        self._check(self.lib.conp_bonded_compute(self.h, C.byref(self.atoms_view(at)), ptr(f), ptr(e2), ptr(w), ptr(ea), ptr(va)))
+        return f, e2, w, ea, va
+
+    def bonded_compute_device(self, d_x: int, d_f: int = 0, d_ev: int = 0, d_eatom: int = 0, d_vatom: int = 0):
+        """conp_bonded_compute_device: raw device pointers (0 = NULL), enqueued on the handle's stream, no synchronisation; d_f [nall][3]
+        is added to, d_ev [8] (ebond, eangle, virial xx, yy, zz, xy, xz, yz), d_eatom [nall], d_vatom [nall][6] are overwritten"""
+        self._check(self.lib.conp_bonded_compute_device(self.h, C.c_void_p(d_x), C.c_void_p(d_f), C.c_void_p(d_ev),
+                                                        C.c_void_p(d_eatom), C.c_void_p(d_vatom)))
 
     def step_tables(self):
         """conp_fix_get_step_tables -> dict of the sizes (nl, n_ele_atoms, ne, n_b_pairs, n_chunks, zn_listed, nall, c_start) and the

@@ -23,6 +23,7 @@
 #include "conp_dev.hpp"
 #include "conp_ghostmap.hpp"
 #include "conp_pairstyle.hpp"
+#include "conp_bondedstyle.hpp"
 #include "conp_ewaldquery.hpp"
 
 using namespace conp::dev;
@@ -2393,10 +2394,12 @@ struct conp_fix : DevCtx {
     HIP_TRY(hipGetLastError());
   }
 
-  // ---- the pair style with its half list (conp_pairstyle.cpp, DESIGN.md sections 16, 17), the ghost map (conp_ghostmap.cpp, 18) and
-  // the exact-Ewald query entries (conp_ewaldquery.cpp, sections 11, 12, 14, 15) ----
+  // ---- the pair style with its half list (conp_pairstyle.cpp, DESIGN.md sections 16, 17), the ghost map (conp_ghostmap.cpp, 18),
+  // the harmonic bonds and angles (conp_bondedstyle.cpp, 21) and the exact-Ewald query entries (conp_ewaldquery.cpp, sections 11, 12,
+  // 14, 15) ----
   PairStyle pair{*this};
   GhostMap ghost{*this};
+  BondedStyle bonded{*this};
   EwaldQuery ew{*this, kt, plan, dplan, tiles_h, ct_ptr_h, d_sf_row_a, d_sf_col_c, d_k_sign};
   bool types_in_range = false;                   // every atoms->type of the last (setup_)post_neighbor lies in [0, ntypes]
 
@@ -3892,6 +3895,52 @@ int conp_pair_compute_device(conp_fix *f, const double *d_x, const double *d_q, 
   if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
   f->drop_graph();
   f->pair_compute_device(d_x, d_q, d_f, d_ev, d_eatom, d_vatom);
+  CONP_GUARD_END
+}
+
+// ---- harmonic bonds and angles: set_params -> set_lists -> compute / compute_device ------------------------
+int conp_bonded_set_params(conp_fix *f, const conp_bonded_params *p) {
+  CONP_GUARD_BEGIN
+  if (!f || !p) throw ConpError(CONP_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(f->env.device));
+  f->drop_graph();
+  f->bonded.set_params(p);
+  CONP_GUARD_END
+}
+
+int conp_bonded_set_lists(conp_fix *f, const conp_bonded_lists *l) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->bonded.have_lists = false;                  // a refused call leaves the handle without lists
+  if (!l) throw ConpError(CONP_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(f->env.device));
+  f->drop_graph();
+  f->bonded.set_lists(l);
+  CONP_GUARD_END
+}
+
+int conp_bonded_compute(conp_fix *f, const conp_atoms *at, double *fo, double *eng, double *virial, double *eatom, double *vatom) {
+  CONP_GUARD_BEGIN
+  if (!f || !at) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->bonded.need_ready("conp_bonded_compute");
+  if (at->nlocal < 0 || at->nghost < 0 || (int64_t)at->nlocal + at->nghost != f->bonded.nall)
+    throw ConpError(CONP_ERR_ARG, "conp_bonded_compute: nlocal + nghost differs from the nall of conp_bonded_set_lists");
+  if (f->bonded.nall > 0 && !at->x) throw ConpError(CONP_ERR_ARG, "conp_bonded_compute: null atom array");
+  if (!fo && !eng && !virial && !eatom && !vatom) return CONP_OK;
+  HIP_TRY(hipSetDevice(f->env.device));
+  f->drop_graph();
+  f->bonded.compute_host(at, fo, eng, virial, eatom, vatom);
+  CONP_GUARD_END
+}
+
+int conp_bonded_compute_device(conp_fix *f, const double *d_x, double *d_f, double *d_ev, double *d_eatom, double *d_vatom) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->bonded.need_ready("conp_bonded_compute_device");
+  if (!d_x) throw ConpError(CONP_ERR_ARG, "conp_bonded_compute_device: null d_x");
+  if (!d_f && !d_ev && !d_eatom && !d_vatom) return CONP_OK;
+  f->drop_graph();
+  f->bonded.enqueue(d_x, d_f, d_ev, d_eatom, d_vatom);
   CONP_GUARD_END
 }
 

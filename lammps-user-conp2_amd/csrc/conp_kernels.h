@@ -364,6 +364,24 @@ struct PairArgs {
 void launch_pair_pack(hipStream_t s, int nall, const double *x, const double *q, double4 *xq);
 // ev [8] = eng_vdwl, eng_coul, virial xx, yy, zz, xy, xz, yz (overwritten, summed in a fixed order), or NULL
 void launch_pair_force(hipStream_t s, const PairArgs &a, double *ev);
+// ---- bonded forces of bond_style / angle_style harmonic (conp_bonded.hip) ----
+constexpr int BONDED_BLOCK = 256;        // threads of a workgroup: one per term (term kernel), one per atom (gather kernel)
+constexpr int BONDED_FINISH = 256;       // threads of the finishing workgroup: rows r, r + 256, ... per thread
+constexpr int BONDED_TERM_W = 13;        // doubles per term record: f on member 1 [3], f on member 3 [3] (bond: 0), energy, v[6]
+struct BondedArgs {
+  int nbond, nangle, nlocal, nall, newton;
+  const int *bond, *angle;               // [nbond][3] i1, i2, type; [nangle][4] i1, i2, i3, type
+  const double *bcoef, *acoef;           // [nbondtypes + 1][2] k, r0; [nangletypes + 1][2] k, theta0
+  double prd[3];                         // > 0: closest image along that dimension
+  const double *x;                       // [nall][3]
+  double *term;                          // [nbond + nangle][BONDED_TERM_W] scratch: bonds first, then angles
+  double *part;                          // [ceil((nbond + nangle) / BONDED_BLOCK)][8] scratch rows (needed with ev != NULL)
+  const int *slot_ptr, *slot;            // [nall + 1], [2 nbond + 3 nangle]: an atom's slots, term * 4 + role, in list order
+  double *f;                             // [nall][3] accumulated, or NULL
+  double *eatom, *vatom;                 // [nall], [nall][6] overwritten, or NULL
+};
+// ev [8] = ebond, eangle, virial xx, yy, zz, xy, xz, yz (overwritten, summed in a fixed order), or NULL
+void launch_bonded(hipStream_t s, const BondedArgs &a, double *ev);
 // ---- the pair style's half list built on the device (conp_neigh.hip) ----
 struct NeighGrid { double lo[3], inv[3]; int n[3]; };     // cell of v along c: clamp((v - lo[c]) * inv[c], 0, n[c] - 1); cells are >= cutneigh wide
 struct NeighRowArgs {
