@@ -25,6 +25,7 @@
 #include "conp_pairstyle.hpp"
 #include "conp_bondedstyle.hpp"
 #include "conp_ewaldquery.hpp"
+#include "conp_pppmmesh.hpp"
 
 using namespace conp::dev;
 namespace {
@@ -51,8 +52,7 @@ struct RankComm : conp::RankOps {
     check(c.allgatherv(c.ctx, send, (int64_t)n * sizeof(int), recv, cb.data(), db.data()), "allgatherv");
   }
   void sum(double *b, int64_t n) override { if (active() && n > 0) check(c.allreduce_sum(c.ctx, b, n), "allreduce_sum"); }
-  // rank r contributes counts[r] doubles (w values per item); recv holds them rank-major
-  void gatherv(const double *send, const std::vector<int> &items, int w, double *recv) {
+  void gatherv(const double *send, const std::vector<int> &items, int w, double *recv) override {
     if (!active()) { std::memcpy(recv, send, (size_t)items[0] * w * sizeof(double)); return; }
     std::vector<int64_t> cb(nranks_), db(nranks_);
     int64_t off = 0;
@@ -107,8 +107,6 @@ struct conp_fix : DevCtx {
   // host state
   KTables kt;
   KPlan plan;
-  PppmPlan pppm;
-  PppmDev dpppm{};
   EleIndex idx;
   PairRows brows, arows;
   ListView alist, blist;
@@ -139,23 +137,6 @@ struct conp_fix : DevCtx {
   // CONP_TIME_HOST=1: where a host-buffer update spends its host time (printed to stderr when the handle is closed)
   const bool time_host = getenv("CONP_TIME_HOST") != nullptr;
   double th[6] = {0, 0, 0, 0, 0, 0};    // list check, staging copies, enqueue, wait, scatter, updates
-  bool pp_im_clean = false;      // the mesh's imaginary brick is all zero (left so by the b path's last backward pass)
-  // PPPMCONP's per-step caches (pppm_conp.cpp: elyte_density_brick + elyte_mapped, u_brick): pp_keep -- a host that overrides
-  // PPPM::make_rho asked for the electrolyte brick of every b_cal (conp_pppm_keep_density); pp_elyte_valid -- d_pp_elyte holds the
-  // brick of the LAST b_cal and nothing has moved since; pp_u_valid -- d_pp_re holds the mesh potential of the total density
-  // (conp_pppm_compute and the other collective entries leave it), so the per-atom entry only gathers from it.
-  bool pp_keep = false, pp_elyte_valid = false, pp_u_valid = false;
-  int pp_elyte_spreads = 0;      // how often the electrolyte atoms were spread onto the mesh (b_cal and density queries)
-  DevBuf<double> d_pp_elyte, d_pp_xg, d_pp_qg;
-  DevBuf<double> d_pp_ex, d_pp_ey, d_pp_kpart, d_pp_fo, d_pp_eo;      // conp_pppm_compute_forces: E_x, E_y bricks, the seven sums, outputs
-  DevBuf<double> d_pp_v[6], d_pp_vo;           // ..._vatom: the six v_ab bricks (xx, yy, zz, xy, xz, yz), the per-atom virial (section 15)
-  DevBuf<int> d_pp_fidx;
-  DevBuf<int> d_pp_iota;
-  // the device-resident PPPM force entry (conp_pppm_compute_forces_device): Q, Q2, M, M2 of the call's atoms
-  // with the workgroups' partial rows behind them; how many leading entries of d_pp_iota are the identity list 0, 1, 2, ...
-  // (pppm_gather_all, the only other writer, resets it)
-  DevBuf<double> d_kf_sums;
-  int pp_iota_n = 0;
   double Btime = 0., Ctime = 0., Ktime = 0.;      // accumulated like :549-552 (seconds)
   hipEvent_t ev_b[3] = {nullptr, nullptr, nullptr};
   bool ev_pending = false;
@@ -176,12 +157,11 @@ struct conp_fix : DevCtx {
   // device state
   bool own_stream = false;
   DevBuf<double> d_x, d_q, d_qc, d_slab_part, d_Gpart, d_G, d_Gw, d_wfull, d_Rp, d_Tz, d_ele_z, d_bk, d_breal, d_b_own,
-      d_eleallq_own, d_qele, d_elesetq, d_eleinitq, d_A, d_cutsq, d_scalars, d_ainve, d_sfr, d_sfi, d_cg_res, d_cg_p, d_Srows, d_xg, d_qg, d_pp_ele, d_pp_scratch,
-      d_cg_ap, d_cg_scal, d_inv_work, d_inv_backup, d_Tzc, d_TzcT, d_Hpart, d_Hc, d_Wz, d_Spk, d_yp, d_f, d_pfacc, d_pp_coeff, d_pp_green, d_pp_tw0, d_pp_tw1,
-      d_pp_tw2, d_pp_re, d_pp_im, d_pp_ew, d_eta_ij, d_fo_ij, d_u0_i, d_diag_atom, d_setzvec;
+      d_eleallq_own, d_qele, d_elesetq, d_eleinitq, d_A, d_cutsq, d_scalars, d_ainve, d_sfr, d_sfi, d_cg_res, d_cg_p, d_Srows, d_xg, d_qg,
+      d_cg_ap, d_cg_scal, d_inv_work, d_inv_backup, d_Tzc, d_TzcT, d_Hpart, d_Hc, d_Wz, d_Spk, d_yp, d_f, d_pfacc, d_eta_ij, d_fo_ij, d_u0_i, d_diag_atom, d_setzvec;
   DevBuf<double2> d_Xt, d_Yt, d_Zt, d_Xe, d_Ye;      // d_Xe / d_Ye: electrode atoms' axis phases [k][ne_pad] (once per run)
   DevBuf<int> d_type, d_atom2eleall, d_elyte_idx, d_p_ikx, d_p_iky, d_p_sgn, d_sf_row_a, d_sf_col_c, d_k_sign, d_k_p, d_k_m,
-      d_elecheck, d_zclass, d_nb_act, d_rt_mine, d_own_rt, d_own_pv, d_ele_pairs, d_a_chunk_group, d_ct_ptr, d_seg_ptr, d_seg_idx, d_hslot_ptr, d_hslot_idx, d_b_rowptr, d_b_ele, d_b_oth, d_a_rowptr, d_a_ele, d_a_oth, d_a_col, d_bl_ilist, d_bl_numneigh, d_bl_first, d_bl_neigh, d_pp_egrid, d_ipiv, d_info, d_cg_done, d_iota, d_ele_csr_ptr, d_ele_csr_of, d_ele_csr_row;
+      d_elecheck, d_zclass, d_nb_act, d_rt_mine, d_own_rt, d_own_pv, d_ele_pairs, d_a_chunk_group, d_ct_ptr, d_seg_ptr, d_seg_idx, d_hslot_ptr, d_hslot_idx, d_b_rowptr, d_b_ele, d_b_oth, d_a_rowptr, d_a_ele, d_a_oth, d_a_col, d_bl_ilist, d_bl_numneigh, d_bl_first, d_bl_neigh, d_ipiv, d_info, d_cg_done, d_iota, d_ele_csr_ptr, d_ele_csr_of, d_ele_csr_row;
   bool left_stale = false;          // the fused GEMV + charge write leaves the fix scalar's group-1 sum to refresh_scalar()
   double left_potdiff = 0.0;
   bool scalars_unfetched = false;   // conp_fix_scatter_device left this update's scalars on the device: compute_scalar brings them over
@@ -239,7 +219,7 @@ struct conp_fix : DevCtx {
     return rp;
   }
 
-  // what the k-space steps shared with EwaldQuery (conp_kspace_common.hpp) read of env
+  // what the k-space steps of EwaldQuery and PppmMesh (conp_kspace_common.hpp) read of env
   KspaceEnv kspace_env() const { return {env.g_ewald, env.qqrd2e, env.slabflag, env.zprd, env.slab_volfactor}; }
   // ---------------------------------------------------------------------------------------------
   void init_device() {
@@ -405,27 +385,7 @@ struct conp_fix : DevCtx {
   // fix_conp.cpp:393-424 linalg_init
   void linalg_init(const conp_atoms *at) {
     if (runstage != 0 || idx.initialised) return;
-    if (args.pppm) {
-      // fix_conp.cpp:401-404: the `pppm` keyword needs the pppm/conp kspace style; here: its mesh and order via conp_env
-      if (env.pppm_nx <= 0 || env.pppm_ny <= 0 || env.pppm_nz <= 0 || env.pppm_order <= 0)
-        throw ConpError(CONP_ERR_ARG, "Fix conp couldn't detect a pppm/conp kspace style (which is required with the pppm flag)");
-      // a mesh line is transformed in LDS: one that does not fit there (about 3400 points; 5120 for a length that is not
-      // 2,3,5-smooth) could not be launched at all -- refused here instead of at the first update
-      for (const int n : {env.pppm_nx, env.pppm_ny, env.pppm_nz})
-        if (pppm_line_lds_bytes(n) > PPPM_LDS_MAX)
-          throw ConpError(CONP_ERR_ARG, "pppm mesh of " + std::to_string(n) + " points along one axis: a line of it does not fit in the "
-                                        "LDS of a workgroup (" + std::to_string(pppm_line_lds_bytes(n)) + " > " + std::to_string(PPPM_LDS_MAX) + " bytes)");
-      const double lo[3] = {env.boxlo_x, env.boxlo_y, env.boxlo_z}, prd[3] = {env.xprd, env.yprd, env.zprd};
-      pppm.build(env.pppm_nx, env.pppm_ny, env.pppm_nz, env.pppm_order, env.g_ewald, env.slab_volfactor, lo, prd);
-      d_pp_coeff.upload(pppm.rho_coeff, stream); d_pp_green.upload(pppm.greensfn, stream);
-      d_pp_tw0.upload(pppm.twid[0], stream); d_pp_tw1.upload(pppm.twid[1], stream); d_pp_tw2.upload(pppm.twid[2], stream);
-      d_pp_re.reserve(pppm.nfft); d_pp_im.reserve(pppm.nfft); pp_im_clean = false;
-      dpppm.nx = pppm.nx; dpppm.ny = pppm.ny; dpppm.nz = pppm.nz; dpppm.order = pppm.order; dpppm.nlower = pppm.nlower;
-      dpppm.nfft = pppm.nfft; dpppm.shift = pppm.shift; dpppm.shiftone = pppm.shiftone; dpppm.delvolinv = pppm.delvolinv;
-      for (int c = 0; c < 3; ++c) { dpppm.delinv[c] = pppm.delinv[c]; dpppm.boxlo[c] = pppm.boxlo[c]; }
-      dpppm.rho_coeff = d_pp_coeff.p; dpppm.greensfn = d_pp_green.p;
-      dpppm.twid[0] = d_pp_tw0.p; dpppm.twid[1] = d_pp_tw1.p; dpppm.twid[2] = d_pp_tw2.p;
-    }
+    if (args.pppm) pm.build(env);
     double qn[2] = {0.0, (double)at->nlocal};              // km_ewald.cpp:72-78: sum q^2 over the owned atoms, Allreduce :77
     for (int i = 0; i < at->nlocal; i++) qn[0] += at->q[i] * at->q[i];
     rc.sum(qn, 2);                                         // (natoms = atom->natoms: the owned atoms of all ranks)
@@ -537,7 +497,7 @@ struct conp_fix : DevCtx {
     if (!idx.initialised) throw ConpError(CONP_ERR_STATE, "post_neighbor before setup_post_neighbor");
     if (!have_blist) throw ConpError(CONP_ERR_STATE, "post_neighbor: no neighbor list (init_list not called)");
     resident_step = -1;
-    pp_elyte_valid = pp_u_valid = false;
+    pm.invalidate();
     ew.invalidate();
     static const bool tren = getenv("CONP_TIME_REN") != nullptr;
     auto tm0 = std::chrono::steady_clock::now();
@@ -1352,18 +1312,7 @@ struct conp_fix : DevCtx {
     HIP_TRY(hipMemsetAsync(d_Tz.p, 0, (size_t)plan.C_pad * ne_pad * sizeof(double), stream));
     launch_ele_tables(stream, dplan, plan.kzt, ne, ne_pad, d_seeds.p, d_Xe.p, d_Ye.p, d_Tz.p, d_Rp.p);
     csk_h.clear(); snk_h.clear();                    // conp_fix_get_ele_trig reads the device tables back on request
-    if (args.pppm) {   // aaa_map_rho (pppm_conp.cpp:318-344): stencil weights and lower-left mesh index of every electrode atom
-      std::vector<int> eg((size_t)ne * 3);
-      std::vector<double> ew((size_t)ne * 24, 0.0);
-      for (int i = 0; i < ne; ++i)
-        for (int c = 0; c < 3; ++c) {
-          const double xlo = xele_h[3 * (size_t)i + c] - pppm.boxlo[c];
-          const int n = static_cast<int>(xlo * pppm.delinv[c] + pppm.shift) - PppmPlan::OFFSET;
-          eg[3 * (size_t)i + c] = n;
-          pppm.rho1d(n + pppm.shiftone - xlo * pppm.delinv[c], &ew[(size_t)i * 24 + 8 * c]);
-        }
-      d_pp_egrid.upload(eg, stream); d_pp_ew.upload(ew, stream);
-    }
+    if (args.pppm) pm.map_electrode(xele_h.data(), ne);
     // z classes: atoms with bitwise equal z share their Tz column
     {
       std::map<double, int> cls;
@@ -1921,7 +1870,7 @@ struct conp_fix : DevCtx {
   // through an index list: the owned ones out of dx / dq, or -- decomposed runs -- every rank's, gathered into d_xg / d_qg.
   void b_cal_device(const double *dx, const double *dq, bool coulyes, bool timed = false) {
     const int ne = idx.elenum_all;
-    pp_elyte_valid = pp_u_valid = false;          // positions / charges may have changed: the mesh caches are this update's or nobody's
+    pm.invalidate();                              // positions / charges may have changed: the mesh caches are this update's or nobody's
     ew.invalidate();                              // (so are the Ewald per-atom potentials)
     const double *ex = decomposed ? d_xg.p : dx, *eq = decomposed ? d_qg.p : dq;
     const int *eidx = decomposed ? d_iota.p : d_elyte_idx.p;
@@ -1938,25 +1887,17 @@ struct conp_fix : DevCtx {
     BRowArgs fin{}, pairs_keep{};
     if (args.pppm) {
       // `pppm` keyword: the k-space b comes from the mesh (pppm_conp.cpp:269-316); the mesh is not sharded -- rank 0 owns it
-      prof.begin("pppm_b", stream);
       // one rank: the real-space pair sums ride in the spread launch and the stencil gather completes the rows of b (slab term,
       // pair sums): no b_real_combine launch behind the mesh (round 4; CONP_TIME_SPLIT: as before)
-      const bool pp_fin = env.nranks == 1 && !nccl && !decomposed && !(timed && time_split);
+      const bool mesh_fin = env.nranks == 1 && !nccl && !decomposed && !(timed && time_split);
       BRowArgs pairs = make_brow(ne, ne_pad, rr0, rr1, d_b_rowptr.p, d_b_ele.p, d_b_oth.p, dx, dq, d_type.p, real_params(), 0,
                                  nullptr, 0, nullptr, nullptr, 0, 0.0, nullptr, nullptr);
       fin = make_brow(ne, ne_pad, rr0, rr1, d_b_rowptr.p, d_b_ele.p, d_b_oth.p, dx, dq, d_type.p, real_params(), 1, d_bk.p, slab,
                       d_ele_z.p, d_slab_part.p, 0, 4.0 * 3.14159265358979323846 / kt.volume, d_b, d_scalars.p + 2);
       fin.breal = d_breal.p;
-      if (env.rank == 0)
-        launch_pppm_b(stream, dpppm, nl, eidx, ex, eq, ne, ne_pad, d_pp_egrid.p, d_pp_ew.p, d_pp_re.p, d_pp_im.p,
-                      d_slab_part.p, &n_slab_part, d_bk.p, &pp_im_clean, pp_fin ? &pairs : nullptr, pp_fin ? d_breal.p : nullptr,
-                      pp_fin ? &fin : nullptr, pp_keep ? (d_pp_elyte.reserve((size_t)dpppm.nfft), d_pp_elyte.p) : nullptr);
-      else
-        d_bk.zero(stream);
-      ++pp_elyte_spreads;
-      pp_elyte_valid = pp_keep && env.rank == 0;
-      prof.end(stream);
-      use_fin = pp_fin;
+      pm.b(nl, eidx, ex, eq, ne, ne_pad, d_slab_part.p, &n_slab_part, d_bk, mesh_fin ? &pairs : nullptr, mesh_fin ? d_breal.p : nullptr,
+           mesh_fin ? &fin : nullptr, env.rank == 0);
+      use_fin = mesh_fin;
     } else {
       // the real-space pair sums depend on x, q only: they ride along in the phase kernel's launch (spare blocks) unless the
       // host-buffer hooks were asked to time the two halves of b_cal separately (CONP_TIME_SPLIT; Ktime / Ctime, fix_conp.cpp:553-568)
@@ -2395,12 +2336,13 @@ struct conp_fix : DevCtx {
   }
 
   // ---- the pair style with its half list (conp_pairstyle.cpp, DESIGN.md sections 16, 17), the ghost map (conp_ghostmap.cpp, 18),
-  // the harmonic bonds and angles (conp_bondedstyle.cpp, 21) and the exact-Ewald query entries (conp_ewaldquery.cpp, sections 11, 12,
-  // 14, 15) ----
+  // the harmonic bonds and angles (conp_bondedstyle.cpp, 21), the exact-Ewald query entries (conp_ewaldquery.cpp, sections 11, 12,
+  // 14, 15) and the PPPM mesh with the update's b and its query entries (conp_pppmmesh.cpp, sections 8, 13, 14, 15) ----
   PairStyle pair{*this};
   GhostMap ghost{*this};
   BondedStyle bonded{*this};
   EwaldQuery ew{*this, kt, plan, dplan, tiles_h, ct_ptr_h, d_sf_row_a, d_sf_col_c, d_k_sign};
+  PppmMesh pm{*this};
   bool types_in_range = false;                   // every atoms->type of the last (setup_)post_neighbor lies in [0, ntypes]
 
   // ---- the fix's re-neighbouring on the device (conp_reneigh.hip): Fix::post_neighbor without host arrays ------
@@ -2455,7 +2397,7 @@ struct conp_fix : DevCtx {
   void post_neighbor_device(const double *dx, const double *dq) {
     post_neighbor_device_check(dx, dq);
     resident_step = -1;
-    pp_elyte_valid = pp_u_valid = false;
+    pm.invalidate();
     ew.invalidate();
     const int nloc = nlocal_cur, ng = ghost.nghost, na = nloc + ng, ne = idx.elenum_all;
     sync();                                       // no kernel may be reading the tables that are replaced
@@ -2832,7 +2774,8 @@ int conp_fix_create(const conp_fix_args *args, const conp_env *env, conp_fix **o
   f->args = *args;
   f->env = *env;
   f->pair.env = {env->ntypes, env->newton_pair, env->g_ewald, env->qqrd2e};
-  f->ew.env = f->kspace_env();
+  f->ew.env = f->pm.env = f->kspace_env();
+  f->pm.xprd = env->xprd; f->pm.yprd = env->yprd;
   const size_t nc = (size_t)(env->ntypes + 1) * (env->ntypes + 1);
   f->cutsq_h.assign(env->cutsq, env->cutsq + nc);
   f->env.cutsq = nullptr;
@@ -3060,7 +3003,7 @@ int conp_fix_info(const conp_fix *f, conp_info *o) {
   int64_t nbp = f->n_b_pairs;
   if (f->np_pending) { HIP_TRY(hipStreamSynchronize(f->stream)); nbp = *f->h_np; }     // (the count of a regrouping still in flight)
   o->n_blist_pairs = nbp;
-  o->inverse_path = f->inverse_path; o->inverse_retries = f->inverse_retries; o->pppm_elyte_spreads = f->pp_elyte_spreads;
+  o->inverse_path = f->inverse_path; o->inverse_retries = f->inverse_retries; o->pppm_elyte_spreads = f->pm.elyte_spreads;
   const bool zn_on = f->zn_use() || f->zn_gen_use();
   o->zn_cols = zn_on ? 16 * f->zn_ncf : 0; o->zn_grid = zn_on ? f->zn_n : 0; o->zn_rows = zn_on ? 128 * (int)f->own_rt_h.size() : 0; o->n_alist_pairs = f->arows.npairs(); o->n_elyte_charged = f->nl;
   o->zn_ranges = zn_on ? f->zn_nrg : 0; o->hc_arithmetic = f->zn_use() && f->zn_frag_arith ? 1 : 0;
@@ -3282,236 +3225,35 @@ int64_t conp_host_pair_rows(int which, const conp_neighlist *l, const conp_atoms
   } catch (const std::exception &e) { last_error() = e.what(); return -1; }
 }
 
-// ---- PPPM coupling beyond b, compute potential/atom --------------------------------------------------------------------------
+// ---- the k-space query entries: PPPM coupling beyond b (PppmMesh), the exact Ewald sum (EwaldQuery), compute potential/atom ----
+// (static: the unnamed namespace alone does not keep a name inside extern "C" out of the library's dynamic symbols)
 namespace {
-void need_pppm(conp_fix *f) {
-  if (!f->args.pppm || f->dpppm.nfft <= 0)
+static void need_pppm(conp_fix *f) {
+  if (!f->args.pppm || !f->pm.ready())
     throw ConpError(CONP_ERR_STATE, "Compute requires a compatible KSpace provider like pppm/conp");   // compute_potential_atom.cpp:110
 }
-// Spatially decomposed ranks: the mesh potentials and density bricks are those of ALL atoms.  Every rank gathers the charged owned
-// atoms of all ranks -- (x, q, kind), ONE conp_comm gather per query -- and spreads them onto its own copy of the whole mesh: a
-// REPLICATED mesh (the reference's ranks own bricks of it and exchange ghost planes, pppm_conp.cpp:114,122 GridComm; the mesh of
-// the `pppm` mode is 10^5..10^6 points), so the collective call gives every rank the same brick and the potentials of its own
-// atoms.  The gathered atoms live in buffers of their OWN (d_pp_xg / d_pp_qg / d_pp_iota): the per-update electrolyte gather of the
-// decomposed b path keeps d_xg / d_qg / d_iota to itself.  counts[kind] / first[kind]: the atoms of a kind are one run of d_pp_iota
-// (0 electrolyte, 1 electrode); kind 2 = all = the whole list.
-struct PpGather { int n[3], first[3]; };
-PpGather pppm_gather_all(conp_fix *f, const conp_atoms *at) {
-  std::vector<double> pack;
-  for (int i = 0; i < at->nlocal; ++i) {
-    if (at->q[i] == 0) continue;
-    pack.push_back(at->x[3 * (size_t)i]); pack.push_back(at->x[3 * (size_t)i + 1]); pack.push_back(at->x[3 * (size_t)i + 2]);
-    pack.push_back(at->q[i]); pack.push_back(at->echeck[i] != 0 ? 1.0 : 0.0);
-  }
-  std::vector<int> counts(f->env.nranks, 0);
-  f->rc.allgather_int((int)(pack.size() / 5), counts.data());
-  int n = 0;
-  for (int v : counts) n += v;
-  std::vector<double> all((size_t)std::max(n, 1) * 5), xs((size_t)std::max(n, 1) * 3), qs(std::max(n, 1));
-  if (pack.empty()) pack.resize(5);
-  f->rc.gatherv(pack.data(), counts, 5, all.data());
-  std::vector<int> iota;
-  iota.reserve(std::max(n, 1));
-  PpGather g{};
-  for (int kind = 0; kind < 2; ++kind) {
-    g.first[kind] = (int)iota.size();
-    for (int k = 0; k < n; ++k) if ((all[5 * (size_t)k + 4] != 0.0) == (kind == 1)) iota.push_back(k);
-    g.n[kind] = (int)iota.size() - g.first[kind];
-  }
-  g.first[2] = 0; g.n[2] = n;
-  for (int k = 0; k < n; ++k) {
-    xs[3 * (size_t)k] = all[5 * (size_t)k]; xs[3 * (size_t)k + 1] = all[5 * (size_t)k + 1]; xs[3 * (size_t)k + 2] = all[5 * (size_t)k + 2];
-    qs[k] = all[5 * (size_t)k + 3];
-  }
-  if (iota.empty()) iota.push_back(0);
-  f->d_pp_iota.upload(iota, f->stream);
-  f->pp_iota_n = 0;
-  f->d_pp_xg.upload(xs, f->stream); f->d_pp_qg.upload(qs, f->stream);
-  f->sync();                       // (the host vectors go out of scope)
-  return g;
-}
-// index lists of the owned atoms that carry charge, by kind (0 electrolyte, 1 electrode, 2 all), and x, q on the device
-int pppm_list(conp_fix *f, const conp_atoms *at, int kind, DevBuf<int> &d_idx) {
-  std::vector<int> idx;
-  for (int i = 0; i < at->nlocal; ++i) {
-    if (at->q[i] == 0) continue;
-    if (kind == 0 && at->echeck[i] != 0) continue;
-    if (kind == 1 && at->echeck[i] == 0) continue;
-    idx.push_back(i);
-  }
-  const int n = (int)idx.size();
-  if (idx.empty()) idx.push_back(0);
-  d_idx.upload(idx, f->stream);
-  return n;
-}
-void pppm_upload(conp_fix *f, const conp_atoms *at) {
+// the atoms of `at` into the handle's d_x, d_q: what the host entries of the mesh hand to PppmMesh
+static void upload_atoms(conp_fix *f, const conp_atoms *at) {
   if (at->nlocal + at->nghost != f->nall) throw ConpError(CONP_ERR_STATE, "atom count changed without post_neighbor");
   f->resident_step = -1;
   f->upload_xq_n(at, f->nall);
 }
-// u_brick of the total density into d_pp_re (what PPPM::compute leaves there with per-atom energies on).  COLLECTIVE under ranks.
-void pppm_total_potential(conp_fix *f, const conp_atoms *at) {
-  DevBuf<int> d_idx;
-  pppm_upload(f, at);
-  f->d_pp_scratch.reserve(2048);
-  if (f->decomposed) {
-    const PpGather g = pppm_gather_all(f, at);
-    launch_pppm_density(f->stream, f->dpppm, g.n[2], f->d_pp_iota.p, f->d_pp_xg.p, f->d_pp_qg.p, f->d_pp_re.p, f->d_pp_scratch.p);
-  } else {
-    const int n = pppm_list(f, at, 2, d_idx);
-    launch_pppm_density(f->stream, f->dpppm, n, d_idx.p, f->d_x.p, f->d_q.p, f->d_pp_re.p, f->d_pp_scratch.p);
-  }
-  ++f->pp_elyte_spreads;
-  launch_pppm_poisson(f->stream, f->dpppm, f->d_pp_re.p, f->d_pp_im.p); f->pp_im_clean = false;
-  HIP_TRY(hipGetLastError());
-  f->sync();                       // d_idx goes out of scope
-  f->pp_u_valid = true;
-}
-
-// ---- Ewald per-atom potential (conp_potential.hip) ----
-void need_ewald(conp_fix *f) {
+static void need_ewald(conp_fix *f) {
   if (f->args.pppm)
     throw ConpError(CONP_ERR_STATE, "conp_ewald_*: this handle's k-space provider is pppm/conp -- use conp_pppm_compute / "
                                     "conp_pppm_compute_group_potential / conp_pppm_compute_particle_potential");
   if (!f->kspace_ready) throw ConpError(CONP_ERR_STATE, "conp_ewald_*: no k-space tables yet (setup_post_neighbor or conp_km_conp_setup)");
 }
 // the handle's check -- before anything is uploaded -- then w o G of the atoms of `at` (EwaldQuery::structure_factor)
-// (static: the unnamed namespace alone does not keep a name inside extern "C" out of the library's dynamic symbols)
 static void ewald_structure_factor(conp_fix *f, const conp_atoms *at) {
   if (at->nlocal + at->nghost != f->nall) throw ConpError(CONP_ERR_STATE, "atom count changed without post_neighbor");
   f->ew.structure_factor(at);
 }
-// the mesh's box: L = the slab-extended z period, V, the unit wave vectors
-struct PppmGeom { double L, V, uk[3]; };
-static PppmGeom pppm_geometry(const conp_fix *f) {
-  const double L = f->env.zprd * f->env.slab_volfactor;
-  return PppmGeom{L, f->env.xprd * f->env.yprd * L, {2.0 * MY_PI / f->env.xprd, 2.0 * MY_PI / f->env.yprd, 2.0 * MY_PI / L}};
-}
-// The mesh solve of the force entries, from the density brick in d_pp_re, in two halves (the device entry gathers the per-atom
-// virial between them).  pppm_mesh_spectra: forward transform; with vb, the six v_ab fields into d_pp_v[] and their pointers into
-// vb (rho^ is still in (re, im) then: the kspace launch overwrites it).  pppm_mesh_forces: pppm_kspace_kernel -- the seven sums
-// into d_pp_kpart[0..6]; d_ev: energy and virial from them (kspace_finish_kernel) -- then, with want_u, u and E_z back into
-// (d_pp_re, d_pp_im) and, with fields, E_x and E_y into (d_pp_ex, d_pp_ey).  The event brackets record under conp_fix_profile only.
-static void pppm_mesh_spectra(conp_fix *f, const PppmGeom &gm, bool fields, double **vb /*[6], or NULL: no per-atom virial*/) {
-  const size_t nf = (size_t)f->dpppm.nfft;
-  if (fields) { f->d_pp_ex.reserve(nf); f->d_pp_ey.reserve(nf); }
-  f->d_pp_kpart.reserve((size_t)7 * (pppm_kspace_workgroups(f->dpppm.nfft) + 1));
-  f->prof.begin("pppm_f_forward", f->stream);
-  launch_pppm_forward(f->stream, f->dpppm, f->d_pp_re.p, f->d_pp_im.p);
-  f->prof.end(f->stream);
-  if (!vb) return;
-  for (int c = 0; c < 6; ++c) { f->d_pp_v[c].reserve(nf); vb[c] = f->d_pp_v[c].p; }
-  launch_pppm_vatom_spectra(f->stream, f->dpppm, gm.uk, f->env.g_ewald, f->d_pp_re.p, f->d_pp_im.p, vb);
-  for (int c = 0; c < 6; c += 2) launch_pppm_backward(f->stream, f->dpppm, vb[c], vb[c + 1]);
-}
-static void pppm_mesh_forces(conp_fix *f, const PppmGeom &gm, bool fields, bool want_u, double *d_ev /*[7], or NULL*/) {
-  f->prof.begin("pppm_f_kspace", f->stream);
-  launch_pppm_kspace(f->stream, f->dpppm, gm.uk, f->env.g_ewald, gm.V, f->d_pp_re.p, f->d_pp_im.p, fields ? f->d_pp_ex.p : nullptr,
-                     fields ? f->d_pp_ey.p : nullptr, f->d_pp_kpart.p + 7, f->d_pp_kpart.p);
-  f->prof.end(f->stream);
-  f->pp_im_clean = false;
-  if (d_ev) launch_kspace_finish(f->stream, kspace_finish_args(f->kspace_env(), gm.V, gm.L), f->d_pp_kpart.p, f->d_kf_sums.p, d_ev);
-  if (!want_u) return;
-  f->prof.begin("pppm_f_backward", f->stream);
-  launch_pppm_backward(f->stream, f->dpppm, f->d_pp_re.p, f->d_pp_im.p);
-  if (fields) launch_pppm_backward(f->stream, f->dpppm, f->d_pp_ex.p, f->d_pp_ey.p);
-  f->prof.end(f->stream);
-}
-// ---- PPPM forces, energy, virial ----
-// PPPM::compute with ik differentiation on the handle's mesh, at the positions and charges of `at`: the brick of every charged atom is
-// spread afresh on every call (a kept electrolyte brick is that of the update's positions: never contracted with atoms that may have
-// moved), forward transform, pppm_kspace_kernel, two packed backward transforms, pppm_force_gather_kernel on the charged owned atoms.
-// COLLECTIVE under decomposed ranks like pppm_total_potential (one tagged gather, a replicated mesh) plus the four sums.  Leaves u in
-// d_pp_re (pp_u_valid), as conp_pppm_compute does.  vatom: [nlocal][6], overwritten: the per-atom virial.
-void pppm_forces(conp_fix *f, const conp_atoms *at, double *fout, double *energy, double *virial, double *eatom, double *vatom) {
-  const PppmGeom gm = pppm_geometry(f);
-  std::vector<int> idx;
-  double four[4];                                     // Q, Q2, M, M2
-  charged_owned(at, idx, four);
-  const int n = (int)idx.size();
-  pppm_upload(f, at);
-  f->d_pp_scratch.reserve(2048);
-  if (f->decomposed) {
-    const PpGather ga = pppm_gather_all(f, at);
-    f->rc.sum(four, 4);
-    launch_pppm_density(f->stream, f->dpppm, ga.n[2], f->d_pp_iota.p, f->d_pp_xg.p, f->d_pp_qg.p, f->d_pp_re.p, f->d_pp_scratch.p);
-  }
-  if (idx.empty()) idx.push_back(0);
-  f->d_pp_fidx.upload(idx, f->stream);
-  if (!f->decomposed) {
-    f->prof.begin("pppm_f_spread", f->stream);
-    launch_pppm_density(f->stream, f->dpppm, n, f->d_pp_fidx.p, f->d_x.p, f->d_q.p, f->d_pp_re.p, f->d_pp_scratch.p);
-    f->prof.end(f->stream);
-  }
-  ++f->pp_elyte_spreads;
-  f->pp_u_valid = false;
-  const bool fields = fout != nullptr && n > 0, want_v = vatom != nullptr && n > 0, per_atom = n > 0 && (fout || eatom);
-  double *vb[6];
-  pppm_mesh_spectra(f, gm, fields, want_v ? vb : nullptr);
-  pppm_mesh_forces(f, gm, fields, true, nullptr);
-  double s7[7];
-  HIP_TRY(hipMemcpyAsync(s7, f->d_pp_kpart.p, 7 * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-  if (want_v) {
-    f->d_pp_vo.reserve(6 * (size_t)at->nlocal);
-    launch_pppm_vatom_gather(f->stream, f->dpppm, n, f->d_pp_fidx.p, f->d_x.p, f->d_q.p, vb, f->env.qqrd2e, f->d_pp_vo.p);
-  }
-  if (per_atom) {
-    if (fout) f->d_pp_fo.reserve(3 * (size_t)at->nlocal);
-    if (eatom) f->d_pp_eo.reserve(at->nlocal);
-    f->prof.begin("pppm_f_gather", f->stream);
-    launch_pppm_force_gather(f->stream, f->dpppm, n, f->d_pp_fidx.p, f->d_x.p, f->d_q.p, fout ? f->d_pp_ex.p : nullptr, f->d_pp_ey.p,
-                             f->d_pp_im.p, f->d_pp_re.p, kspace_out_args(f->kspace_env(), gm.V, gm.L, four), fout ? f->d_pp_fo.p : nullptr,
-                             eatom ? f->d_pp_eo.p : nullptr);
-    f->prof.end(f->stream);
-  }
-  if (eatom) std::fill(eatom, eatom + at->nlocal, 0.0);
-  if (vatom) std::fill(vatom, vatom + 6 * (size_t)at->nlocal, 0.0);
-  download_scatter(*f, at->nlocal, idx, n, per_atom && fout ? f->d_pp_fo.p : nullptr, per_atom && eatom ? f->d_pp_eo.p : nullptr,
-                   want_v ? f->d_pp_vo.p : nullptr, fout, eatom, vatom);
-  f->pp_u_valid = true;
-  if (f->decomposed) {
-    // every rank spread the same atoms, but a mesh point's contributions arrive in no fixed order (atomic adds): the bricks agree to
-    // rounding only.  Rank 0's sums are everybody's (x + 0 + .. + 0 = x): the same energy and virial on every rank, bit for bit.
-    if (f->env.rank != 0) std::fill(s7, s7 + 7, 0.0);
-    f->rc.sum(s7, 7);
-  }
-  if (energy) *energy = kspace_energy(f->kspace_env(), s7[0], four[0], four[1], four[2], four[3], gm.V, gm.L);
-  if (virial) for (int c = 0; c < 6; ++c) virial[c] = f->env.qqrd2e * s7[1 + c];
-}
-// ---- device-resident k-space forces ----
-// pppm_forces on the caller's device arrays: the brick of every owned atom through the identity list, the mesh solve, the gather
-// on every owned atom; the seven sums stay on the device (kspace_finish_kernel reads them).  dvatom: [nlocal][6], overwritten.
-void pppm_forces_device(conp_fix *f, const double *dx, const double *dq, double *df, double *dev, double *deatom, double *dvatom) {
-  const PppmGeom gm = pppm_geometry(f);
-  const int n = f->nlocal_cur;
-  if (n <= 0) { if (dev) HIP_TRY(hipMemsetAsync(dev, 0, 7 * sizeof(double), f->stream)); return; }
-  if (f->pp_iota_n < n) {
-    std::vector<int> iota(n);
-    for (int i = 0; i < n; ++i) iota[i] = i;
-    f->d_pp_iota.upload(iota, f->stream);
-    f->sync();                       // (iota goes out of scope)
-    f->pp_iota_n = n;
-  }
-  f->d_pp_scratch.reserve(2048);
-  f->pp_u_valid = false;             // d_pp_re is overwritten from here on
-  launch_pppm_density(f->stream, f->dpppm, n, f->d_pp_iota.p, dx, dq, f->d_pp_re.p, f->d_pp_scratch.p);
-  ++f->pp_elyte_spreads;
-  kspace_four_sums(*f, f->d_kf_sums, n, dx, dq);
-  const bool fields = df != nullptr, per_atom = df || deatom;
-  double *vb[6];
-  pppm_mesh_spectra(f, gm, fields, dvatom ? vb : nullptr);
-  if (dvatom) launch_pppm_vatom_gather(f->stream, f->dpppm, n, nullptr, dx, dq, vb, f->env.qqrd2e, dvatom);
-  pppm_mesh_forces(f, gm, fields, per_atom, dev);
-  if (per_atom)
-    launch_pppm_force_gather_device(f->stream, f->dpppm, n, dx, dq, fields ? f->d_pp_ex.p : nullptr, f->d_pp_ey.p, f->d_pp_im.p,
-                                    f->d_pp_re.p, kspace_out_args(f->kspace_env(), gm.V, gm.L, nullptr), f->d_kf_sums.p, df, deatom);
-  HIP_TRY(hipGetLastError());
-}
 // the k-space tail of compute potential/atom (compute_potential_atom.cpp:165-175, slab correction :323-345) on the selected owned
 // atoms idx (ascending), whichever provider formed u_i: pot_i -= u_i, + the Gaussian self term of eta atoms, + the slab terms
 // (the sums of q z and q over the owned atoms all-reduced, MPI_Allreduce :331, :337)
-void potential_atom_tail(conp_fix *f, const conp_atoms *at, const conp_potential_args *pa, const int *etasel, const std::vector<int> &idx,
-                         const std::vector<double> &uk, std::vector<double> &pot) {
+static void potential_atom_tail(conp_fix *f, const conp_atoms *at, const conp_potential_args *pa, const int *etasel,
+                                const std::vector<int> &idx, const std::vector<double> &uk, std::vector<double> &pot) {
   for (int i : idx) {
     pot[i] -= uk[i];
     if (pa->eta != 0.0 && etasel[i]) pot[i] += pa->eta * at->q[i] * std::sqrt(2.0) / MY_PIS;
@@ -3534,14 +3276,12 @@ void potential_atom_tail(conp_fix *f, const conp_atoms *at, const conp_potential
 
 // PPPMCONP keeps the electrolyte brick of every b_cal for its make_rho override (pppm_conp.cpp:172-228, 434-450; elyte_mapped is
 // reset by conp_pre_force, pppm_conp.h:42).  on != 0: from the next b_cal on the brick of the update is kept on the device
-// (d_pp_elyte) and conp_pppm_make_rho adds the electrode brick to it instead of spreading the electrolyte again; the call itself
-// drops whatever brick is cached (a new step begins).
+// and conp_pppm_make_rho adds the electrode brick to it instead of spreading the electrolyte again; the call itself drops whatever
+// brick is cached (a new step begins).
 int conp_pppm_keep_density(conp_fix *f, int on) {
   CONP_GUARD_BEGIN
   need_pppm(f);
-  f->pp_keep = on != 0;
-  f->pp_elyte_valid = false;
-  f->pp_u_valid = false;
+  f->pm.keep_density(on != 0);
   CONP_GUARD_END
 }
 
@@ -3552,7 +3292,8 @@ int conp_pppm_compute(conp_fix *f, const conp_atoms *at) {
   CONP_GUARD_BEGIN
   f->drop_graph();
   need_pppm(f);
-  pppm_total_potential(f, at);
+  upload_atoms(f, at);
+  f->pm.total_potential(at, f->d_x.p, f->d_q.p);
   CONP_GUARD_END
 }
 
@@ -3560,41 +3301,8 @@ int conp_pppm_make_rho(conp_fix *f, const conp_atoms *at, double *density, doubl
   CONP_GUARD_BEGIN
   f->drop_graph();
   need_pppm(f);
-  pppm_upload(f, at);
-  const size_t nf = (size_t)f->dpppm.nfft;
-  f->d_pp_scratch.reserve(2048);
-  f->d_pp_ele.reserve(nf);
-  std::vector<double> e(nf), l(nf);
-  DevBuf<int> d_idx0, d_idx1;
-  PpGather g{};
-  if (f->decomposed) g = pppm_gather_all(f, at);          // ONE gather, the atoms tagged with their kind
-  {
-    if (f->decomposed)
-      launch_pppm_density(f->stream, f->dpppm, g.n[1], f->d_pp_iota.p + g.first[1], f->d_pp_xg.p, f->d_pp_qg.p, f->d_pp_ele.p, f->d_pp_scratch.p);
-    else {
-      const int n = pppm_list(f, at, 1, d_idx1);          // ele_make_rho (pppm_conp.cpp:385-426)
-      launch_pppm_density(f->stream, f->dpppm, n, d_idx1.p, f->d_x.p, f->d_q.p, f->d_pp_ele.p, f->d_pp_scratch.p);
-    }
-    HIP_TRY(hipMemcpyAsync(e.data(), f->d_pp_ele.p, nf * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-  }
-  if (f->pp_elyte_valid && !f->decomposed) {
-    // the brick b_cal left for this step (elyte_mapped, pppm_conp.cpp:437-442): no second spread of the electrolyte
-    HIP_TRY(hipMemcpyAsync(l.data(), f->d_pp_elyte.p, nf * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-  } else {
-    if (f->decomposed)
-      launch_pppm_density(f->stream, f->dpppm, g.n[0], f->d_pp_iota.p + g.first[0], f->d_pp_xg.p, f->d_pp_qg.p, f->d_pp_re.p, f->d_pp_scratch.p);
-    else {
-      const int n = pppm_list(f, at, 0, d_idx0);          // elyte_make_rho (:172-228)
-      launch_pppm_density(f->stream, f->dpppm, n, d_idx0.p, f->d_x.p, f->d_q.p, f->d_pp_re.p, f->d_pp_scratch.p);
-    }
-    ++f->pp_elyte_spreads;
-    f->pp_u_valid = false;                                 // (d_pp_re holds a density now)
-    HIP_TRY(hipMemcpyAsync(l.data(), f->d_pp_re.p, nf * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-  }
-  f->sync();
-  if (ele_density) std::memcpy(ele_density, e.data(), nf * sizeof(double));
-  if (elyte_density) std::memcpy(elyte_density, l.data(), nf * sizeof(double));
-  if (density) for (size_t k = 0; k < nf; ++k) density[k] = l[k] + e[k];        // make_rho override :434-450
+  upload_atoms(f, at);
+  f->pm.make_rho(at, f->d_x.p, f->d_q.p, density, ele_density, elyte_density);
   CONP_GUARD_END
 }
 
@@ -3603,19 +3311,13 @@ int conp_pppm_compute_group_potential(conp_fix *f, const conp_atoms *at, const i
   f->drop_graph();
   need_pppm(f);
   if (!sel || !recv) throw ConpError(CONP_ERR_ARG, "null argument");
-  pppm_total_potential(f, at);
+  upload_atoms(f, at);
+  f->pm.total_potential(at, f->d_x.p, f->d_q.p);
   std::vector<int> idx;
   for (int i = 0; i < at->nlocal; ++i) if (sel[i]) idx.push_back(i);
-  if (idx.empty()) return CONP_OK;
-  DevBuf<int> d_idx;
-  DevBuf<double> d_out;
-  d_idx.upload(idx, f->stream);
-  d_out.reserve(at->nlocal);
-  launch_pppm_probe(f->stream, f->dpppm, (int)idx.size(), d_idx.p, f->d_x.p, f->d_q.p, f->d_pp_re.p, 0.0, d_out.p);
-  std::vector<double> out(at->nlocal);
-  HIP_TRY(hipMemcpyAsync(out.data(), d_out.p, (size_t)at->nlocal * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-  f->sync();
-  for (int i : idx) recv[i] = out[i];
+  std::vector<double> out(idx.size());
+  f->pm.probe(idx, f->d_x.p, f->d_q.p, 0.0, out.data());
+  for (size_t k = 0; k < idx.size(); ++k) recv[idx[k]] = out[k];
   CONP_GUARD_END
 }
 
@@ -3628,25 +3330,18 @@ int conp_pppm_compute_particle_potential(conp_fix *f, const conp_atoms *at, int 
   f->drop_graph();
   need_pppm(f);
   if (!u || i < 0 || i >= at->nlocal) throw ConpError(CONP_ERR_ARG, "atom index out of range");
-  if (!f->pp_u_valid) {
+  if (!f->pm.u_valid) {
     if (f->decomposed || f->env.nranks > 1)
       throw ConpError(CONP_ERR_STATE, "pppm/conp/hip: compute_particle_potential is rank-local -- under several MPI ranks the mesh potential "
                                       "has to be formed by a collective call first (conp_pppm_compute / compute_group_potential)");
-    pppm_total_potential(f, at);
+    upload_atoms(f, at);
+    f->pm.total_potential(at, f->d_x.p, f->d_q.p);
   }
   if (at->nlocal + at->nghost != f->nall) throw ConpError(CONP_ERR_STATE, "atom count changed without post_neighbor");
   // the atom's CURRENT position and charge (4 doubles), the brick as it is
   HIP_TRY(hipMemcpyAsync(f->d_x.p + 3 * (size_t)i, at->x + 3 * (size_t)i, 3 * sizeof(double), hipMemcpyHostToDevice, f->stream));
   HIP_TRY(hipMemcpyAsync(f->d_q.p + i, at->q + i, sizeof(double), hipMemcpyHostToDevice, f->stream));
-  std::vector<int> idx(1, i);
-  DevBuf<int> d_idx;
-  DevBuf<double> d_out;
-  d_idx.upload(idx, f->stream);
-  d_out.reserve(at->nlocal);
-  launch_pppm_probe(f->stream, f->dpppm, 1, d_idx.p, f->d_x.p, f->d_q.p, f->d_pp_re.p,
-                    2.0 * f->env.g_ewald / 1.77245385090551602729, d_out.p);
-  HIP_TRY(hipMemcpyAsync(u, d_out.p + i, sizeof(double), hipMemcpyDeviceToHost, f->stream));
-  f->sync();
+  f->pm.probe(std::vector<int>(1, i), f->d_x.p, f->d_q.p, 2.0 * f->env.g_ewald / MY_PIS, u);
   CONP_GUARD_END
 }
 
@@ -3733,11 +3428,12 @@ static int pppm_compute_forces_entry(const char *entry, conp_fix *f, const conp_
     throw ConpError(CONP_ERR_STATE, std::string(entry) + ": this handle's k-space provider is the Ewald sum -- use conp_ewald" +
                                         (entry + std::strlen("conp_pppm")));
   need_pppm(f);
-  pppm_forces(f, at, fout, energy, virial, eatom, vatom);
+  upload_atoms(f, at);
+  f->pm.forces(at, f->d_x.p, f->d_q.p, fout, energy, virial, eatom, vatom);
   CONP_GUARD_END
 }
 // what the device entries refuse, in this order
-void kspace_device_check(conp_fix *f, void (*need)(conp_fix *), const double *dx, const double *dq) {
+static void kspace_device_check(conp_fix *f, void (*need)(conp_fix *), const double *dx, const double *dq) {
   if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
   f->drop_graph();
   need(f);
@@ -3776,7 +3472,7 @@ int conp_pppm_compute_forces_vatom_device(conp_fix *f, const double *d_x, const 
   CONP_GUARD_BEGIN
   kspace_device_check(f, need_pppm, d_x, d_q);
   if (!d_f && !d_ev && !d_eatom && !d_vatom) return CONP_OK;
-  pppm_forces_device(f, d_x, d_q, d_f, d_ev, d_eatom, d_vatom);
+  f->pm.forces_device(f->nlocal_cur, d_x, d_q, d_f, d_ev, d_eatom, d_vatom);
   CONP_GUARD_END
 }
 
@@ -3953,9 +3649,9 @@ int conp_compute_potential_atom(conp_fix *f, const conp_atoms *at, const conp_ne
   if (pa->kspaceflag) { if (f->args.pppm) need_pppm(f); else need_ewald(f); }    // mesh provider, or the exact Ewald sum
   const int nall = at->nlocal + at->nghost;
   const int ntotal = at->nlocal + (f->env.newton_pair ? at->nghost : 0);
-  pppm_upload(f, at);
+  upload_atoms(f, at);
   DevBuf<double> d_pot;
-  DevBuf<int> d_sel, d_eta, d_il, d_nn, d_first, d_neigh, d_idx;
+  DevBuf<int> d_sel, d_eta, d_il, d_nn, d_first, d_neigh;
   d_pot.reserve(nall); d_pot.zero(f->stream);
   d_sel.upload(sel, nall, f->stream);
   std::vector<int> ez(nall, 0);
@@ -3981,30 +3677,13 @@ int conp_compute_potential_atom(conp_fix *f, const conp_atoms *at, const conp_ne
     f->sync();
     potential_atom_tail(f, at, pa, etasel, idx, uk, pot);
   } else if (pa->kspaceflag) {
-    std::vector<int> all;
-    for (int i = 0; i < at->nlocal; ++i) if (at->q[i] != 0) all.push_back(i);
-    const int n = (int)all.size();
-    if (all.empty()) all.push_back(0);
-    d_idx.upload(all, f->stream);
-    f->d_pp_scratch.reserve(2048);
-    if (f->decomposed) {           // all ranks' charged atoms on this rank's copy of the mesh (pppm_gather_all)
-      const PpGather g = pppm_gather_all(f, at);
-      launch_pppm_density(f->stream, f->dpppm, g.n[2], f->d_pp_iota.p, f->d_pp_xg.p, f->d_pp_qg.p, f->d_pp_re.p, f->d_pp_scratch.p);
-    } else
-      launch_pppm_density(f->stream, f->dpppm, n, d_idx.p, f->d_x.p, f->d_q.p, f->d_pp_re.p, f->d_pp_scratch.p);
-    launch_pppm_poisson(f->stream, f->dpppm, f->d_pp_re.p, f->d_pp_im.p); f->pp_im_clean = false;
-    ++f->pp_elyte_spreads; f->pp_u_valid = true;
+    // mesh handle: u_i from the mesh potential of every charged atom (COLLECTIVE under decomposed ranks), gathered at the selection
+    f->pm.total_potential(at, f->d_x.p, f->d_q.p);
     std::vector<int> idx;
     for (int i = 0; i < at->nlocal; ++i) if (sel[i]) idx.push_back(i);
-    DevBuf<int> d_pidx;
-    DevBuf<double> d_uk;
-    d_uk.reserve(std::max(at->nlocal, 1));
-    if (!idx.empty()) {
-      d_pidx.upload(idx, f->stream);
-      launch_pppm_probe(f->stream, f->dpppm, (int)idx.size(), d_pidx.p, f->d_x.p, f->d_q.p, f->d_pp_re.p,
-                        2.0 * f->env.g_ewald / 1.77245385090551602729, d_uk.p);
-      HIP_TRY(hipMemcpyAsync(uk.data(), d_uk.p, (size_t)at->nlocal * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-    }
+    std::vector<double> u(idx.size());
+    f->pm.probe(idx, f->d_x.p, f->d_q.p, 2.0 * f->env.g_ewald / MY_PIS, u.data());
+    for (size_t k = 0; k < idx.size(); ++k) uk[idx[k]] = u[k];
     HIP_TRY(hipMemcpyAsync(pot.data(), d_pot.p, (size_t)nall * sizeof(double), hipMemcpyDeviceToHost, f->stream));
     f->sync();
     potential_atom_tail(f, at, pa, etasel, idx, uk, pot);
@@ -4027,7 +3706,7 @@ int conp_fix_set_comm(conp_fix *f, const conp_comm *comm) {
   f->rc.c = *comm; f->rc.have = true; f->rc.rank_ = comm->rank; f->rc.nranks_ = comm->nranks;
   f->env.rank = comm->rank; f->env.nranks = comm->nranks;
   f->decomposed = true;
-  f->ew.ranks = &f->rc;
+  f->ew.ranks = f->pm.ranks = &f->rc;
   CONP_GUARD_END
 }
 

@@ -7,6 +7,7 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -116,6 +117,10 @@ struct RankOps {
     for (int i = 0; i < n; ++i) recv[i] = send[i];
   }
   virtual void sum(double *, int64_t) {}
+  // rank r contributes items[r] * w doubles; recv holds them rank-major
+  virtual void gatherv(const double *send, const std::vector<int> &items, int w, double *recv) {
+    std::memcpy(recv, send, (size_t)items[0] * w * sizeof(double));
+  }
 };
 
 // ------------------------------------------------------------------------------------------------

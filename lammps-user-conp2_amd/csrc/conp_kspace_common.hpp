@@ -1,5 +1,5 @@
 // The provider-independent steps of the k-space query entries (DESIGN.md sections 11-15): what the exact Ewald entries
-// (conp_ewaldquery.cpp) and the PPPM entries (conp_fix.cpp) share.  Header-only; nothing down to kspace_out_args makes a HIP call.
+// (conp_ewaldquery.cpp) and the PPPM entries (conp_pppmmesh.cpp) share.  Header-only; nothing down to kspace_out_args makes a HIP call.
 #pragma once
 #include <cmath>
 #include <vector>

@@ -225,3 +225,55 @@ def test_per_atom_potential_reads_the_cached_brick_and_the_kept_electrolyte_bric
     b2 = fx.km_b_cal(at)
     assert rel_err(b2, b1) < 1e-12
     fx.close()
+
+
+def test_mesh_cache_follows_every_entry_that_writes_the_brick():
+    """The mesh's cache state (potential / density / nothing usable) after each entry that writes the brick, seen through the spread
+    counter and the per-atom entry: it gathers from a brick that holds the potential of the total density and re-forms one that
+    does not.  Equal values: a re-spread brick adds with f64 atomics in no fixed order (rel 1e-12, as the test above)."""
+    import torch
+    s, at, alist, blist, fx = _pppm_handle("dilute", "ffield", (27, 24, 144), 5)
+    n = 27 * 24 * 144
+    i = int(np.nonzero(at.echeck[:at.nlocal] == 1)[0][2])
+    spreads = lambda: fx.info().pppm_elyte_spreads
+    same = lambda u: u == pytest.approx(u0, rel=1e-12, abs=1e-14)
+    # 1. the collective entry leaves the potential: the per-atom entry gathers
+    fx.pppm_compute(at)
+    c = spreads()
+    u0 = fx.pppm_particle_potential(at, i)
+    assert spreads() == c
+    # 2. the device force entry spreads once and leaves no potential the cache may serve: the per-atom entry re-forms the brick
+    d_x = torch.from_numpy(np.ascontiguousarray(at.x, dtype=np.float64)).cuda()
+    d_q = torch.from_numpy(np.ascontiguousarray(at.q, dtype=np.float64)).cuda()
+    d_f = torch.zeros((at.nlocal, 3), dtype=torch.float64, device="cuda")
+    d_ev = torch.zeros(7, dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    fx.pppm_forces_device(d_x.data_ptr(), d_q.data_ptr(), d_f.data_ptr(), d_ev.data_ptr())
+    u = fx.pppm_particle_potential(at, i)
+    print("after forces_device:", spreads() - c, u - u0)
+    assert spreads() == c + 2 and same(u)
+    # 3. the host force entry leaves the potential
+    fx.pppm_compute_forces(at)
+    c = spreads()
+    u = fx.pppm_particle_potential(at, i)
+    print("after compute_forces:", spreads() - c, u - u0)
+    assert spreads() == c and same(u)
+    # 4. make_rho with nothing kept leaves a density
+    fx.pppm_make_rho(at, n)
+    c = spreads()
+    u = fx.pppm_particle_potential(at, i)
+    print("after make_rho:", spreads() - c, u - u0)
+    assert spreads() == c + 1 and same(u)
+    # 5. potential/atom's k-space part leaves the potential
+    fx.compute_potential_atom(at, blist, np.ones(at.nlocal + at.nghost, np.int32), pair=False, kspace=True)
+    c = spreads()
+    u = fx.pppm_particle_potential(at, i)
+    print("after potential/atom:", spreads() - c, u - u0)
+    assert spreads() == c and same(u)
+    # 6. an update's b overwrites it
+    fx.km_b_cal(at)
+    c = spreads()
+    fx.pppm_particle_potential(at, i)
+    print("after km_b_cal:", spreads() - c)
+    assert spreads() == c + 1
+    fx.close()

@@ -61,6 +61,9 @@ def _decomposed_worker(rank, world, port, name, axis, solver, out):
         rho, rho_e, rho_l = fx.pppm_make_rho(at, nfft)
         sel = (at.echeck[:at.nlocal] != 0).astype(np.int32)
         pot = fx.pppm_group_potential(at, sel)
+        # compute potential/atom's k-space part on the mesh handle: collective too (its own spread of all ranks' atoms, the slab
+        # sums all-reduced), the values of this rank's electrode atoms
+        patom = fx.compute_potential_atom(at, blist, np.ones(at.nlocal + at.nghost, np.int32), pair=False, kspace=True, qsum=True)
         # the per-atom entry is RANK-LOCAL (pppm_conp.cpp:452-485: compute potential/atom calls it once per owned group atom, a
         # different number of times on every rank): rank r asks r + 1 times after the collective entry above left the brick --
         # no collective inside, so nothing hangs --, and each value is the group entry's + 2 g q / sqrt(pi)
@@ -79,7 +82,8 @@ def _decomposed_worker(rank, world, port, name, axis, solver, out):
         except Exception as e:
             refused = "collective" in str(e)
         assert refused or not len(idx)
-        mesh = dict(rho=rho, rho_e=rho_e, pot={int(t): float(v) for t, v, e in zip(at.tag[:at.nlocal], pot, sel) if e})
+        mesh = dict(rho=rho, rho_e=rho_e, pot={int(t): float(v) for t, v, e in zip(at.tag[:at.nlocal], pot, sel) if e},
+                    patom={int(t): float(v) for t, v, e in zip(at.tag[:at.nlocal], patom, sel) if e})
     out[rank] = dict(q0=q0, q1=q1, sc0=sc0, sc1=fx.compute_scalar(), ek=ek, S=S, eleall2tag=m["eleall2tag"].copy(), mesh=mesh,
                      info=(fx.info().elenum, fx.info().elenum_all, fx.info().n_elyte_charged))
     fx.close()
@@ -117,7 +121,9 @@ def test_decomposed_ranks_match_one_rank(name, axis, world, solver):
         rho, rho_e, _ = fx.pppm_make_rho(at, 27 * 24 * 144)
         sel = (at.echeck[:at.nlocal] != 0).astype(np.int32)
         pot = fx.pppm_group_potential(at, sel)
-        mesh1 = dict(rho=rho, rho_e=rho_e, pot={int(t): float(v) for t, v, e in zip(at.tag[:at.nlocal], pot, sel) if e})
+        patom = fx.compute_potential_atom(at, blist, np.ones(at.nlocal + at.nghost, np.int32), pair=False, kspace=True, qsum=True)
+        mesh1 = dict(rho=rho, rho_e=rho_e, pot={int(t): float(v) for t, v, e in zip(at.tag[:at.nlocal], pot, sel) if e},
+                     patom={int(t): float(v) for t, v, e in zip(at.tag[:at.nlocal], patom, sel) if e})
     fx.close()
     mgr = mp.Manager(); out = mgr.dict()
     port = 29600 + (os.getpid() + 7 * axis + world) % 300
@@ -138,15 +144,19 @@ def test_decomposed_ranks_match_one_rank(name, axis, world, solver):
     if solver == "pppm":
         # every rank holds the whole mesh: the same bricks as one rank (the spread adds in another order: f64 atomics), and the
         # potentials of its own electrode atoms
-        allpot = {}
+        allpot, allpatom = {}, {}
         for r in range(world):
             mr = out[r]["mesh"]
             assert rel_err(mr["rho"], mesh1["rho"]) < 1e-12 and rel_err(mr["rho_e"], mesh1["rho_e"]) < 1e-12
             assert not (set(mr["pot"]) & set(allpot))
-            allpot.update(mr["pot"])
-        assert sorted(allpot) == sorted(mesh1["pot"])
+            allpot.update(mr["pot"]); allpatom.update(mr["patom"])
+        assert sorted(allpot) == sorted(mesh1["pot"]) and sorted(allpatom) == sorted(mesh1["patom"])
         pscale = max(abs(v) for v in mesh1["pot"].values())
         assert max(abs(allpot[t] - mesh1["pot"][t]) for t in allpot) < 1e-10 * pscale
+        # potential/atom on the mesh handle (with the slab sums of all ranks in the slab case): the one-rank values, by tag
+        ascale = max(abs(v) for v in mesh1["patom"].values())
+        assert ascale > 0
+        assert max(abs(allpatom[t] - mesh1["patom"][t]) for t in allpatom) < 1e-10 * ascale
     if solver != "cg":
         # the projected inverse in the ranks' own (rank-major) numbering == the one-rank matrix permuted by tag
         pos1 = {int(t): i for i, t in enumerate(tags1)}
