@@ -774,6 +774,91 @@ int conp_bonded_compute_device(conp_fix *fix, const double *d_x /*[nall][3]*/, d
                                double *d_ev /*[8] ebond, eangle, virial xx,yy,zz,xy,xz,yz; overwritten*/,
                                double *d_eatom /*[nall]*/, double *d_vatom /*[nall][6]*/);
 
+/* ---- time integration: `fix nve` and `fix nvt` on the device ------------------------------------------------
+ * Velocity Verlet with one Nose-Hoover chain per thermostatted group: LAMMPS' FixNH / FixNVE / ComputeTemp @ 27May2021 at the
+ * reference decks' keywords (`fix ID group nvt temp Tstart Tstop Tdamp`: tchain 3, tloop 1, drag 0, no barostat, per-type masses, no
+ * bias).  All arithmetic is double, in the order written (products left to right), no contraction.
+ * An atom i < nlocal belongs to at most one group g = group[i] (-1: not integrated, the electrode of the decks).  Per group: style
+ * (nve or nvt), dof, t_period, and on the device the chain state eta[3], eta_dot[3], eta_dotdot[3], t_current, t_target.  eta_dot[3]
+ * below is the constant 0 behind the chain's end.
+ * Constants: dtv = dt;  dtf = 0.5 dt ftm2v;  dthalf = 0.5 dt;  dt4 = 0.25 dt;  dt8 = 0.125 dt;  t_freq = 1 / t_period;
+ *   kt = boltz t_target;  ke_target = dof kt.
+ * temp(g):  t = sum over the atoms i of g of (vx^2 + vy^2 + vz^2) mass[type[i]];  t_current = t (mvv2e / (dof boltz)).
+ *   (LAMMPS adds in ascending i; the library adds per workgroup and then over workgroups, in a fixed order of its own.)
+ * nve_v:  dtfm = dtf / mass[type[i]];  v += dtfm f.        nve_x:  x += dtv v.
+ * Masses:  eta_mass[0] = dof kt / t_freq^2;  eta_mass[k >= 1] = kt / t_freq^2   (kt from the STORED t_target).
+ * Setup (conp_integrate_setup_device):  t_current = temp(g) for every group; for an nvt group also: store t_target, the masses,
+ *   eta_dotdot[k >= 1] = (eta_mass[k-1] eta_dot[k-1]^2 - kt) / eta_mass[k].
+ * Initial (conp_integrate_initial_device), per group:  nvt: store t_target, the chain half-step, v *= factor_eta;  then nve_v, nve_x.
+ * Final (conp_integrate_final_device), per group:  nve_v;  t_current = temp(g);  nvt: the chain half-step, v *= factor_eta.
+ * Chain half-step (FixNH::nhc_temp_integrate):
+ *    1. the masses from the stored t_target
+ *    2. eta_dotdot[0] = (dof boltz t_current - ke_target) / eta_mass[0]
+ *    3. for k = 2, 1:  e = exp(-dt8 eta_dot[k+1]);  eta_dot[k] *= e;  eta_dot[k] += eta_dotdot[k] dt4;  eta_dot[k] *= e
+ *    4. e = exp(-dt8 eta_dot[1]);  eta_dot[0] *= e;  eta_dot[0] += eta_dotdot[0] dt4;  eta_dot[0] *= e
+ *    5. factor_eta = exp(-dthalf eta_dot[0])
+ *    6. t_current *= factor_eta factor_eta      (the temperature of the scaled velocities, not summed again)
+ *    7. eta_dotdot[0] as in 2, from the new t_current
+ *    8. eta[k] += dthalf eta_dot[k], k = 0, 1, 2
+ *    9. eta_dot[0] *= e;  eta_dot[0] += eta_dotdot[0] dt4;  eta_dot[0] *= e      (e of step 4)
+ *   10. for k = 1, 2:  e = exp(-dt8 eta_dot[k+1]);  eta_dot[k] *= e;
+ *                      eta_dotdot[k] = (eta_mass[k-1] eta_dot[k-1]^2 - kt) / eta_mass[k];  eta_dot[k] += eta_dotdot[k] dt4;  eta_dot[k] *= e
+ * Thermostat energy (FixNH::compute_scalar):  ke_target eta[0] + 0.5 eta_mass[0] eta_dot[0]^2
+ *                                             + sum over k >= 1 of (kt eta[k] + 0.5 eta_mass[k] eta_dot[k]^2).
+ * d_out [ngroups][4], overwritten, per group:  t_current;  ke = 0.5 mvv2e t;  the thermostat energy;  eta_dot[0].
+ *   conp_integrate_temperature_device: temp(g) and ke of d_v as it is, energy and eta_dot[0] of the chain as it is; nothing is stored.
+ *   conp_integrate_final_device: the values of the velocities the entry leaves: t_current after step 6 and, formed the same way,
+ *   ke = (0.5 mvv2e t) (factor_eta factor_eta), t summed after nve_v.  For an nve group factor_eta is 1 and is not applied; its
+ *   thermostat energy and eta_dot[0] are exactly 0.0.  A group without atoms: t_current and ke are exactly 0.0.
+ * t_target is a HOST array [ngroups], read at call time and passed to the kernels by value: the engine evaluates the ramp
+ *   Tstart -> Tstop.  Entries of nve groups are checked and otherwise unused.
+ * State (conp_integrate_get_state / _set_state): [ngroups][8] per group eta[3], eta_dot[3], t_current, t_target -- what FixNH writes
+ *   to a restart file, plus the two temperatures.  Both are host entries and synchronise.  set_state seeds every group's row,
+ *   forms eta_dotdot[k >= 1] as setup does (a finished half-step leaves exactly these values, so a handle seeded with another's
+ *   get_state continues byte for byte) and counts as the setup; call conp_integrate_setup_device after it to take t_current from the
+ *   velocities instead, as a LAMMPS restart does.  Rows of nve groups: eta and eta_dot are stored as 0.
+ * Order: conp_integrate_set_params (copies and uploads the arrays, reserves all scratch, zeroes every chain; may allocate and
+ *   synchronise; afterwards the owned atoms keep their local order, the precondition conp_fix_post_neighbor_device already has) ->
+ *   conp_integrate_setup_device (once per run, with the velocities of the run's start) -> per step conp_integrate_initial_device ->
+ *   the force entries -> conp_integrate_final_device.  A device step: conp_integrate_initial_device -> conp_ghost_fill_device ->
+ *   conp_fix_pre_force_device -> ... -> conp_ghost_fold_device -> conp_integrate_final_device.
+ * CONP_ERR_STATE: any other entry before conp_integrate_set_params; initial or final before setup (or set_state) when a group is nvt.
+ * CONP_ERR_ARG: a NULL struct or array; ngroups outside [1, CONP_INTEGRATE_MAX_GROUPS]; nlocal < 0; a type outside [1, ntypes]; a
+ *   group outside [-1, ngroups); a style other than 0 and 1; a mass, dt, ftm2v, mvv2e, boltz, dof or (nvt) t_period that is not
+ *   positive and finite; a t_target that is negative or not finite, or 0 for an nvt group; a state entry that is not finite; a NULL
+ *   d_x, d_v or d_f.  A refused conp_integrate_set_params leaves the handle WITHOUT an integrator; every other refused call changes
+ *   nothing.  nlocal == 0: CONP_OK, nothing advances, d_out is zeroed.  d_out NULL: conp_integrate_final_device writes none,
+ *   conp_integrate_temperature_device does nothing.
+ * Reproducibility: no sum meets an atomic; every output is a pure function of the input and the state, byte-identical from run to
+ *   run.  Atoms with group -1 and rows from nlocal on are neither read nor written: x and v stay bit for bit.
+ * The step entries enqueue on the handle's stream and make no device allocation, no copy to the host and no synchronisation.
+ * They need nothing of the fix but its stream: they work from conp_fix_create on, on Ewald and `pppm` handles, and are rank-local,
+ * never collective (decomposed handles are allowed: a group's temperature is then this rank's).
+ * There are no host-array twins of the step entries: a host engine has its own integrator and would gain nothing from staging
+ * x, v and f through the device. */
+#define CONP_INTEGRATE_MAX_GROUPS 8
+#define CONP_INTEGRATE_CHAIN 3                 /* LAMMPS' default tchain; tloop = 1, drag = 0 */
+typedef struct {
+  int nlocal, ntypes, ngroups;                 /* 1 <= ngroups <= CONP_INTEGRATE_MAX_GROUPS */
+  const int *type;                             /* [nlocal], 1..ntypes                       */
+  const int *group;                            /* [nlocal], -1 = not integrated, else 0..ngroups-1 */
+  const double *mass;                          /* [ntypes + 1], entry 0 unused, > 0, finite  */
+  const int *style;                            /* [ngroups] 0 = nve, 1 = nvt                 */
+  const double *dof;                           /* [ngroups] temperature->dof of the group (the engine subtracts extra_dof and constraints) */
+  const double *t_period;                      /* [ngroups] Tdamp; read for nvt groups only  */
+  double dt, ftm2v, mvv2e, boltz;              /* update->dt and force->...                   */
+} conp_integrate_params;
+
+int conp_integrate_set_params(conp_fix *fix, const conp_integrate_params *p);
+int conp_integrate_setup_device(conp_fix *fix, const double *d_v /*[nlocal][3]*/, const double *t_target /*HOST [ngroups]*/);
+int conp_integrate_initial_device(conp_fix *fix, double *d_x /*[nlocal][3]*/, double *d_v /*[nlocal][3]*/, const double *d_f /*[nlocal][3]*/,
+                                  const double *t_target /*HOST [ngroups]*/);
+int conp_integrate_final_device(conp_fix *fix, double *d_v /*[nlocal][3]*/, const double *d_f /*[nlocal][3]*/,
+                                double *d_out /*[ngroups][4], overwritten; NULL: none*/);
+int conp_integrate_temperature_device(conp_fix *fix, const double *d_v /*[nlocal][3]*/, double *d_out /*[ngroups][4], overwritten*/);
+int conp_integrate_get_state(conp_fix *fix, double *state /*HOST [ngroups][8]*/);
+int conp_integrate_set_state(conp_fix *fix, const double *state /*HOST [ngroups][8]*/);
+
 /* per-kernel timing of the last N updates via HIP events on the library's stream (bench.py roofline leg).
  * enable: 0 off, 1 a pair of events around every kernel, 2 around every 4th launch of the dominant kernel (sk_gemm) only --
  * cheap enough to stay on inside a timed region (an event pair drains the queue around the kernel it brackets). */

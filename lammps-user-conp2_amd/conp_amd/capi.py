@@ -90,6 +90,12 @@ class conp_bonded_params(C.Structure):
                 ("angle_k", C.POINTER(C.c_double)), ("angle_theta0", C.POINTER(C.c_double)), ("newton_bond", C.c_int)]
 
 
+class conp_integrate_params(C.Structure):
+    _fields_ = [("nlocal", C.c_int), ("ntypes", C.c_int), ("ngroups", C.c_int), ("type", C.POINTER(C.c_int)), ("group", C.POINTER(C.c_int)),
+                ("mass", C.POINTER(C.c_double)), ("style", C.POINTER(C.c_int)), ("dof", C.POINTER(C.c_double)),
+                ("t_period", C.POINTER(C.c_double)), ("dt", C.c_double), ("ftm2v", C.c_double), ("mvv2e", C.c_double), ("boltz", C.c_double)]
+
+
 class conp_bonded_lists(C.Structure):
     _fields_ = [("nlocal", C.c_int), ("nall", C.c_int), ("nbond", C.c_int), ("bond", C.POINTER(C.c_int)), ("nangle", C.c_int),
                 ("angle", C.POINTER(C.c_int)), ("prd", C.c_double * 3)]
@@ -138,6 +144,8 @@ SYMBOLS = [
     "conp_fix_post_neighbor_device", "conp_fix_get_step_tables",
     "conp_fix_post_force_device",
     "conp_bonded_set_params", "conp_bonded_set_lists", "conp_bonded_compute", "conp_bonded_compute_device",
+    "conp_integrate_set_params", "conp_integrate_setup_device", "conp_integrate_initial_device", "conp_integrate_final_device",
+    "conp_integrate_temperature_device", "conp_integrate_get_state", "conp_integrate_set_state",
 ]
 
 
@@ -298,6 +306,14 @@ def load_library():
         lib.conp_bonded_set_lists.argtypes = [vp, C.POINTER(conp_bonded_lists)]
         lib.conp_bonded_compute.argtypes = [vp, C.POINTER(conp_atoms), dp, dp, dp, dp, dp]
         lib.conp_bonded_compute_device.argtypes = [vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "conp_integrate_set_params"):
+        lib.conp_integrate_set_params.argtypes = [vp, C.POINTER(conp_integrate_params)]
+        lib.conp_integrate_setup_device.argtypes = [vp, vp, dp]
+        lib.conp_integrate_initial_device.argtypes = [vp, vp, vp, vp, dp]
+        lib.conp_integrate_final_device.argtypes = [vp, vp, vp, vp]
+        lib.conp_integrate_temperature_device.argtypes = [vp, vp, vp]
+        lib.conp_integrate_get_state.argtypes = [vp, dp]
+        lib.conp_integrate_set_state.argtypes = [vp, dp]
     lib.conp_compute_potential_atom.argtypes = [vp, C.POINTER(conp_atoms), C.POINTER(conp_neighlist), ip, ip,
                                                 C.POINTER(conp_potential_args), dp]
     lib.conp_fix_set_comm.argtypes = [vp, C.POINTER(conp_comm)]
@@ -915,6 +931,62 @@ class FixConp:
         is added to, d_ev [8] (ebond, eangle, virial xx, yy, zz, xy, xz, yz), d_eatom [nall], d_vatom [nall][6] are overwritten"""
         self._check(self.lib.conp_bonded_compute_device(self.h, C.c_void_p(d_x), C.c_void_p(d_f), C.c_void_p(d_ev),
                                                         C.c_void_p(d_eatom), C.c_void_p(d_vatom)))
+
+    # -- velocity Verlet and Nose-Hoover chains: set_params -> setup_device -> initial / final per step (DESIGN.md section 22) ------
+    def integrate_set_params(self, type, group, mass, style, dof, t_period, dt, ftm2v, mvv2e, boltz):
+        """conp_integrate_set_params: type [nlocal] (1..ntypes), group [nlocal] (-1 = not integrated), mass per type WITHOUT the unused
+        entry 0, style / dof / t_period per group (style 0 = nve, 1 = nvt).  Copied and uploaded; zeroes every chain"""
+        ty = np.ascontiguousarray(type, dtype=np.int32).reshape(-1)
+        gr = np.ascontiguousarray(group, dtype=np.int32).reshape(-1)
+        assert ty.size == gr.size
+        m = np.ascontiguousarray(np.concatenate([[0.0], np.asarray(mass, dtype=np.float64).reshape(-1)]))
+        st = np.ascontiguousarray(style, dtype=np.int32).reshape(-1)
+        df = np.ascontiguousarray(dof, dtype=np.float64).reshape(-1)
+        tp = np.ascontiguousarray(t_period, dtype=np.float64).reshape(-1)
+        assert st.size == df.size == tp.size
+        p = conp_integrate_params(nlocal=ty.size, ntypes=m.size - 1, ngroups=st.size, type=_iptr(ty), group=_iptr(gr), mass=_dptr(m),
+                                  style=_iptr(st), dof=_dptr(df), t_period=_dptr(tp), dt=dt, ftm2v=ftm2v, mvv2e=mvv2e, boltz=boltz)
+        self._integrate_ngroups = 0
+        self._check(self.lib.conp_integrate_set_params(self.h, C.byref(p)))
+        self._integrate_ngroups = int(st.size)
+
+    def _integrate_targets(self, t_target):
+        if t_target is None:
+            return None, None
+        t = np.ascontiguousarray(t_target, dtype=np.float64).reshape(-1)
+        assert t.size == getattr(self, "_integrate_ngroups", t.size)
+        return t, _dptr(t)
+
+    def integrate_setup_device(self, d_v: int, t_target=None):
+        """conp_integrate_setup_device: raw device pointer d_v [nlocal][3], t_target a host array [ngroups]; enqueued, no synchronisation"""
+        keep, tp = self._integrate_targets(t_target)
+        self._check(self.lib.conp_integrate_setup_device(self.h, C.c_void_p(d_v), tp))
+
+    def integrate_initial_device(self, d_x: int, d_v: int, d_f: int, t_target=None):
+        """conp_integrate_initial_device: chain half-step, v *= factor_eta, v += dtfm f, x += dtv v; one launch, no synchronisation"""
+        keep, tp = self._integrate_targets(t_target)
+        self._check(self.lib.conp_integrate_initial_device(self.h, C.c_void_p(d_x), C.c_void_p(d_v), C.c_void_p(d_f), tp))
+
+    def integrate_final_device(self, d_v: int, d_f: int, d_out: int = 0):
+        """conp_integrate_final_device: v += dtfm f, temperature, chain half-step, v *= factor_eta; d_out [ngroups][4] (t_current, ke,
+        thermostat energy, eta_dot[0]) is overwritten (0 = NULL); no synchronisation"""
+        self._check(self.lib.conp_integrate_final_device(self.h, C.c_void_p(d_v), C.c_void_p(d_f), C.c_void_p(d_out)))
+
+    def integrate_temperature_device(self, d_v: int, d_out: int):
+        """conp_integrate_temperature_device: d_out [ngroups][4] of d_v and the chains as they are; nothing is stored"""
+        self._check(self.lib.conp_integrate_temperature_device(self.h, C.c_void_p(d_v), C.c_void_p(d_out)))
+
+    def integrate_get_state(self):
+        """conp_integrate_get_state -> [ngroups][8]: eta[3], eta_dot[3], t_current, t_target per group (synchronises)"""
+        st = np.full((max(getattr(self, "_integrate_ngroups", 0), 1), 8), np.nan)
+        self._check(self.lib.conp_integrate_get_state(self.h, _dptr(st)))
+        return st[:self._integrate_ngroups]
+
+    def integrate_set_state(self, state):
+        """conp_integrate_set_state: [ngroups][8] as integrate_get_state returns it; counts as the setup (synchronises)"""
+        st = np.ascontiguousarray(state, dtype=np.float64).reshape(-1, 8)
+        assert st.shape[0] == getattr(self, "_integrate_ngroups", st.shape[0])
+        self._check(self.lib.conp_integrate_set_state(self.h, _dptr(st)))
 
     def step_tables(self):
         """conp_fix_get_step_tables -> dict of the sizes (nl, n_ele_atoms, ne, n_b_pairs, n_chunks, zn_listed, nall, c_start) and the

@@ -24,6 +24,7 @@
 #include "conp_ghostmap.hpp"
 #include "conp_pairstyle.hpp"
 #include "conp_bondedstyle.hpp"
+#include "conp_integrator.hpp"
 #include "conp_ewaldquery.hpp"
 #include "conp_pppmmesh.hpp"
 
@@ -2336,11 +2337,12 @@ struct conp_fix : DevCtx {
   }
 
   // ---- the pair style with its half list (conp_pairstyle.cpp, DESIGN.md sections 16, 17), the ghost map (conp_ghostmap.cpp, 18),
-  // the harmonic bonds and angles (conp_bondedstyle.cpp, 21), the exact-Ewald query entries (conp_ewaldquery.cpp, sections 11, 12,
+  // the harmonic bonds and angles (conp_bondedstyle.cpp, 21), the integrator (conp_integrator.cpp, 22), the exact-Ewald query entries (conp_ewaldquery.cpp, sections 11, 12,
   // 14, 15) and the PPPM mesh with the update's b and its query entries (conp_pppmmesh.cpp, sections 8, 13, 14, 15) ----
   PairStyle pair{*this};
   GhostMap ghost{*this};
   BondedStyle bonded{*this};
+  Integrator integ{*this};
   EwaldQuery ew{*this, kt, plan, dplan, tiles_h, ct_ptr_h, d_sf_row_a, d_sf_col_c, d_k_sign};
   PppmMesh pm{*this};
   bool types_in_range = false;                   // every atoms->type of the last (setup_)post_neighbor lies in [0, ntypes]
@@ -3637,6 +3639,80 @@ int conp_bonded_compute_device(conp_fix *f, const double *d_x, double *d_f, doub
   if (!d_f && !d_ev && !d_eatom && !d_vatom) return CONP_OK;
   f->drop_graph();
   f->bonded.enqueue(d_x, d_f, d_ev, d_eatom, d_vatom);
+  CONP_GUARD_END
+}
+
+// ---- velocity Verlet and the Nose-Hoover chain: set_params -> setup_device -> initial / final per step ------
+int conp_integrate_set_params(conp_fix *f, const conp_integrate_params *p) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->integ.have_params = false;                  // a refused call leaves the handle without an integrator
+  if (!p) throw ConpError(CONP_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(f->env.device));
+  f->drop_graph();
+  f->integ.set_params(p);
+  CONP_GUARD_END
+}
+
+int conp_integrate_setup_device(conp_fix *f, const double *d_v, const double *t_target) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->integ.need_params("conp_integrate_setup_device");
+  if (!d_v) throw ConpError(CONP_ERR_ARG, "conp_integrate_setup_device: null d_v");
+  f->drop_graph();
+  f->integ.setup(d_v, t_target);
+  CONP_GUARD_END
+}
+
+int conp_integrate_initial_device(conp_fix *f, double *d_x, double *d_v, const double *d_f, const double *t_target) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->integ.need_setup("conp_integrate_initial_device");
+  if (!d_x || !d_v || !d_f) throw ConpError(CONP_ERR_ARG, "conp_integrate_initial_device: null d_x, d_v or d_f");
+  f->drop_graph();
+  f->integ.initial(d_x, d_v, d_f, t_target);
+  CONP_GUARD_END
+}
+
+int conp_integrate_final_device(conp_fix *f, double *d_v, const double *d_f, double *d_out) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->integ.need_setup("conp_integrate_final_device");
+  if (!d_v || !d_f) throw ConpError(CONP_ERR_ARG, "conp_integrate_final_device: null d_v or d_f");
+  f->drop_graph();
+  f->integ.final_(d_v, d_f, d_out);
+  CONP_GUARD_END
+}
+
+int conp_integrate_temperature_device(conp_fix *f, const double *d_v, double *d_out) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->integ.need_params("conp_integrate_temperature_device");
+  if (!d_v) throw ConpError(CONP_ERR_ARG, "conp_integrate_temperature_device: null d_v");
+  if (!d_out) return CONP_OK;
+  f->drop_graph();
+  f->integ.temperature(d_v, d_out);
+  CONP_GUARD_END
+}
+
+int conp_integrate_get_state(conp_fix *f, double *state) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->integ.need_params("conp_integrate_get_state");
+  if (!state) throw ConpError(CONP_ERR_ARG, "conp_integrate_get_state: null state");
+  HIP_TRY(hipSetDevice(f->env.device));
+  f->integ.get_state(state);
+  CONP_GUARD_END
+}
+
+int conp_integrate_set_state(conp_fix *f, const double *state) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->integ.need_params("conp_integrate_set_state");
+  if (!state) throw ConpError(CONP_ERR_ARG, "conp_integrate_set_state: null state");
+  HIP_TRY(hipSetDevice(f->env.device));
+  f->drop_graph();
+  f->integ.set_state(state);
   CONP_GUARD_END
 }
 

@@ -382,6 +382,33 @@ struct BondedArgs {
 };
 // ev [8] = ebond, eangle, virial xx, yy, zz, xy, xz, yz (overwritten, summed in a fixed order), or NULL
 void launch_bonded(hipStream_t s, const BondedArgs &a, double *ev);
+// ---- velocity Verlet and the Nose-Hoover chain (conp_integrate.hip) ----
+constexpr int INTEGRATE_BLOCK = 256;     // threads of a workgroup: one per atom
+constexpr int INTEGRATE_FINISH = 256;    // threads of the finishing workgroup: partial rows r, r + 256, ... per thread
+constexpr int INTEGRATE_G = CONP_INTEGRATE_MAX_GROUPS;
+constexpr int INTEGRATE_STATE_W = 12;    // doubles of a group's state row: eta[3], eta_dot[3], eta_dotdot[3], t_current, t_target, unused
+enum { INTEGRATE_TEMPERATURE = 0, INTEGRATE_SETUP = 1, INTEGRATE_FINAL = 2 };      // what the finishing workgroup does with the sums
+struct IntegrateArgs {
+  int nlocal, ngroups;
+  const int *type, *group;               // [nlocal]; group -1: the atom is neither read nor written
+  const double *mass;                    // [ntypes + 1]
+  double dtv, dtf, dthalf, dt4, dt8, mvv2e, boltz;
+  int style[INTEGRATE_G];                // 0 = nve, 1 = nvt
+  double dof[INTEGRATE_G], t_freq[INTEGRATE_G], t_target[INTEGRATE_G];
+  double *x, *v;                         // [nlocal][3]
+  const double *f;                       // [nlocal][3]
+  const double *state_in;                // [ngroups][INTEGRATE_STATE_W]
+  double *state_out;                     // initial: the OTHER state buffer (every workgroup reads state_in); finish, seed: may be state_in
+  double *part;                          // [ceil(nlocal / INTEGRATE_BLOCK)][INTEGRATE_G] scratch rows
+  double *factor;                        // [INTEGRATE_G] scratch: factor_eta of the final chain half-step (1.0 for nve)
+  double *out;                           // [ngroups][4] t_current, ke, thermostat energy, eta_dot[0]; or NULL
+};
+// chain half-step in every workgroup, v *= factor_eta, nve_v, nve_x: one launch
+void launch_integrate_initial(hipStream_t s, const IntegrateArgs &a);
+// update: nve_v with the per-workgroup sums of m v^2 (else the sums alone); then the finishing workgroup in `mode`; scale: v *= factor
+void launch_integrate_sums(hipStream_t s, const IntegrateArgs &a, bool update, int mode, bool scale);
+// state_out rows from raw [ngroups][8] rows (eta, eta_dot, t_current, t_target) in a.state_in: eta_dotdot[k >= 1] as setup forms it
+void launch_integrate_seed(hipStream_t s, const IntegrateArgs &a);
 // ---- the pair style's half list built on the device (conp_neigh.hip) ----
 struct NeighGrid { double lo[3], inv[3]; int n[3]; };     // cell of v along c: clamp((v - lo[c]) * inv[c], 0, n[c] - 1); cells are >= cutneigh wide
 struct NeighRowArgs {
