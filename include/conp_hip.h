@@ -908,11 +908,26 @@ enum {
   CONP_PATH_SK_CLASSIC = 1 << 12,        /* large planar systems: sk_gemm over all kz columns instead of the z-window contraction (conp_zn.hip) */
   CONP_PATH_ZN_WIDE = 1 << 13,           /* z-window: 48 window columns also where 32 would do (the second template form on medium boxes) */
   CONP_PATH_ZC_PHASE_LOADS = 1 << 14,    /* planar electrodes: the finishing dot kernel loads its electrode phases per thread instead of staging the rows in LDS */
-  CONP_PATH_HC_TABLES = 1 << 15          /* z-window: the piece sums read their piece lists also where the addresses are arithmetic */
+  CONP_PATH_HC_TABLES = 1 << 15,         /* z-window: the piece sums read their piece lists also where the addresses are arithmetic */
+  CONP_PATH_SOLVE_NO_LATTICE = 1 << 16   /* solve: packed symmetric tiles also where the electrodes are a lattice (no block-circulant table) */
 };
 void conp_debug_set_paths(unsigned mask);
 void conp_debug_set_sk_workgroups(int n);
 void conp_debug_set_ew_block(int n);
+/* cap of the basis atoms whose table slabs the lattice form of the solve stages at a time (0 = as many as fit), process-wide and read
+ * once per matrix: for the tests that run several stages on a small box */
+void conp_debug_set_lat_stage(int n);
+
+/* Which form the fused solve (one-rank `fix conp`, inverse solver) multiplies the current matrix in -- decided at the first update
+ * after the matrix changed.  form_out = {form, nx, ny, nbasis}: form 0 full rows, 1 packed symmetric tiles (from 2048 electrode
+ * atoms up), 2 the block-circulant table of lattice-periodic electrodes, -1 not decided yet; nx, ny, nbasis the lattice the
+ * electrode positions proposed (0 where they proposed none, or the form was not looked for).  dev_out = {max |S_ij - T[basis_i]
+ * [basis_j][cell_j - cell_i]|, max |S_ij|} of the pass that tested the matrix against that lattice (form 2: dev <= 1e-10 max). */
+int conp_fix_get_solve_form(conp_fix *fix, int *form_out /*[4]*/, double *dev_out /*[2]*/);
+/* the host's lattice search on its own (no device): the smallest axis-aligned translations (lx / nx, 0, 0), (0, ly / ny, 0) that map
+ * the n points x [n][3] onto themselves, periodic in x and y, matched within 1e-4.  Returns 1 and dims = {nx, ny, nbasis},
+ * row [nbasis][nx][ny] -> point, pos [n][3] = (basis, cx, cy) of every point; 0 when the points are no such lattice. */
+int conp_host_find_lattice(int n, const double *x, double lx, double ly, int *dims /*[3]*/, int *row /*[n]*/, int *pos /*[3 n]*/);
 
 
 /* ---- the fix's log file (fix_conp.cpp:119 `outf`) ----

@@ -125,7 +125,8 @@ SYMBOLS = [
     "conp_fix_set_stream",
     "conp_fix_bind_device_buffers", "conp_fix_row_range", "conp_fix_b_cal_device", "conp_fix_solve_device",
     "conp_fix_scatter_device", "conp_fix_pre_force_device", "conp_fix_profile", "conp_fix_profile_read", "conp_debug_check_guards",
-    "conp_debug_set_paths", "conp_debug_set_sk_workgroups", "conp_debug_set_ew_block",
+    "conp_debug_set_paths", "conp_debug_set_sk_workgroups", "conp_debug_set_ew_block", "conp_debug_set_lat_stage",
+    "conp_fix_get_solve_form", "conp_host_find_lattice",
     "conp_fix_pin_host_arrays", "conp_fix_unpin_host_arrays", "conp_host_alloc", "conp_host_free",
     "conp_fix_write_timing", "conp_fix_log_drain", "conp_fix_mesg_drain",
     "conp_fix_set_comm", "conp_rccl_unique_id", "conp_fix_comm_init_rccl", "conp_rccl_available", "conp_fix_comm_destroy_rccl",
@@ -156,6 +157,8 @@ PATH_SK_CLASSIC = 4096      # (512, 1024, 2048: retired test paths, ignored by t
 PATH_ZN_WIDE = 8192         # z-window: 48 window columns also where 32 would do
 PATH_ZC_PHASE_LOADS = 16384     # finishing dot kernel: electrode phases loaded per thread, not staged in LDS
 PATH_HC_TABLES = 32768          # z-window: the piece sums read their piece lists, not arithmetic addresses
+PATH_SOLVE_NO_LATTICE = 65536   # solve: packed symmetric tiles also where the electrodes are a lattice
+SOLVE_FORMS = {-1: "undecided", 0: "rows", 1: "packed", 2: "lattice"}
 
 
 class test_paths:
@@ -183,6 +186,23 @@ def set_ew_block(n: int):
     """test hook (conp_debug_set_ew_block): cap of the atom block of the conp_ewald_* entries, rounded up to a multiple of 64;
     0 = the library's choice.  Process-wide, read at every call"""
     load_library().conp_debug_set_ew_block(int(n))
+
+
+def set_lat_stage(n: int):
+    """test hook (conp_debug_set_lat_stage): cap of the basis atoms the lattice solve stages at a time; 0 = as many as fit.
+    Process-wide, read once per matrix"""
+    load_library().conp_debug_set_lat_stage(int(n))
+
+
+def find_lattice(x, lx, ly):
+    """the library's host lattice search (no device): None, or dict(nx, ny, nbasis, row[nbasis, nx, ny], pos[n, 3])"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    n = len(x)
+    dims, row, pos = np.zeros(3, np.int32), np.zeros(n, np.int32), np.zeros((n, 3), np.int32)
+    if not load_library().conp_host_find_lattice(n, _dptr(x), float(lx), float(ly), _iptr(dims), _iptr(row), _iptr(pos)):
+        return None
+    nx, ny, nb = (int(v) for v in dims)
+    return dict(nx=nx, ny=ny, nbasis=nb, row=row.reshape(nb, nx, ny), pos=pos)
 
 
 def load_library():
@@ -234,6 +254,11 @@ def load_library():
     lib.conp_fix_get_matrix.argtypes = [vp, dp]
     lib.conp_fix_set_matrix.argtypes = [vp, dp, C.c_int]
     lib.conp_fix_get_vectors.argtypes = [vp, dp, dp, dp]
+    if hasattr(lib, "conp_fix_get_solve_form"):       # (comparison builds of earlier rounds lack the lattice form)
+        lib.conp_fix_get_solve_form.argtypes = [vp, ip, dp]
+        lib.conp_host_find_lattice.argtypes = [C.c_int, dp, C.c_double, C.c_double, ip, ip, ip]
+        lib.conp_debug_set_lat_stage.argtypes = [C.c_int]
+        lib.conp_debug_set_lat_stage.restype = None
     lib.conp_fix_get_sfac.argtypes = [vp, dp, dp]
     lib.conp_fix_get_ele_trig.argtypes = [vp, dp, dp]
     lib.conp_inv_project.argtypes = [vp, C.c_int, dp, C.c_int, C.c_int, dp, C.c_double, dp]
@@ -505,6 +530,12 @@ class FixConp:
     def set_matrix(self, a, runstage):
         a = np.ascontiguousarray(a, dtype=np.float64)
         self._check(self.lib.conp_fix_set_matrix(self.h, _dptr(a), runstage))
+
+    def solve_form(self):
+        """dict(form="rows" | "packed" | "lattice" | "undecided", nx, ny, nbasis, dev, smax): conp_fix_get_solve_form"""
+        f, d = np.zeros(4, np.int32), np.zeros(2)
+        self._check(self.lib.conp_fix_get_solve_form(self.h, _iptr(f), _dptr(d)))
+        return dict(form=SOLVE_FORMS[int(f[0])], nx=int(f[1]), ny=int(f[2]), nbasis=int(f[3]), dev=float(d[0]), smax=float(d[1]))
 
     def vectors(self):
         ne = self.info().elenum_all

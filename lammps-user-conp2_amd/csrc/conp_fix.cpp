@@ -2162,10 +2162,49 @@ struct conp_fix : DevCtx {
   bool use_sym_gemv() const {
     return !gemv_rows && idx.elenum_all >= 2048;
   }
+  // Lattice-periodic electrodes (conp_kernels.hip "GEMV ... as a BLOCK-CIRCULANT matrix"): where the packed copy would be made, the
+  // electrode positions propose a lattice (EleLattice) and one pass over the matrix measures how far it is from the table of its
+  // cell-(0, 0) rows.  A deviation of rounding size (the symmetry test's own 1e-10 of the largest entry) -> the solve multiplies the
+  // table, and neither the packed copy nor the slot plane is made.  Decided once per matrix generation, like the packed copy.
+  const bool no_lattice = path_on(CONP_PATH_SOLVE_NO_LATTICE);      // test path / A-B switch: always the packed form
+  int solve_form = -1;              // of matrix generation spk_of: 0 full rows, 1 packed tiles, 2 lattice table
+  bool lat_geom = false;            // the positions gave a lattice the kernel can run (lat, lat_sh), whatever the matrix said then
+  double lat_dev = 0.0, lat_smax = 0.0;      // max |S_ij - T[..]| and max |S_ij| of that pass
+  EleLattice lat;
+  LatShape lat_sh;
+  DevBuf<double> d_latT;
+  DevBuf<int> d_lat_row, d_lat_pos;
+  bool try_lattice() {
+    const int ne = idx.elenum_all;
+    lat_geom = false; lat_dev = lat_smax = 0.0;
+    if (no_lattice || xele_h.size() != (size_t)ne * 3) return false;
+    if (!lat.find(ne, xele_h.data(), env.xprd, env.yprd)) return false;
+    lat_sh = lat_shape(lat.nx, lat.ny, lat.nbasis);
+    if (!lat_sh.R) return false;              // fewer than 16 cells, or two lattice vectors beyond a stage's LDS
+    lat_geom = true;
+    d_lat_row.upload(lat.row, stream); d_lat_pos.upload(lat.pos, stream);
+    d_latT.reserve((size_t)ne * lat.nbasis);
+    d_symstat.reserve(2);
+    launch_lat_table(stream, ne, lat.nbasis, lat.nx * lat.ny, d_A.p, d_lat_row.p, d_latT.p);
+    launch_lat_dev(stream, ne, lat.nx, lat.ny, lat.nbasis, d_A.p, d_lat_pos.p, d_latT.p, d_symstat.p);
+    unsigned long long st[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(st, d_symstat.p, sizeof st, hipMemcpyDeviceToHost, stream));
+    sync();
+    std::memcpy(&lat_smax, &st[0], sizeof lat_smax); std::memcpy(&lat_dev, &st[1], sizeof lat_dev);
+    if (lat_dev <= 1e-10 * lat_smax) return true;
+    mesgf("conp/hip: the solve matrix does not follow the electrode lattice (max |S_ij - T| = %.3g, max |S_ij| = %.3g): packed tiles are multiplied\n",
+          lat_dev, lat_smax);
+    return false;
+  }
   void solve_scatter_fused(double *d_q_atoms, double potdiff) {
     const int ne = idx.elenum_all;
-    if (use_sym_gemv()) {
-      if (spk_of != s_generation) {
+    if (!use_sym_gemv()) solve_form = 0;
+    else if (spk_of != s_generation) {
+      if (try_lattice()) {
+        solve_form = 2;
+        spk_of = s_generation;
+        d_Spk.release(); d_yp.release();
+      } else {
         d_Spk.reserve(sym_packed_doubles(ne_pad));
         d_yp.reserve((size_t)(ne_pad / 128) * ne_pad);
         d_symstat.reserve(2);
@@ -2180,11 +2219,21 @@ struct conp_fix : DevCtx {
         std::memcpy(&mx, &st[0], sizeof mx); std::memcpy(&md, &st[1], sizeof md);
         spk_symmetric = md <= 1e-10 * mx;
         spk_of = s_generation;
+        solve_form = spk_symmetric ? 1 : 0;
         if (!spk_symmetric)
           mesgf("conp/hip: the solve matrix is not symmetric (max |S_ij - S_ji| = %.3g, max |S_ij| = %.3g): full rows are multiplied\n", md, mx);
       }
     }
-    if (use_sym_gemv() && spk_symmetric) {
+    if (solve_form == 2) {
+      prof.begin("gemv_charge", stream);
+      launch_lat_gemv(stream, lat_sh, lat.nx, lat.ny, lat.nbasis, d_latT.p, d_lat_row.p, d_b, d_eleallq, d_elesetq.p,
+                      args.qinit ? d_eleinitq.p : nullptr, potdiff, d_ele_csr_ptr.p, d_ele_csr_of.p, d_qele.p, d_q_atoms);
+      prof.end(stream);
+      left_stale = true; left_potdiff = potdiff;
+      HIP_TRY(hipGetLastError());
+      return;
+    }
+    if (solve_form == 1) {
       prof.begin("gemv_charge", stream);
       launch_sym_gemv_finish(stream, ne, ne_pad, d_Spk.p, d_b, d_yp.p, d_eleallq, d_elesetq.p, args.qinit ? d_eleinitq.p : nullptr,
                              potdiff, d_ele_csr_ptr.p, d_ele_csr_of.p, d_ele_csr_row.p, d_qele.p, d_q_atoms);
@@ -3060,6 +3109,17 @@ int conp_fix_set_matrix(conp_fix *f, const double *aaa, int runstage) {
   CONP_GUARD_END
 }
 
+int conp_fix_get_solve_form(conp_fix *f, int *form_out, double *dev_out) {
+  CONP_GUARD_BEGIN
+  const bool fused = f->can_fuse_solve() && f->use_sym_gemv();
+  const bool decided = f->spk_of == f->s_generation;
+  form_out[0] = !fused ? 0 : decided ? f->solve_form : -1;
+  const bool geom = fused && decided && f->lat_geom;
+  form_out[1] = geom ? f->lat.nx : 0; form_out[2] = geom ? f->lat.ny : 0; form_out[3] = geom ? f->lat.nbasis : 0;
+  dev_out[0] = geom ? f->lat_dev : 0.0; dev_out[1] = geom ? f->lat_smax : 0.0;
+  CONP_GUARD_END
+}
+
 int conp_fix_get_vectors(conp_fix *f, double *bbb_all, double *eleallq, double *elesetq) {
   CONP_GUARD_BEGIN
   f->drop_graph();
@@ -3189,6 +3249,17 @@ int conp_host_ktables(double g_ewald, double accuracy, double slab_volfactor, in
   if (plan_m) std::memcpy(plan_m, pl.k_m.data(), K * sizeof(int));
   if (plan_sign) std::memcpy(plan_sign, pl.k_sign.data(), K * sizeof(int));
   CONP_GUARD_END
+}
+
+int conp_host_find_lattice(int n, const double *x, double lx, double ly, int *dims, int *row, int *pos) {
+  try {
+    EleLattice l;
+    if (!l.find(n, x, lx, ly)) return 0;
+    dims[0] = l.nx; dims[1] = l.ny; dims[2] = l.nbasis;
+    if (row) std::memcpy(row, l.row.data(), (size_t)n * sizeof(int));
+    if (pos) std::memcpy(pos, l.pos.data(), 3 * (size_t)n * sizeof(int));
+    return 1;
+  } catch (const std::exception &e) { last_error() = e.what(); return 0; }
 }
 
 int conp_host_index(int n0, const int *tag0, const int *echeck0, int n1, const int *tag1, const int *echeck1, int *sizes,

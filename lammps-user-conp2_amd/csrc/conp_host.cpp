@@ -601,4 +601,113 @@ void build_a_rows(const ListView &l, int nlocal, const int *tag, const int *eche
   finish_rows(raw, idx.elenum_all, true, out);
 }
 
+// ------------------------------------------------------------------------------------------------
+// EleLattice
+// ------------------------------------------------------------------------------------------------
+namespace {
+constexpr double LAT_TOL = 1e-4;      // A: far below any interatomic distance
+// the atoms on a grid of 0.01 A (wrapped x and y, z as it is): the atom within LAT_TOL of a point, by a look at the cells around it
+struct PointGrid {
+  static constexpr double H = 0.01;
+  int n; const double *x; double lx, ly, zlo;
+  int64_t ncx, ncy, ncz;
+  std::vector<std::pair<int64_t, int>> cells;      // (cell key, atom), sorted
+  static double wrap(double v, double L) { v -= L * std::floor(v / L); return v < L ? v : 0.0; }
+  static double nearest(double d, double L) { return d - L * std::nearbyint(d / L); }
+  int64_t key(int64_t ix, int64_t iy, int64_t iz) const { return (ix * ncy + iy) * ncz + iz; }
+  bool build(int n_, const double *x_, double lx_, double ly_) {
+    n = n_; x = x_; lx = lx_; ly = ly_;
+    double zhi = zlo = x[2];
+    for (int i = 0; i < n; ++i) { zlo = std::min(zlo, x[3 * (size_t)i + 2]); zhi = std::max(zhi, x[3 * (size_t)i + 2]); }
+    ncx = (int64_t)(lx / H) + 1; ncy = (int64_t)(ly / H) + 1; ncz = (int64_t)((zhi - zlo) / H) + 1;
+    if (!(lx > 0 && ly > 0) || ncx > (1 << 20) || ncy > (1 << 20) || ncz > (1 << 20)) return false;
+    cells.resize(n);
+    for (int i = 0; i < n; ++i) {
+      const double *p = x + 3 * (size_t)i;
+      cells[i] = {key((int64_t)(wrap(p[0], lx) / H), (int64_t)(wrap(p[1], ly) / H), (int64_t)((p[2] - zlo) / H)), i};
+    }
+    std::sort(cells.begin(), cells.end());
+    return true;
+  }
+  int at(double px, double py, double pz) const {
+    const int64_t ix = (int64_t)(wrap(px, lx) / H), iy = (int64_t)(wrap(py, ly) / H), iz = (int64_t)std::floor((pz - zlo) / H);
+    // (two cells to either side in x and y: the last cell of a wrapped axis is a partial one)
+    for (int64_t dx = -2; dx <= 2; ++dx)
+      for (int64_t dy = -2; dy <= 2; ++dy)
+        for (int64_t dz = -1; dz <= 1; ++dz) {
+          if (iz + dz < 0 || iz + dz >= ncz) continue;
+          const int64_t k = key((ix + dx + ncx) % ncx, (iy + dy + ncy) % ncy, iz + dz);
+          for (auto it = std::lower_bound(cells.begin(), cells.end(), std::make_pair(k, 0)); it != cells.end() && it->first == k; ++it) {
+            const double *q = x + 3 * (size_t)it->second;
+            if (std::fabs(nearest(q[0] - px, lx)) < LAT_TOL && std::fabs(nearest(q[1] - py, ly)) < LAT_TOL && std::fabs(q[2] - pz) < LAT_TOL)
+              return it->second;
+          }
+        }
+    return -1;
+  }
+  // p[i] = the atom at x_i + t along `axis`; false unless that is a permutation of the atoms
+  bool perm(int axis, double t, std::vector<int> &p) const {
+    p.assign(n, -1);
+    std::vector<char> hit(n, 0);
+    for (int i = 0; i < n; ++i) {
+      const double *q = x + 3 * (size_t)i;
+      const int j = at(q[0] + (axis == 0 ? t : 0.0), q[1] + (axis == 1 ? t : 0.0), q[2]);
+      if (j < 0 || hit[j]) return false;
+      hit[j] = 1; p[i] = j;
+    }
+    return true;
+  }
+  // the smallest translation along `axis` that maps the atoms onto themselves: one of the distances from atom 0 to the atoms in line
+  // with it, or the box length (always a solution)
+  bool smallest(int axis, int &cells_out, std::vector<int> &p) const {
+    const double L = axis == 0 ? lx : ly;
+    std::vector<double> cand;
+    for (int j = 1; j < n; ++j) {
+      const double *q = x + 3 * (size_t)j;
+      const double d0 = nearest(q[0] - x[0], lx), d1 = nearest(q[1] - x[1], ly);
+      if (std::fabs(axis == 0 ? d1 : d0) >= LAT_TOL || std::fabs(q[2] - x[2]) >= LAT_TOL) continue;
+      const double d = wrap(axis == 0 ? d0 : d1, L);
+      if (d > LAT_TOL && d < L - LAT_TOL) cand.push_back(d);
+    }
+    std::sort(cand.begin(), cand.end());
+    cand.push_back(L);
+    for (double t : cand) {
+      const long m = std::lround(L / t);
+      if (m < 1 || std::fabs(m * t - L) > LAT_TOL) continue;
+      if (perm(axis, L / m, p)) { cells_out = (int)m; return true; }
+    }
+    return false;
+  }
+};
+}  // namespace
+
+bool EleLattice::find(int n, const double *x, double lx, double ly) {
+  nx = ny = nbasis = 0; row.clear(); pos.clear();
+  if (n < 1) return false;
+  PointGrid g;
+  std::vector<int> px, py;
+  if (!g.build(n, x, lx, ly) || !g.smallest(0, nx, px) || !g.smallest(1, ny, py)) return false;
+  if (n % (nx * ny)) return false;
+  a = lx / nx; b = ly / ny; nbasis = n / (nx * ny);
+  // cell (0, 0): the atoms within [0, a) x [0, b) of atom 0 (taken from 10 tolerances below it), in index order
+  std::vector<int> basis;
+  for (int i = 0; i < n; ++i)
+    if (PointGrid::wrap(x[3 * (size_t)i] - x[0] + 10 * LAT_TOL, lx) < a && PointGrid::wrap(x[3 * (size_t)i + 1] - x[1] + 10 * LAT_TOL, ly) < b)
+      basis.push_back(i);
+  if ((int)basis.size() != nbasis) return false;
+  row.assign(n, -1); pos.assign(3 * (size_t)n, -1);
+  for (int be = 0; be < nbasis; ++be) {
+    int i0 = basis[be];
+    for (int cx = 0; cx < nx; ++cx, i0 = px[i0]) {
+      int i = i0;
+      for (int cy = 0; cy < ny; ++cy, i = py[i]) {
+        if (pos[3 * (size_t)i] >= 0) return false;                 // an atom reached twice: the cells do not tile the set
+        row[((size_t)be * nx + cx) * ny + cy] = i;
+        pos[3 * (size_t)i] = be; pos[3 * (size_t)i + 1] = cx; pos[3 * (size_t)i + 2] = cy;
+      }
+    }
+  }
+  return true;                                                       // (n slots, n distinct atoms: every atom has its place)
+}
+
 }  // namespace conp

@@ -104,6 +104,21 @@ struct PppmPlan {
 void electrode_seeds(const KTables &kt, int ne, const double *xele /*[ne][3]*/, std::vector<double> &seeds);
 
 // ------------------------------------------------------------------------------------------------
+// EleLattice: the axis-aligned translation group of the electrode atoms (no reference counterpart: the lattice form of the solve,
+// conp_kernels.hip lat_gemv_kernel).  The smallest a, b > 0 for which (a, 0, 0) and (0, b, 0) map the atoms onto themselves,
+// periodic in x and y, positions matched within 1e-4 A.  Cell (0, 0) is the cell of atom 0, the basis atoms are its atoms in index
+// order; row[(beta * nx + cx) * ny + cy] is the atom `beta` of cell (0, 0) translated by (cx a, cy b).  The positions only propose
+// this map: whether the solve matrix has the symmetry is measured on the matrix.
+// ------------------------------------------------------------------------------------------------
+struct EleLattice {
+  int nx = 0, ny = 0, nbasis = 0;
+  double a = 0, b = 0;
+  std::vector<int> row;          // [nbasis][nx][ny] -> atom
+  std::vector<int> pos;          // [n][3]: (beta, cx, cy) of every atom
+  bool find(int n, const double *x /*[n][3]*/, double lx, double ly);   // false: no such pair of translations
+};
+
+// ------------------------------------------------------------------------------------------------
 // RankOps: the collectives FixConp::post_neighbor / linalg_init make on `world` (fix_conp.cpp:415, 492, 523, 535).  The default
 // is one rank; conp_fix.cpp implements it on the host's conp_comm callbacks for spatially decomposed runs.
 // ------------------------------------------------------------------------------------------------

@@ -15,6 +15,7 @@ namespace conp {
 bool path_on(unsigned bit);
 int debug_sk_workgroups();
 int debug_ew_block();                        // conp_debug_set_ew_block: cap of the Ewald entries' block width (0: the library's choice)
+int debug_lat_stage();                       // conp_debug_set_lat_stage: cap of the basis atoms the lattice solve stages at a time (0: what fits)
 const char *env_knob(const char *name);      // operational knob: getenv + one line on stderr the first time a set knob is read
 
 // raise a kernel's dynamic-LDS limit, only when a launch needs more than it was last given: per-update launches must not
@@ -318,6 +319,23 @@ void launch_sym_pack(hipStream_t s, int ne, int ne_pad, const double *S, double 
 void launch_sym_gemv_finish(hipStream_t s, int n, int ne_pad, const double *Spk, const double *b, double *yp /*[ne_pad / 128][ne_pad]*/,
                             double *y, const double *elesetq, const double *eleinitq, double potdiff, const int *atoms_ptr,
                             const int *atoms_of, const int *atoms_row /*row of every CSR entry*/, double *q_ele, double *q_atoms);
+// the same GEMV + charge write for lattice-periodic electrodes: S_ij = T[basis_i][basis_j][cell_j - cell_i] (conp_kernels.hip,
+// "GEMV with the projected inverse as a BLOCK-CIRCULANT matrix").  lat_row [nb][nx][ny] -> row, lat_pos [ne][3] = (basis, cx, cy).
+struct LatShape {
+  int R = 0;        // rows per thread, consecutive along y (4 where ny is a multiple of 4, else 1); 0: the form cannot run
+  int sy = 0;       // LDS stride of a row of ny table / b entries
+  int G = 0;        // basis atoms (table slabs + b vectors) staged at a time
+  int CB = 0;       // cells per workgroup
+  size_t lds = 0;   // bytes of dynamic LDS
+};
+LatShape lat_shape(int nx, int ny, int nb);
+void launch_lat_table(hipStream_t s, int ne, int nb, int ncell, const double *S, const int *lat_row, double *T /*[nb][nb][nx][ny]*/);
+// stat [2] (device): receives the bit patterns of max |S_ij| and max |S_ij - T[..]| -- how block-circulant the matrix is
+void launch_lat_dev(hipStream_t s, int ne, int nx, int ny, int nb, const double *S, const int *lat_pos, const double *T,
+                    unsigned long long *stat);
+void launch_lat_gemv(hipStream_t s, const LatShape &sh, int nx, int ny, int nb, const double *T, const int *lat_row, const double *b,
+                     double *y, const double *elesetq, const double *eleinitq, double potdiff, const int *atoms_ptr,
+                     const int *atoms_of, double *q_ele, double *q_atoms);
 void launch_gemv_rows(hipStream_t s, int n, int row0, int row1, const double *S, const double *b, double *y);
 // all rows + the charge write of plain `fix conp` in one launch (atoms_ptr / atoms_of: electrode row -> its owned and ghost atoms)
 void launch_gemv_finish(hipStream_t s, int n, const double *S, const double *b, double *y, const double *elesetq,

@@ -36,6 +36,7 @@ const char *env_knob(const char *name) {
 static std::atomic<unsigned> g_paths{0};
 static std::atomic<int> g_sk_nwg{0};
 static std::atomic<int> g_ew_block{0};
+static std::atomic<int> g_lat_stage{0};
 bool path_on(unsigned bit) {
   const unsigned m = g_paths.load(std::memory_order_relaxed);
   if (m & bit) {
@@ -47,8 +48,10 @@ bool path_on(unsigned bit) {
 }
 int debug_sk_workgroups() { return g_sk_nwg.load(std::memory_order_relaxed); }
 int debug_ew_block() { return g_ew_block.load(std::memory_order_relaxed); }
+int debug_lat_stage() { return g_lat_stage.load(std::memory_order_relaxed); }
 extern "C" void conp_debug_set_paths(unsigned mask) { g_paths.store(mask, std::memory_order_relaxed); }
 extern "C" void conp_debug_set_sk_workgroups(int n) { g_sk_nwg.store(n > 0 ? n : 0, std::memory_order_relaxed); }
+extern "C" void conp_debug_set_lat_stage(int n) { g_lat_stage.store(n > 0 ? n : 0, std::memory_order_relaxed); }
 extern "C" void conp_debug_set_ew_block(int n) { g_ew_block.store(n > 0 ? (n + 63) / 64 * 64 : 0, std::memory_order_relaxed); }
 
 __device__ double block_sum_1024(double v, double *red);
@@ -2104,6 +2107,223 @@ void launch_sym_gemv_finish(hipStream_t s, int n, int ne_pad, const double *Spk,
   hipLaunchKernelGGL(sym_gemv_kernel, dim3(nb * (nb + 1) / 2), dim3(256), 0, s, n, ne_pad, Spk, b, yp);
   hipLaunchKernelGGL(sym_finish_kernel, dim3((n + SF_R - 1) / SF_R), dim3(4 * SF_R), 0, s, n, ne_pad, nb, (const double *)yp, y, elesetq, eleinitq,
                      potdiff, atoms_ptr, atoms_of, atoms_row, q_ele, q_atoms);
+}
+
+// ---- GEMV with the projected inverse as a BLOCK-CIRCULANT matrix: a table of Ne * nbasis numbers instead of the matrix -------
+// Electrodes that are perfect lattices (nx x ny cells of nbasis atoms, periodic in x and y) give a matrix A that is invariant under
+// the lattice translations, and so are its inverse and the projected inverse S:  S_ij = T[basis_i][basis_j][cell_j - cell_i].  The
+// host proposes the map (conp_host.cpp EleLattice, from the positions), lat_table_kernel reads T off the rows of cell (0, 0) and
+// lat_dev_kernel measures max |S_ij - T[..]| over the whole matrix, once per matrix; the caller takes this form only for a deviation
+// of rounding size (conp_fix.cpp solve_scatter_fused).  q = S b is then nbasis^2 circular correlations on the nx x ny torus: at the
+// headline size 256 KB of table and 32 KB of b out of L2 instead of 69 MB of packed tiles out of HBM, and 16.8 M fmas.
+//
+// lat_gemv_kernel: workgroup = (basis atom beta, CB consecutive cells, cy fastest), 512 threads = (part, row group).  A row group is
+// R = 4 rows consecutive along y (R = 1 where ny is no multiple of 4), a part a fixed subset of the rows (beta', cx') of the staged
+// tables: part p takes the rows p, p + P, ... of every stage, walks each along y and adds its ny terms in order onto the group's R
+// accumulators (independent chains).  With R = 4 a quad of table entries and a quad of b entries serve 16 fmas: the four rows of a
+// group need T[dy], T[dy - 1], T[dy - 2], T[dy - 3] for the same b[cy'], so the previous quad stays in registers -- 4 LDS doubles
+// per 8 fmas instead of 16 (LDS bandwidth, not the fma rate, bounds this kernel).  The torus is addressed by one conditional
+// subtraction per quad (cy) and one per table row (cx); no integer division inside the loops over terms.
+// Stage: the slabs T[beta][beta'] and b[beta'] (b gathered into lattice order through lat_row) of G basis atoms beta' in LDS, rows
+// padded to sy = ny + 2 doubles (consecutive rows start 4 banks apart; 16-byte alignment kept).  G = all of them where 16 nx sy
+// nbasis bytes fit 144 KB (the headline box: 72 KB, one stage, one workgroup per CU), else as many as fit, the accumulators carried from stage to stage.
+// Sum of a row: the parts of a wavefront by shuffle-adds (lanes rg + nrg k), the eight wavefronts through LDS as
+// ((w0 + w1) + (w2 + w3)) + ((w4 + w5) + (w6 + w7)).  Every row is finished by its workgroup: no slot plane, no second launch, no
+// atomics; the order of every sum is fixed -> bitwise reproducible.
+// Rounding chain of a term (tests/lattice_ref.py chain restates it): a part's fmas, ny * sum over the stages of
+// ceil(G nx / P) (the first rounds the product, each later one the running sum), + log2(64 / nrg) shuffle-adds + 3.
+// Headline (nx 32, ny 16, nbasis 8: CB 16, nrg 4, P 128, one stage): 2 * 16 + 4 + 3 = 39.  `big` (64 x 32 cells: CB 64, nrg 16, P 32,
+// G 4, two stages): 2 * 8 * 32 + 2 + 3 = 517.
+// Then exactly sym_finish_kernel's tail for the row: y, q = y + dV setq (+ qinit) without contraction, and the row's owned and
+// ghost copies in q_atoms through its CSR list.  The row's constants and list bounds are requested before the stage.
+constexpr int LG_THREADS = 512;
+constexpr size_t LG_LDS = 65536;          // what the table slab and the b vector of ONE basis atom may take (else: no lattice form)
+constexpr size_t LG_LDS_MAX = 147456;     // what a workgroup's stage may take of the CU's 160 KB
+LatShape lat_shape(int nx, int ny, int nb) {
+  LatShape sh;
+  if (nx < 1 || ny < 1 || nb < 1 || (long)nx * ny < 16) return sh;
+  const int R = ny % 4 == 0 ? 4 : 1;
+  size_t sy = R == 4 ? ny + 2 : (ny | 1);
+  if (16 * (size_t)nx * sy > LG_LDS) sy = ny;
+  if (16 * (size_t)nx * sy > LG_LDS) return sh;                  // two lattice vectors do not fit a stage
+  sh.sy = (int)sy;
+  sh.G = (int)std::min<size_t>(nb, LG_LDS_MAX / (16 * (size_t)nx * sy));
+  if (debug_lat_stage() > 0) sh.G = std::min(sh.G, debug_lat_stage());
+  const int ncell = nx * ny;
+  int CB = R;                                                    // the largest block that still gives 256 workgroups
+  while (2 * CB <= 64 * R && 2 * CB <= ncell && (long)nb * ((ncell + 2 * CB - 1) / (2 * CB)) >= 256) CB *= 2;
+  sh.CB = CB;
+  sh.lds = std::max<size_t>(16 * (size_t)sh.G * nx * sy, 80 * (size_t)CB);
+  sh.R = R;
+  return sh;
+}
+
+__global__ __launch_bounds__(256) void lat_table_kernel(int ne, int nb, int ncell, const double *__restrict__ S,
+                                                        const int *__restrict__ lat_row, double *__restrict__ T) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)nb * ne) return;
+  const int beta = (int)(i / ne), j = (int)(i - (size_t)beta * ne);             // j = beta' * ncell + (dx * ny + dy)
+  T[i] = S[(size_t)lat_row[(size_t)beta * ncell] * ne + lat_row[j]];
+}
+
+__global__ __launch_bounds__(256) void lat_dev_kernel(int ne, int nx, int ny, int nb, const double *__restrict__ S,
+                                                      const int *__restrict__ lat_pos, const double *__restrict__ T,
+                                                      unsigned long long *__restrict__ stat /*[2]: bits of max |S_ij|, max |S_ij - T|*/) {
+  const int i = blockIdx.x;
+  const int bi = lat_pos[3 * i], cxi = lat_pos[3 * i + 1], cyi = lat_pos[3 * i + 2];
+  const double *Ti = T + (size_t)bi * nb * nx * ny;
+  double mx = 0.0, md = 0.0;
+  for (int j = threadIdx.x; j < ne; j += 256) {
+    int dx = lat_pos[3 * j + 1] - cxi, dy = lat_pos[3 * j + 2] - cyi;
+    if (dx < 0) dx += nx;
+    if (dy < 0) dy += ny;
+    const double v = S[(size_t)i * ne + j], t = Ti[((size_t)lat_pos[3 * j] * nx + dx) * ny + dy];
+    mx = fmax(mx, fabs(v));
+    md = fmax(md, fabs(v - t));
+  }
+  // (the exact, order-independent reduction of sym_pack_kernel)
+  for (int off = 32; off > 0; off >>= 1) { mx = fmax(mx, __shfl_down(mx, off, 64)); md = fmax(md, __shfl_down(md, off, 64)); }
+  if ((threadIdx.x & 63) == 0) { atomicMax(stat, f64_bits_abs(mx)); atomicMax(stat + 1, f64_bits_abs(md)); }
+}
+
+template <int R>
+__global__ __launch_bounds__(LG_THREADS) void lat_gemv_kernel(int nx, int ny, int nb, int sy, int G, int CB, const double *__restrict__ T,
+                                                              const int *__restrict__ lat_row, const double *__restrict__ b,
+                                                              double *__restrict__ y, const double *__restrict__ elesetq,
+                                                              const double *__restrict__ eleinitq, double potdiff,
+                                                              const int *__restrict__ atoms_ptr, const int *__restrict__ atoms_of,
+                                                              double *__restrict__ q_ele, double *__restrict__ q_atoms) {
+  extern __shared__ __attribute__((aligned(16))) double lat_lds[];
+  const int ncell = nx * ny, nblk = (ncell + CB - 1) / CB;
+  const int beta = blockIdx.x / nblk, c0 = (blockIdx.x - beta * nblk) * CB;
+  const int tid = threadIdx.x, nrg = CB / R, rg = tid & (nrg - 1), part = tid / nrg, P = LG_THREADS / nrg;
+  // the row this thread finishes (tid < CB), its constants and its run of the atom list: requested before the stage
+  int row = -1, k0 = 0, k1 = 0;
+  double sq = 0.0, iq = 0.0;
+  if (tid < CB && c0 + tid < ncell) {
+    row = lat_row[(size_t)beta * ncell + c0 + tid];
+    sq = elesetq[row];
+    if (eleinitq) iq = eleinitq[row];
+    if (q_atoms) { k0 = atoms_ptr[row]; k1 = atoms_ptr[row + 1]; }
+  }
+  const int cg = c0 + rg * R;                       // first cell of the row group (a group never straddles a row of cells: R | ny)
+  const bool live = cg < ncell;
+  const int cx = live ? cg / ny : 0, cy0 = live ? cg - cx * ny : 0;
+  double acc[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) acc[r] = 0.0;
+  double *Ts = lat_lds, *bs = lat_lds + (size_t)G * nx * sy;
+  for (int g0 = 0; g0 < nb; g0 += G) {
+    const int gn = nb - g0 < G ? nb - g0 : G, nel = gn * ncell, nrows = gn * nx;
+    const double *Tsrc = T + ((size_t)beta * nb + g0) * ncell;
+    const int *msrc = lat_row + (size_t)g0 * ncell;
+    if (g0) __syncthreads();
+    if constexpr (R == 4) {
+#pragma unroll 4
+      for (int i = 2 * tid; i < nel; i += 2 * LG_THREADS) {
+        const int r = i / ny, c = i - r * ny;
+        const double2 t = *reinterpret_cast<const double2 *>(Tsrc + i);
+        const int2 m = *reinterpret_cast<const int2 *>(msrc + i);
+        const double2 bv = make_double2(b[m.x], b[m.y]);
+        *reinterpret_cast<double2 *>(Ts + r * sy + c) = t;
+        *reinterpret_cast<double2 *>(bs + r * sy + c) = bv;
+      }
+    } else {
+#pragma unroll 4
+      for (int i = tid; i < nel; i += LG_THREADS) {
+        const int r = i / ny, c = i - r * ny;
+        Ts[r * sy + c] = Tsrc[i];
+        bs[r * sy + c] = b[msrc[i]];
+      }
+    }
+    __syncthreads();
+    if (live) {
+      for (int it = part; it < nrows; it += P) {
+        const int gl = it / nx, cxp = it - gl * nx;                 // (beta' of the stage, cx')
+        int dx = cxp - cx;
+        if (dx < 0) dx += nx;
+        const double *tr = Ts + (gl * nx + dx) * sy, *br = bs + it * sy;
+        if constexpr (R == 4) {
+          double2 p01 = *reinterpret_cast<const double2 *>(tr + ny - 4), p23 = *reinterpret_cast<const double2 *>(tr + ny - 2);
+          int qb = cy0;
+          for (int e0 = 0; e0 < ny; e0 += 4) {
+            const double2 c01 = *reinterpret_cast<const double2 *>(tr + e0), c23 = *reinterpret_cast<const double2 *>(tr + e0 + 2);
+            const double2 b01 = *reinterpret_cast<const double2 *>(br + qb), b23 = *reinterpret_cast<const double2 *>(br + qb + 2);
+            acc[0] = fma(c01.x, b01.x, acc[0]); acc[0] = fma(c01.y, b01.y, acc[0]); acc[0] = fma(c23.x, b23.x, acc[0]); acc[0] = fma(c23.y, b23.y, acc[0]);
+            acc[1] = fma(p23.y, b01.x, acc[1]); acc[1] = fma(c01.x, b01.y, acc[1]); acc[1] = fma(c01.y, b23.x, acc[1]); acc[1] = fma(c23.x, b23.y, acc[1]);
+            acc[2] = fma(p23.x, b01.x, acc[2]); acc[2] = fma(p23.y, b01.y, acc[2]); acc[2] = fma(c01.x, b23.x, acc[2]); acc[2] = fma(c01.y, b23.y, acc[2]);
+            acc[3] = fma(p01.y, b01.x, acc[3]); acc[3] = fma(p23.x, b01.y, acc[3]); acc[3] = fma(p23.y, b23.x, acc[3]); acc[3] = fma(c01.x, b23.y, acc[3]);
+            p01 = c01; p23 = c23;
+            qb += 4;
+            if (qb >= ny) qb -= ny;
+          }
+        } else {
+          int q = cy0;
+          for (int e = 0; e < ny; ++e) {
+            acc[0] = fma(tr[e], br[q], acc[0]);
+            if (++q == ny) q = 0;
+          }
+        }
+      }
+    }
+  }
+  // the parts of a wavefront (lanes rg + nrg k), then the eight wavefronts in a fixed tree
+  for (int off = 32; off >= nrg; off >>= 1) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] += __shfl_xor(acc[r], off, 64);
+  }
+  __syncthreads();                                  // the stage is done with: its LDS carries the sums now
+  double *red = lat_lds, *vq = lat_lds + 8 * CB;    // red [8][CB], vq [CB], then ks [CB], ke [CB]
+  int *ks = reinterpret_cast<int *>(vq + CB), *ke = ks + CB;
+  const int lane = tid & 63, wave = tid >> 6;
+  if (lane < nrg) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) red[wave * CB + rg * R + r] = acc[r];
+  }
+  __syncthreads();
+  if (tid < CB) {
+    const double r = ((red[tid] + red[CB + tid]) + (red[2 * CB + tid] + red[3 * CB + tid])) +
+                     ((red[4 * CB + tid] + red[5 * CB + tid]) + (red[6 * CB + tid] + red[7 * CB + tid]));
+    double v;
+    {
+#pragma clang fp contract(off)
+      v = r + potdiff * sq;
+      if (eleinitq) v += iq;
+    }
+    if (row >= 0) { y[row] = r; q_ele[row] = v; }
+    vq[tid] = v; ks[tid] = k0; ke[tid] = k1;
+  }
+  __syncthreads();
+  if (!q_atoms) return;
+  const int rl = tid & (CB - 1);
+  const double v = vq[rl];
+  for (int k = ks[rl] + tid / CB, k1r = ke[rl]; k < k1r; k += LG_THREADS / CB) q_atoms[atoms_of[k]] = v;
+}
+
+void launch_lat_table(hipStream_t s, int ne, int nb, int ncell, const double *S, const int *lat_row, double *T) {
+  const size_t n = (size_t)nb * ne;
+  hipLaunchKernelGGL(lat_table_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ne, nb, ncell, S, lat_row, T);
+}
+void launch_lat_dev(hipStream_t s, int ne, int nx, int ny, int nb, const double *S, const int *lat_pos, const double *T,
+                    unsigned long long *stat) {
+  (void)hipMemsetAsync(stat, 0, 2 * sizeof(unsigned long long), s);
+  hipLaunchKernelGGL(lat_dev_kernel, dim3(ne), dim3(256), 0, s, ne, nx, ny, nb, S, lat_pos, T, stat);
+}
+void launch_lat_gemv(hipStream_t s, const LatShape &sh, int nx, int ny, int nb, const double *T, const int *lat_row, const double *b,
+                     double *y, const double *elesetq, const double *eleinitq, double potdiff, const int *atoms_ptr,
+                     const int *atoms_of, double *q_ele, double *q_atoms) {
+  const int ncell = nx * ny, grid = nb * ((ncell + sh.CB - 1) / sh.CB);
+  static DynLdsCache granted4{}, granted1{};
+  if (sh.lds > 65536) {
+    if (sh.R == 4) ensure_dyn_lds(lat_gemv_kernel<4>, sh.lds, granted4);
+    else ensure_dyn_lds(lat_gemv_kernel<1>, sh.lds, granted1);
+  }
+  if (sh.R == 4)
+    hipLaunchKernelGGL(lat_gemv_kernel<4>, dim3(grid), dim3(LG_THREADS), sh.lds, s, nx, ny, nb, sh.sy, sh.G, sh.CB, T, lat_row, b, y,
+                       elesetq, eleinitq, potdiff, atoms_ptr, atoms_of, q_ele, q_atoms);
+  else
+    hipLaunchKernelGGL(lat_gemv_kernel<1>, dim3(grid), dim3(LG_THREADS), sh.lds, s, nx, ny, nb, sh.sy, sh.G, sh.CB, T, lat_row, b, y,
+                       elesetq, eleinitq, potdiff, atoms_ptr, atoms_of, q_ele, q_atoms);
 }
 
 void launch_gemv_rows(hipStream_t s, int n, int row0, int row1, const double *S, const double *b, double *y) {
