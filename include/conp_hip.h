@@ -859,6 +859,116 @@ int conp_integrate_temperature_device(conp_fix *fix, const double *d_v /*[nlocal
 int conp_integrate_get_state(conp_fix *fix, double *state /*HOST [ngroups][8]*/);
 int conp_integrate_set_state(conp_fix *fix, const double *state /*HOST [ngroups][8]*/);
 
+/* ---- constraints: `fix shake` on the device -----------------------------------------------------------------
+ * Bond and angle constraints of small clusters: LAMMPS' FixShake @ 27May2021 at the reference decks' keywords (`fix ID group shake
+ * tol iter 0 t ... b ... [a ...]`), without rRESPA, per-atom rmass or RATTLE.  All arithmetic is double, in the order written
+ * (products left to right), no contraction.
+ * Clusters: [ncluster][7] = flag, i0, i1, i2, t0, t1, t2 with LAMMPS' shake_flag:
+ *   flag 2: one bond i0-i1 of length d0 = bond_distance[t0];
+ *   flag 3: two bonds from the centre i0: i0-i1 (d0 = bond_distance[t0]) and i0-i2 (d1 = bond_distance[t1]);
+ *   flag 1: the two bonds of flag 3 and the angle: the distance i1-i2 is d2 = angle_distance[t2]
+ *           (= sqrt(d0^2 + d1^2 - 2 d0 d1 cos(theta0)) of the angle type).
+ *   Fields a flag does not use are ignored.  Flag 4 (three bonds) is refused.  Every index is an owned atom in [0, nlocal), the
+ *   indices of a cluster are distinct and an atom belongs to AT MOST ONE cluster: conp_shake_set_params checks all of it, and
+ *   because of it no output meets an atomic.  The engine subtracts 1, 2 or 3 from a group's dof per cluster of flag 2, 3 or 1.
+ * Constants:  dtv = dt;  dtfsq = dt dt ftm2v in conp_shake_post_force_device, dtfsq = 0.5 dt dt ftm2v in conp_shake_setup_device and
+ *   conp_shake_correct_device;  im_k = 1.0 / mass[type[i_k]];  dtfmsq_k = dtfsq / mass[type[i_k]].
+ * Difference a - b with minimum image, per dimension c:  d = a[c] - b[c];  where prd[c] > 0 and fabs(d) > 0.5 prd[c]:  d += prd[c] if
+ *   d < 0, else d -= prd[c].  One pass, for r and s alike.
+ * Unconstrained position of a cluster atom:  xs = x + dtv v + dtfmsq f  (left to right), formed in the cluster's thread; for
+ *   conp_shake_correct_device v and f count as 0 and xs = x.
+ * r01 = x0 - x1, r02 = x0 - x2, r12 = x1 - x2;  s01, s02, s12 the same differences of xs;  rNNsq, sNNsq their squares (x x + y y + z z),
+ *   r0102 = r01 . r02, r0112 = r01 . r12, r0212 = r02 . r12, and s.r dot products the same way.
+ * Flag 2:  a = (im0 + im1) (im0 + im1) r01sq;  b = 2.0 (im0 + im1) (s01 . r01);  c = s01sq - d0 d0;  determ = b b - 4.0 a c;
+ *   determ < 0: determ = 0, counted;  lamda = (-b + sqrt(determ)) / (2.0 a) if b > 0, else (-b - sqrt(determ)) / (2.0 a);
+ *   lamda /= dtfsq;  f0 += lamda r01;  f1 -= lamda r01;
+ *   v = lamda (r01x r01x, r01y r01y, r01z r01z, r01x r01y, r01x r01z, r01y r01z), each (lamda r_a) r_b.
+ * Flag 3:  a11 = 2.0 (im0 + im1) (s01 . r01);  a12 = 2.0 im0 (s01 . r02);  a21 = 2.0 im0 (s02 . r01);  a22 = 2.0 (im0 + im2) (s02 . r02);
+ *   determ = a11 a22 - a12 a21;  determ == 0: the cluster adds nothing and is counted (LAMMPS aborts; a kernel cannot);
+ *   determinv = 1.0 / determ;  a11inv = a22 determinv;  a12inv = -a12 determinv;  a21inv = -a21 determinv;  a22inv = a11 determinv;
+ *   quad1_0101 = (im0 + im1) (im0 + im1) r01sq;  quad1_0202 = im0 im0 r02sq;  quad1_0102 = 2.0 (im0 + im1) im0 r0102;
+ *   quad2_0202 = (im0 + im2) (im0 + im2) r02sq;  quad2_0101 = im0 im0 r01sq;  quad2_0102 = 2.0 (im0 + im2) im0 r0102;
+ *   lamda01 = lamda02 = 0, niter = 0, done = false;  while not done and niter < max_iter:
+ *     quad1 = quad1_0101 l01 l01 + quad1_0202 l02 l02 + quad1_0102 l01 l02;  quad2 likewise (0101, 0202, 0102);
+ *     b1 = d0 d0 - s01sq - quad1;  b2 = d1 d1 - s02sq - quad2;
+ *     l01_new = a11inv b1 + a12inv b2;  l02_new = a21inv b1 + a22inv b2;
+ *     done = true;  if fabs(l01_new - l01) > tolerance or fabs(l02_new - l02) > tolerance: done = false;
+ *     l01 = l01_new;  l02 = l02_new;  if fabs(l01) > 1e150 or fabs(l02) > 1e150: done = true;  niter++
+ *   l01 /= dtfsq;  l02 /= dtfsq;  f0 += l01 r01 + l02 r02;  f1 -= l01 r01;  f2 -= l02 r02;
+ *   v_ab = l01 r01_a r01_b + l02 r02_a r02_b  for ab = xx, yy, zz, xy, xz, yz.
+ * Flag 1, three unknowns l01, l02, l12:
+ *   a11 = 2.0 (im0 + im1) (s01 . r01);  a12 = 2.0 im0 (s01 . r02);         a13 = -2.0 im1 (s01 . r12);
+ *   a21 = 2.0 im0 (s02 . r01);          a22 = 2.0 (im0 + im2) (s02 . r02);  a23 = 2.0 im2 (s02 . r12);
+ *   a31 = -2.0 im1 (s12 . r01);         a32 = 2.0 im2 (s12 . r02);          a33 = 2.0 (im1 + im2) (s12 . r12);
+ *   determ = a11 a22 a33 + a12 a23 a31 + a13 a21 a32 - a11 a23 a32 - a12 a21 a33 - a13 a22 a31;  determ == 0 as for flag 3;
+ *   determinv = 1.0 / determ;
+ *   a11inv = determinv (a22 a33 - a23 a32);   a12inv = -determinv (a12 a33 - a13 a32);  a13inv = determinv (a12 a23 - a13 a22);
+ *   a21inv = -determinv (a21 a33 - a23 a31);  a22inv = determinv (a11 a33 - a13 a31);   a23inv = -determinv (a11 a23 - a13 a21);
+ *   a31inv = determinv (a21 a32 - a22 a31);   a32inv = -determinv (a11 a32 - a12 a31);  a33inv = determinv (a11 a22 - a12 a21);
+ *   quadK = qK_0101 l01 l01 + qK_0202 l02 l02 + qK_1212 l12 l12 + qK_0102 l01 l02 + qK_0112 l01 l12 + qK_0212 l02 l12, with
+ *     q1: (im0 + im1) (im0 + im1) r01sq;  im0 im0 r02sq;  im1 im1 r12sq;  2.0 (im0 + im1) im0 r0102;  -2.0 (im0 + im1) im1 r0112;
+ *         -2.0 im0 im1 r0212
+ *     q2: im0 im0 r01sq;  (im0 + im2) (im0 + im2) r02sq;  im2 im2 r12sq;  2.0 (im0 + im2) im0 r0102;  2.0 im0 im2 r0112;
+ *         2.0 (im0 + im2) im2 r0212
+ *     q3: im1 im1 r01sq;  im2 im2 r02sq;  (im1 + im2) (im1 + im2) r12sq;  -2.0 im1 im2 r0102;  -2.0 (im1 + im2) im1 r0112;
+ *         2.0 (im1 + im2) im2 r0212
+ *   b1, b2 as for flag 3;  b3 = d2 d2 - s12sq - quad3;  lK_new = aK1inv b1 + aK2inv b2 + aK3inv b3;  the loop, its stop rule and the
+ *   1e150 guard as for flag 3, over three values;  each l /= dtfsq;
+ *   f0 += l01 r01 + l02 r02;  f1 -= l01 r01 - l12 r12;  f2 -= l02 r02 + l12 r12;
+ *   v_ab = l01 r01_a r01_b + l02 r02_a r02_b + l12 r12_a r12_b.
+ * conp_shake_post_force_device and conp_shake_setup_device add the constraint force into d_f (FixShake::post_force and ::setup; they
+ *   differ in dtfsq alone).  conp_shake_correct_device (FixShake::correct_coordinates) forms the same force from 0.0 with v = f = 0
+ *   and moves the cluster atoms: x_k += dtfmsq_k fc_k.
+ * d_out [9], overwritten:  the virial xx, yy, zz, xy, xz, yz (every cluster counts whole: all its atoms are owned);  the number of
+ *   clusters that left the loop at max_iter without done;  the number with a zero (flags 3, 1) or negative (flag 2) determinant;
+ *   the largest niter (0 for flag 2).  The counts are integer-valued doubles.
+ * d_vatom [nlocal][6], overwritten: each atom of a cluster gets v / n, n = 2 (flag 2) or 3 (flags 3, 1), as Fix::v_tally gives it;
+ *   rows of atoms in no cluster are exactly 0.0.
+ * conp_shake_check_device: d_out[0] = the largest |r - d| / d over the bond constraints, d_out[1] the same over the 1-2 distances
+ *   of the flag-1 clusters (r by minimum image); 0.0 where there is none.
+ * Order and reproducibility: one thread per cluster reads a cluster atom's f (or x), adds to it once and stores it.  The virial is
+ *   summed over clusters in the caller's order: per workgroup in a fixed tree, then over the workgroups in ascending order by one
+ *   finishing workgroup; counts and maxima do not depend on order.  Every output is a pure function of the input, byte-identical
+ *   from call to call.  Atoms in no cluster and rows from nlocal on are neither read nor written (d_vatom: zeroed).
+ * Order: conp_shake_set_params (copies and uploads, reserves all scratch; may allocate and synchronise; afterwards the owned atoms
+ *   keep their local order).  At the start of a run: conp_shake_correct_device -> the force entries -> conp_shake_setup_device ->
+ *   conp_integrate_setup_device.  Per step: conp_integrate_initial_device -> ... -> conp_ghost_fold_device ->
+ *   conp_shake_post_force_device -> conp_integrate_final_device: the constraint force needs the folded total force, as LAMMPS'
+ *   post_force runs behind reverse_comm.  The constraint is met by the NEXT nve_x, not by the velocities; with `fix nvt` the
+ *   scaling between the two half-steps is ignored, exactly as LAMMPS ignores it.
+ * CONP_ERR_STATE: any other entry before conp_shake_set_params.
+ * CONP_ERR_ARG: a NULL struct, or a NULL array with a positive count; a negative count; a type outside [1, ntypes]; a flag outside
+ *   {1, 2, 3}; an index outside [0, nlocal) or repeated in a cluster; an atom in two clusters; a distance type out of range; a
+ *   distance (of any type), mass, dt, ftm2v or tolerance that is not positive and finite; max_iter < 1; a negative or non-finite prd;
+ *   a NULL d_x, d_v or d_f.  A refused conp_shake_set_params leaves the handle WITHOUT constraints; every other refused call changes
+ *   nothing.  ncluster == 0: CONP_OK, d_out is zeroed, nothing else is touched.  d_out NULL: the finishing launch is skipped (one
+ *   launch per call); conp_shake_check_device then does nothing.
+ * The step entries enqueue on the handle's stream and make no device allocation, no copy to the host and no synchronisation.
+ * They need nothing of the fix but its stream: they work from conp_fix_create on, on Ewald and `pppm` handles, and are rank-local,
+ * never collective.  Out of scope: flag 4, RATTLE, rRESPA, rmass, clusters with ghost members, the `stats` print-out. */
+typedef struct {
+  int nlocal, ntypes;
+  const int *type;                      /* [nlocal] 1..ntypes */
+  const double *mass;                   /* [ntypes + 1], entry 0 unused */
+  int nbondtypes, nangletypes;
+  const double *bond_distance;          /* [nbondtypes + 1]  constraint length per bond type (bond r0), entry 0 unused */
+  const double *angle_distance;         /* [nangletypes + 1] 1-2 distance per angle type: sqrt(d1^2 + d2^2 - 2 d1 d2 cos(theta0)) */
+  int ncluster;
+  const int *cluster;                   /* [ncluster][7]  flag, i0, i1, i2, t0, t1, t2 */
+  double tolerance; int max_iter;       /* fix shake's tol and iter */
+  double dt, ftm2v;                     /* update->dt, force->ftm2v */
+  double prd[3];                        /* > 0: minimum image in that dimension; 0: differences as they are */
+} conp_shake_params;
+
+int conp_shake_set_params(conp_fix *fix, const conp_shake_params *p);
+int conp_shake_correct_device(conp_fix *fix, double *d_x /*[nlocal][3], cluster atoms moved*/);
+int conp_shake_setup_device(conp_fix *fix, const double *d_x /*[nlocal][3]*/, const double *d_v /*[nlocal][3]*/,
+                            double *d_f /*[nlocal][3], added to*/, double *d_out /*[9], overwritten; NULL: none*/);
+int conp_shake_post_force_device(conp_fix *fix, const double *d_x /*[nlocal][3]*/, const double *d_v /*[nlocal][3]*/,
+                                 double *d_f /*[nlocal][3], added to*/, double *d_out /*[9], overwritten; NULL: none*/,
+                                 double *d_vatom /*[nlocal][6], overwritten; NULL: none*/);
+int conp_shake_check_device(conp_fix *fix, const double *d_x /*[nlocal][3]*/, double *d_out /*[2], overwritten*/);
+
 /* per-kernel timing of the last N updates via HIP events on the library's stream (bench.py roofline leg).
  * enable: 0 off, 1 a pair of events around every kernel, 2 around every 4th launch of the dominant kernel (sk_gemm) only --
  * cheap enough to stay on inside a timed region (an event pair drains the queue around the kernel it brackets). */

@@ -96,6 +96,19 @@ class conp_integrate_params(C.Structure):
                 ("t_period", C.POINTER(C.c_double)), ("dt", C.c_double), ("ftm2v", C.c_double), ("mvv2e", C.c_double), ("boltz", C.c_double)]
 
 
+class conp_shake_params(C.Structure):
+    _fields_ = [("nlocal", C.c_int), ("ntypes", C.c_int), ("type", C.POINTER(C.c_int)), ("mass", C.POINTER(C.c_double)),
+                ("nbondtypes", C.c_int), ("nangletypes", C.c_int), ("bond_distance", C.POINTER(C.c_double)),
+                ("angle_distance", C.POINTER(C.c_double)), ("ncluster", C.c_int), ("cluster", C.POINTER(C.c_int)),
+                ("tolerance", C.c_double), ("max_iter", C.c_int), ("dt", C.c_double), ("ftm2v", C.c_double), ("prd", C.c_double * 3)]
+
+
+def shake_angle_distance(d1, d2, theta0_rad):
+    """the 1-2 distance `fix shake` constrains for an angle type: sqrt(d1^2 + d2^2 - 2 d1 d2 cos(theta0)), the two bond lengths and
+    the angle's theta0 in radians -> conp_shake_params.angle_distance"""
+    return float(np.sqrt(d1 * d1 + d2 * d2 - 2.0 * d1 * d2 * np.cos(theta0_rad)))
+
+
 class conp_bonded_lists(C.Structure):
     _fields_ = [("nlocal", C.c_int), ("nall", C.c_int), ("nbond", C.c_int), ("bond", C.POINTER(C.c_int)), ("nangle", C.c_int),
                 ("angle", C.POINTER(C.c_int)), ("prd", C.c_double * 3)]
@@ -147,6 +160,8 @@ SYMBOLS = [
     "conp_bonded_set_params", "conp_bonded_set_lists", "conp_bonded_compute", "conp_bonded_compute_device",
     "conp_integrate_set_params", "conp_integrate_setup_device", "conp_integrate_initial_device", "conp_integrate_final_device",
     "conp_integrate_temperature_device", "conp_integrate_get_state", "conp_integrate_set_state",
+    "conp_shake_set_params", "conp_shake_correct_device", "conp_shake_setup_device", "conp_shake_post_force_device",
+    "conp_shake_check_device",
 ]
 
 
@@ -339,6 +354,12 @@ def load_library():
         lib.conp_integrate_temperature_device.argtypes = [vp, vp, vp]
         lib.conp_integrate_get_state.argtypes = [vp, dp]
         lib.conp_integrate_set_state.argtypes = [vp, dp]
+    if hasattr(lib, "conp_shake_set_params"):
+        lib.conp_shake_set_params.argtypes = [vp, C.POINTER(conp_shake_params)]
+        lib.conp_shake_correct_device.argtypes = [vp, vp]
+        lib.conp_shake_setup_device.argtypes = [vp, vp, vp, vp, vp]
+        lib.conp_shake_post_force_device.argtypes = [vp, vp, vp, vp, vp, vp]
+        lib.conp_shake_check_device.argtypes = [vp, vp, vp]
     lib.conp_compute_potential_atom.argtypes = [vp, C.POINTER(conp_atoms), C.POINTER(conp_neighlist), ip, ip,
                                                 C.POINTER(conp_potential_args), dp]
     lib.conp_fix_set_comm.argtypes = [vp, C.POINTER(conp_comm)]
@@ -962,6 +983,39 @@ class FixConp:
         is added to, d_ev [8] (ebond, eangle, virial xx, yy, zz, xy, xz, yz), d_eatom [nall], d_vatom [nall][6] are overwritten"""
         self._check(self.lib.conp_bonded_compute_device(self.h, C.c_void_p(d_x), C.c_void_p(d_f), C.c_void_p(d_ev),
                                                         C.c_void_p(d_eatom), C.c_void_p(d_vatom)))
+
+    # -- SHAKE constraints: set_params -> correct_device at a run's start, setup_device, post_force_device per step (section 23) ------
+    def shake_set_params(self, type, mass, bond_distance, angle_distance, cluster, tolerance, max_iter, dt, ftm2v, prd=(0.0, 0.0, 0.0)):
+        """conp_shake_set_params: type [nlocal] (1..ntypes); mass, bond_distance, angle_distance per type WITHOUT the unused entry 0;
+        cluster [ncluster][7] = flag, i0, i1, i2, t0, t1, t2 (flag 2: one bond, 3: two bonds, 1: two bonds and the angle).  Copied and
+        uploaded; may allocate and synchronise"""
+        ty = np.ascontiguousarray(type, dtype=np.int32).reshape(-1)
+        lead = lambda a: np.ascontiguousarray(np.concatenate([[0.0], np.asarray(a, dtype=np.float64).reshape(-1)]))
+        m, bd, ad = lead(mass), lead(bond_distance), lead(angle_distance)
+        cl = np.ascontiguousarray(cluster, dtype=np.int32).reshape(-1, 7)
+        p = conp_shake_params(nlocal=ty.size, ntypes=m.size - 1, type=_iptr(ty) if ty.size else None, mass=_dptr(m),
+                              nbondtypes=bd.size - 1, nangletypes=ad.size - 1, bond_distance=_dptr(bd), angle_distance=_dptr(ad),
+                              ncluster=cl.shape[0], cluster=_iptr(cl) if cl.size else None, tolerance=tolerance, max_iter=int(max_iter),
+                              dt=dt, ftm2v=ftm2v, prd=(C.c_double * 3)(*prd))
+        self._check(self.lib.conp_shake_set_params(self.h, C.byref(p)))
+
+    def shake_correct_device(self, d_x: int):
+        """conp_shake_correct_device: moves the cluster atoms of d_x [nlocal][3] onto the constraints (to the tolerance); one launch"""
+        self._check(self.lib.conp_shake_correct_device(self.h, C.c_void_p(d_x)))
+
+    def shake_setup_device(self, d_x: int, d_v: int, d_f: int, d_out: int = 0):
+        """conp_shake_setup_device: the constraint force of a run's start (dtfsq = 0.5 dt dt ftm2v) added to d_f; d_out [9] or 0"""
+        self._check(self.lib.conp_shake_setup_device(self.h, C.c_void_p(d_x), C.c_void_p(d_v), C.c_void_p(d_f), C.c_void_p(d_out)))
+
+    def shake_post_force_device(self, d_x: int, d_v: int, d_f: int, d_out: int = 0, d_vatom: int = 0):
+        """conp_shake_post_force_device: the constraint force added to d_f [nlocal][3]; d_out [9] (virial xx, yy, zz, xy, xz, yz,
+        unconverged clusters, bad determinants, largest niter) and d_vatom [nlocal][6] are overwritten (0 = NULL); no synchronisation"""
+        self._check(self.lib.conp_shake_post_force_device(self.h, C.c_void_p(d_x), C.c_void_p(d_v), C.c_void_p(d_f), C.c_void_p(d_out),
+                                                          C.c_void_p(d_vatom)))
+
+    def shake_check_device(self, d_x: int, d_out: int):
+        """conp_shake_check_device: d_out [2] = largest |r - d| / d over the bonds, over the 1-2 distances of the flag-1 clusters"""
+        self._check(self.lib.conp_shake_check_device(self.h, C.c_void_p(d_x), C.c_void_p(d_out)))
 
     # -- velocity Verlet and Nose-Hoover chains: set_params -> setup_device -> initial / final per step (DESIGN.md section 22) ------
     def integrate_set_params(self, type, group, mass, style, dof, t_period, dt, ftm2v, mvv2e, boltz):

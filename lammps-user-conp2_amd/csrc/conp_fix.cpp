@@ -25,6 +25,7 @@
 #include "conp_pairstyle.hpp"
 #include "conp_bondedstyle.hpp"
 #include "conp_integrator.hpp"
+#include "conp_shakestyle.hpp"
 #include "conp_ewaldquery.hpp"
 #include "conp_pppmmesh.hpp"
 
@@ -2386,12 +2387,13 @@ struct conp_fix : DevCtx {
   }
 
   // ---- the pair style with its half list (conp_pairstyle.cpp, DESIGN.md sections 16, 17), the ghost map (conp_ghostmap.cpp, 18),
-  // the harmonic bonds and angles (conp_bondedstyle.cpp, 21), the integrator (conp_integrator.cpp, 22), the exact-Ewald query entries (conp_ewaldquery.cpp, sections 11, 12,
+  // the harmonic bonds and angles (conp_bondedstyle.cpp, 21), the integrator (conp_integrator.cpp, 22), the constraints (conp_shakestyle.cpp, 23), the exact-Ewald query entries (conp_ewaldquery.cpp, sections 11, 12,
   // 14, 15) and the PPPM mesh with the update's b and its query entries (conp_pppmmesh.cpp, sections 8, 13, 14, 15) ----
   PairStyle pair{*this};
   GhostMap ghost{*this};
   BondedStyle bonded{*this};
   Integrator integ{*this};
+  ShakeStyle shake{*this};
   EwaldQuery ew{*this, kt, plan, dplan, tiles_h, ct_ptr_h, d_sf_row_a, d_sf_col_c, d_k_sign};
   PppmMesh pm{*this};
   bool types_in_range = false;                   // every atoms->type of the last (setup_)post_neighbor lies in [0, ntypes]
@@ -3784,6 +3786,59 @@ int conp_integrate_set_state(conp_fix *f, const double *state) {
   HIP_TRY(hipSetDevice(f->env.device));
   f->drop_graph();
   f->integ.set_state(state);
+  CONP_GUARD_END
+}
+
+// ---- SHAKE constraints: set_params -> correct at a run's start, setup, post_force per step ----------------
+int conp_shake_set_params(conp_fix *f, const conp_shake_params *p) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->shake.have_params = false;                  // a refused call leaves the handle without constraints
+  if (!p) throw ConpError(CONP_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(f->env.device));
+  f->drop_graph();
+  f->shake.set_params(p);
+  CONP_GUARD_END
+}
+
+int conp_shake_correct_device(conp_fix *f, double *d_x) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->shake.need_params("conp_shake_correct_device");
+  if (!d_x) throw ConpError(CONP_ERR_ARG, "conp_shake_correct_device: null d_x");
+  f->drop_graph();
+  f->shake.correct(d_x);
+  CONP_GUARD_END
+}
+
+int conp_shake_setup_device(conp_fix *f, const double *d_x, const double *d_v, double *d_f, double *d_out) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->shake.need_params("conp_shake_setup_device");
+  if (!d_x || !d_v || !d_f) throw ConpError(CONP_ERR_ARG, "conp_shake_setup_device: null d_x, d_v or d_f");
+  f->drop_graph();
+  f->shake.force(d_x, d_v, d_f, d_out, nullptr, true);
+  CONP_GUARD_END
+}
+
+int conp_shake_post_force_device(conp_fix *f, const double *d_x, const double *d_v, double *d_f, double *d_out, double *d_vatom) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->shake.need_params("conp_shake_post_force_device");
+  if (!d_x || !d_v || !d_f) throw ConpError(CONP_ERR_ARG, "conp_shake_post_force_device: null d_x, d_v or d_f");
+  f->drop_graph();
+  f->shake.force(d_x, d_v, d_f, d_out, d_vatom, false);
+  CONP_GUARD_END
+}
+
+int conp_shake_check_device(conp_fix *f, const double *d_x, double *d_out) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->shake.need_params("conp_shake_check_device");
+  if (!d_x) throw ConpError(CONP_ERR_ARG, "conp_shake_check_device: null d_x");
+  if (!d_out) return CONP_OK;
+  f->drop_graph();
+  f->shake.check(d_x, d_out);
   CONP_GUARD_END
 }
 

@@ -427,6 +427,30 @@ void launch_integrate_initial(hipStream_t s, const IntegrateArgs &a);
 void launch_integrate_sums(hipStream_t s, const IntegrateArgs &a, bool update, int mode, bool scale);
 // state_out rows from raw [ngroups][8] rows (eta, eta_dot, t_current, t_target) in a.state_in: eta_dotdot[k >= 1] as setup forms it
 void launch_integrate_seed(hipStream_t s, const IntegrateArgs &a);
+// ---- SHAKE bond and angle constraints (conp_shake.hip) ----
+constexpr int SHAKE_BLOCK = 64;          // threads of a workgroup: one per cluster (and, with d_vatom, one per atom row to zero): one wave, no barrier
+constexpr int SHAKE_FINISH = 256;        // threads of the finishing workgroup: partial rows r, r + 256, ... per thread
+constexpr int SHAKE_PART_W = 9;          // doubles of a partial row: virial [6], unconverged, bad determinant, largest niter
+enum { SHAKE_FORCE = 0, SHAKE_CORRECT = 1 };                 // add the constraint force into f, or move x by it (v = f = 0)
+struct ShakeArgs {
+  int ncluster, nlocal, max_iter;
+  const int *cluster;                    // [ncluster][7] flag, i0, i1, i2, t0, t1, t2
+  const int *type;                       // [nlocal]
+  const int *member;                     // [nlocal] 1: the atom is in a cluster (its d_vatom row is the cluster's to write)
+  const double *mass, *bond_d, *angle_d; // [ntypes + 1], [nbondtypes + 1], [nangletypes + 1]
+  double dtv, dtfsq, tolerance;
+  double prd[3];
+  double *x;                             // [nlocal][3]; stored by SHAKE_CORRECT only
+  const double *v;                       // [nlocal][3]; NULL with SHAKE_CORRECT
+  double *f;                             // [nlocal][3] added to; NULL with SHAKE_CORRECT
+  double *vatom;                         // [nlocal][6] overwritten, or NULL
+  double *part;                          // [workgroups][SHAKE_PART_W] scratch rows, or NULL (no d_out)
+};
+// one launch over max(ncluster, vatom ? nlocal : 0) threads; out [9] != NULL: the finishing workgroup behind it
+void launch_shake(hipStream_t s, const ShakeArgs &a, int mode, double *out);
+// out [2] = largest |r - d| / d over the bonds, over the 1-2 distances of the flag-1 clusters
+void launch_shake_check(hipStream_t s, const ShakeArgs &a, double *out);
+inline int shake_rows(int nthreads) { return (nthreads + SHAKE_BLOCK - 1) / SHAKE_BLOCK; }     // workgroups, and rows of a.part
 // ---- the pair style's half list built on the device (conp_neigh.hip) ----
 struct NeighGrid { double lo[3], inv[3]; int n[3]; };     // cell of v along c: clamp((v - lo[c]) * inv[c], 0, n[c] - 1); cells are >= cutneigh wide
 struct NeighRowArgs {
