@@ -969,6 +969,78 @@ int conp_shake_post_force_device(conp_fix *fix, const double *d_x /*[nlocal][3]*
                                  double *d_vatom /*[nlocal][6], overwritten; NULL: none*/);
 int conp_shake_check_device(conp_fix *fix, const double *d_x /*[nlocal][3]*/, double *d_out /*[2], overwritten*/);
 
+/* ---- `fix efield` with a constant field, and the per-group sums of the thermo columns, on the device ----
+ * Two rank-local members of the handle that need nothing of the fix but its stream (the coupled field also reads one device slot
+ * of it): they work from conp_fix_create on, on Ewald and `pppm` handles, and are never collective.  All arithmetic is double in the
+ * order written below, products left to right, without contraction; no sum meets an atomic: per workgroup a fixed tree, then the
+ * rows of the workgroups in a fixed order by a finishing workgroup.  Every output is a pure function of the input, byte-identical
+ * from call to call.  Row offsets are formed in size_t.  Rows from nlocal on are neither read nor written.  The step entries
+ * (conp_efield_post_force_device, conp_observe_device) enqueue on the handle's stream and make no device allocation, no copy to
+ * the host and no synchronisation; the set_params entries copy and upload their arrays, reserve all scratch, and may allocate and
+ * synchronise.
+ *
+ * Unwrapped coordinates, both entries: with d_image, u_c = x_c + ((double)image_c prd_c), the ghost arithmetic of
+ * conp_ghost_fill_device; with a NULL d_image, u_c = x_c.
+ *
+ * conp_efield_*: the force q E on the selected owned atoms (the decks' `fix efield all efield 0 0 $(-v/lz)` beside
+ * `fix conp ... ffield`).
+ *   The field: ex = qe2f e[0], ey = qe2f e[1], formed on the host.  couple == 0: ez = qe2f e[2].  couple == 1: every thread forms
+ *     ez = qe2f (e[2] + couple_scale s) on the device, where s is the double the last update of a conq or cond handle left as the
+ *     fix scalar -- the value conp_fix_compute_scalar would return, read where the charge write stored it, without a host copy
+ *     (the decks: `variable efi equal -f_e/lz`, couple_scale = -1 / lz, e[2] = 0).  e is HOST memory, read at call time.
+ *   Per atom i < nlocal with sel[i] != 0:  fx = q ex, fy = q ey, fz = q ez;  f[i] += (fx, fy, fz);
+ *     energy term -((fx ux + fy uy) + fz uz);  v = (fx ux, fy uy, fz uz, fx uy, fx uz, fy uz).
+ *   d_out [11]: the energy, sum fx, sum fy, sum fz, the six sums of v, the number of selected atoms.  d_vatom [nlocal][6]: v for a
+ *     selected atom, exactly 0.0 for an unselected row below nlocal (zeroed by the same launch).  Unselected rows of d_f are
+ *     neither read nor written.  One launch without d_out, two with it.
+ *   The rule is the constant-field branch of LAMMPS' FixEfield (energy and virial from unwrapped coordinates).  With an equal-style
+ *     variable LAMMPS tallies no energy: an engine that mimics that branch ignores d_out[0].
+ *   CONP_ERR_STATE: conp_efield_post_force_device before conp_efield_set_params; couple == 1 before the handle's first update.
+ *   CONP_ERR_ARG: a NULL struct; NULL sel with nlocal > 0; negative nlocal; qe2f, an e component or couple_scale that is not
+ *     finite; a negative or non-finite prd; NULL d_x, d_q, d_f or e; couple outside {0, 1}; couple == 1 on a handle that is neither
+ *     conq nor cond (the engine knows a conp handle's potdiff itself).  A refused conp_efield_set_params leaves the handle WITHOUT a
+ *     field; every other refused call changes nothing.  nlocal == 0: CONP_OK, d_out is zeroed.
+ *   Order in a step: behind the update (conp_fix_pre_force_device), before conp_shake_post_force_device; the field touches owned
+ *     rows only, so its place relative to conp_ghost_fold_device is free.
+ *
+ * conp_observe_*: per-group sums for groups that may overlap (`compute reduce sum v_q`, the cell dipole `v_qz`, `compute temp`).
+ *   Bit g of mask[i] makes atom i a member of group g.  d_out [ngroups][CONP_OBSERVE_W], per group over its members i < nlocal:
+ *     column 0 the member count (as a double), 1 sum q, 2-4 sum q ux, sum q uy, sum q uz,
+ *     5 sum m ((vx vx + vy vy) + vz vz), 6-8 sum m vx, sum m vy, sum m vz, 9 sum m, with m = mass[type[i]].
+ *   Columns 5-8 are exactly 0.0 with a NULL d_v; an empty group is a row of 0.0.  The engine forms the temperature
+ *     col5 mvv2e / (dof boltz), `reduce ave` and the centre-of-mass velocity itself.  Two launches.
+ *   CONP_ERR_STATE: conp_observe_device before conp_observe_set_params.
+ *   CONP_ERR_ARG: a NULL struct, or a NULL array with a positive count; a negative count; ngroups outside
+ *     [1, CONP_OBSERVE_MAX_GROUPS]; a mask bit at or above ngroups; a type outside [1, ntypes]; a mass that is not positive and
+ *     finite; a negative or non-finite prd; a NULL d_x, d_q or d_out.  A refused conp_observe_set_params leaves the handle WITHOUT
+ *     groups; every other refused call changes nothing.  nlocal == 0: CONP_OK, d_out is zeroed.
+ * Out of scope: fix zmirror, fix setforce, atom-style and region-restricted fields, dipole torques, pressure assembly. */
+#define CONP_OBSERVE_MAX_GROUPS 16
+#define CONP_OBSERVE_W 10
+typedef struct {
+  int nlocal;
+  const int *sel;                       /* [nlocal] 0 / 1: the atoms of the fix's group; HOST, copied */
+  double qe2f;                          /* force->qe2f */
+  double prd[3];                        /* box lengths that d_image counts */
+} conp_efield_params;
+typedef struct {
+  int nlocal, ntypes, ngroups;
+  const int *type;                      /* [nlocal] 1..ntypes */
+  const int *mask;                      /* [nlocal], bit g = member of group g */
+  const double *mass;                   /* [ntypes + 1], entry 0 unused */
+  double prd[3];                        /* box lengths that d_image counts */
+} conp_observe_params;
+
+int conp_efield_set_params(conp_fix *fix, const conp_efield_params *p);
+int conp_efield_post_force_device(conp_fix *fix, const double *d_x /*[nlocal][3]*/, const double *d_q /*[nlocal]*/,
+                                  const int *d_image /*[nlocal][3] or NULL*/, double *d_f /*[nlocal][3], added to*/,
+                                  const double *e /*HOST [3], V/length, read at call time*/, int couple, double couple_scale,
+                                  double *d_out /*[11], overwritten; NULL: none*/, double *d_vatom /*[nlocal][6], overwritten; NULL: none*/);
+int conp_observe_set_params(conp_fix *fix, const conp_observe_params *p);
+int conp_observe_device(conp_fix *fix, const double *d_x /*[nlocal][3]*/, const double *d_q /*[nlocal]*/,
+                        const double *d_v /*[nlocal][3] or NULL*/, const int *d_image /*[nlocal][3] or NULL*/,
+                        double *d_out /*[ngroups][CONP_OBSERVE_W], overwritten*/);
+
 /* per-kernel timing of the last N updates via HIP events on the library's stream (bench.py roofline leg).
  * enable: 0 off, 1 a pair of events around every kernel, 2 around every 4th launch of the dominant kernel (sk_gemm) only --
  * cheap enough to stay on inside a timed region (an event pair drains the queue around the kernel it brackets). */

@@ -103,6 +103,18 @@ class conp_shake_params(C.Structure):
                 ("tolerance", C.c_double), ("max_iter", C.c_int), ("dt", C.c_double), ("ftm2v", C.c_double), ("prd", C.c_double * 3)]
 
 
+OBSERVE_MAX_GROUPS, OBSERVE_W = 16, 10      # CONP_OBSERVE_MAX_GROUPS, CONP_OBSERVE_W
+
+
+class conp_efield_params(C.Structure):
+    _fields_ = [("nlocal", C.c_int), ("sel", C.POINTER(C.c_int)), ("qe2f", C.c_double), ("prd", C.c_double * 3)]
+
+
+class conp_observe_params(C.Structure):
+    _fields_ = [("nlocal", C.c_int), ("ntypes", C.c_int), ("ngroups", C.c_int), ("type", C.POINTER(C.c_int)),
+                ("mask", C.POINTER(C.c_int)), ("mass", C.POINTER(C.c_double)), ("prd", C.c_double * 3)]
+
+
 def shake_angle_distance(d1, d2, theta0_rad):
     """the 1-2 distance `fix shake` constrains for an angle type: sqrt(d1^2 + d2^2 - 2 d1 d2 cos(theta0)), the two bond lengths and
     the angle's theta0 in radians -> conp_shake_params.angle_distance"""
@@ -162,6 +174,7 @@ SYMBOLS = [
     "conp_integrate_temperature_device", "conp_integrate_get_state", "conp_integrate_set_state",
     "conp_shake_set_params", "conp_shake_correct_device", "conp_shake_setup_device", "conp_shake_post_force_device",
     "conp_shake_check_device",
+    "conp_efield_set_params", "conp_efield_post_force_device", "conp_observe_set_params", "conp_observe_device",
 ]
 
 
@@ -360,6 +373,11 @@ def load_library():
         lib.conp_shake_setup_device.argtypes = [vp, vp, vp, vp, vp]
         lib.conp_shake_post_force_device.argtypes = [vp, vp, vp, vp, vp, vp]
         lib.conp_shake_check_device.argtypes = [vp, vp, vp]
+    if hasattr(lib, "conp_efield_set_params"):
+        lib.conp_efield_set_params.argtypes = [vp, C.POINTER(conp_efield_params)]
+        lib.conp_efield_post_force_device.argtypes = [vp, vp, vp, vp, vp, dp, C.c_int, C.c_double, vp, vp]
+        lib.conp_observe_set_params.argtypes = [vp, C.POINTER(conp_observe_params)]
+        lib.conp_observe_device.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.conp_compute_potential_atom.argtypes = [vp, C.POINTER(conp_atoms), C.POINTER(conp_neighlist), ip, ip,
                                                 C.POINTER(conp_potential_args), dp]
     lib.conp_fix_set_comm.argtypes = [vp, C.POINTER(conp_comm)]
@@ -1016,6 +1034,42 @@ class FixConp:
     def shake_check_device(self, d_x: int, d_out: int):
         """conp_shake_check_device: d_out [2] = largest |r - d| / d over the bonds, over the 1-2 distances of the flag-1 clusters"""
         self._check(self.lib.conp_shake_check_device(self.h, C.c_void_p(d_x), C.c_void_p(d_out)))
+
+    # -- fix efield and the per-group thermo sums: set_params once, the device entries per step / per thermo output (section 24) ------
+    def efield_set_params(self, sel, qe2f, prd=(0.0, 0.0, 0.0)):
+        """conp_efield_set_params: sel [nlocal] 0 / 1 (the atoms the field acts on), force->qe2f, the box lengths d_image counts.
+        Copied and uploaded; may allocate and synchronise"""
+        se = np.ascontiguousarray(sel, dtype=np.int32).reshape(-1)
+        p = conp_efield_params(nlocal=se.size, sel=_iptr(se) if se.size else None, qe2f=qe2f, prd=(C.c_double * 3)(*prd))
+        self._check(self.lib.conp_efield_set_params(self.h, C.byref(p)))
+
+    def efield_post_force_device(self, d_x: int, d_q: int, d_f: int, e, d_image: int = 0, couple: int = 0, couple_scale: float = 0.0,
+                                 d_out: int = 0, d_vatom: int = 0):
+        """conp_efield_post_force_device: q E added to the selected rows of d_f [nlocal][3]; e = (ex, ey, ez) on the host, V / length;
+        couple 1: ez = qe2f (e[2] + couple_scale s) with s the fix scalar the last update of this conq / cond handle left on the
+        device.  d_out [11] (energy, sum f [3], virial [6], selected atoms) and d_vatom [nlocal][6] are overwritten (0 = NULL);
+        enqueued, no synchronisation"""
+        ev = np.ascontiguousarray(e, dtype=np.float64).reshape(3)
+        self._check(self.lib.conp_efield_post_force_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q), C.c_void_p(d_image), C.c_void_p(d_f),
+                                                           _dptr(ev), int(couple), float(couple_scale), C.c_void_p(d_out),
+                                                           C.c_void_p(d_vatom)))
+
+    def observe_set_params(self, type, mask, mass, ngroups, prd=(0.0, 0.0, 0.0)):
+        """conp_observe_set_params: type [nlocal] (1..ntypes), mask [nlocal] (bit g = member of group g; groups may overlap), mass per
+        type WITHOUT the unused entry 0.  Copied and uploaded; may allocate and synchronise"""
+        ty = np.ascontiguousarray(type, dtype=np.int32).reshape(-1)
+        mk = np.ascontiguousarray(mask, dtype=np.int32).reshape(-1)
+        assert ty.size == mk.size
+        m = np.ascontiguousarray(np.concatenate([[0.0], np.asarray(mass, dtype=np.float64).reshape(-1)]))
+        p = conp_observe_params(nlocal=ty.size, ntypes=m.size - 1, ngroups=int(ngroups), type=_iptr(ty) if ty.size else None,
+                                mask=_iptr(mk) if mk.size else None, mass=_dptr(m), prd=(C.c_double * 3)(*prd))
+        self._check(self.lib.conp_observe_set_params(self.h, C.byref(p)))
+
+    def observe_device(self, d_x: int, d_q: int, d_out: int, d_v: int = 0, d_image: int = 0):
+        """conp_observe_device: d_out [ngroups][10] = per group the member count, sum q, sum q u [3], sum m v.v, sum m v [3], sum m
+        (u unwrapped with d_image; columns 5-8 are 0.0 without d_v); enqueued, no synchronisation"""
+        self._check(self.lib.conp_observe_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q), C.c_void_p(d_v), C.c_void_p(d_image),
+                                                 C.c_void_p(d_out)))
 
     # -- velocity Verlet and Nose-Hoover chains: set_params -> setup_device -> initial / final per step (DESIGN.md section 22) ------
     def integrate_set_params(self, type, group, mass, style, dof, t_period, dt, ftm2v, mvv2e, boltz):

@@ -26,6 +26,7 @@
 #include "conp_bondedstyle.hpp"
 #include "conp_integrator.hpp"
 #include "conp_shakestyle.hpp"
+#include "conp_fieldstyle.hpp"
 #include "conp_ewaldquery.hpp"
 #include "conp_pppmmesh.hpp"
 
@@ -166,6 +167,7 @@ struct conp_fix : DevCtx {
       d_elecheck, d_zclass, d_nb_act, d_rt_mine, d_own_rt, d_own_pv, d_ele_pairs, d_a_chunk_group, d_ct_ptr, d_seg_ptr, d_seg_idx, d_hslot_ptr, d_hslot_idx, d_b_rowptr, d_b_ele, d_b_oth, d_a_rowptr, d_a_ele, d_a_oth, d_a_col, d_bl_ilist, d_bl_numneigh, d_bl_first, d_bl_neigh, d_ipiv, d_info, d_cg_done, d_iota, d_ele_csr_ptr, d_ele_csr_of, d_ele_csr_row;
   bool left_stale = false;          // the fused GEMV + charge write leaves the fix scalar's group-1 sum to refresh_scalar()
   double left_potdiff = 0.0;
+  bool scalar_slot_written = false; // conq, cond: an update has left the fix scalar in d_scalars[3] (what a coupled conp_efield_post_force_device reads)
   bool scalars_unfetched = false;   // conp_fix_scatter_device left this update's scalars on the device: compute_scalar brings them over
   DevBuf<unsigned char> d_mask;
   DevBuf<SkItem> d_items;
@@ -2289,6 +2291,7 @@ struct conp_fix : DevCtx {
     HIP_TRY(hipGetLastError());
     // the group-1 sum (conq, cond: the potential difference) of THIS update is in d_scalars; the host copy is fetched on demand
     left_stale = false; scalars_unfetched = true; left_potdiff = potdiff;
+    if (args.conq || args.cond) scalar_slot_written = true;
   }
 
   void finish_scalar(double potdiff) {
@@ -2387,13 +2390,16 @@ struct conp_fix : DevCtx {
   }
 
   // ---- the pair style with its half list (conp_pairstyle.cpp, DESIGN.md sections 16, 17), the ghost map (conp_ghostmap.cpp, 18),
-  // the harmonic bonds and angles (conp_bondedstyle.cpp, 21), the integrator (conp_integrator.cpp, 22), the constraints (conp_shakestyle.cpp, 23), the exact-Ewald query entries (conp_ewaldquery.cpp, sections 11, 12,
+  // the harmonic bonds and angles (conp_bondedstyle.cpp, 21), the integrator (conp_integrator.cpp, 22), the constraints (conp_shakestyle.cpp, 23),
+  // the field and the per-group sums (conp_fieldstyle.cpp, 24), the exact-Ewald query entries (conp_ewaldquery.cpp, sections 11, 12,
   // 14, 15) and the PPPM mesh with the update's b and its query entries (conp_pppmmesh.cpp, sections 8, 13, 14, 15) ----
   PairStyle pair{*this};
   GhostMap ghost{*this};
   BondedStyle bonded{*this};
   Integrator integ{*this};
   ShakeStyle shake{*this};
+  FieldStyle field{*this};
+  ObserveStyle obs{*this};
   EwaldQuery ew{*this, kt, plan, dplan, tiles_h, ct_ptr_h, d_sf_row_a, d_sf_col_c, d_k_sign};
   PppmMesh pm{*this};
   bool types_in_range = false;                   // every atoms->type of the last (setup_)post_neighbor lies in [0, ntypes]
@@ -3839,6 +3845,61 @@ int conp_shake_check_device(conp_fix *f, const double *d_x, double *d_out) {
   if (!d_out) return CONP_OK;
   f->drop_graph();
   f->shake.check(d_x, d_out);
+  CONP_GUARD_END
+}
+
+// ---- fix efield and the per-group thermo sums: set_params once, the step entries enqueue only ----------------
+int conp_efield_set_params(conp_fix *f, const conp_efield_params *p) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->field.have_params = false;                  // a refused call leaves the handle without a field
+  if (!p) throw ConpError(CONP_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(f->env.device));
+  f->drop_graph();
+  f->field.set_params(p);
+  CONP_GUARD_END
+}
+
+int conp_efield_post_force_device(conp_fix *f, const double *d_x, const double *d_q, const int *d_image, double *d_f, const double *e,
+                                  int couple, double couple_scale, double *d_out, double *d_vatom) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->field.need_params("conp_efield_post_force_device");
+  if (!d_x || !d_q || !d_f || !e) throw ConpError(CONP_ERR_ARG, "conp_efield_post_force_device: null d_x, d_q, d_f or e");
+  if (!std::isfinite(e[0]) || !std::isfinite(e[1]) || !std::isfinite(e[2]) || !std::isfinite(couple_scale))
+    throw ConpError(CONP_ERR_ARG, "conp_efield_post_force_device: e or couple_scale is not finite");
+  if (couple != 0 && couple != 1) throw ConpError(CONP_ERR_ARG, "conp_efield_post_force_device: couple is neither 0 nor 1");
+  const double *d_scalar = nullptr;
+  if (couple == 1) {
+    if (!f->args.conq && !f->args.cond)
+      throw ConpError(CONP_ERR_ARG, "conp_efield_post_force_device: a coupled field needs a conq or cond handle (a conp handle's potential "
+                                    "difference is the engine's own number)");
+    if (!f->scalar_slot_written) throw ConpError(CONP_ERR_STATE, "conp_efield_post_force_device: a coupled field before the handle's first update");
+    d_scalar = f->d_scalars.p + 3;               // where scatter_device leaves the fix scalar of conq and cond
+  }
+  f->drop_graph();
+  f->field.post_force(d_x, d_q, d_image, d_f, e, d_scalar, couple_scale, d_out, d_vatom);
+  CONP_GUARD_END
+}
+
+int conp_observe_set_params(conp_fix *f, const conp_observe_params *p) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->obs.have_params = false;                    // a refused call leaves the handle without groups
+  if (!p) throw ConpError(CONP_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(f->env.device));
+  f->drop_graph();
+  f->obs.set_params(p);
+  CONP_GUARD_END
+}
+
+int conp_observe_device(conp_fix *f, const double *d_x, const double *d_q, const double *d_v, const int *d_image, double *d_out) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->obs.need_params("conp_observe_device");
+  if (!d_x || !d_q || !d_out) throw ConpError(CONP_ERR_ARG, "conp_observe_device: null d_x, d_q or d_out");
+  f->drop_graph();
+  f->obs.observe(d_x, d_q, d_v, d_image, d_out);
   CONP_GUARD_END
 }
 

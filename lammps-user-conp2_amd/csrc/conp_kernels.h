@@ -451,6 +451,42 @@ void launch_shake(hipStream_t s, const ShakeArgs &a, int mode, double *out);
 // out [2] = largest |r - d| / d over the bonds, over the 1-2 distances of the flag-1 clusters
 void launch_shake_check(hipStream_t s, const ShakeArgs &a, double *out);
 inline int shake_rows(int nthreads) { return (nthreads + SHAKE_BLOCK - 1) / SHAKE_BLOCK; }     // workgroups, and rows of a.part
+// ---- fix efield and the per-group thermo sums (conp_efield.hip) ----
+constexpr int EFIELD_BLOCK = 256;        // threads of a workgroup: one per atom
+constexpr int EFIELD_FINISH = 256;       // threads of the finishing workgroup: partial rows r, r + 256, ... per thread
+constexpr int EFIELD_W = 11;             // doubles of a partial row and of d_out: energy, sum f [3], virial [6], selected atoms
+constexpr int OBSERVE_BLOCK = 256;       // threads of a workgroup: one per atom
+constexpr int OBSERVE_FINISH = 256;      // threads of a finishing workgroup (one per group): partial rows r, r + 256, ... per thread
+constexpr int OBSERVE_W = CONP_OBSERVE_W;
+struct EfieldArgs {
+  int nlocal;
+  const int *sel;                        // [nlocal] 0 / 1
+  const double *x, *q;                   // [nlocal][3], [nlocal]
+  const int *image;                      // [nlocal][3] or NULL: u = x
+  double *f;                             // [nlocal][3] added to (selected rows only)
+  double ex, ey, ez;                     // qe2f e; ez is used where scalar == NULL
+  double qe2f, e2, couple_scale;         // scalar != NULL: ez = qe2f (e2 + couple_scale *scalar), formed by every thread
+  const double *scalar;                  // the fix scalar's slot of the handle (conq, cond), or NULL
+  double prd[3];
+  double *vatom;                         // [nlocal][6] overwritten (unselected rows: 0.0), or NULL
+  double *part;                          // [ceil(nlocal / EFIELD_BLOCK)][EFIELD_W] scratch rows, or NULL (no d_out)
+};
+// one launch over the owned atoms; out [EFIELD_W] != NULL: the finishing workgroup behind it
+void launch_efield(hipStream_t s, const EfieldArgs &a, double *out);
+struct ObserveArgs {
+  int nlocal, ngroups;
+  const int *type, *mask;                // [nlocal]; bit g of mask: member of group g
+  const double *mass;                    // [ntypes + 1]
+  const double *x, *q;                   // [nlocal][3], [nlocal]
+  const double *v;                       // [nlocal][3] or NULL: columns 5-8 are 0.0
+  const int *image;                      // [nlocal][3] or NULL: u = x
+  double prd[3];
+  double *part;                          // [ceil(nlocal / OBSERVE_BLOCK)][ngroups][OBSERVE_W] scratch rows
+};
+// the per-workgroup rows, then ngroups finishing workgroups: out [ngroups][OBSERVE_W]
+void launch_observe(hipStream_t s, const ObserveArgs &a, double *out);
+inline int efield_rows(int nlocal) { return (nlocal + EFIELD_BLOCK - 1) / EFIELD_BLOCK; }
+inline int observe_rows(int nlocal) { return (nlocal + OBSERVE_BLOCK - 1) / OBSERVE_BLOCK; }
 // ---- the pair style's half list built on the device (conp_neigh.hip) ----
 struct NeighGrid { double lo[3], inv[3]; int n[3]; };     // cell of v along c: clamp((v - lo[c]) * inv[c], 0, n[c] - 1); cells are >= cutneigh wide
 struct NeighRowArgs {
