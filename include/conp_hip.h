@@ -1014,7 +1014,7 @@ int conp_shake_check_device(conp_fix *fix, const double *d_x /*[nlocal][3]*/, do
  *     [1, CONP_OBSERVE_MAX_GROUPS]; a mask bit at or above ngroups; a type outside [1, ntypes]; a mass that is not positive and
  *     finite; a negative or non-finite prd; a NULL d_x, d_q or d_out.  A refused conp_observe_set_params leaves the handle WITHOUT
  *     groups; every other refused call changes nothing.  nlocal == 0: CONP_OK, d_out is zeroed.
- * Out of scope: fix zmirror, fix setforce, atom-style and region-restricted fields, dipole torques, pressure assembly. */
+ * fix zmirror: conp_zmirror_* below.  Out of scope: fix setforce, atom-style and region-restricted fields, dipole torques, pressure assembly. */
 #define CONP_OBSERVE_MAX_GROUPS 16
 #define CONP_OBSERVE_W 10
 typedef struct {
@@ -1040,6 +1040,87 @@ int conp_observe_set_params(conp_fix *fix, const conp_observe_params *p);
 int conp_observe_device(conp_fix *fix, const double *d_x /*[nlocal][3]*/, const double *d_q /*[nlocal]*/,
                         const double *d_v /*[nlocal][3] or NULL*/, const int *d_image /*[nlocal][3] or NULL*/,
                         double *d_out /*[ngroups][CONP_OBSERVE_W], overwritten*/);
+
+/* ---- `neigh_modify exclude` in the device list build, and `fix zmirror` --------------------------------------
+ * What the reference's tests/zmirror deck needs beyond sections 16-24; both are rank-local members of the handle.
+ *
+ * conp_pair_set_exclusions / conp_pair_build_list_exclude_device: conp_pair_build_list_device with LAMMPS'
+ * Neighbor::exclusion(i, j, type_i, type_j, mask, molecule) as written.  A candidate pair that passes the distance and the
+ * orientation test of conp_pair_build_list_device is DROPPED if any of these holds:
+ *   type rules:      ex_type[type_i][type_j] is set -- every (type_i[k], type_j[k]) sets [i][j] and [j][i], as LAMMPS does;
+ *   group rules:     for some m, (mask_i & group_bit1[m] and mask_j & group_bit2[m]) or (mask_i & group_bit2[m] and mask_j & group_bit1[m]);
+ *   molecule rules:  for some m, mask_i & mol_bit[m] and mask_j & mol_bit[m], and molecule_i == molecule_j (mol_intra[m] != 0:
+ *                    molecule/intra) or molecule_i != molecule_j (mol_intra[m] == 0: molecule/inter).
+ * The test applies to every candidate, owned or ghost: d_type, d_mask, d_molecule are DEVICE arrays [nall] whose ghost rows the
+ * engine fills with conp_ghost_fill_int_device (the handle's own type table is stale for new ghosts at this point of a
+ * re-neighbouring and is not used).  A dropped pair is absent -- not kept with special bits --, and the test comes before the
+ * special-bond classification.  A d_type[j] outside [0, ntypes] is clamped for the table look-up (type 0 matches no rule).
+ * Everything else is the contract of conp_pair_build_list_device word for word: the set rule, newton on and off, the special bits
+ * and minimum_image_check, ilist / numneigh / first, byte-identical results from build to build, the reservations for the compute
+ * entries, conp_pair_list_moved_device, conp_pair_get_list, use by conp_fix_post_neighbor_device, and what a refused build leaves
+ * behind.  A row is the plain build's row with the excluded entries removed and the order kept.
+ * With no rule in force (conp_pair_set_exclusions with all counts 0, or with NULL, which clears every rule) the build is the plain
+ * build, byte for byte, and reads no per-atom array (the three pointers of `at` may be NULL; `at` itself may not).
+ *   Limits: at most 16 group rules and 16 molecule rules; any number of type pairs.
+ *   CONP_ERR_STATE: either entry before conp_pair_set_params; the build entry before a successful conp_pair_set_exclusions.
+ *   CONP_ERR_ARG, conp_pair_set_exclusions: a negative count; more than 16 group or molecule rules; a count > 0 with a NULL array;
+ *     with ntype_pairs > 0 an ntypes that differs from conp_pair_set_params', or a type outside [1, ntypes]; a group or molecule bit
+ *     mask of 0.  A refused conp_pair_set_exclusions leaves the handle WITHOUT rules: the build entry answers CONP_ERR_STATE until a
+ *     call succeeds.  A second call replaces the rules of the first.  The handle's list is not touched.
+ *   CONP_ERR_ARG, the build entry: a NULL at; a NULL per-atom array that a rule in force needs -- d_type with type rules, d_mask
+ *     with group or molecule rules, d_molecule with molecule rules; and every refusal of conp_pair_build_list_device.
+ *   conp_pair_build_list_device itself ignores the rules: it stays the plain build.
+ *
+ * conp_zmirror_*: FixZmirror of the reference on one rank.  After the first half of the integrator, x of every atom of the receiving
+ * group (jgroupbit) is set to (x, y, zoffset - z) of its partner in the sending group (groupbit), zoffset = 2 boxlo_z + zprd formed
+ * in that order on the host.  conp_zmirror_set_params restates FixZmirror::setup and the one-rank branch of post_integrate: the tag
+ * ranges [send_mintag, send_maxtag], [recv_mintag, recv_maxtag] over the two groups; for every owned atom i of the sending group, in
+ * ascending i, the target is the owned atom with tag  tag[i] - send_mintag + recv_mintag.  The (source, target) pairs go to the
+ * device once: owned indices are stable in the device engine (conp_atoms_wrap_device remaps in place).  tag and mask are HOST
+ * arrays [nlocal], read once.
+ *   conp_zmirror_post_integrate_device: if ntimestep % nevery == 0, one launch, one thread per pair:
+ *     x[dst] = (x[src][0], x[src][1], zoffset - x[src][2]), bit-equal to float64 as written; otherwise nothing is launched and the
+ *     call returns CONP_OK.  Enqueued on the handle's stream: no allocation, no copy, no synchronisation.  Velocities, image
+ *     counters, ghost rows (conp_ghost_fill_device follows) and every row that is no target stay untouched.
+ *   No target is a source (refused below), so the copy in place equals the reference's snapshot of the sources before it writes.
+ *   On one rank the reference repeats the copy at end_of_step; the repeat is the identity, because x has not changed since
+ *   post_integrate, and has no entry here.  v of the mirrored atoms is NOT updated: the engine keeps them out
+ *   of every integrator group (conp_integrate_*) and chooses its SHAKE clusters accordingly.
+ *   conp_zmirror_get_map: *npairs and, with non-NULL arrays, src [npairs] and dst [npairs] (host).
+ *   CONP_ERR_STATE: conp_zmirror_post_integrate_device or conp_zmirror_get_map before conp_zmirror_set_params.
+ *   CONP_ERR_ARG: a NULL struct, tag or mask; negative nlocal; nevery < 1; zprd or boxlo_z not finite; a tag that occurs twice; an
+ *     empty sending or receiving group; unequal tag ranges (the reference's "Groups do not have same number of tags"); a target tag
+ *     that no owned atom has; a target outside the receiving group; a target that is itself in the sending group; a NULL d_x.  A
+ *     refused conp_zmirror_set_params leaves the handle WITHOUT a mirror; every other refused call changes nothing.
+ *   Order in a step: conp_integrate_initial_device -> conp_zmirror_post_integrate_device -> conp_ghost_fill_device ->
+ *     conp_fix_pre_force_device -> ...; at a re-neighbouring: ... -> conp_ghost_build_device -> conp_ghost_fill_device /
+ *     conp_ghost_fill_int_device (tag, type, mask, molecule) -> conp_pair_build_list_exclude_device -> conp_fix_post_neighbor_device.
+ * Out of scope: per-type-pair list cutoffs, triclinic boxes, the multi-rank comm_and_remap, mirrored velocities. */
+typedef struct {
+  int ntypes;                           /* must equal the ntypes of conp_pair_set_params when ntype_pairs > 0 */
+  int ntype_pairs;
+  const int *type_i, *type_j;           /* HOST [ntype_pairs], 1-based */
+  int ngroup_pairs;
+  const int *group_bit1, *group_bit2;   /* HOST [ngroup_pairs], LAMMPS group bit masks (1 << g) */
+  int nmol;
+  const int *mol_bit, *mol_intra;       /* HOST [nmol]; intra != 0: molecule/intra, 0: molecule/inter */
+} conp_pair_exclusions;
+typedef struct {
+  const int *d_type, *d_mask, *d_molecule;      /* DEVICE, each [nall]; NULL where no rule in force reads it */
+} conp_pair_exclude_atoms;
+int conp_pair_set_exclusions(conp_fix *fix, const conp_pair_exclusions *e /* NULL: clears every rule */);
+int conp_pair_build_list_exclude_device(conp_fix *fix, const double *d_x, const conp_pair_build_args *a,
+                                        const conp_pair_exclude_atoms *at);
+typedef struct {
+  int nlocal;
+  const int *tag, *mask;                /* HOST [nlocal], read once */
+  int groupbit, jgroupbit;              /* sending group, receiving group */
+  int nevery;                           /* >= 1 */
+  double boxlo_z, zprd;                 /* zoffset = 2 boxlo_z + zprd */
+} conp_zmirror_params;
+int conp_zmirror_set_params(conp_fix *fix, const conp_zmirror_params *p);
+int conp_zmirror_post_integrate_device(conp_fix *fix, double *d_x /*[>= nlocal][3]*/, long long ntimestep);
+int conp_zmirror_get_map(conp_fix *fix, int *npairs, int *src, int *dst);   /* arrays NULL: count only */
 
 /* per-kernel timing of the last N updates via HIP events on the library's stream (bench.py roofline leg).
  * enable: 0 off, 1 a pair of events around every kernel, 2 around every 4th launch of the dominant kernel (sk_gemm) only --

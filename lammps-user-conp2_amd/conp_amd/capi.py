@@ -115,6 +115,21 @@ class conp_observe_params(C.Structure):
                 ("mask", C.POINTER(C.c_int)), ("mass", C.POINTER(C.c_double)), ("prd", C.c_double * 3)]
 
 
+class conp_pair_exclusions(C.Structure):
+    _fields_ = [("ntypes", C.c_int), ("ntype_pairs", C.c_int), ("type_i", C.POINTER(C.c_int)), ("type_j", C.POINTER(C.c_int)),
+                ("ngroup_pairs", C.c_int), ("group_bit1", C.POINTER(C.c_int)), ("group_bit2", C.POINTER(C.c_int)),
+                ("nmol", C.c_int), ("mol_bit", C.POINTER(C.c_int)), ("mol_intra", C.POINTER(C.c_int))]
+
+
+class conp_pair_exclude_atoms(C.Structure):
+    _fields_ = [("d_type", C.c_void_p), ("d_mask", C.c_void_p), ("d_molecule", C.c_void_p)]
+
+
+class conp_zmirror_params(C.Structure):
+    _fields_ = [("nlocal", C.c_int), ("tag", C.POINTER(C.c_int)), ("mask", C.POINTER(C.c_int)), ("groupbit", C.c_int),
+                ("jgroupbit", C.c_int), ("nevery", C.c_int), ("boxlo_z", C.c_double), ("zprd", C.c_double)]
+
+
 def shake_angle_distance(d1, d2, theta0_rad):
     """the 1-2 distance `fix shake` constrains for an angle type: sqrt(d1^2 + d2^2 - 2 d1 d2 cos(theta0)), the two bond lengths and
     the angle's theta0 in radians -> conp_shake_params.angle_distance"""
@@ -175,6 +190,8 @@ SYMBOLS = [
     "conp_shake_set_params", "conp_shake_correct_device", "conp_shake_setup_device", "conp_shake_post_force_device",
     "conp_shake_check_device",
     "conp_efield_set_params", "conp_efield_post_force_device", "conp_observe_set_params", "conp_observe_device",
+    "conp_pair_set_exclusions", "conp_pair_build_list_exclude_device",
+    "conp_zmirror_set_params", "conp_zmirror_post_integrate_device", "conp_zmirror_get_map",
 ]
 
 
@@ -378,6 +395,12 @@ def load_library():
         lib.conp_efield_post_force_device.argtypes = [vp, vp, vp, vp, vp, dp, C.c_int, C.c_double, vp, vp]
         lib.conp_observe_set_params.argtypes = [vp, C.POINTER(conp_observe_params)]
         lib.conp_observe_device.argtypes = [vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "conp_pair_set_exclusions"):
+        lib.conp_pair_set_exclusions.argtypes = [vp, C.POINTER(conp_pair_exclusions)]
+        lib.conp_pair_build_list_exclude_device.argtypes = [vp, vp, C.POINTER(conp_pair_build_args), C.POINTER(conp_pair_exclude_atoms)]
+        lib.conp_zmirror_set_params.argtypes = [vp, C.POINTER(conp_zmirror_params)]
+        lib.conp_zmirror_post_integrate_device.argtypes = [vp, vp, C.c_longlong]
+        lib.conp_zmirror_get_map.argtypes = [vp, ip, ip, ip]
     lib.conp_compute_potential_atom.argtypes = [vp, C.POINTER(conp_atoms), C.POINTER(conp_neighlist), ip, ip,
                                                 C.POINTER(conp_potential_args), dp]
     lib.conp_fix_set_comm.argtypes = [vp, C.POINTER(conp_comm)]
@@ -885,6 +908,55 @@ class FixConp:
                                  d_nspecial=d_nspecial or None, d_special=d_special or None, maxspecial=int(maxspecial),
                                  prd_half=(C.c_double * 3)(*[float(v) for v in prd_half]))
         self._check(self.lib.conp_pair_build_list_device(self.h, C.c_void_p(d_x), C.byref(a)))
+
+    # -- neigh_modify exclude in the device build --------------------------------------------------
+    def pair_set_exclusions(self, ntypes=0, type_pairs=(), group_pairs=(), molecule=(), clear=False):
+        """conp_pair_set_exclusions: type_pairs [(ti, tj)] 1-based, group_pairs [(bit1, bit2)] LAMMPS group bit masks, molecule
+        [(bit, intra)] (intra True: molecule/intra, False: molecule/inter); clear=True passes NULL (every rule cleared)"""
+        if clear:
+            self._check(self.lib.conp_pair_set_exclusions(self.h, None))
+            return
+        arr = lambda rows, k: np.ascontiguousarray([int(r[k]) for r in rows], dtype=np.int32)
+        ti, tj = arr(type_pairs, 0), arr(type_pairs, 1)
+        g1, g2 = arr(group_pairs, 0), arr(group_pairs, 1)
+        mb, mi = arr(molecule, 0), arr(molecule, 1)
+        ptr = lambda a: _iptr(a) if a.size else None
+        e = conp_pair_exclusions(ntypes=int(ntypes), ntype_pairs=ti.size, type_i=ptr(ti), type_j=ptr(tj), ngroup_pairs=g1.size,
+                                 group_bit1=ptr(g1), group_bit2=ptr(g2), nmol=mb.size, mol_bit=ptr(mb), mol_intra=ptr(mi))
+        self._check(self.lib.conp_pair_set_exclusions(self.h, C.byref(e)))
+
+    def pair_build_list_exclude_device(self, d_x: int, nlocal: int, nall: int, cutneigh: float, d_type: int = 0, d_mask: int = 0,
+                                       d_molecule: int = 0, d_tag: int = 0, d_nspecial: int = 0, d_special: int = 0,
+                                       maxspecial: int = 0, prd_half=(0.0, 0.0, 0.0)):
+        """conp_pair_build_list_exclude_device: pair_build_list_device without the pairs the rules of pair_set_exclusions drop;
+        d_type, d_mask, d_molecule [nall] (device pointers, 0 = NULL where no rule in force reads it).  May allocate and synchronise"""
+        a = conp_pair_build_args(nlocal=int(nlocal), nall=int(nall), cutneigh=float(cutneigh), d_tag=d_tag or None,
+                                 d_nspecial=d_nspecial or None, d_special=d_special or None, maxspecial=int(maxspecial),
+                                 prd_half=(C.c_double * 3)(*[float(v) for v in prd_half]))
+        at = conp_pair_exclude_atoms(d_type=d_type or None, d_mask=d_mask or None, d_molecule=d_molecule or None)
+        self._check(self.lib.conp_pair_build_list_exclude_device(self.h, C.c_void_p(d_x), C.byref(a), C.byref(at)))
+
+    # -- fix zmirror (DESIGN.md section 25) ------------------------------------------------------------------------------
+    def zmirror_set_params(self, tag, mask, groupbit, jgroupbit, nevery, boxlo_z, zprd):
+        """conp_zmirror_set_params: tag, mask [nlocal] (host); groupbit: the sending group, jgroupbit: the receiving group"""
+        tg, mk = np.ascontiguousarray(tag, dtype=np.int32), np.ascontiguousarray(mask, dtype=np.int32)
+        p = conp_zmirror_params(nlocal=tg.size, tag=_iptr(tg), mask=_iptr(mk), groupbit=int(groupbit), jgroupbit=int(jgroupbit),
+                                nevery=int(nevery), boxlo_z=float(boxlo_z), zprd=float(zprd))
+        self._check(self.lib.conp_zmirror_set_params(self.h, C.byref(p)))
+
+    def zmirror_post_integrate_device(self, d_x: int, ntimestep: int = 0):
+        """conp_zmirror_post_integrate_device: x[dst] = (x[src][0], x[src][1], zoffset - x[src][2]) on d_x when ntimestep % nevery == 0;
+        enqueued on the handle's stream, no synchronisation"""
+        self._check(self.lib.conp_zmirror_post_integrate_device(self.h, C.c_void_p(d_x), int(ntimestep)))
+
+    def zmirror_get_map(self):
+        """conp_zmirror_get_map -> (src [npairs], dst [npairs]) owned indices, ascending source index"""
+        n = C.c_int()
+        null = C.POINTER(C.c_int)()
+        self._check(self.lib.conp_zmirror_get_map(self.h, C.byref(n), null, null))
+        src, dst = np.zeros(max(n.value, 1), np.int32), np.zeros(max(n.value, 1), np.int32)
+        self._check(self.lib.conp_zmirror_get_map(self.h, C.byref(n), _iptr(src), _iptr(dst)))
+        return src[:n.value], dst[:n.value]
 
     def pair_list_moved_device(self, d_x: int, trigger: float, d_flag: int):
         """conp_pair_list_moved_device: *d_flag (a device int, overwritten) = an owned atom moved further than `trigger` since the

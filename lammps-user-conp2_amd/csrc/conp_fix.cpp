@@ -27,6 +27,7 @@
 #include "conp_integrator.hpp"
 #include "conp_shakestyle.hpp"
 #include "conp_fieldstyle.hpp"
+#include "conp_zmirrorstyle.hpp"
 #include "conp_ewaldquery.hpp"
 #include "conp_pppmmesh.hpp"
 
@@ -2391,7 +2392,7 @@ struct conp_fix : DevCtx {
 
   // ---- the pair style with its half list (conp_pairstyle.cpp, DESIGN.md sections 16, 17), the ghost map (conp_ghostmap.cpp, 18),
   // the harmonic bonds and angles (conp_bondedstyle.cpp, 21), the integrator (conp_integrator.cpp, 22), the constraints (conp_shakestyle.cpp, 23),
-  // the field and the per-group sums (conp_fieldstyle.cpp, 24), the exact-Ewald query entries (conp_ewaldquery.cpp, sections 11, 12,
+  // the field and the per-group sums (conp_fieldstyle.cpp, 24), the z mirror (conp_zmirrorstyle.cpp, 25), the exact-Ewald query entries (conp_ewaldquery.cpp, sections 11, 12,
   // 14, 15) and the PPPM mesh with the update's b and its query entries (conp_pppmmesh.cpp, sections 8, 13, 14, 15) ----
   PairStyle pair{*this};
   GhostMap ghost{*this};
@@ -2400,6 +2401,7 @@ struct conp_fix : DevCtx {
   ShakeStyle shake{*this};
   FieldStyle field{*this};
   ObserveStyle obs{*this};
+  ZmirrorStyle zmirror{*this};
   EwaldQuery ew{*this, kt, plan, dplan, tiles_h, ct_ptr_h, d_sf_row_a, d_sf_col_c, d_k_sign};
   PppmMesh pm{*this};
   bool types_in_range = false;                   // every atoms->type of the last (setup_)post_neighbor lies in [0, ntypes]
@@ -3589,6 +3591,26 @@ int conp_pair_build_list_device(conp_fix *f, const double *d_x, const conp_pair_
   CONP_GUARD_END
 }
 
+// ---- neigh_modify exclude on the device build ----------------------------------------------------------------
+int conp_pair_set_exclusions(conp_fix *f, const conp_pair_exclusions *e) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->pair.have_excl = false;                     // a refused call leaves the handle without rules
+  HIP_TRY(hipSetDevice(f->env.device));
+  f->drop_graph();
+  f->pair.set_exclusions(e);
+  CONP_GUARD_END
+}
+
+int conp_pair_build_list_exclude_device(conp_fix *f, const double *d_x, const conp_pair_build_args *a, const conp_pair_exclude_atoms *at) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(f->env.device));
+  f->drop_graph();
+  f->pair.build_list(d_x, a, at, true);
+  CONP_GUARD_END
+}
+
 int conp_pair_list_moved_device(conp_fix *f, const double *d_x, double trigger, int *d_flag) {
   CONP_GUARD_BEGIN
   if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
@@ -3900,6 +3922,38 @@ int conp_observe_device(conp_fix *f, const double *d_x, const double *d_q, const
   if (!d_x || !d_q || !d_out) throw ConpError(CONP_ERR_ARG, "conp_observe_device: null d_x, d_q or d_out");
   f->drop_graph();
   f->obs.observe(d_x, d_q, d_v, d_image, d_out);
+  CONP_GUARD_END
+}
+
+// ---- fix zmirror: set_params once, the step entry enqueues one launch -------------------------------------------
+int conp_zmirror_set_params(conp_fix *f, const conp_zmirror_params *p) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->zmirror.have_params = false;                // a refused call leaves the handle without a mirror
+  if (!p) throw ConpError(CONP_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(f->env.device));
+  f->drop_graph();
+  f->zmirror.set_params(p);
+  CONP_GUARD_END
+}
+
+int conp_zmirror_post_integrate_device(conp_fix *f, double *d_x, long long ntimestep) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->zmirror.need_params("conp_zmirror_post_integrate_device");
+  if (!d_x) throw ConpError(CONP_ERR_ARG, "conp_zmirror_post_integrate_device: null d_x");
+  f->drop_graph();
+  f->zmirror.post_integrate(d_x, ntimestep);
+  CONP_GUARD_END
+}
+
+int conp_zmirror_get_map(conp_fix *f, int *npairs, int *src, int *dst) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->zmirror.need_params("conp_zmirror_get_map");
+  if (npairs) *npairs = f->zmirror.npairs;
+  if (src) std::copy(f->zmirror.src_h.begin(), f->zmirror.src_h.end(), src);
+  if (dst) std::copy(f->zmirror.dst_h.begin(), f->zmirror.dst_h.end(), dst);
   CONP_GUARD_END
 }
 

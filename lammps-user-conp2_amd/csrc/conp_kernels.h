@@ -487,6 +487,10 @@ struct ObserveArgs {
 void launch_observe(hipStream_t s, const ObserveArgs &a, double *out);
 inline int efield_rows(int nlocal) { return (nlocal + EFIELD_BLOCK - 1) / EFIELD_BLOCK; }
 inline int observe_rows(int nlocal) { return (nlocal + OBSERVE_BLOCK - 1) / OBSERVE_BLOCK; }
+// ---- fix zmirror (conp_zmirror.hip) ----
+constexpr int ZMIRROR_BLOCK = 256;       // threads of a workgroup: one per (source, target) pair
+// x[dst] = (x[src][0], x[src][1], zoffset - x[src][2]) for the npairs records of `map` (x: source, y: target)
+void launch_zmirror(hipStream_t s, int npairs, const int2 *map, double zoffset, double *x);
 // ---- the pair style's half list built on the device (conp_neigh.hip) ----
 struct NeighGrid { double lo[3], inv[3]; int n[3]; };     // cell of v along c: clamp((v - lo[c]) * inv[c], 0, n[c] - 1); cells are >= cutneigh wide
 struct NeighRowArgs {
@@ -509,6 +513,19 @@ void launch_neigh_extent(hipStream_t s, int nall, const double *x, double *ext /
 void launch_neigh_bin(hipStream_t s, int nall, const double *x, const NeighGrid &g, int *cell, int *slot, int *count, int *start,
                       long long *total, int *unsorted, double4 *sorted);
 void launch_neigh_rows(hipStream_t s, const NeighRowArgs &a, bool fill);
+// neigh_modify exclude: the rules travel in the kernel arguments, the type table is a device array
+constexpr int NEIGH_EXCL_MAX = 16;       // group rules, and molecule rules
+struct NeighExclArgs {
+  int ntype, ngroup, nmol;               // rules in force of each kind (ntype: 0 or 1 -- the table is consulted or not)
+  int nt1;                               // ntypes + 1: the width of ex_type
+  const unsigned char *ex_type;          // [nt1][nt1] 0 / 1, row and column 0 clear
+  int gbit1[NEIGH_EXCL_MAX], gbit2[NEIGH_EXCL_MAX];
+  int mbit[NEIGH_EXCL_MAX];
+  unsigned mintra;                       // bit m: molecule rule m is molecule/intra, else molecule/inter
+  const int *type, *mask, *molecule;     // [nall] each; NULL where no rule in force reads it
+};
+// the rows of launch_neigh_rows without the candidates Neighbor::exclusion drops (an excluded lane votes 0)
+void launch_neigh_rows_exclude(hipStream_t s, const NeighRowArgs &a, const NeighExclArgs &ex, bool fill);
 void launch_neigh_scan(hipStream_t s, int n, const int *in, int *out /*[n] exclusive*/, long long *total);
 void launch_neigh_iota(hipStream_t s, int n, int *out);
 void launch_neigh_moved(hipStream_t s, int nlocal, const double *x, const double *xb, double trigsq, int *flag);

@@ -10,13 +10,15 @@
 //   neigh_scatter_kernel  unsorted[start[cell] + slot] = atom
 //   neigh_sort_kernel     one workgroup per cell: a member's place is the number of members with a smaller index (indices are
 //                         distinct: a permutation) -> members ascending by atom index, stored as (x, y, z, index) records
-//   neigh_row_kernel      <FILL, SPECIAL>: one wavefront per owner, four per workgroup.  The 27 cells around the owner's are walked in
+//   neigh_row_kernel      <FILL, SPECIAL, EXCLUDE> (EXCLUDE: with the exclusion test of section 25): one wavefront per owner, four per workgroup.  The 27 cells around the owner's are walked in
 //                         a fixed order, lanes stride over a cell's members and test the pair; accepted entries are compacted with a
 //                         ballot and a popcount prefix, so a row's order is the traversal order.  The count pass writes numneigh, the
 //                         fill pass the entries: the same code
 //   neigh_iota_kernel     ilist = 0 .. nlocal-1
 //   neigh_moved_kernel    one workgroup, one reduction: flag = any owned atom further than `trigger` from its place at the build
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "conp_kernels.h"
 
@@ -141,8 +143,35 @@ __global__ __launch_bounds__(256) void neigh_sort_kernel(const int *__restrict__
   }
 }
 
-template <bool FILL, bool SPECIAL>
-__global__ __launch_bounds__(256) void neigh_row_kernel(NeighRowArgs a) {
+// Neighbor::exclusion(i, j, ..) of LAMMPS for one candidate: the owner's class data are wave-uniform, the candidate's are gathered
+// by the lanes that already pass the distance and orientation tests (variant (a))
+__device__ __forceinline__ bool neigh_excluded(const NeighExclArgs &ex, int ti, int mi, int moli, int j) {
+  if (ex.ntype) {
+    const int tj = min(max(ex.type[j], 0), ex.nt1 - 1);
+    if (ex.ex_type[ti * ex.nt1 + tj]) return true;
+  }
+  if (ex.ngroup | ex.nmol) {
+    const int mj = ex.mask[j];
+    for (int m = 0; m < ex.ngroup; ++m) {
+      if ((mi & ex.gbit1[m]) && (mj & ex.gbit2[m])) return true;
+      if ((mi & ex.gbit2[m]) && (mj & ex.gbit1[m])) return true;
+    }
+    if (ex.nmol) {
+      const int molj = ex.molecule[j];
+      for (int m = 0; m < ex.nmol; ++m)
+        if ((mi & ex.mbit[m]) && (mj & ex.mbit[m])) {
+          if ((ex.mintra >> m) & 1u) { if (moli == molj) return true; }
+          else if (moli != molj) return true;
+        }
+    }
+  }
+  return false;
+}
+
+struct NeighNoExcl {};                           // the second argument of the instantiations without the exclusion test
+
+template <bool FILL, bool SPECIAL, bool EXCLUDE>
+__global__ __launch_bounds__(256) void neigh_row_kernel(NeighRowArgs a, std::conditional_t<EXCLUDE, NeighExclArgs, NeighNoExcl> ex) {
 #pragma clang fp contract(off)
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (i >= a.nlocal) return;                     // (whole waves leave; the kernel has no barrier)
@@ -157,6 +186,12 @@ __global__ __launch_bounds__(256) void neigh_row_kernel(NeighRowArgs a) {
     n2 = min(max(a.nspecial[3 * (size_t)i + 1], 0), n3);
     n1 = min(max(a.nspecial[3 * (size_t)i], 0), n2);
     spec = a.special + (size_t)i * a.maxspecial;
+  }
+  int ti = 0, mi = 0, moli = 0;                  // EXCLUDE: the owner's type (clamped into the table), mask and molecule id
+  if constexpr (EXCLUDE) {
+    if (ex.ntype) ti = min(max(ex.type[i], 0), ex.nt1 - 1);
+    if (ex.ngroup | ex.nmol) mi = ex.mask[i];
+    if (ex.nmol) moli = ex.molecule[i];
   }
   int *row = FILL ? a.neigh + a.first[i] : nullptr;
   const int room = FILL ? a.numneigh[i] : 0;     // what the count pass found: the fill pass never stores past it
@@ -187,6 +222,9 @@ __global__ __launch_bounds__(256) void neigh_row_kernel(NeighRowArgs a) {
               else keep = p.z > zi || (p.z == zi && (p.y > yi || (p.y == yi && p.x > xi)));
             }
             entry = j;
+            if constexpr (EXCLUDE) {
+              if (keep) keep = !neigh_excluded(ex, ti, mi, moli, j);           // a dropped pair is absent: it votes 0
+            }
             if (SPECIAL && keep) {
               const int tj = a.tag[j];
               int pos = -1;
@@ -240,8 +278,15 @@ __global__ __launch_bounds__(1024) void neigh_moved_kernel(int nlocal, const dou
 template <bool FILL>
 void launch_neigh_rows_t(hipStream_t s, const NeighRowArgs &a) {
   const dim3 grid((a.nlocal + 3) / 4), block(256);
-  if (a.tag) hipLaunchKernelGGL((neigh_row_kernel<FILL, true>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((neigh_row_kernel<FILL, false>), grid, block, 0, s, a);
+  if (a.tag) hipLaunchKernelGGL((neigh_row_kernel<FILL, true, false>), grid, block, 0, s, a, NeighNoExcl{});
+  else hipLaunchKernelGGL((neigh_row_kernel<FILL, false, false>), grid, block, 0, s, a, NeighNoExcl{});
+}
+
+template <bool FILL>
+void launch_neigh_rows_exclude_t(hipStream_t s, const NeighRowArgs &a, const NeighExclArgs &ex) {
+  const dim3 grid((a.nlocal + 3) / 4), block(256);
+  if (a.tag) hipLaunchKernelGGL((neigh_row_kernel<FILL, true, true>), grid, block, 0, s, a, ex);
+  else hipLaunchKernelGGL((neigh_row_kernel<FILL, false, true>), grid, block, 0, s, a, ex);
 }
 
 }  // namespace
@@ -267,6 +312,12 @@ void launch_neigh_rows(hipStream_t s, const NeighRowArgs &a, bool fill) {
   if (a.nlocal <= 0) return;
   if (fill) launch_neigh_rows_t<true>(s, a);
   else launch_neigh_rows_t<false>(s, a);
+}
+
+void launch_neigh_rows_exclude(hipStream_t s, const NeighRowArgs &a, const NeighExclArgs &ex, bool fill) {
+  if (a.nlocal <= 0) return;
+  if (fill) launch_neigh_rows_exclude_t<true>(s, a, ex);
+  else launch_neigh_rows_exclude_t<false>(s, a, ex);
 }
 
 void launch_neigh_scan(hipStream_t s, int n, const int *in, int *out, long long *total) {

@@ -84,20 +84,74 @@ static NeighGrid neigh_grid(const double ext[6], double cutneigh, int nall_) {
   return g;
 }
 
-void PairStyle::build_list(const double *dx, const conp_pair_build_args *a) {
+// neigh_modify exclude type / group / molecule/intra / molecule/inter: the rules are checked and kept on the
+// host (they travel in the kernel arguments), the symmetric type table goes to the device
+void PairStyle::set_exclusions(const conp_pair_exclusions *e) {
+  have_excl = false;                       // a refused call leaves the handle without rules
+  const std::string who = "conp_pair_set_exclusions: ";
+  if (!have_params) throw ConpError(CONP_ERR_STATE, who + "before conp_pair_set_params");
+  NeighExclArgs x{};
+  x.nt1 = env.ntypes + 1;
+  std::vector<unsigned char> tab((size_t)x.nt1 * x.nt1, 0);
+  if (e) {
+    if (e->ntype_pairs < 0 || e->ngroup_pairs < 0 || e->nmol < 0) throw ConpError(CONP_ERR_ARG, who + "negative count");
+    if (e->ngroup_pairs > NEIGH_EXCL_MAX || e->nmol > NEIGH_EXCL_MAX)
+      throw ConpError(CONP_ERR_ARG, who + "more than 16 group or molecule rules");
+    if ((e->ntype_pairs > 0 && (!e->type_i || !e->type_j)) || (e->ngroup_pairs > 0 && (!e->group_bit1 || !e->group_bit2)) ||
+        (e->nmol > 0 && (!e->mol_bit || !e->mol_intra)))
+      throw ConpError(CONP_ERR_ARG, who + "a positive count with a null array");
+    if (e->ntype_pairs > 0 && e->ntypes != env.ntypes) throw ConpError(CONP_ERR_ARG, who + "ntypes differs from conp_pair_set_params'");
+    for (int k = 0; k < e->ntype_pairs; ++k) {
+      const int ti = e->type_i[k], tj = e->type_j[k];
+      if (ti < 1 || ti > env.ntypes || tj < 1 || tj > env.ntypes) throw ConpError(CONP_ERR_ARG, who + "a type outside [1, ntypes]");
+      tab[(size_t)ti * x.nt1 + tj] = tab[(size_t)tj * x.nt1 + ti] = 1;
+    }
+    for (int k = 0; k < e->ngroup_pairs; ++k) {
+      if (e->group_bit1[k] == 0 || e->group_bit2[k] == 0) throw ConpError(CONP_ERR_ARG, who + "a group bit mask of 0");
+      x.gbit1[k] = e->group_bit1[k]; x.gbit2[k] = e->group_bit2[k];
+    }
+    for (int k = 0; k < e->nmol; ++k) {
+      if (e->mol_bit[k] == 0) throw ConpError(CONP_ERR_ARG, who + "a molecule bit mask of 0");
+      x.mbit[k] = e->mol_bit[k];
+      if (e->mol_intra[k]) x.mintra |= 1u << k;
+    }
+    x.ntype = e->ntype_pairs > 0; x.ngroup = e->ngroup_pairs; x.nmol = e->nmol;
+  }
+  ctx.sync();                                       // no kernel may be reading the old table
+  d_ex_type.upload(tab, ctx.stream);
+  ctx.sync();                                       // `tab` leaves scope
+  excl = x;
+  have_excl = true;
+}
+
+void PairStyle::build_list(const double *dx, const conp_pair_build_args *a, const conp_pair_exclude_atoms *at, bool exclude) {
   have_list = false;                       // a build that is refused leaves the handle without a list
   list_built = false;
-  if (!have_params) throw ConpError(CONP_ERR_STATE, "conp_pair_build_list_device before conp_pair_set_params");
-  if (!dx || !a) throw ConpError(CONP_ERR_ARG, "null argument");
+  const std::string who = exclude ? "conp_pair_build_list_exclude_device: " : "conp_pair_build_list_device: ";
+  const char *entry = exclude ? "conp_pair_build_list_exclude_device" : "conp_pair_build_list_device";
+  if (!have_params) throw ConpError(CONP_ERR_STATE, std::string(entry) + " before conp_pair_set_params");
+  if (exclude && !have_excl) throw ConpError(CONP_ERR_STATE, std::string(entry) + " before conp_pair_set_exclusions");
+  if (!dx || !a || (exclude && !at)) throw ConpError(CONP_ERR_ARG, "null argument");
   if (a->nlocal < 0 || a->nall < 0 || a->nlocal > a->nall || a->nall > 0x3FFFFFFF)
-    throw ConpError(CONP_ERR_ARG, "conp_pair_build_list_device: bad sizes");
+    throw ConpError(CONP_ERR_ARG, who + "bad sizes");
   if (!(a->cutneigh * a->cutneigh >= cutsq_max) || !(a->cutneigh > 0.0) || !std::isfinite(a->cutneigh))
-    throw ConpError(CONP_ERR_ARG, "conp_pair_build_list_device: cutneigh^2 is below the largest cutsq of conp_pair_set_params");
+    throw ConpError(CONP_ERR_ARG, who + "cutneigh^2 is below the largest cutsq of conp_pair_set_params");
   const int nsp = (a->d_tag != nullptr) + (a->d_nspecial != nullptr) + (a->d_special != nullptr);
-  if (nsp != 0 && nsp != 3) throw ConpError(CONP_ERR_ARG, "conp_pair_build_list_device: d_tag, d_nspecial, d_special: all three or none");
-  if (nsp == 3 && a->maxspecial < 0) throw ConpError(CONP_ERR_ARG, "conp_pair_build_list_device: negative maxspecial");
+  if (nsp != 0 && nsp != 3) throw ConpError(CONP_ERR_ARG, who + "d_tag, d_nspecial, d_special: all three or none");
+  if (nsp == 3 && a->maxspecial < 0) throw ConpError(CONP_ERR_ARG, who + "negative maxspecial");
   for (int c = 0; c < 3; ++c)
-    if (!(a->prd_half[c] >= 0.0)) throw ConpError(CONP_ERR_ARG, "conp_pair_build_list_device: prd_half is negative or not a number");
+    if (!(a->prd_half[c] >= 0.0)) throw ConpError(CONP_ERR_ARG, who + "prd_half is negative or not a number");
+  NeighExclArgs ex = excl;                          // rules in force: the rows are built with the exclusion test
+  const bool filter = exclude && (ex.ntype || ex.ngroup || ex.nmol);
+  if (filter) {
+    if (ex.ntype && !at->d_type) throw ConpError(CONP_ERR_ARG, who + "type rules need d_type");
+    if ((ex.ngroup || ex.nmol) && !at->d_mask) throw ConpError(CONP_ERR_ARG, who + "group and molecule rules need d_mask");
+    if (ex.nmol && !at->d_molecule) throw ConpError(CONP_ERR_ARG, who + "molecule rules need d_molecule");
+    ex.type = ex.ntype ? at->d_type : nullptr;
+    ex.mask = ex.ngroup || ex.nmol ? at->d_mask : nullptr;
+    ex.molecule = ex.nmol ? at->d_molecule : nullptr;
+    ex.ex_type = d_ex_type.p;
+  }
   const int nl = a->nlocal, na = a->nall;
   ctx.sync();                                       // no kernel may be reading the old list
   d_ilist.reserve((size_t)std::max(nl, 1));
@@ -118,7 +172,7 @@ void PairStyle::build_list(const double *dx, const conp_pair_build_args *a) {
     ctx.sync();
     bool finite = ext[6] == 0.0;
     for (int c = 0; c < 3; ++c) finite = finite && std::isfinite(ext[3 + c] - ext[c]);
-    if (!finite) throw ConpError(CONP_ERR_NUMERIC, "conp_pair_build_list_device: a coordinate is not finite");
+    if (!finite) throw ConpError(CONP_ERR_NUMERIC, who + "a coordinate is not finite");
     const NeighGrid g = neigh_grid(ext, a->cutneigh, na);
     const int ncell = g.n[0] * g.n[1] * g.n[2];
     d_nb_count.reserve((size_t)ncell); d_nb_start.reserve((size_t)ncell + 1);
@@ -134,14 +188,16 @@ void PairStyle::build_list(const double *dx, const conp_pair_build_args *a) {
     r.numneigh = d_numneigh.p; r.first = d_first.p; r.neigh = nullptr;
     HIP_TRY(hipMemsetAsync(d_numneigh.p, 0, (size_t)na * sizeof(int), ctx.stream));      // rows of i >= nlocal: 0
     HIP_TRY(hipMemsetAsync(d_first.p, 0, (size_t)na * sizeof(int), ctx.stream));
-    launch_neigh_rows(ctx.stream, r, false);
+    if (filter) launch_neigh_rows_exclude(ctx.stream, r, ex, false);
+    else launch_neigh_rows(ctx.stream, r, false);
     launch_neigh_scan(ctx.stream, nl, d_numneigh.p, d_first.p, d_nb_total.p);
     HIP_TRY(hipMemcpyAsync(&total, d_nb_total.p, sizeof total, hipMemcpyDeviceToHost, ctx.stream));
     ctx.sync();
-    if (total >= (1ll << 31)) throw ConpError(CONP_ERR_NUMERIC, "conp_pair_build_list_device: 2^31 pairs or more (first is int)");
+    if (total >= (1ll << 31)) throw ConpError(CONP_ERR_NUMERIC, who + "2^31 pairs or more (first is int)");
     d_neigh.reserve((size_t)std::max<long long>(total, 1));
     r.neigh = d_neigh.p;
-    launch_neigh_rows(ctx.stream, r, true);
+    if (filter) launch_neigh_rows_exclude(ctx.stream, r, ex, true);
+    else launch_neigh_rows(ctx.stream, r, true);
     launch_neigh_iota(ctx.stream, nl, d_ilist.p);
     if (nl > 0) HIP_TRY(hipMemcpyAsync(d_nb_xbuild.p, dx, (size_t)nl * 3 * sizeof(double), hipMemcpyDeviceToDevice, ctx.stream));
     HIP_TRY(hipGetLastError());

@@ -25,9 +25,17 @@ struct PairStyle {
   dev::DevBuf<int> d_nb_cell, d_nb_slot, d_nb_count, d_nb_start, d_nb_unsorted;
   dev::DevBuf<long long> d_nb_total;
 
+  // neigh_modify exclude: the rules of conp_pair_set_exclusions; the table and the device pointers of `excl`
+  // are filled in per build
+  bool have_excl = false;
+  NeighExclArgs excl{};
+  dev::DevBuf<unsigned char> d_ex_type;
+
   void set_params(const conp_pair_params *p);
   void set_list(const conp_neighlist *l, int nall_);
-  void build_list(const double *dx, const conp_pair_build_args *a);
+  void set_exclusions(const conp_pair_exclusions *e);      // a refused call leaves the handle without rules
+  // exclude: conp_pair_build_list_exclude_device (the rules of set_exclusions, the class arrays of `at`); else the plain build
+  void build_list(const double *dx, const conp_pair_build_args *a, const conp_pair_exclude_atoms *at = nullptr, bool exclude = false);
   void list_moved(const double *dx, double trigger, int *dflag);
   void get_list(int *inum_, int *nall_, int64_t *nneigh_, int *ilist, int *numneigh, int *first, int *neigh);
   void need_ready(const char *who) const {
