@@ -700,6 +700,64 @@ int conp_fix_get_step_tables(conp_fix *fix, int64_t *sizes /*[8] or NULL*/, int 
 int conp_fix_post_force_device(conp_fix *fix, const double *d_x /*[nall][3]*/, const double *d_q /*[nall]*/,
                                double *d_f /*[nall][3], added to; NULL: none*/, double *d_out /*[9], overwritten; NULL: none*/);
 
+/* ---- atomic-free pair and Gaussian-correction forces --------------------------------------------------------
+ * conp_pair_compute_device and conp_fix_post_force_device add forces (and eatom, vatom) with float atomics: those outputs reproduce
+ * to rounding only.  The entries below are their twins without a float atomic: every output is byte-identical from call to call and
+ * from run to run on the same input.  They need the TRANSPOSED list: a half list names each pair once, in its owner's row, and to sum
+ * an atom's terms in a fixed order the atom must also find the pairs in which it is the j.
+ * The transposed list of a flattened half list (inum, ilist, numneigh, first, neigh) over nall atoms is three device arrays:
+ *   own_row  [nall]       the ii with ilist[ii] == a, or -1 (numneigh and first are read for listed owners only);
+ *   tr_ptr   [nall + 1]   tr_ptr[a + 1] - tr_ptr[a] = the listed slots p = first[i] + jj with (neigh[p] & 0x3FFFFFFF) == a;
+ *   tr_entry [n]          n = tr_ptr[nall] listed slots; for atom a its slots in ASCENDING SLOT ORDER p, each as
+ *                         i | (neigh[p] & 0xC0000000): the owner with the special bits of that slot.
+ * The arrays are a pure function of the list -- a stable sort of the listed slots by j --, byte-identical from build to build.
+ * conp_pair_transpose_list_device transposes the pair style's list, uploaded (conp_pair_set_list) or built
+ * (conp_pair_build_list[_exclude]_device): call it after the list at every re-neighbouring.  conp_fix_transpose_list_device
+ * transposes the FIX's own half list: call it after conp_fix_(setup_)post_neighbor or conp_fix_post_neighbor_device.  Both may
+ * allocate and synchronise (the slot count reaches the host), like the other re-neighbouring entries.  Without a list:
+ * CONP_ERR_STATE.  An owner that occurs twice in ilist (or lies outside [0, nall)): CONP_ERR_ARG; 2^31 slots or more:
+ * CONP_ERR_NUMERIC; a refused call leaves no index.  An index is dropped by whatever replaces its list: the pair style's by
+ * conp_pair_set_list and both builds (refused ones too), the fix's by conp_fix_(setup_)post_neighbor and
+ * conp_fix_post_neighbor_device.  The lifetime rule of section 19 carries over: a later pair-list build touches neither the fix's
+ * list nor its index.
+ * conp_pair_get_transposed_list downloads an index (synchronous; for tests): which 0 the pair style's, 1 the fix's; the sizes, and
+ * with non-NULL arrays own_row [nall], tr_ptr [nall + 1], tr_entry [n].  which outside {0, 1}: CONP_ERR_ARG; no valid index of that
+ * kind: CONP_ERR_STATE.
+ *
+ * conp_pair_compute_ordered_device: the signature, arguments, refusals and contract of conp_pair_compute_device (one stream; after
+ * the first call at a list size no allocation, no copy to the host, no synchronisation; d_f added to, d_ev / d_eatom / d_vatom
+ * overwritten; all outputs NULL: CONP_OK), and CONP_ERR_STATE when the pair style's index is missing or belongs to an earlier list.
+ * The arithmetic of a pair is conp_pair_compute_device's, operation for operation; a pair gives j exactly the negative of what it
+ * gives i.  SUMMATION ORDER, per atom a that can receive (every atom with newton on, a < nlocal with newton off), one wavefront of
+ * 64 lanes:
+ *   1. lane l adds, starting from +0.0, the terms of a's own row at jj = l, l + 64, ... (the pairs in which a is the owner: del =
+ *      x_a - x_j, +del fpair), then the terms of a's transposed entries k = l, l + 64, ... counted from tr_ptr[a] (the pairs in which
+ *      a is the j, evaluated in their OWNER's orientation: del = x_owner - x_a, types [type_owner][type_a], prefactor qqrd2e q_owner
+ *      q_a / r; a receives -(del fpair), and the same half of eatom / vatom as the owner);
+ *   2. the 64 lane sums are added by the shuffle tree  v += lane[l + 32]; += [l + 16]; += 8; 4; 2; 1  (lane 0 holds the result);
+ *   3. lane 0 stores  out[a] = out[a] + sum  once per output.  A row is written exactly when the atomic entry writes it: a is a listed
+ *      owner with a non-empty row, or the j of a listed pair inside its cutoff; every other row keeps its bytes, and with newton off
+ *      no ghost row is written.
+ * d_ev: the lane assignment over an owner's row is conp_pair_compute_device's, every owner's eight sums are stored as one row and the
+ * rows are added by the same finishing kernel: d_ev is byte-identical to conp_pair_compute_device's for the same input.
+ *
+ * conp_fix_post_force_ordered_device: the signature, pair set, gates, EHGO branch and refusals of conp_fix_post_force_device, and
+ * CONP_ERR_STATE without a valid index of the fix's list.  d_out is formed by conp_fix_post_force_device's own kernels: the same
+ * bytes.  The forces are gathered per atom that is no electrode atom (the term lands on the pair's other member only), in the order
+ * above: own row (+del forcecoul, no newton gate), then the transposed entries under newton || a < nlocal (-(del forcecoul), owner's
+ * orientation), the shuffle tree, one plain add per atom with a contributing pair.  The membership test precedes every coordinate
+ * load.
+ * A reproducible device step: conp_fix_pre_force_device -> conp_ewald_compute_forces_device -> conp_pair_compute_ordered_device ->
+ * conp_fix_post_force_ordered_device -> conp_ghost_fold_device.  (The PPPM mesh spread still uses float atomics.) */
+int conp_pair_transpose_list_device(conp_fix *fix);
+int conp_fix_transpose_list_device(conp_fix *fix);
+int conp_pair_get_transposed_list(conp_fix *fix, int which, int *nall, int64_t *n, int *own_row, int *tr_ptr, int *tr_entry);
+int conp_pair_compute_ordered_device(conp_fix *fix, const double *d_x, const double *d_q,
+                                     double *d_f /*[nall][3], added to; NULL: none*/, double *d_ev /*[8]; NULL ok*/,
+                                     double *d_eatom /*[nall]; NULL ok*/, double *d_vatom /*[nall][6]; NULL ok*/);
+int conp_fix_post_force_ordered_device(conp_fix *fix, const double *d_x /*[nall][3]*/, const double *d_q /*[nall]*/,
+                                       double *d_f /*[nall][3], added to; NULL: none*/, double *d_out /*[9], overwritten; NULL: none*/);
+
 /* ---- bonded forces: `bond_style harmonic` and `angle_style harmonic` on the device -------------------------
  * The bond and angle loops of LAMMPS' bond_harmonic.cpp and angle_harmonic.cpp @ 27May2021 with Bond::ev_tally's and
  * Angle::ev_tally's energy, virial and per-atom tallies.  All arithmetic is double, in the order written, no contraction.

@@ -192,6 +192,8 @@ SYMBOLS = [
     "conp_efield_set_params", "conp_efield_post_force_device", "conp_observe_set_params", "conp_observe_device",
     "conp_pair_set_exclusions", "conp_pair_build_list_exclude_device",
     "conp_zmirror_set_params", "conp_zmirror_post_integrate_device", "conp_zmirror_get_map",
+    "conp_pair_transpose_list_device", "conp_fix_transpose_list_device", "conp_pair_get_transposed_list",
+    "conp_pair_compute_ordered_device", "conp_fix_post_force_ordered_device",
 ]
 
 
@@ -401,6 +403,12 @@ def load_library():
         lib.conp_zmirror_set_params.argtypes = [vp, C.POINTER(conp_zmirror_params)]
         lib.conp_zmirror_post_integrate_device.argtypes = [vp, vp, C.c_longlong]
         lib.conp_zmirror_get_map.argtypes = [vp, ip, ip, ip]
+    if hasattr(lib, "conp_pair_compute_ordered_device"):
+        lib.conp_pair_transpose_list_device.argtypes = [vp]
+        lib.conp_fix_transpose_list_device.argtypes = [vp]
+        lib.conp_pair_get_transposed_list.argtypes = [vp, C.c_int, ip, C.POINTER(C.c_int64), ip, ip, ip]
+        lib.conp_pair_compute_ordered_device.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        lib.conp_fix_post_force_ordered_device.argtypes = [vp, vp, vp, vp, vp]
     lib.conp_compute_potential_atom.argtypes = [vp, C.POINTER(conp_atoms), C.POINTER(conp_neighlist), ip, ip,
                                                 C.POINTER(conp_potential_args), dp]
     lib.conp_fix_set_comm.argtypes = [vp, C.POINTER(conp_comm)]
@@ -1028,6 +1036,41 @@ class FixConp:
         """conp_fix_post_force_device: raw device pointers (0 = NULL), enqueued on the handle's stream, no synchronisation; d_f [nall][3]
         is added to, d_out [9] (self energy, eng_coul, virial xx, yy, zz, xy, xz, yz, contributing pairs) is overwritten"""
         self._check(self.lib.conp_fix_post_force_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q), C.c_void_p(d_f), C.c_void_p(d_out)))
+
+    # -- the transposed lists and the atomic-free twins of the two pair entries (DESIGN.md section 26) ----------------------
+    def pair_transpose_list_device(self):
+        """conp_pair_transpose_list_device: the transposed index of the pair style's list, after every pair_set_list or list build;
+        may allocate and synchronise"""
+        self._check(self.lib.conp_pair_transpose_list_device(self.h))
+
+    def fix_transpose_list_device(self):
+        """conp_fix_transpose_list_device: the transposed index of the fix's own half list, after every (setup_)post_neighbor or
+        post_neighbor_device; may allocate and synchronise"""
+        self._check(self.lib.conp_fix_transpose_list_device(self.h))
+
+    def pair_get_transposed_list(self, which: int = 0):
+        """conp_pair_get_transposed_list: which 0 the pair style's index, 1 the fix's -> (own_row [nall], tr_ptr [nall + 1],
+        tr_entry [n]); synchronous"""
+        nall, n = C.c_int(), C.c_int64()
+        null = C.POINTER(C.c_int)()
+        self._check(self.lib.conp_pair_get_transposed_list(self.h, int(which), C.byref(nall), C.byref(n), null, null, null))
+        own, ptr = np.zeros(max(nall.value, 1), np.int32), np.zeros(nall.value + 1, np.int32)
+        ent = np.zeros(max(n.value, 1), np.int32)
+        self._check(self.lib.conp_pair_get_transposed_list(self.h, int(which), C.byref(nall), C.byref(n), _iptr(own), _iptr(ptr),
+                                                           _iptr(ent)))
+        return own[:nall.value], ptr, ent[:n.value]
+
+    def pair_compute_ordered_device(self, d_x: int, d_q: int, d_f: int = 0, d_ev: int = 0, d_eatom: int = 0, d_vatom: int = 0):
+        """conp_pair_compute_ordered_device: pair_compute_device without a float atomic -- every output byte-identical from call to
+        call; needs pair_transpose_list_device after the list"""
+        self._check(self.lib.conp_pair_compute_ordered_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q), C.c_void_p(d_f),
+                                                              C.c_void_p(d_ev), C.c_void_p(d_eatom), C.c_void_p(d_vatom)))
+
+    def post_force_ordered_device(self, d_x: int, d_q: int, d_f: int = 0, d_out: int = 0):
+        """conp_fix_post_force_ordered_device: post_force_device without a float atomic; needs fix_transpose_list_device after the
+        fix's re-neighbouring"""
+        self._check(self.lib.conp_fix_post_force_ordered_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q), C.c_void_p(d_f),
+                                                                C.c_void_p(d_out)))
 
     STEP_TABLES = ("elyte_idx", "ele_pairs", "csr_ptr", "csr_of", "csr_row", "b_rowptr", "b_ele", "b_oth", "g0c")
 

@@ -23,6 +23,7 @@
 #include "conp_dev.hpp"
 #include "conp_ghostmap.hpp"
 #include "conp_pairstyle.hpp"
+#include "conp_transpose.hpp"
 #include "conp_bondedstyle.hpp"
 #include "conp_integrator.hpp"
 #include "conp_shakestyle.hpp"
@@ -502,6 +503,7 @@ struct conp_fix : DevCtx {
     if (!idx.initialised) throw ConpError(CONP_ERR_STATE, "post_neighbor before setup_post_neighbor");
     if (!have_blist) throw ConpError(CONP_ERR_STATE, "post_neighbor: no neighbor list (init_list not called)");
     resident_step = -1;
+    fix_tr.valid = false;                      // the index of the list that is replaced (section 26)
     pm.invalidate();
     ew.invalidate();
     static const bool tren = getenv("CONP_TIME_REN") != nullptr;
@@ -2395,6 +2397,11 @@ struct conp_fix : DevCtx {
   // the field and the per-group sums (conp_fieldstyle.cpp, 24), the z mirror (conp_zmirrorstyle.cpp, 25), the exact-Ewald query entries (conp_ewaldquery.cpp, sections 11, 12,
   // 14, 15) and the PPPM mesh with the update's b and its query entries (conp_pppmmesh.cpp, sections 8, 13, 14, 15) ----
   PairStyle pair{*this};
+  // the transposed indices of the pair style's list and of the fix's own (conp_transpose.hip, section 26).  pair_tr belongs to the
+  // list generation it was built from; fix_tr is dropped by every (setup_)post_neighbor[_device]
+  TransposedList pair_tr{*this}, fix_tr{*this};
+  unsigned long long pair_tr_gen = 0;
+  bool pair_tr_valid() const { return pair_tr.valid && pair.have_list && pair_tr_gen == pair.list_gen; }
   GhostMap ghost{*this};
   BondedStyle bonded{*this};
   Integrator integ{*this};
@@ -2458,6 +2465,7 @@ struct conp_fix : DevCtx {
   void post_neighbor_device(const double *dx, const double *dq) {
     post_neighbor_device_check(dx, dq);
     resident_step = -1;
+    fix_tr.valid = false;                      // the index of the list that is replaced (section 26)
     pm.invalidate();
     ew.invalidate();
     const int nloc = nlocal_cur, ng = ghost.nghost, na = nloc + ng, ne = idx.elenum_all;
@@ -2616,6 +2624,68 @@ struct conp_fix : DevCtx {
       throw ConpError(CONP_ERR_ARG, "conp_pair_compute_device: an atom type of the last post_neighbor lies outside [0, ntypes]");
     if (!df && !dev && !dea && !dva) return;
     pair.enqueue(dx, dq, d_type.p, nlocal_cur, df, dev, dea, dva);
+  }
+
+  // ---- the atomic-free twins ------------------------------------------------------------------------------
+  void pair_transpose_list() {
+    if (!pair.have_list) throw ConpError(CONP_ERR_STATE, "conp_pair_transpose_list_device before conp_pair_set_list");
+    pair_tr.build("conp_pair_transpose_list_device",
+                  TransposeArgs{pair.inum, pair.d_ilist.p, pair.d_numneigh.p, pair.d_first.p, pair.d_neigh.p, pair.nall});
+    pair_tr_gen = pair.list_gen;
+  }
+  void fix_transpose_list() {
+    if (!idx.initialised || nlocal_cur <= 0 || nall <= 0)
+      throw ConpError(CONP_ERR_STATE, "conp_fix_transpose_list_device before a post_neighbor");
+    fix_tr.build("conp_fix_transpose_list_device",
+                 TransposeArgs{bl_inum, d_bl_ilist.p, d_bl_numneigh.p, d_bl_first.p, d_bl_neigh.p, nall});
+  }
+  void get_transposed_list(int which, int *nall_, int64_t *n_, int *own_row, int *tr_ptr, int *tr_entry) {
+    if (which != 0 && which != 1) throw ConpError(CONP_ERR_ARG, "conp_pair_get_transposed_list: which is neither 0 nor 1");
+    if (which == 0 && !pair_tr_valid())
+      throw ConpError(CONP_ERR_STATE, "conp_pair_get_transposed_list: no transposed list of the handle's current pair list "
+                                      "(conp_pair_transpose_list_device after the list)");
+    (which ? fix_tr : pair_tr).get("conp_pair_get_transposed_list", nall_, n_, own_row, tr_ptr, tr_entry);
+  }
+
+  void pair_compute_ordered_device(const double *dx, const double *dq, double *df, double *dev, double *dea, double *dva) {
+    if (!dx || !dq) throw ConpError(CONP_ERR_ARG, "null argument");
+    pair.need_ready("conp_pair_compute_ordered_device");
+    if (nall <= 0 || pair.nall != nall || d_type.n < (size_t)nall)
+      throw ConpError(CONP_ERR_STATE, "conp_pair_compute_ordered_device: the nall of conp_pair_set_list is not the atom count of the last "
+                                      "post_neighbor (whose type array the entry reads)");
+    if (!types_in_range)
+      throw ConpError(CONP_ERR_ARG, "conp_pair_compute_ordered_device: an atom type of the last post_neighbor lies outside [0, ntypes]");
+    if (!pair_tr_valid() || pair_tr.nall != pair.nall)
+      throw ConpError(CONP_ERR_STATE, "conp_pair_compute_ordered_device: no transposed list of the handle's current pair list "
+                                      "(conp_pair_transpose_list_device after every conp_pair_set_list or list build)");
+    if (!df && !dev && !dea && !dva) return;
+    const TransposedView tv = pair_tr.view();
+    pair.enqueue(dx, dq, d_type.p, nlocal_cur, df, dev, dea, dva, &tv);
+  }
+
+  // d_out from the atomic entry's own kernels (the <no force, sums> instantiation and the finish: the same bytes), the forces gathered
+  void post_force_ordered_device(const double *dx, const double *dq, double *df, double *dout) {
+    if (!dx || !dq) throw ConpError(CONP_ERR_ARG, "null argument");
+    if (decomposed) throw ConpError(CONP_ERR_STATE, "device-resident updates take replicated atoms (conp_env.rank / nranks); "
+                                                    "spatially decomposed runs use the host-buffer hooks");
+    if (runstage < 2 || !idx.initialised || nlocal_cur <= 0 || nall <= 0) throw ConpError(CONP_ERR_STATE, "post_force before setup");
+    if (!fix_tr.valid || fix_tr.nall != nall)
+      throw ConpError(CONP_ERR_STATE, "conp_fix_post_force_ordered_device: no transposed list of the fix's current list "
+                                      "(conp_fix_transpose_list_device after every conp_fix_post_neighbor[_device])");
+    drop_graph();
+    if (!df && !dout) return;
+    if (dout) d_pfd_part.reserve(8 * (size_t)std::max((bl_inum + 3) / 4, 1));
+    const double k_self = ehgo_active ? env.qqrd2e * 1.0 : env.qqrd2e * 1.0 * args.eta;                       // :1198, :1180
+    const double k_div = std::sqrt(2.0) * 1.77245385090551602729;
+    prof.begin("post_force_ordered", stream);
+    if (dout)
+      launch_post_force_device(stream, bl_inum, d_bl_ilist.p, d_bl_numneigh.p, d_bl_first.p, d_bl_neigh.p, nlocal_cur, env.newton_pair != 0,
+                               dx, dq, d_type.p, d_atom2eleall.p, real_params(), env.qqrd2e, k_self, k_div, nullptr, d_pfd_part.p, dout);
+    if (df)
+      launch_post_force_ordered(stream, fix_tr.view(), d_bl_numneigh.p, d_bl_first.p, d_bl_neigh.p, nlocal_cur, env.newton_pair != 0, dx, dq,
+                                d_type.p, d_atom2eleall.p, real_params(), env.qqrd2e, df);
+    prof.end(stream);
+    HIP_TRY(hipGetLastError());
   }
 
   // fix_conp.cpp:677-695 b_cal / update_bk
@@ -3694,6 +3764,50 @@ int conp_pair_compute_device(conp_fix *f, const double *d_x, const double *d_q, 
   if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
   f->drop_graph();
   f->pair_compute_device(d_x, d_q, d_f, d_ev, d_eatom, d_vatom);
+  CONP_GUARD_END
+}
+
+// ---- the transposed lists and the atomic-free twins ---------------------------------------------------------
+int conp_pair_transpose_list_device(conp_fix *f) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(f->env.device));
+  f->drop_graph();
+  f->pair_transpose_list();
+  CONP_GUARD_END
+}
+
+int conp_fix_transpose_list_device(conp_fix *f) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(f->env.device));
+  f->drop_graph();
+  f->fix_transpose_list();
+  CONP_GUARD_END
+}
+
+int conp_pair_get_transposed_list(conp_fix *f, int which, int *nall, int64_t *n, int *own_row, int *tr_ptr, int *tr_entry) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(f->env.device));
+  f->drop_graph();
+  f->get_transposed_list(which, nall, n, own_row, tr_ptr, tr_entry);
+  CONP_GUARD_END
+}
+
+int conp_pair_compute_ordered_device(conp_fix *f, const double *d_x, const double *d_q, double *d_f, double *d_ev, double *d_eatom,
+                                     double *d_vatom) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->drop_graph();
+  f->pair_compute_ordered_device(d_x, d_q, d_f, d_ev, d_eatom, d_vatom);
+  CONP_GUARD_END
+}
+
+int conp_fix_post_force_ordered_device(conp_fix *f, const double *d_x, const double *d_q, double *d_f, double *d_out) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->post_force_ordered_device(d_x, d_q, d_f, d_out);     // (checks, then drop_graph(): a refused call leaves the handle as it was)
   CONP_GUARD_END
 }
 

@@ -382,6 +382,29 @@ struct PairArgs {
 void launch_pair_pack(hipStream_t s, int nall, const double *x, const double *q, double4 *xq);
 // ev [8] = eng_vdwl, eng_coul, virial xx, yy, zz, xy, xz, yz (overwritten, summed in a fixed order), or NULL
 void launch_pair_force(hipStream_t s, const PairArgs &a, double *ev);
+// ---- the transposed half list and the atomic-free twins of the two pair entries (conp_transpose.hip) ----
+struct TransposeArgs {                   // any flattened half list on the device; numneigh / first are read for listed owners only
+  int inum;
+  const int *ilist, *numneigh, *first, *neigh;
+  int nall;
+};
+struct TransposedView {                  // own_row [nall], tr_ptr [nall + 1], tr_entry [tr_ptr[nall]] (conp_transpose.hpp)
+  const int *own_row, *tr_ptr, *tr_entry;
+  int nall;
+};
+// own_row (cleared to -1 by the caller); *flag |= 1: an owner listed twice, |= 2: an owner outside [0, nall)
+void launch_tr_owners(hipStream_t s, const TransposeArgs &a, int *own_row, int *flag);
+void launch_tr_count(hipStream_t s, const TransposeArgs &a, int *cnt /*[nall], cleared by the caller*/);
+void launch_tr_close(hipStream_t s, int nall, const long long *total, int *tr_ptr);      // tr_ptr[nall] = *total
+// keys [tr_ptr[nall]]: (slot << 32 | entry) of every listed slot, grouped by j in arrival order; cursor [nall] cleared by the caller
+void launch_tr_fill(hipStream_t s, const TransposeArgs &a, const int *tr_ptr, int *cursor, long long *keys);
+void launch_tr_sort(hipStream_t s, int nall, const int *tr_ptr, const long long *keys, int *tr_entry);   // by rank: ascending slot
+// conp_pair_compute_ordered_device: launch_pair_force without a float atomic (one wavefront per receiving atom)
+void launch_pair_force_ordered(hipStream_t s, const PairArgs &a, const TransposedView &t, double *ev);
+// conp_fix_post_force_ordered_device: the forces of launch_post_force_device gathered per atom, one plain add per receiving atom
+void launch_post_force_ordered(hipStream_t s, const TransposedView &t, const int *numneigh, const int *first, const int *neigh, int nlocal,
+                               int newton, const double *x, const double *q, const int *type, const int *atom2eleall, RealParams rp,
+                               double qqrd2e, double *f);
 // ---- bonded forces of bond_style / angle_style harmonic (conp_bonded.hip) ----
 constexpr int BONDED_BLOCK = 256;        // threads of a workgroup: one per term (term kernel), one per atom (gather kernel)
 constexpr int BONDED_FINISH = 256;       // threads of the finishing workgroup: rows r, r + 256, ... per thread

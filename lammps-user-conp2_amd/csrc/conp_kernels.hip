@@ -2676,6 +2676,86 @@ void launch_post_force_device(hipStream_t s, int inum, const int *ilist, const i
                        type, rp.ehgo ? rp.u0_i : nullptr, k_self, k_div, out);
 }
 
+// ---- the atomic-free twin of the device entry's forces (conp_fix_post_force_ordered_device) ------------------
+// post_force_device_kernel's gates and arithmetic for one pair in its OWNER's orientation (i the owner), operation for operation:
+// forcecoul of a pair with exactly one electrode member (the caller has tested the membership); false: outside a gate.
+__device__ __forceinline__ bool post_force_term(const RealParams &rp, double qqrd2e, int tij, double rsq, double qi, double qj,
+                                                double &forcecoul) {
+#pragma clang fp contract(off)
+  if (!(rsq < rp.cutsq[tij])) return false;
+  const double etarij2 = rp.eta * rp.eta * rsq;
+  if (!(etarij2 < 5.8)) return false;                              // :1419 (ERFC_MAX, not its square -- kept as written)
+  const double prefactor = qqrd2e * qi * qj;
+  double fterm;
+  if (rp.ehgo) {                                                   // ehgo_force :1568-1573
+    const double etaij = rp.eta_ij[tij], foij = rp.fo_ij[tij];
+    const double e2 = etaij * etaij * rsq;
+    fterm = e2 * foij * exp(-0.5 * e2) - ferfcr_sqrt_dev(e2) * etaij;
+  } else fterm = -ferfcr_sqrt_dev(etarij2) * rp.eta;              // eta_force :1477-1480
+  forcecoul = prefactor * fterm;
+  return true;
+}
+
+// One wavefront per atom `at` of [0, nall).  The term's force lands on the pair's member that is NO electrode atom, so an electrode
+// atom's wave leaves at once.  The lanes stride over at's own row (the pairs in which it is the i: +del forcecoul, no newton gate, as
+// in post_force_device_kernel), then over its transposed entries (the j side, under newton || at < nlocal: -(del forcecoul) with
+// del = x_owner - x_at and the types [type_owner][type_at]).  The membership test comes before any coordinate load.  Fixed shuffle
+// tree, then lane 0 adds with one plain read-add-write -- only for an atom with a contributing pair, as the atomic kernel.
+__global__ __launch_bounds__(256) void post_force_ordered_kernel(TransposedView tv, const int *__restrict__ numneigh,
+                                                                 const int *__restrict__ first, const int *__restrict__ neigh, int nlocal,
+                                                                 int newton, const double *__restrict__ x, const double *__restrict__ q,
+                                                                 const int *__restrict__ type, const int *__restrict__ atom2eleall,
+                                                                 RealParams rp, double qqrd2e, double *__restrict__ f) {
+#pragma clang fp contract(off)
+  const int at = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (at >= tv.nall) return;
+  if (atom2eleall[at] >= 0) return;
+  const int nt1 = rp.ntypes + 1;
+  const size_t a3 = 3 * (size_t)at;
+  double fx = 0.0, fy = 0.0, fz = 0.0;
+  bool got = false;
+  if (tv.own_row[at] >= 0) {
+    const int *jl = neigh + first[at];
+    const int jn = numneigh[at];
+    for (int jj = lane; jj < jn; jj += 64) {
+      const int j = jl[jj] & 0x3FFFFFFF;
+      if (atom2eleall[j] < 0) continue;                              // exactly one electrode member: nearly every pair ends here
+      const size_t j3 = 3 * (size_t)j;
+      const double delx = x[a3] - x[j3], dely = x[a3 + 1] - x[j3 + 1], delz = x[a3 + 2] - x[j3 + 2];
+      const double rsq = delx * delx + dely * dely + delz * delz;
+      double forcecoul;
+      if (!post_force_term(rp, qqrd2e, type[at] * nt1 + type[j], rsq, q[at], q[j], forcecoul)) continue;
+      got = true;
+      fx += delx * forcecoul; fy += dely * forcecoul; fz += delz * forcecoul;
+    }
+  }
+  if (newton || at < nlocal) {
+    const int lo = tv.tr_ptr[at], hi = tv.tr_ptr[at + 1];
+    for (int k = lo + lane; k < hi; k += 64) {
+      const int i = tv.tr_entry[k] & 0x3FFFFFFF;
+      if (atom2eleall[i] < 0) continue;
+      const size_t i3 = 3 * (size_t)i;
+      const double delx = x[i3] - x[a3], dely = x[i3 + 1] - x[a3 + 1], delz = x[i3 + 2] - x[a3 + 2];
+      const double rsq = delx * delx + dely * dely + delz * delz;
+      double forcecoul;
+      if (!post_force_term(rp, qqrd2e, type[i] * nt1 + type[at], rsq, q[i], q[at], forcecoul)) continue;
+      got = true;
+      fx += -(delx * forcecoul); fy += -(dely * forcecoul); fz += -(delz * forcecoul);
+    }
+  }
+  if (__ballot(got) == 0) return;
+  fx = wave_sum(fx); fy = wave_sum(fy); fz = wave_sum(fz);
+  if (lane == 0) { f[a3] = f[a3] + fx; f[a3 + 1] = f[a3 + 1] + fy; f[a3 + 2] = f[a3 + 2] + fz; }
+}
+
+void launch_post_force_ordered(hipStream_t s, const TransposedView &t, const int *numneigh, const int *first, const int *neigh, int nlocal,
+                               int newton, const double *x, const double *q, const int *type, const int *atom2eleall, RealParams rp,
+                               double qqrd2e, double *f) {
+  if (t.nall > 0)
+    hipLaunchKernelGGL(post_force_ordered_kernel, dim3((t.nall + 3) / 4), dim3(256), 0, s, t, numneigh, first, neigh, nlocal, newton, x, q,
+                       type, atom2eleall, rp, qqrd2e, f);
+}
+
 // sum of v over the group-1 ("left") electrode atoms (totsetq :1098-1104); one workgroup
 __global__ __launch_bounds__(1024) void left_sum_kernel(int ne, const int *__restrict__ elecheck,
                                                         const double *__restrict__ v, double *__restrict__ out) {

@@ -11,6 +11,8 @@
 //                        EV: the eight sums (eng_vdwl, eng_coul, virial[6]) are reduced per wave and written as one row per owner.
 //                        LDS: the per-type-pair table sits in LDS (up to PAIR_LDS_ENTRIES type pairs); else it is read from global.
 //   pair_finish_kernel   adds the rows in a fixed order (no atomics): energy and virial are bit-reproducible from run to run.
+//   pair_ordered_kernel  <EV, ATOM, LDS>: the atomic-free twin (section 26): one wavefront per receiving atom gathers its own row and
+//                        its transposed entries (conp_transpose.hip); forces, eatom and vatom are bit-reproducible too.
 #include <hip/hip_runtime.h>
 
 #include "conp_kernels.h"
@@ -175,7 +177,171 @@ void launch_pair_force_t(hipStream_t s, const PairArgs &a) {
   else hipLaunchKernelGGL((pair_force_kernel<EV, ATOM, false>), grid, block, 0, s, a);
 }
 
+// ---- the atomic-free twin (conp_pair_compute_ordered_device) ------------------------------------------------
+// pair_force_kernel's pair body, operation for operation, as one function: fpair (and with E the two energies) of a pair at rsq whose
+// table record is t, qi and qj in the OWNER's orientation (prefactor = qqrd2e qi qj / r).  false: outside cutsq, nothing is set.
+template <bool E>
+__device__ __forceinline__ bool pair_term(const PairArgs &a, const double *__restrict__ t, double qi, double qj, int sb, double rsq,
+                                          double &fpair, double &evdwl, double &ecoul) {
+#pragma clang fp contract(off)
+  if (!(rsq < t[0])) return false;
+  const double fc = a.special_coul[sb], fl = a.special_lj[sb];
+  const double r2inv = 1.0 / rsq;
+  double forcecoul = 0.0, forcelj = 0.0;
+  ecoul = 0.0; evdwl = 0.0;
+  if (rsq < a.cut_coulsq) {
+    const double r = sqrt(rsq);
+    const double grij = a.g_ewald * r;
+    const double expm2 = exp(-grij * grij);
+    const double tt = 1.0 / (1.0 + 0.3275911 * grij);
+    const double erfc_ = tt * (0.254829592 + tt * (-0.284496736 + tt * (1.421413741 + tt * (-1.453152027 + tt * 1.061405429)))) * expm2;
+    const double prefactor = a.qqrd2e * qi * qj / r;
+    forcecoul = prefactor * (erfc_ + 1.12837917 * grij * expm2);
+    if (fc < 1.0) forcecoul -= (1.0 - fc) * prefactor;
+    if (E) {
+      ecoul = prefactor * erfc_;
+      if (fc < 1.0) ecoul -= (1.0 - fc) * prefactor;
+    }
+  }
+  if (rsq < t[1]) {
+    const double r6inv = r2inv * r2inv * r2inv;
+    forcelj = r6inv * (t[2] * r6inv - t[3]);
+    if (E) evdwl = fl * (r6inv * (t[4] * r6inv - t[5]) - t[6]);
+  }
+  fpair = (forcecoul + fl * forcelj) * r2inv;
+  return true;
+}
+
+// One wavefront per atom `at` of [0, nall), four per workgroup.  The lanes stride first over at's own row (if own_row[at] >= 0): the
+// pairs in which it is the i, with pair_force_kernel's lane assignment, so that the row's eight sums are that kernel's to the byte;
+// then over at's transposed entries: the pairs in which it is the j, each in its OWNER's orientation (del = x_owner - x_at, types
+// [type_owner][type_at]), of which at receives -(del fpair) and the owner's half of eatom / vatom.  An atom receives under
+// newton || at < nlocal; an atom that cannot receive only records its row's sums (EV).  The wave's sums go through the fixed shuffle
+// tree and lane 0 adds them with one plain read-add-write per output: no float atomic.  A row is written exactly when
+// pair_force_kernel writes it: an own row with entries, or a transposed pair inside its cutoff.
+template <bool EV, bool ATOM, bool LDS>
+__global__ __launch_bounds__(256) void pair_ordered_kernel(PairArgs a, TransposedView tv) {
+#pragma clang fp contract(off)
+  __shared__ double tab_s[LDS ? PAIR_LDS_ENTRIES * PAIR_TAB_W : 1];
+  const double *tab = a.tab;
+  if (LDS) {
+    for (int k = threadIdx.x; k < a.ntab * PAIR_TAB_W; k += 256) tab_s[k] = a.tab[k];
+    __syncthreads();
+    tab = tab_s;
+  }
+  const int at = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (at >= tv.nall) return;                     // (whole waves leave, after the only barrier)
+  const int ii = tv.own_row[at];
+  const bool recv = a.newton || at < a.nlocal;
+  if (!recv && !(EV && ii >= 0)) return;
+  const double4 pa = a.xq[at];
+  const int ta = a.type[at];
+  double fx = 0.0, fy = 0.0, fz = 0.0, ei = 0.0;
+  double vi[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  double s[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  int jn = 0;
+  if (ii >= 0) {                                 // the pairs in which `at` is the owner
+    const int *jl = a.neigh + a.first[at];
+    jn = a.numneigh[at];
+    const int trow = ta * a.nt1;
+    for (int jj = lane; jj < jn; jj += 64) {
+      const int jraw = jl[jj];
+      const int sb = (jraw >> 30) & 3, j = jraw & PAIR_MASK;
+      const double4 pj = a.xq[j];
+      const double delx = pa.x - pj.x, dely = pa.y - pj.y, delz = pa.z - pj.z;
+      const double rsq = delx * delx + dely * dely + delz * delz;
+      double fpair, evdwl, ecoul;
+      if (!pair_term<EV || ATOM>(a, tab + (size_t)(trow + a.type[j]) * PAIR_TAB_W, pa.w, pj.w, sb, rsq, fpair, evdwl, ecoul)) continue;
+      fx += delx * fpair; fy += dely * fpair; fz += delz * fpair;
+      if (EV || ATOM) {
+        const double v[6] = {delx * delx * fpair, dely * dely * fpair, delz * delz * fpair,
+                             delx * dely * fpair, delx * delz * fpair, dely * delz * fpair};
+        if (EV) {
+          double w = 1.0;
+          if (!a.newton) w = (at < a.nlocal ? 0.5 : 0.0) + (j < a.nlocal ? 0.5 : 0.0);
+          s[0] += w * evdwl; s[1] += w * ecoul;
+#pragma unroll
+          for (int k = 0; k < 6; ++k) s[2 + k] += w * v[k];
+        }
+        if (ATOM) {
+          ei += 0.5 * (evdwl + ecoul);
+#pragma unroll
+          for (int k = 0; k < 6; ++k) vi[k] += 0.5 * v[k];
+        }
+      }
+    }
+  }
+  bool got = false;
+  if (recv) {                                    // the pairs in which `at` is the j, ascending slot order
+    const int lo = tv.tr_ptr[at], hi = tv.tr_ptr[at + 1];
+    for (int k = lo + lane; k < hi; k += 64) {
+      const int e = tv.tr_entry[k];
+      const int sb = (e >> 30) & 3, i = e & PAIR_MASK;
+      const double4 pi = a.xq[i];
+      const double delx = pi.x - pa.x, dely = pi.y - pa.y, delz = pi.z - pa.z;
+      const double rsq = delx * delx + dely * dely + delz * delz;
+      double fpair, evdwl, ecoul;
+      if (!pair_term<ATOM>(a, tab + (size_t)(a.type[i] * a.nt1 + ta) * PAIR_TAB_W, pi.w, pa.w, sb, rsq, fpair, evdwl, ecoul)) continue;
+      got = true;
+      fx += -(delx * fpair); fy += -(dely * fpair); fz += -(delz * fpair);
+      if (ATOM) {
+        ei += 0.5 * (evdwl + ecoul);
+        vi[0] += 0.5 * (delx * delx * fpair); vi[1] += 0.5 * (dely * dely * fpair); vi[2] += 0.5 * (delz * delz * fpair);
+        vi[3] += 0.5 * (delx * dely * fpair); vi[4] += 0.5 * (delx * delz * fpair); vi[5] += 0.5 * (dely * delz * fpair);
+      }
+    }
+  }
+  const bool any_tr = __ballot(got) != 0;
+  const bool write = recv && (jn > 0 || any_tr);
+  fx = pair_wave_sum(fx); fy = pair_wave_sum(fy); fz = pair_wave_sum(fz);
+  if (ATOM) {
+    ei = pair_wave_sum(ei);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) vi[k] = pair_wave_sum(vi[k]);
+  }
+  if (EV) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s[k] = pair_wave_sum(s[k]);
+  }
+  if (lane != 0) return;
+  if (write) {
+    if (a.f) {
+      double *fa = a.f + 3 * (size_t)at;
+      fa[0] = fa[0] + fx; fa[1] = fa[1] + fy; fa[2] = fa[2] + fz;
+    }
+    if (ATOM) {
+      if (a.eatom) a.eatom[at] = a.eatom[at] + ei;
+      if (a.vatom) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) a.vatom[6 * (size_t)at + k] = a.vatom[6 * (size_t)at + k] + vi[k];
+      }
+    }
+  }
+  if (EV && ii >= 0) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) a.part[8 * (size_t)ii + k] = s[k];
+  }
+}
+
+template <bool EV, bool ATOM>
+void launch_pair_ordered_t(hipStream_t s, const PairArgs &a, const TransposedView &t) {
+  const dim3 grid((t.nall + 3) / 4), block(256);
+  if (a.ntab <= PAIR_LDS_ENTRIES) hipLaunchKernelGGL((pair_ordered_kernel<EV, ATOM, true>), grid, block, 0, s, a, t);
+  else hipLaunchKernelGGL((pair_ordered_kernel<EV, ATOM, false>), grid, block, 0, s, a, t);
+}
+
 }  // namespace
+
+void launch_pair_force_ordered(hipStream_t s, const PairArgs &a, const TransposedView &t, double *ev) {
+  const bool do_ev = ev != nullptr, do_atom = a.eatom != nullptr || a.vatom != nullptr;
+  if (a.inum > 0 && t.nall > 0) {
+    if (do_ev && do_atom) launch_pair_ordered_t<true, true>(s, a, t);
+    else if (do_ev) launch_pair_ordered_t<true, false>(s, a, t);
+    else if (do_atom) launch_pair_ordered_t<false, true>(s, a, t);
+    else launch_pair_ordered_t<false, false>(s, a, t);
+  }
+  if (do_ev) hipLaunchKernelGGL(pair_finish_kernel, dim3(1), dim3(1024), 0, s, a.inum, a.part, ev);
+}
 
 void launch_pair_pack(hipStream_t s, int nall, const double *x, const double *q, double4 *xq) {
   if (nall > 0) hipLaunchKernelGGL(pair_pack_kernel, dim3((nall + 255) / 256), dim3(256), 0, s, nall, x, q, xq);

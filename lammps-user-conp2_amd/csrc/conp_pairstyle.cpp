@@ -35,6 +35,7 @@ void PairStyle::set_params(const conp_pair_params *p) {
 void PairStyle::set_list(const conp_neighlist *l, int nall_) {
   have_list = false;                       // a list that is refused leaves the handle without one
   list_built = false;
+  ++list_gen;
   if (nall_ < 0 || l->inum < 0 || l->inum > nall_ || l->nneigh < 0) throw ConpError(CONP_ERR_ARG, "conp_pair_set_list: bad sizes");
   if (l->inum > 0 && (!l->ilist || !l->numneigh || !l->first)) throw ConpError(CONP_ERR_ARG, "conp_pair_set_list: null list array");
   if (l->nneigh > 0 && !l->neigh) throw ConpError(CONP_ERR_ARG, "conp_pair_set_list: null neighbour array");
@@ -127,6 +128,7 @@ void PairStyle::set_exclusions(const conp_pair_exclusions *e) {
 void PairStyle::build_list(const double *dx, const conp_pair_build_args *a, const conp_pair_exclude_atoms *at, bool exclude) {
   have_list = false;                       // a build that is refused leaves the handle without a list
   list_built = false;
+  ++list_gen;
   const std::string who = exclude ? "conp_pair_build_list_exclude_device: " : "conp_pair_build_list_device: ";
   const char *entry = exclude ? "conp_pair_build_list_exclude_device" : "conp_pair_build_list_device";
   if (!have_params) throw ConpError(CONP_ERR_STATE, std::string(entry) + " before conp_pair_set_params");
@@ -237,7 +239,8 @@ void PairStyle::get_list(int *inum_, int *nall_, int64_t *nneigh_, int *ilist, i
 }
 
 // pack + force kernel (+ finish) on the stream; eatom / vatom are overwritten: zeroed first, then accumulated
-void PairStyle::enqueue(const double *dx, const double *dq, const int *dtype, int nlocal_, double *df, double *dev, double *dea, double *dva) {
+void PairStyle::enqueue(const double *dx, const double *dq, const int *dtype, int nlocal_, double *df, double *dev, double *dea, double *dva,
+                        const TransposedView *tv) {
   PairArgs a;
   a.inum = inum; a.ilist = d_ilist.p; a.numneigh = d_numneigh.p; a.first = d_first.p; a.neigh = d_neigh.p;
   a.nlocal = nlocal_; a.newton = env.newton_pair != 0;
@@ -247,9 +250,10 @@ void PairStyle::enqueue(const double *dx, const double *dq, const int *dtype, in
   a.f = df; a.eatom = dea; a.vatom = dva; a.part = d_part.p;
   if (dea && nall > 0) HIP_TRY(hipMemsetAsync(dea, 0, (size_t)nall * sizeof(double), ctx.stream));
   if (dva && nall > 0) HIP_TRY(hipMemsetAsync(dva, 0, (size_t)nall * 6 * sizeof(double), ctx.stream));
-  ctx.prof.begin("pair_force", ctx.stream);
+  ctx.prof.begin(tv ? "pair_force_ordered" : "pair_force", ctx.stream);
   launch_pair_pack(ctx.stream, nall, dx, dq, d_xq.p);
-  launch_pair_force(ctx.stream, a, dev);
+  if (tv) launch_pair_force_ordered(ctx.stream, a, *tv, dev);
+  else launch_pair_force(ctx.stream, a, dev);
   ctx.prof.end(ctx.stream);
   HIP_TRY(hipGetLastError());
 }

@@ -9,6 +9,7 @@ struct PairStyle {
   dev::DevCtx &ctx;                                                     // the handle's stream, wait and profiler
   struct Env { int ntypes, newton_pair; double g_ewald, qqrd2e; } env{};      // what the pair style reads of conp_env
   bool have_params = false, have_list = false;
+  unsigned long long list_gen = 0;        // counts the lists the handle has held: a transposed index (section 26) belongs to one
   int nall = 0, inum = 0, ntab = 0;
   double cut_coul = 0.0, special_lj[4] = {1, 1, 1, 1}, special_coul[4] = {1, 1, 1, 1};
   dev::DevBuf<double> d_tab, d_part, d_x, d_q, d_f, d_ev, d_ea, d_va;
@@ -42,7 +43,9 @@ struct PairStyle {
     if (!have_params) throw dev::ConpError(CONP_ERR_STATE, std::string(who) + " before conp_pair_set_params");
     if (!have_list) throw dev::ConpError(CONP_ERR_STATE, std::string(who) + " before conp_pair_set_list");
   }
-  void enqueue(const double *dx, const double *dq, const int *dtype, int nlocal_, double *df, double *dev, double *dea, double *dva);
+  // tv: the list's transposed index -- the atomic-free kernel of section 26; NULL: the atomic kernel
+  void enqueue(const double *dx, const double *dq, const int *dtype, int nlocal_, double *df, double *dev, double *dea, double *dva,
+               const TransposedView *tv = nullptr);
   // dx, dq: device arrays of the call's atoms, or NULL (at->x, at->q are staged); downloads and adds into f, overwrites the rest
   void compute_host(const conp_atoms *at, const double *dx, const double *dq, double *f, double *eng, double *vir, double *eatom, double *vatom);
 };
