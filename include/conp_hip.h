@@ -758,6 +758,52 @@ int conp_pair_compute_ordered_device(conp_fix *fix, const double *d_x, const dou
 int conp_fix_post_force_ordered_device(conp_fix *fix, const double *d_x /*[nall][3]*/, const double *d_q /*[nall]*/,
                                        double *d_f /*[nall][3], added to; NULL: none*/, double *d_out /*[9], overwritten; NULL: none*/);
 
+/* ---- `compute potential/atom` on the device -----------------------------------------------------------------
+ * conp_compute_potential_atom without the host: device pointers in the layout of conp_fix_pre_force_device, everything enqueued on
+ * the handle's stream; after the first call at a given size no device allocation, no copy to the host, no synchronisation.
+ * Rank-local, on one rank: a decomposed handle (conp_fix_set_comm) gets CONP_ERR_STATE.
+ * ntotal = nlocal + (newton_pair ? nghost : 0) of the last (setup_)post_neighbor[_device].
+ * d_flags [nall]: bit 0 -- the row is selected (mask & groupbit); bit 1 -- eta_check.  The caller keeps its ghost rows with
+ * conp_ghost_fill_int_device, like tag and mask.  d_targets [ntargets]: the selected OWNED rows, ascending; it must name exactly
+ * the owned rows with bit 0 set -- not checked.
+ * RESULT.  A selected row of [0, ntotal) gets what conp_compute_potential_atom gives that row, in volts; every other row of
+ * [0, ntotal) is written 0.0 (the reference clears the array; the host entry's partial sums on unselected rows are not reproduced);
+ * rows from ntotal on are not touched.  With newton on a ghost row holds its pair partial times qqr2e / qe2f: the caller finishes
+ * with conp_ghost_fold_device(fix, d_pot, 1), as for d_eatom.
+ * PAIR PART (args->pairflag): over the pair style's current list (conp_pair_set_list or either device build) and its transposed
+ * index (conp_pair_transpose_list_device); without a list, or with an index that is missing or belongs to an earlier list:
+ * CONP_ERR_STATE, as conp_pair_compute_ordered_device.  Constants and types are the host entry's: the fix's cutsq table, the
+ * reference's min(cut_coul, 5.8 / g)^2, env.g_ewald, the types of the last post_neighbor.  The arithmetic of a pair is the host
+ * entry's, operation for operation, no contraction: rsq floored at 1e-10, both cutoff tests, the five-term erfc polynomial, the
+ * eta branch with ne2 = eta bit of owner + eta bit of neighbour behind its 5.8 gate; special bits are masked off and ignored.  No
+ * float atomic: each selected row a is gathered by one wavefront in the order of section 26 -- own row jj = l, l + 64, ... with the
+ * term q_j dudq, then the transposed entries from tr_ptr[a] with the term q_owner dudq at rsq in the owner's orientation, the
+ * shuffle tree, one store.  A partner with q == 0 contributes nothing.  Unselected rows do no pair work.  Every byte of d_pot is
+ * the same from call to call and from run to run on an Ewald handle.
+ * K-SPACE PART (args->kspaceflag), on the ntargets owned targets: u_i of conp_ewald_compute_particle_potential on an Ewald handle
+ * (the exact sum over every owned atom of the call), the mesh potential of conp_pppm_compute_particle_potential on a `pppm` handle
+ * (the brick of every owned atom; its spread uses float atomics).  Then, in the host entry's order,
+ *   pot = (((pair - u) + [eta bit] eta q sqrt(2) / sqrt(pi)) + z slabcorr) - [qsumflag] (2 pi / V) Q z^2,   times qqr2e / qe2f,
+ * under env.slabflag with slabcorr = 2 (2 pi / V) M; Q = sum q and M = sum q z over the owned atoms of the call, summed on the
+ * device in a fixed order.
+ * reuse_kspace != 0 skips the structure factor (the mesh solve) and projects from what the last device k-space force entry left on
+ * this handle: conp_ewald_compute_forces[_vatom]_device, or conp_pppm_compute_forces[_vatom]_device called with d_f or d_eatom --
+ * the per-step case update -> forces -> potential at the same x and q.  The handle keeps one validity bit: those entries set it;
+ * every update, every re-neighbouring entry, set_matrix, new k tables, the host query entries (conp_ewald_* / conp_pppm_* with host
+ * arrays, conp_compute_potential_atom) and a call of this entry without reuse clear it.  Reuse without a valid bit:
+ * CONP_ERR_STATE, nothing changed.  As with the cached S above, the handle cannot tell that atoms moved or charges changed without
+ * an update: reusing after that is the caller's error and returns CONP_OK.  With or without reuse the force entries' next call is
+ * unaffected.
+ * REFUSALS.  CONP_ERR_ARG: NULL fix, d_x, d_q or args; ntargets < 0 or > nlocal; NULL d_targets with ntargets > 0; NULL d_flags
+ * when the pair part runs or eta != 0.  CONP_ERR_STATE: before (setup_)post_neighbor, and the cases above.  NULL d_pot: CONP_OK,
+ * nothing done.  Both flags zero: [0, ntotal) is zeroed.
+ * A step with the potentials: ... -> conp_ghost_fold_device(d_f, 3) -> conp_potential_atom_device(reuse_kspace = 1) ->
+ * conp_ghost_fold_device(d_pot, 1). */
+int conp_potential_atom_device(conp_fix *fix, const double *d_x /*[nall][3]*/, const double *d_q /*[nall]*/,
+                               const int *d_flags /*[nall]: bit 0 selected (mask & groupbit), bit 1 eta_check*/,
+                               int ntargets, const int *d_targets /*[ntargets] selected OWNED atoms, ascending*/,
+                               const conp_potential_args *args, int reuse_kspace, double *d_pot /*[ntotal], overwritten*/);
+
 /* ---- bonded forces: `bond_style harmonic` and `angle_style harmonic` on the device -------------------------
  * The bond and angle loops of LAMMPS' bond_harmonic.cpp and angle_harmonic.cpp @ 27May2021 with Bond::ev_tally's and
  * Angle::ev_tally's energy, virial and per-atom tallies.  All arithmetic is double, in the order written, no contraction.

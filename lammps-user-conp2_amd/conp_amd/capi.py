@@ -194,6 +194,7 @@ SYMBOLS = [
     "conp_zmirror_set_params", "conp_zmirror_post_integrate_device", "conp_zmirror_get_map",
     "conp_pair_transpose_list_device", "conp_fix_transpose_list_device", "conp_pair_get_transposed_list",
     "conp_pair_compute_ordered_device", "conp_fix_post_force_ordered_device",
+    "conp_potential_atom_device",
 ]
 
 
@@ -411,11 +412,33 @@ def load_library():
         lib.conp_fix_post_force_ordered_device.argtypes = [vp, vp, vp, vp, vp]
     lib.conp_compute_potential_atom.argtypes = [vp, C.POINTER(conp_atoms), C.POINTER(conp_neighlist), ip, ip,
                                                 C.POINTER(conp_potential_args), dp]
+    if hasattr(lib, "conp_potential_atom_device"):
+        lib.conp_potential_atom_device.argtypes = [vp, vp, vp, vp, C.c_int, vp, C.POINTER(conp_potential_args), C.c_int, vp]
     lib.conp_fix_set_comm.argtypes = [vp, C.POINTER(conp_comm)]
     lib.conp_rccl_unique_id.argtypes = [C.c_void_p]
     lib.conp_fix_comm_init_rccl.argtypes = [vp, C.c_void_p]
     _LIB = lib
     return lib
+
+
+def potential_selection(sel, etasel, nlocal):
+    """(flags, targets, ntargets) of conp_potential_atom_device from the host entry's selections: sel, etasel [nall] (nonzero: the
+    row is selected / an eta_check atom; etasel None: nobody).  flags [nall] int32 -- bit 0 selected, bit 1 eta_check; targets
+    int32 -- the selected rows below nlocal, ascending (one entry, unused, when there is none: an array to upload)"""
+    sel = np.asarray(sel).reshape(-1)
+    flags = (sel != 0).astype(np.int32)
+    if etasel is not None:
+        es = np.asarray(etasel).reshape(-1)
+        if es.size != sel.size:
+            raise ValueError("sel and etasel differ in length")
+        flags |= (es != 0).astype(np.int32) << 1
+    if not 0 <= int(nlocal) <= sel.size:
+        raise ValueError("nlocal outside [0, len(sel)]")
+    targets = np.flatnonzero(flags[:int(nlocal)] & 1).astype(np.int32)
+    ntargets = int(targets.size)
+    if ntargets == 0:
+        targets = np.zeros(1, np.int32)
+    return np.ascontiguousarray(flags), targets, ntargets
 
 
 def _dptr(a):
@@ -1071,6 +1094,17 @@ class FixConp:
         fix's re-neighbouring"""
         self._check(self.lib.conp_fix_post_force_ordered_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q), C.c_void_p(d_f),
                                                                 C.c_void_p(d_out)))
+
+    # -- compute potential/atom on the device (DESIGN.md section 27) ---------------------------------------------------------
+    def potential_atom_device(self, d_x: int, d_q: int, d_flags: int, ntargets: int, d_targets: int, d_pot: int, eta=0.0, pair=True,
+                              kspace=True, qsum=True, reuse_kspace=False):
+        """conp_potential_atom_device: compute_potential_atom on device arrays, enqueued on the handle's stream.  d_flags [nall]
+        int32 (bit 0 selected, bit 1 eta_check), d_targets [ntargets] int32 the selected owned rows ascending (potential_selection
+        makes both); d_pot [ntotal] float64 overwritten.  reuse_kspace: project from what the last device k-space force entry left.
+        With newton on the caller folds: ghost_fold_device(d_pot, 1)"""
+        pa = conp_potential_args(pairflag=int(pair), kspaceflag=int(kspace), qsumflag=int(qsum), eta=float(eta))
+        self._check(self.lib.conp_potential_atom_device(self.h, C.c_void_p(d_x), C.c_void_p(d_q), C.c_void_p(d_flags), int(ntargets),
+                                                        C.c_void_p(d_targets), C.byref(pa), int(bool(reuse_kspace)), C.c_void_p(d_pot)))
 
     STEP_TABLES = ("elyte_idx", "ele_pairs", "csr_ptr", "csr_of", "csr_row", "b_rowptr", "b_ele", "b_oth", "g0c")
 

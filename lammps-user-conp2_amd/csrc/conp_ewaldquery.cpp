@@ -162,7 +162,7 @@ void EwaldQuery::structure_factor(const conp_atoms *at) {
   launch_ew_gw(ctx.stream, dplan, d_ew_G.p, d_ew_Gwf.p);
   HIP_TRY(hipGetLastError());
   ctx.sync();                       // (the host vectors go out of scope)
-  g_valid = true; u_valid = false;
+  g_valid = true; u_valid = false; dev_valid = false;
 }
 // g_i and u_i = g_i + 2 g_ewald q_i / sqrt(pi) of the owned atoms idx (local indices), at their positions in `at`, from d_ew_Gwf:
 // block by block, the block's phase tables, b_project_kernel, ew_out_kernel.  Rank-local.  g, u: [nlocal], only idx written.
@@ -248,6 +248,42 @@ void EwaldQuery::forces_device(int n, const double *dx, const double *dq, double
   if (df || deatom || dvatom) {
     tiles_ready();
     force_blocks(n, nb_pad, dx, nullptr, kspace_out_args(env, V, L, nullptr), df, deatom, dvatom);
+  }
+  HIP_TRY(hipGetLastError());
+  dev_valid = true;                              // d_ew_Gwf is that of (dx, dq): potential_device may reuse it
+}
+// ---- compute potential/atom on the device ----
+// project on the caller's device arrays.  Without reuse: S of the n owned atoms as forces_device forms it, every atom a column.  Then
+// the targets in blocks of block(nt): their x and q gathered into the padded block buffers, the block's phase tables,
+// b_project_kernel, ew_out_kernel scattering u through d_targets.  The force entry's next call forms everything it reads afresh.
+void EwaldQuery::potential_device(int n, const double *dx, const double *dq, int nt, const int *d_targets, bool reuse, double *d_u) {
+  if (!reuse) {
+    const int nb_pad = block(n);
+    const int ntot = (n + nb_pad - 1) / nb_pad * nb_pad;
+    reserve(nb_pad);
+    d_ew_q.reserve(ntot);
+    HIP_TRY(hipMemcpyAsync(d_ew_q.p, dq, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, ctx.stream));
+    if (ntot > n) HIP_TRY(hipMemsetAsync(d_ew_q.p + n, 0, (size_t)(ntot - n) * sizeof(double), ctx.stream));
+    invalidate();                                // d_ew_G, d_ew_Gwf and the host entries' scratch are overwritten from here on
+    build_S(dx, d_ew_q.p, n, nb_pad);
+    launch_ew_gw(ctx.stream, dplan, d_ew_G.p, d_ew_Gwf.p);
+  }
+  if (nt > 0) {
+    const int nb_pad = block(nt);
+    const int ntot = (nt + nb_pad - 1) / nb_pad * nb_pad;
+    reserve(nb_pad);
+    d_ew_x.reserve(3 * (size_t)ntot); d_ew_q.reserve(ntot);
+    launch_pot_gather(ctx.stream, nt, ntot, d_targets, dx, dq, d_ew_x.p, d_ew_q.p);
+    tiles_ready();
+    d_ew_bk.reserve((size_t)4 * nb_pad);
+    d_ew_g.reserve(n);
+    const double selfc = 2.0 * env.g_ewald / MY_PIS;
+    for (int b0 = 0; b0 < nt; b0 += nb_pad) {
+      const int nb = std::min(nb_pad, nt - b0);
+      tables(b0, nb, nb_pad);
+      launch_b_project(ctx.stream, dplan, nb_pad, d_ew_ctptr.p, d_ew_tiles.p, d_ew_Gwf.p, d_ew_Rp.p, d_ew_Tz.p, d_ew_bk.p);
+      launch_ew_out(ctx.stream, nb, nb_pad, d_ew_bk.p, d_targets + b0, d_ew_q.p + b0, selfc, d_ew_g.p, d_u);
+    }
   }
   HIP_TRY(hipGetLastError());
 }

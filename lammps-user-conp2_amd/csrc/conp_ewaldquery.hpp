@@ -21,7 +21,10 @@ struct EwaldQuery {
   // every owned atom (the per-atom entry's cache).  Both are dropped by every update, re-neighbour, set_matrix and k-table setup.
   bool g_valid = false, u_valid = false;
   std::vector<double> u_h;
-  void invalidate() { g_valid = u_valid = false; }
+  // dev_valid: d_ew_Gwf holds w o G of the arrays the last forces_device saw, which potential_device may reuse (DESIGN.md section
+  // 27).  Dropped with the other two, and by every other writer of d_ew_G / d_ew_Gwf (structure_factor, potential_device's own S).
+  bool dev_valid = false;
+  void invalidate() { g_valid = u_valid = dev_valid = false; }
   // the handle has a new plan: the caches go, and the phase tables' zeroed padding, d_ew_kv and the tile lists are the old plan's
   void replan() { invalidate(); tables_nb = 0; kv_ready_ = tiles_ready_ = false; }
 
@@ -29,6 +32,9 @@ struct EwaldQuery {
   void project(const conp_atoms *at, const std::vector<int> &idx, double *g, double *u);
   void forces(const conp_atoms *at, double *fout, double *energy, double *virial, double *eatom, double *vatom);
   void forces_device(int n, const double *dx, const double *dq, double *df, double *dev, double *deatom, double *dvatom);
+  // d_u[t] = u_t = g_t + 2 g_ewald q_t / sqrt(pi) at the nt owned targets d_targets (device, ascending) of the n owned atoms (dx, dq);
+  // reuse: from d_ew_Gwf as forces_device left it (dev_valid), else S of the call's atoms is formed first.  Enqueues only.
+  void potential_device(int n, const double *dx, const double *dq, int nt, const int *d_targets, bool reuse, double *d_u);
 
   int tables_nb = 0;                // block width the phase-table buffers were zeroed for (padding entries stay zero); 0: none
   bool kv_ready_ = false, tiles_ready_ = false;      // d_ew_kv / d_ew_tiles, d_ew_ctptr hold the current plan's

@@ -29,6 +29,7 @@
 #include "conp_shakestyle.hpp"
 #include "conp_fieldstyle.hpp"
 #include "conp_zmirrorstyle.hpp"
+#include "conp_potatomstyle.hpp"
 #include "conp_ewaldquery.hpp"
 #include "conp_pppmmesh.hpp"
 
@@ -2394,7 +2395,7 @@ struct conp_fix : DevCtx {
 
   // ---- the pair style with its half list (conp_pairstyle.cpp, DESIGN.md sections 16, 17), the ghost map (conp_ghostmap.cpp, 18),
   // the harmonic bonds and angles (conp_bondedstyle.cpp, 21), the integrator (conp_integrator.cpp, 22), the constraints (conp_shakestyle.cpp, 23),
-  // the field and the per-group sums (conp_fieldstyle.cpp, 24), the z mirror (conp_zmirrorstyle.cpp, 25), the exact-Ewald query entries (conp_ewaldquery.cpp, sections 11, 12,
+  // the field and the per-group sums (conp_fieldstyle.cpp, 24), the z mirror (conp_zmirrorstyle.cpp, 25), compute potential/atom (conp_potatomstyle.cpp, 27), the exact-Ewald query entries (conp_ewaldquery.cpp, sections 11, 12,
   // 14, 15) and the PPPM mesh with the update's b and its query entries (conp_pppmmesh.cpp, sections 8, 13, 14, 15) ----
   PairStyle pair{*this};
   // the transposed indices of the pair style's list and of the fix's own (conp_transpose.hip, section 26).  pair_tr belongs to the
@@ -2409,6 +2410,7 @@ struct conp_fix : DevCtx {
   FieldStyle field{*this};
   ObserveStyle obs{*this};
   ZmirrorStyle zmirror{*this};
+  PotentialAtom potatom{*this};
   EwaldQuery ew{*this, kt, plan, dplan, tiles_h, ct_ptr_h, d_sf_row_a, d_sf_col_c, d_k_sign};
   PppmMesh pm{*this};
   bool types_in_range = false;                   // every atoms->type of the last (setup_)post_neighbor lies in [0, ntypes]
@@ -4124,6 +4126,65 @@ int conp_compute_potential_atom(conp_fix *f, const conp_atoms *at, const conp_ne
   }
   const double evs = f->env.qqr2e / f->env.qe2f;                                  // :99, :214
   for (int i = 0; i < ntotal; ++i) potential[i] = pot[i] * evs;
+  CONP_GUARD_END
+}
+
+// ---- compute potential/atom on the device: the entry above without the host -- the pair part gathered per
+// selected row from the pair style's list and its transposed index (no float atomic), the provider's potential_device on the owned
+// targets, one finishing launch.  Every check precedes the first launch: a refused call changes nothing.
+int conp_potential_atom_device(conp_fix *f, const double *d_x, const double *d_q, const int *d_flags, int ntargets, const int *d_targets,
+                               const conp_potential_args *pa, int reuse_kspace, double *d_pot) {
+  CONP_GUARD_BEGIN
+  const std::string who = "conp_potential_atom_device: ";
+  if (!f || !d_x || !d_q || !pa) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->drop_graph();
+  if (f->decomposed) throw ConpError(CONP_ERR_STATE, "device-resident updates take replicated atoms (conp_env.rank / nranks); "
+                                                     "spatially decomposed runs use the host-buffer hooks");
+  if (!f->idx.initialised || f->nlocal_cur <= 0 || f->nall <= 0) throw ConpError(CONP_ERR_STATE, who + "before a post_neighbor");
+  const int nlocal = f->nlocal_cur, ntotal = f->env.newton_pair ? f->nall : nlocal;
+  if (ntargets < 0 || ntargets > nlocal) throw ConpError(CONP_ERR_ARG, who + "ntargets outside [0, nlocal]");
+  if (ntargets > 0 && !d_targets) throw ConpError(CONP_ERR_ARG, who + "null d_targets");
+  if (!d_flags && (pa->pairflag || pa->eta != 0.0)) throw ConpError(CONP_ERR_ARG, who + "the pair part and eta need d_flags");
+  if (pa->pairflag) {
+    if (!f->pair.have_list) throw ConpError(CONP_ERR_STATE, who + "the pair part needs the pair style's list (conp_pair_set_list or a device build)");
+    if (f->pair.nall != f->nall || f->d_type.n < (size_t)f->nall)
+      throw ConpError(CONP_ERR_STATE, who + "the nall of the pair style's list is not the atom count of the last post_neighbor "
+                                            "(whose type array the entry reads)");
+    if (!f->types_in_range) throw ConpError(CONP_ERR_ARG, who + "an atom type of the last post_neighbor lies outside [0, ntypes]");
+    if (!f->pair_tr_valid() || f->pair_tr.nall != f->pair.nall)
+      throw ConpError(CONP_ERR_STATE, who + "no transposed list of the handle's current pair list "
+                                            "(conp_pair_transpose_list_device after every conp_pair_set_list or list build)");
+  }
+  const bool mesh = f->args.pppm != 0, reuse = pa->kspaceflag && reuse_kspace != 0;
+  if (pa->kspaceflag) { if (mesh) need_pppm(f); else need_ewald(f); }
+  if (reuse && !(mesh ? f->pm.dev_u_valid : f->ew.dev_valid))
+    throw ConpError(CONP_ERR_STATE, who + "reuse_kspace without what a device k-space force entry left since the last update, "
+                                          "re-neighbouring or host query (conp_ewald_compute_forces_device / "
+                                          "conp_pppm_compute_forces_device with d_f or d_eatom)");
+  if (!d_pot) return CONP_OK;
+  const double evs = f->env.qqr2e / f->env.qe2f;                                  // compute_potential_atom.cpp:99, :214
+  if (pa->pairflag) {
+    PotPairArgs a{};
+    a.ntotal = ntotal; a.nlocal = nlocal; a.ntypes = f->env.ntypes;
+    a.numneigh = f->pair.d_numneigh.p; a.first = f->pair.d_first.p; a.neigh = f->pair.d_neigh.p;
+    a.x = d_x; a.q = d_q; a.type = f->d_type.p; a.flags = d_flags;
+    a.cutsq = f->d_cutsq.p; a.cut_coulsq = f->real_params().cut_coulsq; a.g_ewald = f->env.g_ewald; a.eta = pa->eta;
+    a.scale_owned = pa->kspaceflag ? 1.0 : evs; a.scale_ghost = evs;      // (the finish multiplies the owned targets)
+    a.pot = d_pot;
+    f->potatom.pair_part(a, f->pair_tr.view());
+  } else
+    HIP_TRY(hipMemsetAsync(d_pot, 0, (size_t)ntotal * sizeof(double), f->stream));
+  if (pa->kspaceflag) {
+    double *d_u = f->potatom.u_buffer(nlocal);
+    if (mesh) f->pm.potential_device(nlocal, d_x, d_q, ntargets, d_targets, reuse, 2.0 * f->env.g_ewald / MY_PIS, d_u);
+    else f->ew.potential_device(nlocal, d_x, d_q, ntargets, d_targets, reuse, d_u);
+    PotFinishArgs a{};
+    a.nt = ntargets; a.slab = f->env.slabflag ? 1 : 0; a.qsum = pa->qsumflag ? 1 : 0;
+    a.targets = d_targets; a.flags = d_flags; a.x = d_x; a.q = d_q;
+    a.eta = pa->eta; a.evs = evs; a.pot = d_pot;
+    a.pi2vol = 2 * 3.14159265358979323846 / (f->env.xprd * f->env.yprd * f->env.zprd * f->env.slab_volfactor);
+    f->potatom.finish(a, nlocal);
+  }
   CONP_GUARD_END
 }
 

@@ -405,6 +405,30 @@ void launch_pair_force_ordered(hipStream_t s, const PairArgs &a, const Transpose
 void launch_post_force_ordered(hipStream_t s, const TransposedView &t, const int *numneigh, const int *first, const int *neigh, int nlocal,
                                int newton, const double *x, const double *q, const int *type, const int *atom2eleall, RealParams rp,
                                double qqrd2e, double *f);
+// ---- compute potential/atom on the device (conp_potatom.hip) ----
+struct PotPairArgs {
+  int ntotal, nlocal, ntypes;            // rows [0, ntotal) are written: nlocal (+ nghost with newton on)
+  const int *numneigh, *first, *neigh;   // the pair style's half list (rows of listed owners only are read)
+  const double *x, *q;                   // [nall][3], [nall]
+  const int *type, *flags;               // [nall]; flags bit 0: selected, bit 1: eta_check
+  const double *cutsq;                   // [ntypes + 1][ntypes + 1]
+  double cut_coulsq, g_ewald, eta;
+  double scale_owned, scale_ghost;       // what a selected owned / ghost row's sum is multiplied by before the store
+  double *pot;                           // [ntotal] overwritten: 0.0 on unselected rows
+};
+// the pair part gathered per selected row in section 26's order, one store per row, no float atomic
+void launch_pot_pair(hipStream_t s, const PotPairArgs &a, const TransposedView &t);
+// x, q of the nt targets into xg [ntot][3], qg [ntot]; entries from nt on: the origin, no charge
+void launch_pot_gather(hipStream_t s, int nt, int ntot, const int *targets, const double *x, const double *q, double *xg, double *qg);
+struct PotFinishArgs {
+  int nt, slab, qsum;
+  const int *targets, *flags;            // [nt] owned rows; flags may be NULL with eta == 0
+  const double *x, *q, *u;               // u [nlocal]: the k-space potential by owned index
+  const double *four;                    // Q, Q2, M, M2 of the owned atoms (read under slab)
+  double eta, pi2vol, evs;               // 2 pi / V, qqr2e / qe2f
+  double *pot;                           // pot[i] = ((((pot[i] - u[i]) + eta self term) + z slabcorr) - qsum term) evs at the targets
+};
+void launch_pot_finish(hipStream_t s, const PotFinishArgs &a);
 // ---- bonded forces of bond_style / angle_style harmonic (conp_bonded.hip) ----
 constexpr int BONDED_BLOCK = 256;        // threads of a workgroup: one per term (term kernel), one per atom (gather kernel)
 constexpr int BONDED_FINISH = 256;       // threads of the finishing workgroup: rows r, r + 256, ... per thread

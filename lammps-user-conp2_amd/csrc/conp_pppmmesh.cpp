@@ -50,6 +50,7 @@ void PppmMesh::b(int nl, const int *eidx, const double *ex, const double *eq, in
     d_bk.zero(ctx.stream);
   ++elyte_spreads;
   elyte_valid = keep && rank0;
+  dev_u_valid = false;             // (the update's mesh pass went through d_pp_re)
   ctx.prof.end(ctx.stream);
 }
 
@@ -120,7 +121,7 @@ void PppmMesh::spread_charged(const conp_atoms *at, const int *d_list, int n, co
   } else
     density(n, d_list, dx, dq, d_pp_re.p);
   ++elyte_spreads;
-  u_valid = false;                 // (d_pp_re holds a density now)
+  u_valid = dev_u_valid = false;   // (d_pp_re holds a density now)
 }
 
 void PppmMesh::total_potential(const conp_atoms *at, const double *dx, const double *dq) {
@@ -171,7 +172,7 @@ void PppmMesh::make_rho(const conp_atoms *at, const double *dx, const double *dq
       density(n, d_idx0.p, dx, dq, d_pp_re.p);
     }
     ++elyte_spreads;
-    u_valid = false;                                        // (d_pp_re holds a density now)
+    u_valid = dev_u_valid = false;                          // (d_pp_re holds a density now)
     HIP_TRY(hipMemcpyAsync(l.data(), d_pp_re.p, nf * sizeof(double), hipMemcpyDeviceToHost, ctx.stream));
   }
   ctx.sync();
@@ -270,17 +271,19 @@ void PppmMesh::forces(const conp_atoms *at, const double *dx, const double *dq, 
 // ---- device-resident k-space forces ----
 // forces on the caller's device arrays: the brick of the n owned atoms through the identity list, the mesh solve, the gather on
 // every owned atom; the seven sums stay on the device (kspace_finish_kernel reads them).  dvatom: [n][6], overwritten.
+void PppmMesh::identity_list(int n) {
+  if (iota_n >= n) return;
+  std::vector<int> iota(n);
+  for (int i = 0; i < n; ++i) iota[i] = i;
+  d_pp_iota.upload(iota, ctx.stream);
+  ctx.sync();                        // (iota goes out of scope)
+  iota_n = n;
+}
 void PppmMesh::forces_device(int n, const double *dx, const double *dq, double *df, double *dev, double *deatom, double *dvatom) {
   const Geom gm = geometry();
   if (n <= 0) { if (dev) HIP_TRY(hipMemsetAsync(dev, 0, 7 * sizeof(double), ctx.stream)); return; }
-  if (iota_n < n) {
-    std::vector<int> iota(n);
-    for (int i = 0; i < n; ++i) iota[i] = i;
-    d_pp_iota.upload(iota, ctx.stream);
-    ctx.sync();                      // (iota goes out of scope)
-    iota_n = n;
-  }
-  u_valid = false;                   // d_pp_re is overwritten from here on
+  identity_list(n);
+  u_valid = dev_u_valid = false;     // d_pp_re is overwritten from here on
   density(n, d_pp_iota.p, dx, dq, d_pp_re.p);
   ++elyte_spreads;
   kspace_four_sums(ctx, d_kf_sums, n, dx, dq);
@@ -292,6 +295,22 @@ void PppmMesh::forces_device(int n, const double *dx, const double *dq, double *
   if (per_atom)
     launch_pppm_force_gather_device(ctx.stream, dpppm, n, dx, dq, fields ? d_pp_ex.p : nullptr, d_pp_ey.p, d_pp_im.p, d_pp_re.p,
                                     kspace_out_args(env, gm.V, gm.L, nullptr), d_kf_sums.p, df, deatom);
+  HIP_TRY(hipGetLastError());
+  dev_u_valid = per_atom;            // u of (dx, dq) is back in d_pp_re: potential_device may reuse it
+}
+// ---- compute potential/atom on the device ----
+// total_potential + probe on the caller's device arrays: the brick of the n owned atoms through the identity list (a zero charge
+// spreads zeros), the Poisson solve, the stencil gather at the targets, written by owned index.
+void PppmMesh::potential_device(int n, const double *dx, const double *dq, int nt, const int *d_targets, bool reuse, double self_coef,
+                                double *d_u) {
+  if (!reuse) {
+    identity_list(n);
+    u_valid = dev_u_valid = false;   // d_pp_re is overwritten from here on (a kept electrolyte brick is not: as in forces_device)
+    density(n, d_pp_iota.p, dx, dq, d_pp_re.p);
+    ++elyte_spreads;
+    launch_pppm_poisson(ctx.stream, dpppm, d_pp_re.p, d_pp_im.p); im_clean = false;
+  }
+  if (nt > 0) launch_pppm_probe(ctx.stream, dpppm, nt, d_targets, dx, dq, d_pp_re.p, self_coef, d_u);
   HIP_TRY(hipGetLastError());
 }
 

@@ -25,10 +25,12 @@ struct PppmMesh {
   // PPPM::make_rho asked for the electrolyte brick of every b_cal (conp_pppm_keep_density); elyte_valid -- d_pp_elyte holds the
   // brick of the LAST b_cal and nothing has moved since; u_valid -- d_pp_re holds the mesh potential of the total density
   // (total_potential and forces leave it), so probe only gathers from it.  Otherwise d_pp_re holds a density or nothing usable.
-  bool keep = false, elyte_valid = false, u_valid = false;
+  // dev_u_valid -- d_pp_re holds the mesh potential forces_device left (called with d_f or d_eatom), which potential_device may
+  // reuse; dropped with the other caches and by every other writer of d_pp_re.
+  bool keep = false, elyte_valid = false, u_valid = false, dev_u_valid = false;
   int elyte_spreads = 0;            // how often the electrolyte atoms were spread onto the mesh (b and the density queries)
   // positions / charges may have changed (an update, a re-neighbour): the caches are this step's or nobody's
-  void invalidate() { elyte_valid = u_valid = false; }
+  void invalidate() { elyte_valid = u_valid = dev_u_valid = false; }
   void keep_density(bool on) { keep = on; invalidate(); }
 
   // The update's entry (pppm_conp.cpp:269-316): the k-space b of the ne electrode atoms from the nl electrolyte atoms eidx of
@@ -47,6 +49,9 @@ struct PppmMesh {
   void forces(const conp_atoms *at, const double *dx, const double *dq, double *fout, double *energy, double *virial, double *eatom,
               double *vatom);
   void forces_device(int n, const double *dx, const double *dq, double *df, double *dev, double *deatom, double *dvatom);
+  // d_u[t] = the mesh potential at the nt owned targets d_targets (device, ascending) of the n owned atoms (dx, dq) minus
+  // self_coef q_t; reuse: from the brick as forces_device left it (dev_u_valid), else density and mesh solve first.  Enqueues only.
+  void potential_device(int n, const double *dx, const double *dq, int nt, const int *d_targets, bool reuse, double self_coef, double *d_u);
 
  private:
   PppmPlan pppm;
@@ -67,6 +72,7 @@ struct PppmMesh {
   struct Gather { int n[3], first[3]; };
   Gather gather_all(const conp_atoms *at);
   int list(const conp_atoms *at, int kind, dev::DevBuf<int> &d_idx);
+  void identity_list(int n);                   // d_pp_iota's first n entries are 0, 1, 2, ... afterwards
   void density(int n, const int *d_list, const double *dx, const double *dq, double *rho);
   struct Geom { double L, V, uk[3]; };         // the mesh's box: L = the slab-extended z period, V, the unit wave vectors
   Geom geometry() const;
