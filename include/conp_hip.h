@@ -878,6 +878,91 @@ int conp_bonded_compute_device(conp_fix *fix, const double *d_x /*[nall][3]*/, d
                                double *d_ev /*[8] ebond, eangle, virial xx,yy,zz,xy,xz,yz; overwritten*/,
                                double *d_eatom /*[nall]*/, double *d_vatom /*[nall][6]*/);
 
+/* ---- torsional forces: `dihedral_style opls | harmonic` and `improper_style harmonic | cvff` on the device --
+ * What an all-atom force field (OPLS-AA, CL&P, ...) adds to the bonds and angles above.  The 1-4 pair scaling of such a force field
+ * is the pair list's business: it travels in the special bits of the pair entries (special_lj / special_coul) and is not touched
+ * here.  A sibling of the conp_bonded_* entries with the same contract; this text is the definition, one geometry for all four
+ * styles.  All arithmetic is double, in the order written (sums and products left to right), no contraction.
+ * newton = newton_bond of conp_dihedral_set_params; nlocal, nall, prd those of conp_dihedral_set_lists.
+ * Term (i1, i2, i3, i4, t), of either list.  Images by the closest-image rule of the bonded block above, bit for bit:
+ *   x1' the closest image of x1 seen from x2;  x3' that of x3 seen from x2;  x4' that of x4 seen from x3'.
+ *   F = x1' - x2;  G = x2 - x3';  H = x4' - x3'
+ *   A = F x G = (Fy Gz - Fz Gy, Fz Gx - Fx Gz, Fx Gy - Fy Gx);  B = H x G likewise;  C = B x A likewise
+ *   A2 = Ax Ax + Ay Ay + Az Az;  B2 = B . B;  g = sqrt(G . G)          (every dot product: x + y, then + z)
+ *   Degenerate term, A2 == 0 or B2 == 0 or g == 0 (collinear members): the term contributes exactly nothing -- its forces, its
+ *   energy and its virial are 0.0.
+ *   phi = atan2((C . G) / g, A . B)                      trans is pi, cis is 0: LAMMPS' convention for these styles
+ *   Gradient of phi:  ga = g / A2;  gb = g / B2;  sa = (F . G) / (A2 g);  sb = (H . G) / (B2 g)
+ *     d1 = -(ga A);  d4 = gb B;  s = sa A - sb B;  d3 = (-d4) - s;  (d2 = (-d1) + s is not formed)
+ *   With the style's energy e(phi) and derivative de(phi) below and p = -de:
+ *     f1 = p d1;  f3 = p d3;  f4 = p d4;  f2 = -((f1 + f3) + f4)
+ *     f[i_m] += f_m  if newton or i_m < nlocal
+ *     v = six(F, f1) + six(-G, f3) + six(H - G, f4),  six(u, w) = (ux wx, uy wy, uz wz, ux wy, ux wz, uy wz): the form of
+ *     Dihedral::ev_tally, sum over the members of (x_m - x_2) (x) f_m
+ *   Tally: with newton e and v are counted whole, else 0.25 e and 0.25 v once per owned member.  eatom gets 0.25 e and vatom 0.25 v
+ *   per member, each under the force's condition.  Hence with newton sum eatom = edihedral + eimproper and sum vatom = virial.
+ * This formulation has no 1 / sin(phi) and needs no clamp; it is exact to rounding through phi = 0 and phi = pi.
+ * Styles (the coefficient rows are [4] per type, row 0 unused):
+ *   dihedral opls, K1 K2 K3 K4 as dihedral_coeff gives them (the halves are applied here); s_k = sin(k phi), c_k = cos(k phi) with
+ *     the argument formed as (double)k * phi:
+ *     e  = 0.5 (K1 (1 + c_1) + K2 (1 - c_2) + K3 (1 + c_3) + K4 (1 - c_4))
+ *     de = 0.5 (2 (K2 s_2) - K1 s_1 - 3 (K3 s_3) + 4 (K4 s_4))
+ *   dihedral harmonic and improper cvff, K d n (d = +1 or -1, n an integer):  a = n phi
+ *     e = K (1 + d cos(a));  de = -(K d n sin(a))
+ *   improper harmonic, K chi0 (chi0 in RADIANS):  u = fabs(phi) - chi0
+ *     e = K u u;  de = 2 K (phi - copysign(chi0, phi))         LAMMPS' acos(c) - chi0, smooth through the planar minimum
+ * n: 0..6 for cvff (LAMMPS' range); 0..CONP_DIHEDRAL_MAX_N for dihedral harmonic.
+ * The two ways to hand over lists are those of the bonded block: neighbor->dihedrallist / improperlist with ghost indices and
+ * prd = {0, 0, 0} at every re-neighbour, or owned indices and the box lengths once.
+ * Order and reproducibility: no output meets an atomic.  conp_dihedral_set_lists builds a per-atom table of the (term, role) slots
+ * an atom takes part in, dihedrals first in list order, then impropers in list order, the roles of a term in member order; an atom's
+ * contributions to f, eatom and vatom are summed from 0.0 by one thread in that order and added to f once; energy and virial are
+ * added over terms in a fixed order.  Every output is a pure function of the input: byte-identical from call to call and between
+ * the host and the device entry.  Rows of atoms in no term (or, with newton off, of ghosts): f is untouched bit for bit, eatom /
+ * vatom are exactly 0.0.
+ * Order: conp_dihedral_set_params (once per run, or after dihedral_coeff / improper_coeff changes) -> conp_dihedral_set_lists -> the
+ * compute entries.  CONP_ERR_STATE: a compute entry before set_params or set_lists; set_lists before set_params.
+ * conp_dihedral_set_params after conp_dihedral_set_lists DROPS the lists (they were checked against the old tables): set them again.
+ * CONP_ERR_ARG: a NULL struct; a NULL array with a positive count; a negative count; nlocal > nall; an index outside [0, nall); a
+ * type outside [1, ntypes]; an unknown style; a positive type count or a non-empty list for a style that is 0; a coefficient that
+ * is not finite; d other than +1 or -1; n not an integer or outside its range above; a negative or non-finite prd; NULL d_x /
+ * atoms; atoms->nlocal + nghost != nall.  A refused conp_dihedral_set_lists leaves the handle without lists; a refused
+ * conp_dihedral_set_params leaves tables and lists as they were.  All outputs NULL: CONP_OK, nothing done.  Empty lists: the
+ * outputs are zeroed, f is untouched.
+ * The entries need nothing of the fix but its stream: they work from conp_fix_create on, on Ewald and `pppm` handles, and they are
+ * rank-local, never collective (decomposed handles are allowed).
+ * Device entry: everything is enqueued on the handle's stream; conp_dihedral_set_lists reserves all scratch, so a compute call
+ * makes no device allocation, no copy to the host and no synchronisation.  A device step: ... -> conp_pair_compute_device ->
+ * conp_bonded_compute_device -> conp_dihedral_compute_device -> conp_fix_post_force_device -> conp_ghost_fold_device.
+ * Host entry: stages atoms->x (only x is read), is synchronous and adds into f.
+ * Out of scope: dihedral charmm (its 1-4 weights), multi/harmonic, fourier, class2, hybrid; SHAKE flag 4. */
+#define CONP_DIHEDRAL_MAX_N 12          /* the largest multiplicity n of `dihedral_style harmonic` */
+typedef struct {
+  int dihedral_style;                   /* 0 none, 1 opls, 2 harmonic */
+  int ndihedraltypes;                   /* 0 with style 0 */
+  const double *dihedral_coef;          /* [ndihedraltypes + 1][4], row 0 unused: opls K1 K2 K3 K4; harmonic K, d, n, 0 */
+  int improper_style;                   /* 0 none, 1 harmonic, 2 cvff */
+  int nimpropertypes;                   /* 0 with style 0 */
+  const double *improper_coef;          /* [nimpropertypes + 1][4], row 0 unused: harmonic K, chi0 (RADIANS), 0, 0; cvff K, d, n, 0 */
+  int newton_bond;                      /* force->newton_bond */
+} conp_dihedral_params;
+
+typedef struct {
+  int nlocal, nall;                     /* every index below is < nall; i < nlocal is an owned atom */
+  int ndihedral; const int *dihedral;   /* [ndihedral][5] i1, i2, i3, i4, type  -- neighbor->dihedrallist */
+  int nimproper; const int *improper;   /* [nimproper][5] i1, i2, i3, i4, type  -- neighbor->improperlist */
+  double prd[3];                        /* as conp_bonded_lists */
+} conp_dihedral_lists;
+
+int conp_dihedral_set_params(conp_fix *fix, const conp_dihedral_params *p);   /* copied */
+int conp_dihedral_set_lists(conp_fix *fix, const conp_dihedral_lists *l);     /* host arrays, copied and uploaded; may allocate and synchronise */
+int conp_dihedral_compute(conp_fix *fix, const conp_atoms *atoms, double *f /*[nall][3] accumulated*/,
+                          double *eng /*[2] edihedral, eimproper*/, double *virial /*[6]*/, double *eatom /*[nall] overwritten*/,
+                          double *vatom /*[nall][6] overwritten*/);
+int conp_dihedral_compute_device(conp_fix *fix, const double *d_x /*[nall][3]*/, double *d_f /*[nall][3] accumulated*/,
+                                 double *d_ev /*[8] edihedral, eimproper, virial xx,yy,zz,xy,xz,yz; overwritten*/,
+                                 double *d_eatom /*[nall]*/, double *d_vatom /*[nall][6]*/);
+
 /* ---- time integration: `fix nve` and `fix nvt` on the device ------------------------------------------------
  * Velocity Verlet with one Nose-Hoover chain per thermostatted group: LAMMPS' FixNH / FixNVE / ComputeTemp @ 27May2021 at the
  * reference decks' keywords (`fix ID group nvt temp Tstart Tstop Tdamp`: tchain 3, tloop 1, drag 0, no barostat, per-type masses, no

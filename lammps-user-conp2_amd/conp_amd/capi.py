@@ -141,6 +141,17 @@ class conp_bonded_lists(C.Structure):
                 ("angle", C.POINTER(C.c_int)), ("prd", C.c_double * 3)]
 
 
+class conp_dihedral_params(C.Structure):
+    _fields_ = [("dihedral_style", C.c_int), ("ndihedraltypes", C.c_int), ("dihedral_coef", C.POINTER(C.c_double)),
+                ("improper_style", C.c_int), ("nimpropertypes", C.c_int), ("improper_coef", C.POINTER(C.c_double)),
+                ("newton_bond", C.c_int)]
+
+
+class conp_dihedral_lists(C.Structure):
+    _fields_ = [("nlocal", C.c_int), ("nall", C.c_int), ("ndihedral", C.c_int), ("dihedral", C.POINTER(C.c_int)),
+                ("nimproper", C.c_int), ("improper", C.POINTER(C.c_int)), ("prd", C.c_double * 3)]
+
+
 class conp_info(C.Structure):
     _fields_ = [("elenum", C.c_int), ("elenum_all", C.c_int), ("elytenum", C.c_int), ("maxtag_all", C.c_int),
                 ("runstage", C.c_int), ("kcount", C.c_int), ("kcount_flat", C.c_int), ("kcount_expand", C.c_int),
@@ -185,6 +196,7 @@ SYMBOLS = [
     "conp_fix_post_neighbor_device", "conp_fix_get_step_tables",
     "conp_fix_post_force_device",
     "conp_bonded_set_params", "conp_bonded_set_lists", "conp_bonded_compute", "conp_bonded_compute_device",
+    "conp_dihedral_set_params", "conp_dihedral_set_lists", "conp_dihedral_compute", "conp_dihedral_compute_device",
     "conp_integrate_set_params", "conp_integrate_setup_device", "conp_integrate_initial_device", "conp_integrate_final_device",
     "conp_integrate_temperature_device", "conp_integrate_get_state", "conp_integrate_set_state",
     "conp_shake_set_params", "conp_shake_correct_device", "conp_shake_setup_device", "conp_shake_post_force_device",
@@ -379,6 +391,11 @@ def load_library():
         lib.conp_bonded_set_lists.argtypes = [vp, C.POINTER(conp_bonded_lists)]
         lib.conp_bonded_compute.argtypes = [vp, C.POINTER(conp_atoms), dp, dp, dp, dp, dp]
         lib.conp_bonded_compute_device.argtypes = [vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "conp_dihedral_compute"):
+        lib.conp_dihedral_set_params.argtypes = [vp, C.POINTER(conp_dihedral_params)]
+        lib.conp_dihedral_set_lists.argtypes = [vp, C.POINTER(conp_dihedral_lists)]
+        lib.conp_dihedral_compute.argtypes = [vp, C.POINTER(conp_atoms), dp, dp, dp, dp, dp]
+        lib.conp_dihedral_compute_device.argtypes = [vp, vp, vp, vp, vp, vp]
     if hasattr(lib, "conp_integrate_set_params"):
         lib.conp_integrate_set_params.argtypes = [vp, C.POINTER(conp_integrate_params)]
         lib.conp_integrate_setup_device.argtypes = [vp, vp, dp]
@@ -1150,6 +1167,59 @@ class FixConp:
         is added to, d_ev [8] (ebond, eangle, virial xx, yy, zz, xy, xz, yz), d_eatom [nall], d_vatom [nall][6] are overwritten"""
         self._check(self.lib.conp_bonded_compute_device(self.h, C.c_void_p(d_x), C.c_void_p(d_f), C.c_void_p(d_ev),
                                                         C.c_void_p(d_eatom), C.c_void_p(d_vatom)))
+
+    # -- dihedrals (opls, harmonic) and impropers (harmonic, cvff): set_params -> set_lists -> compute / compute_device (section 28) --
+    DIHEDRAL_STYLES = {None: 0, "none": 0, "opls": 1, "harmonic": 2}
+    IMPROPER_STYLES = {None: 0, "none": 0, "harmonic": 1, "cvff": 2}
+
+    def dihedral_set_params(self, dihedral_style=None, dihedral_coef=(), improper_style=None, improper_coef=(), newton_bond=True):
+        """conp_dihedral_set_params: styles by name (None: no such terms); the coefficient rows WITHOUT the unused row 0 and without
+        the padding to four columns (dihedral type t reads dihedral_coef[t - 1]): opls K1 K2 K3 K4, harmonic and cvff K d n, improper
+        harmonic K chi0 in radians; copied by the library.  Drops the handle's dihedral lists"""
+        def tab(rows):
+            r = np.asarray(rows, dtype=np.float64)
+            r = r.reshape(-1, r.shape[-1] if r.ndim == 2 else 4)
+            t = np.zeros((len(r) + 1, 4))
+            t[1:, :r.shape[1]] = r
+            return np.ascontiguousarray(t)
+        dc, ic = tab(dihedral_coef), tab(improper_coef)
+        p = conp_dihedral_params(dihedral_style=self.DIHEDRAL_STYLES[dihedral_style], ndihedraltypes=len(dc) - 1, dihedral_coef=_dptr(dc),
+                                 improper_style=self.IMPROPER_STYLES[improper_style], nimpropertypes=len(ic) - 1, improper_coef=_dptr(ic),
+                                 newton_bond=int(newton_bond))
+        self._check(self.lib.conp_dihedral_set_params(self.h, C.byref(p)))
+
+    def dihedral_set_lists(self, nlocal, nall, dihedrals=None, impropers=None, prd=(0.0, 0.0, 0.0)):
+        """conp_dihedral_set_lists: dihedrals and impropers [n][5] (i1, i2, i3, i4, type), local indices below nall; prd > 0: closest
+        image along that dimension.  Copied and uploaded; may allocate and synchronise"""
+        d = np.ascontiguousarray(np.zeros((0, 5)) if dihedrals is None else dihedrals, dtype=np.int32).reshape(-1, 5)
+        i = np.ascontiguousarray(np.zeros((0, 5)) if impropers is None else impropers, dtype=np.int32).reshape(-1, 5)
+        l = conp_dihedral_lists(nlocal=int(nlocal), nall=int(nall), ndihedral=d.shape[0], dihedral=_iptr(d) if d.size else None,
+                                nimproper=i.shape[0], improper=_iptr(i) if i.size else None, prd=(C.c_double * 3)(*prd))
+        self._check(self.lib.conp_dihedral_set_lists(self.h, C.byref(l)))
+
+    def dihedral_compute(self, at, forces=True, eng=True, virial=True, eatom=True, vatom=True, f=None):
+        """conp_dihedral_compute on host arrays (only at.x is read) -> (f [nall][3] (added to `f`, zeros by default), eng [2] =
+        edihedral, eimproper, W [6], eatom [nall], vatom [nall][6]); what was not asked for is None"""
+        n = at.nlocal + at.nghost
+        if forces:
+            f = np.zeros((n, 3)) if f is None else f
+            assert f.dtype == np.float64 and f.flags.c_contiguous and f.shape == (n, 3)
+        else:
+            f = None
+        e2 = np.full(2, np.nan) if eng else None
+        w = np.full(6, np.nan) if virial else None
+        ea = np.full(n, np.nan) if eatom else None
+        va = np.full((n, 6), np.nan) if vatom else None
+        ptr = lambda a: _dptr(a) if a is not None else None
+        self._check(self.lib.conp_dihedral_compute(self.h, C.byref(self.atoms_view(at)), ptr(f), ptr(e2), ptr(w), ptr(ea), ptr(va)))
+        return f, e2, w, ea, va
+
+    def dihedral_compute_device(self, d_x: int, d_f: int = 0, d_ev: int = 0, d_eatom: int = 0, d_vatom: int = 0):
+        """conp_dihedral_compute_device: raw device pointers (0 = NULL), enqueued on the handle's stream, no synchronisation; d_f
+        [nall][3] is added to, d_ev [8] (edihedral, eimproper, virial xx, yy, zz, xy, xz, yz), d_eatom [nall], d_vatom [nall][6] are
+        overwritten"""
+        self._check(self.lib.conp_dihedral_compute_device(self.h, C.c_void_p(d_x), C.c_void_p(d_f), C.c_void_p(d_ev),
+                                                          C.c_void_p(d_eatom), C.c_void_p(d_vatom)))
 
     # -- SHAKE constraints: set_params -> correct_device at a run's start, setup_device, post_force_device per step (section 23) ------
     def shake_set_params(self, type, mass, bond_distance, angle_distance, cluster, tolerance, max_iter, dt, ftm2v, prd=(0.0, 0.0, 0.0)):

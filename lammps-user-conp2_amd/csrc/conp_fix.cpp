@@ -25,6 +25,7 @@
 #include "conp_pairstyle.hpp"
 #include "conp_transpose.hpp"
 #include "conp_bondedstyle.hpp"
+#include "conp_dihedralstyle.hpp"
 #include "conp_integrator.hpp"
 #include "conp_shakestyle.hpp"
 #include "conp_fieldstyle.hpp"
@@ -2394,7 +2395,7 @@ struct conp_fix : DevCtx {
   }
 
   // ---- the pair style with its half list (conp_pairstyle.cpp, DESIGN.md sections 16, 17), the ghost map (conp_ghostmap.cpp, 18),
-  // the harmonic bonds and angles (conp_bondedstyle.cpp, 21), the integrator (conp_integrator.cpp, 22), the constraints (conp_shakestyle.cpp, 23),
+  // the harmonic bonds and angles (conp_bondedstyle.cpp, 21), the dihedrals and impropers (conp_dihedralstyle.cpp, 28), the integrator (conp_integrator.cpp, 22), the constraints (conp_shakestyle.cpp, 23),
   // the field and the per-group sums (conp_fieldstyle.cpp, 24), the z mirror (conp_zmirrorstyle.cpp, 25), compute potential/atom (conp_potatomstyle.cpp, 27), the exact-Ewald query entries (conp_ewaldquery.cpp, sections 11, 12,
   // 14, 15) and the PPPM mesh with the update's b and its query entries (conp_pppmmesh.cpp, sections 8, 13, 14, 15) ----
   PairStyle pair{*this};
@@ -2405,6 +2406,7 @@ struct conp_fix : DevCtx {
   bool pair_tr_valid() const { return pair_tr.valid && pair.have_list && pair_tr_gen == pair.list_gen; }
   GhostMap ghost{*this};
   BondedStyle bonded{*this};
+  DihedralStyle dihedral{*this};
   Integrator integ{*this};
   ShakeStyle shake{*this};
   FieldStyle field{*this};
@@ -3856,6 +3858,52 @@ int conp_bonded_compute_device(conp_fix *f, const double *d_x, double *d_f, doub
   if (!d_f && !d_ev && !d_eatom && !d_vatom) return CONP_OK;
   f->drop_graph();
   f->bonded.enqueue(d_x, d_f, d_ev, d_eatom, d_vatom);
+  CONP_GUARD_END
+}
+
+// ---- dihedrals and impropers: set_params -> set_lists -> compute / compute_device ------------------------
+int conp_dihedral_set_params(conp_fix *f, const conp_dihedral_params *p) {
+  CONP_GUARD_BEGIN
+  if (!f || !p) throw ConpError(CONP_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(f->env.device));
+  f->drop_graph();
+  f->dihedral.set_params(p);
+  CONP_GUARD_END
+}
+
+int conp_dihedral_set_lists(conp_fix *f, const conp_dihedral_lists *l) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->dihedral.have_lists = false;                  // a refused call leaves the handle without lists
+  if (!l) throw ConpError(CONP_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(f->env.device));
+  f->drop_graph();
+  f->dihedral.set_lists(l);
+  CONP_GUARD_END
+}
+
+int conp_dihedral_compute(conp_fix *f, const conp_atoms *at, double *fo, double *eng, double *virial, double *eatom, double *vatom) {
+  CONP_GUARD_BEGIN
+  if (!f || !at) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->dihedral.need_ready("conp_dihedral_compute");
+  if (at->nlocal < 0 || at->nghost < 0 || (int64_t)at->nlocal + at->nghost != f->dihedral.nall)
+    throw ConpError(CONP_ERR_ARG, "conp_dihedral_compute: nlocal + nghost differs from the nall of conp_dihedral_set_lists");
+  if (f->dihedral.nall > 0 && !at->x) throw ConpError(CONP_ERR_ARG, "conp_dihedral_compute: null atom array");
+  if (!fo && !eng && !virial && !eatom && !vatom) return CONP_OK;
+  HIP_TRY(hipSetDevice(f->env.device));
+  f->drop_graph();
+  f->dihedral.compute_host(at, fo, eng, virial, eatom, vatom);
+  CONP_GUARD_END
+}
+
+int conp_dihedral_compute_device(conp_fix *f, const double *d_x, double *d_f, double *d_ev, double *d_eatom, double *d_vatom) {
+  CONP_GUARD_BEGIN
+  if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
+  f->dihedral.need_ready("conp_dihedral_compute_device");
+  if (!d_x) throw ConpError(CONP_ERR_ARG, "conp_dihedral_compute_device: null d_x");
+  if (!d_f && !d_ev && !d_eatom && !d_vatom) return CONP_OK;
+  f->drop_graph();
+  f->dihedral.enqueue(d_x, d_f, d_ev, d_eatom, d_vatom);
   CONP_GUARD_END
 }
 

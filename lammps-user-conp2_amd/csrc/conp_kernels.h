@@ -447,6 +447,27 @@ struct BondedArgs {
 };
 // ev [8] = ebond, eangle, virial xx, yy, zz, xy, xz, yz (overwritten, summed in a fixed order), or NULL
 void launch_bonded(hipStream_t s, const BondedArgs &a, double *ev);
+// ---- dihedral_style opls / harmonic and improper_style harmonic / cvff (conp_dihedral.hip) ----
+constexpr int DIHEDRAL_BLOCK = 256;      // threads of a workgroup: one per term (term kernel), one per atom (gather kernel)
+constexpr int DIHEDRAL_FINISH = 256;     // threads of the finishing workgroup: rows r, r + 256, ... per thread
+constexpr int DIHEDRAL_TERM_W = 16;      // doubles per term record: f on member 1 [3], on 3 [3], on 4 [3], energy, v[6]: 128 bytes
+enum { DIHEDRAL_NONE = 0, DIHEDRAL_OPLS = 1, DIHEDRAL_HARMONIC = 2 };
+enum { IMPROPER_NONE = 0, IMPROPER_HARMONIC = 1, IMPROPER_CVFF = 2 };
+struct DihedralArgs {
+  int ndihedral, nimproper, nlocal, nall, newton;
+  int dstyle, istyle;                    // DIHEDRAL_*, IMPROPER_*
+  const int *dihedral, *improper;        // [ndihedral][5], [nimproper][5]: i1, i2, i3, i4, type
+  const double *dcoef, *icoef;           // [ntypes + 1][4]: opls K1 K2 K3 K4; harmonic / cvff K d n 0; improper harmonic K chi0 0 0
+  double prd[3];                         // > 0: closest image along that dimension
+  const double *x;                       // [nall][3]
+  double *term;                          // [ndihedral + nimproper][DIHEDRAL_TERM_W] scratch, 128-byte aligned: dihedrals first
+  double *part;                          // [ceil((ndihedral + nimproper) / DIHEDRAL_BLOCK)][8] scratch rows (needed with ev != NULL)
+  const int *slot_ptr, *slot;            // [nall + 1], [4 (ndihedral + nimproper)]: an atom's slots, term * 4 + role, in list order
+  double *f;                             // [nall][3] accumulated, or NULL
+  double *eatom, *vatom;                 // [nall], [nall][6] overwritten, or NULL
+};
+// ev [8] = edihedral, eimproper, virial xx, yy, zz, xy, xz, yz (overwritten, summed in a fixed order), or NULL
+void launch_dihedral(hipStream_t s, const DihedralArgs &a, double *ev);
 // ---- velocity Verlet and the Nose-Hoover chain (conp_integrate.hip) ----
 constexpr int INTEGRATE_BLOCK = 256;     // threads of a workgroup: one per atom
 constexpr int INTEGRATE_FINISH = 256;    // threads of the finishing workgroup: partial rows r, r + 256, ... per thread
