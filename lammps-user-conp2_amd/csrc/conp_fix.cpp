@@ -2,8 +2,6 @@
 // Method names mirror FixConp / KSpaceModuleEwald (fix_conp.h:37-74, kspacemodule.h:30-40); citations are
 // file:line in /root/reference.  There is no CPU fallback: every compute entry point needs the HIP device.
 #include <hip/hip_runtime.h>
-#include <dlfcn.h>
-#include <rccl/rccl.h>   // types and enums only: the entry points are resolved with dlopen when a communicator is asked for
 
 #include <algorithm>
 #include <cmath>
@@ -33,78 +31,9 @@
 #include "conp_potatomstyle.hpp"
 #include "conp_ewaldquery.hpp"
 #include "conp_pppmmesh.hpp"
+#include "conp_exchange.hpp"
 
 using namespace conp::dev;
-namespace {
-
-// ---- ranks: the host's conp_comm callbacks behind the RankOps interface of conp_host.hpp ----------------------------------
-struct RankComm : conp::RankOps {
-  conp_comm c{};
-  bool have = false;            // callbacks present: the atoms handed to the hooks are this rank's sub-domain
-  int rank_ = 0, nranks_ = 1;
-  int nranks() const override { return nranks_; }
-  int rank() const override { return rank_; }
-  bool active() const { return have && nranks_ > 1; }
-  static void check(int rc, const char *what) {
-    if (rc != 0) throw ConpError(CONP_ERR_STATE, std::string("conp_comm callback failed: ") + what);
-  }
-  void allreduce_max_int(int *v, int n) override { if (active()) check(c.allreduce_max_int(c.ctx, v, n), "allreduce_max_int"); }
-  void allgather_int(int v, int *out) override {
-    if (active()) check(c.allgather_int(c.ctx, v, out), "allgather_int"); else out[0] = v;
-  }
-  void allgatherv_int(const int *send, int n, int *recv, const int *counts, const int *displs) override {
-    if (!active()) { for (int i = 0; i < n; ++i) recv[i] = send[i]; return; }
-    std::vector<int64_t> cb(nranks_), db(nranks_);
-    for (int r = 0; r < nranks_; ++r) { cb[r] = (int64_t)counts[r] * sizeof(int); db[r] = (int64_t)displs[r] * sizeof(int); }
-    check(c.allgatherv(c.ctx, send, (int64_t)n * sizeof(int), recv, cb.data(), db.data()), "allgatherv");
-  }
-  void sum(double *b, int64_t n) override { if (active() && n > 0) check(c.allreduce_sum(c.ctx, b, n), "allreduce_sum"); }
-  void gatherv(const double *send, const std::vector<int> &items, int w, double *recv) override {
-    if (!active()) { std::memcpy(recv, send, (size_t)items[0] * w * sizeof(double)); return; }
-    std::vector<int64_t> cb(nranks_), db(nranks_);
-    int64_t off = 0;
-    for (int r = 0; r < nranks_; ++r) { cb[r] = (int64_t)items[r] * w * sizeof(double); db[r] = off; off += cb[r]; }
-    check(c.allgatherv(c.ctx, send, cb[rank_], recv, cb.data(), db.data()), "allgatherv");
-  }
-};
-
-// ---- RCCL, resolved at run time (the library stays loadable where no RCCL is installed; torch's bundled copy and the
-// system's share a soname, whichever the process loaded first serves both) -------------------------------------------------
-struct Rccl {
-  void *lib = nullptr;
-  ncclResult_t (*GetUniqueId)(ncclUniqueId *) = nullptr;
-  ncclResult_t (*CommInitRank)(ncclComm_t *, int, ncclUniqueId, int) = nullptr;
-  ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-  ncclResult_t (*AllReduce)(const void *, void *, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-  ncclResult_t (*AllGather)(const void *, void *, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
-  const char *(*GetErrorString)(ncclResult_t) = nullptr;
-  void load() {
-    if (lib) return;
-    for (const char *name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
-      lib = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
-      if (lib) break;
-    }
-    if (!lib) throw ConpError(CONP_ERR_NO_DEVICE, std::string("cannot load librccl: ") + dlerror());
-    auto sym = [&](const char *n) {
-      void *p = dlsym(lib, n);
-      if (!p) throw ConpError(CONP_ERR_NO_DEVICE, std::string("librccl lacks ") + n);
-      return p;
-    };
-    GetUniqueId = reinterpret_cast<decltype(GetUniqueId)>(sym("ncclGetUniqueId"));
-    CommInitRank = reinterpret_cast<decltype(CommInitRank)>(sym("ncclCommInitRank"));
-    CommDestroy = reinterpret_cast<decltype(CommDestroy)>(sym("ncclCommDestroy"));
-    AllReduce = reinterpret_cast<decltype(AllReduce)>(sym("ncclAllReduce"));
-    AllGather = reinterpret_cast<decltype(AllGather)>(sym("ncclAllGather"));
-    GetErrorString = reinterpret_cast<decltype(GetErrorString)>(sym("ncclGetErrorString"));
-  }
-  void ok(ncclResult_t r, const char *what) {
-    if (r != ncclSuccess) throw ConpError(CONP_ERR_NO_DEVICE, std::string("RCCL error in ") + what + ": " + (GetErrorString ? GetErrorString(r) : "?"));
-  }
-};
-Rccl g_rccl;   // plain pointers, no destructor: nothing of it runs at exit
-
-}  // namespace
-
 using namespace conp;
 
 struct conp_fix : DevCtx {
@@ -122,9 +51,7 @@ struct conp_fix : DevCtx {
   int ne_pad = 0, nl = 0, nl_pad = 0, nall = 0;
   int row0 = 0, row1 = 0, rows_per = 0, num_cus = 256;
   // several ranks: host callbacks (spatially decomposed atoms) and / or an RCCL communicator (device-resident collectives)
-  RankComm rc;
-  bool decomposed = false;       // conp_fix_set_comm was called: atoms and lists are this rank's sub-domain
-  ncclComm_t nccl = nullptr;
+  RankExchange xch{*this};
   bool s_sharded = false;        // the projected inverse is stored by rows [row0, row1) only (d_Srows)
   std::vector<int> elyte_counts;   // decomposed: charged electrolyte atoms per rank (gather layout of d_xg / d_qg)
   int nl_local = 0;
@@ -206,7 +133,7 @@ struct conp_fix : DevCtx {
                    1e6 * th[2] / th[5], 1e6 * th[3] / th[5], 1e6 * th[4] / th[5]);
     prof.collect();
     drop_graph();
-    if (nccl) { (void)hipStreamSynchronize(stream); (void)g_rccl.CommDestroy(nccl); nccl = nullptr; }
+    xch.destroy_rccl();      // here, not in xch's destructor: members go after this body, the stream in it
     if (pin_x || pin_q) { (void)hipStreamSynchronize(stream); if (pin_x) (void)hipHostUnregister(const_cast<double *>(pin_x)); if (pin_q) (void)hipHostUnregister(const_cast<double *>(pin_q)); }
     if (h_pin) { (void)hipStreamSynchronize(stream); (void)hipHostFree(h_pin); }
     if (h_np) { (void)hipStreamSynchronize(stream); (void)hipHostFree(h_np); }
@@ -396,11 +323,11 @@ struct conp_fix : DevCtx {
     if (args.pppm) pm.build(env);
     double qn[2] = {0.0, (double)at->nlocal};              // km_ewald.cpp:72-78: sum q^2 over the owned atoms, Allreduce :77
     for (int i = 0; i < at->nlocal; i++) qn[0] += at->q[i] * at->q[i];
-    rc.sum(qn, 2);                                         // (natoms = atom->natoms: the owned atoms of all ranks)
+    xch.cb.sum(qn, 2);                                         // (natoms = atom->natoms: the owned atoms of all ranks)
     km_conp_setup(qn[0], (int64_t)std::llround(qn[1]));
     evscale = env.qe2f / env.qqr2e;                        // :412
     ehgo_setup_tables();                                   // FixConp::init :296-299
-    idx.linalg_init(at->nlocal, at->tag, &rc);
+    idx.linalg_init(at->nlocal, at->tag, &xch.cb);
   }
 
   // ---- uploads of a re-neighbour.  A hipMemcpyAsync out of pageable memory blocks the caller per call (the runtime stages it and
@@ -543,7 +470,7 @@ struct conp_fix : DevCtx {
       ren_upload(d_bl_first, blist.first, (size_t)std::max(iown, 1), locked);
     }
     mark("list upload");
-    const bool grew = idx.post_neighbor(at->nlocal, at->tag, at->echeck, &elyte_grew, &rc);
+    const bool grew = idx.post_neighbor(at->nlocal, at->tag, at->echeck, &elyte_grew, &xch.cb);
     const int ne = idx.elenum_all;
     if (grew) {
       ne_pad = (ne + 127) / 128 * 128;
@@ -617,7 +544,7 @@ struct conp_fix : DevCtx {
   std::vector<int> zn_ch_lo, zn_ch_hi;      // per chunk of the ordered list: lowest / highest first tap relative to zn_c_start
   int zn_c_start = 0;
   int *zn_flag_host = nullptr, *zn_flag_dev = nullptr;      // a page-locked word the window kernel stores 1 into when a tap leaves its window
-  bool zn_eligible() const { return !decomposed && !args.pppm && nl >= zn_min_atoms && !path_on(CONP_PATH_SK_CLASSIC); }
+  bool zn_eligible() const { return !xch.decomposed && !args.pppm && nl >= zn_min_atoms && !path_on(CONP_PATH_SK_CLASSIC); }
   bool zn_use() const { return zn_listed && !zn_off && zn_eligible() && sk_projects() && nzc > 0; }
   // rough electrodes (no z classes; one rank): the same contraction, the ranges' raw windows -> rows on the z grid -> G (conp_zn.hip)
   bool zn_gen_use() const { return zn_listed && !zn_off && zn_eligible() && !sk_projects() && nzc == 0 && env.nranks <= 1 && zn_nrg > 0; }
@@ -645,7 +572,7 @@ struct conp_fix : DevCtx {
   // z-order the list (stable: atoms of one cell keep their list order) and cut it into ranges with a window origin each
   void zn_order_list(const conp_atoms *at) {
     zn_listed = false; zn_off = false;
-    if (getenv("CONP_TIME_REN")) std::fprintf(stderr, "  z-window: eligible %d (decomposed %d pppm %d nl %d) plan.nz %d\n", (int)zn_eligible(), (int)decomposed, args.pppm, nl, plan.nz);
+    if (getenv("CONP_TIME_REN")) std::fprintf(stderr, "  z-window: eligible %d (decomposed %d pppm %d nl %d) plan.nz %d\n", (int)zn_eligible(), (int)xch.decomposed, args.pppm, nl, plan.nz);
     if (!zn_eligible() || plan.nz <= 0) return;
     const int n = zn_grid_setup();
     const int nlist = (int)elyte_idx_h.size();
@@ -819,6 +746,13 @@ struct conp_fix : DevCtx {
     *zn_flag_host = 0;
     return raised;
   }
+  // ... and raised once the list stands again: the re-neighbouring itself is good
+  static void zn_raise_after_rebuild(bool overflowed) {
+    if (overflowed)
+      throw ConpError(CONP_ERR_NUMERIC, "a device-resident update's z-window overflowed before this re-neighbouring (an electrolyte atom drifted "
+                                        "more than 2.5 A in z): the charges of the updates since the previous list build are invalid; the list "
+                                        "is rebuilt at the new positions");
+  }
   // once per plan / z-class table: the window's Fourier transform (Gauss-Legendre quadrature on the host), the grid's phases, P
   void zn_ensure_tables() {
     if (zn_tables_current) return;
@@ -864,11 +798,11 @@ struct conp_fix : DevCtx {
     elyte_idx_h.clear();
     for (int i = 0; i < at->nlocal; ++i) if (at->echeck[i] == 0 && at->q[i] != 0) elyte_idx_h.push_back(i);
     nl_local = nl = (int)elyte_idx_h.size();
-    if (decomposed) {
+    if (xch.decomposed) {
       // every rank's charged electrolyte atoms enter every rank's structure factors: their (x, q) are all-gathered at each
       // update (b_cal) into d_xg / d_qg, rank-major; the phase kernel then walks that compact array
       elyte_counts.assign(env.nranks, 0);
-      rc.allgather_int(nl_local, elyte_counts.data());
+      xch.cb.allgather_int(nl_local, elyte_counts.data());
       nl = 0;
       for (int v : elyte_counts) nl += v;
       std::vector<int> iota(std::max(nl, 1));
@@ -953,7 +887,7 @@ struct conp_fix : DevCtx {
       ++k;
     }
     if (!stale && k != n) stale = 1;
-    rc.allreduce_max_int(&stale, 1);       // decomposed: the gather layout is common to all ranks, so is the decision
+    xch.cb.allreduce_max_int(&stale, 1);       // decomposed: the gather layout is common to all ranks, so is the decision
     return stale != 0;
   }
   // decomposed runs: this rank's charged electrolyte atoms -> everybody (MPI_Allgatherv), then onto the device
@@ -965,7 +899,7 @@ struct conp_fix : DevCtx {
       xq_pack[4 * (size_t)k + 2] = at->x[3 * (size_t)i + 2]; xq_pack[4 * (size_t)k + 3] = at->q[i];
     }
     xq_all.resize((size_t)std::max(nl, 1) * 4);
-    rc.gatherv(xq_pack.data(), elyte_counts, 4, xq_all.data());
+    xch.cb.gatherv(xq_pack.data(), elyte_counts, 4, xq_all.data());
     // de-interleave into the layouts the kernels read: x [nl][3], q [nl]
     double *st = pinned((size_t)ne_pad + 8 + (size_t)nl * 4) + ne_pad + 8;
     sync();
@@ -985,7 +919,7 @@ struct conp_fix : DevCtx {
   void ele_comm(const double *send /*[elenum][w]*/, int w, double *recv /*[Ne][w]*/) {
     const int ne = idx.elenum_all;
     ele_comm_buf.resize((size_t)std::max(ne, 1) * w);
-    rc.gatherv(send, idx.elenum_list, w, ele_comm_buf.data());
+    xch.cb.gatherv(send, idx.elenum_list, w, ele_comm_buf.data());
     for (int iall = 0; iall < ne; ++iall)
       for (int c = 0; c < w; ++c) recv[(size_t)idx.elebuf2eleall[iall] * w + c] = ele_comm_buf[(size_t)iall * w + c];
   }
@@ -1452,27 +1386,18 @@ struct conp_fix : DevCtx {
   }
 
   // km_ewald.cpp:147-151 + :584-666 : k-space part of A into d_A (strict lower triangle + diagonal + slab on j <= i)
-  // several ranks with a way to sum matrices (RCCL or the host callbacks): the tiles are dealt to the ranks
-  // (an RCCL communicator of ONE rank takes the same path: that is how the call sites are tested on a one-GPU box)
-  bool setup_sharded() const { return nccl != nullptr || (env.nranks > 1 && rc.active()); }
+  // several ranks with a way to sum matrices (xch.can_exchange()): the tiles are dealt to the ranks, and here is the
   // sum of the ranks' zero-initialised partial matrices (fix_conp.cpp:816-822 gathers rows instead; every element here is
   // written by one rank's k-space tile and at most one rank's real-space row, so the sum does not depend on the order)
   void allreduce_matrix(double *A, size_t n) {
-    if (!setup_sharded()) return;
-    if (nccl) {
-      g_rccl.ok(g_rccl.AllReduce(A, A, n, ncclDouble, ncclSum, nccl, stream), "all-reduce(A)");
-      return;
-    }
-    std::vector<double> h(n);
-    HIP_TRY(hipMemcpyAsync(h.data(), A, n * sizeof(double), hipMemcpyDeviceToHost, stream));
-    sync();
-    rc.sum(h.data(), (int64_t)n);
-    HIP_TRY(hipMemcpyAsync(A, h.data(), n * sizeof(double), hipMemcpyHostToDevice, stream));
-    sync();
+    if (!xch.can_exchange()) return;
+    std::vector<double> h(xch.has_comm() ? 0 : n);
+    xch.sum(A, n, h.data(), "all-reduce(A)");
+    if (!xch.has_comm()) sync();      // the upload reads h
   }
   void km_a_cal_device() {
     const int ne = idx.elenum_all;
-    const int trank = setup_sharded() ? env.rank : 0, tranks = setup_sharded() ? env.nranks : 1;
+    const int trank = xch.can_exchange() ? env.rank : 0, tranks = xch.can_exchange() ? env.nranks : 1;
     // planar electrodes (z classes, as in the projection's fast path): contraction over the planar rows only -- ~100x fewer flops.
     // CONP_A_GENERAL: comparison switch, always the (planar, kz) contraction.
     if (nzc > 0 && nzc <= 8 && !path_on(CONP_PATH_A_GENERAL)) {
@@ -1545,7 +1470,7 @@ struct conp_fix : DevCtx {
       d_diag_atom.upload(da, stream);
       diag_atom = d_diag_atom.p;
     }
-    const bool sharded = setup_sharded();
+    const bool sharded = xch.can_exchange();
     if (!sharded || env.rank == 0)         // diagonal and slab term once (they overwrite / add on the whole lower triangle)
       launch_a_diag_slab(stream, ne, diag_k, diag_self, diag_atom, kt.slabflag == 1, pref, d_ele_z.p, d_A.p);
     build_a_rows(alist, at->nlocal, at->tag, at->echeck, idx, env.newton_pair != 0, arows);
@@ -1555,7 +1480,7 @@ struct conp_fix : DevCtx {
     prof.begin("a_real", stream);
     // real-space rows: a sub-domain's list only holds the rows of its own electrode atoms (fix_conp.cpp:1242-1276); with
     // replicated atoms the rows are split by the row range
-    const bool by_range = sharded && !decomposed;
+    const bool by_range = sharded && !xch.decomposed;
     launch_a_real(stream, ne, by_range ? row0 : 0, by_range ? row1 : ne, d_a_rowptr.p, d_a_ele.p, d_a_oth.p, d_a_col.p, d_x.p,
                   d_type.p, real_params(), d_A.p);
     prof.end(stream);
@@ -1590,7 +1515,7 @@ struct conp_fix : DevCtx {
     std::fclose(fp);
     if (too_many) throw ConpError(CONP_ERR_IO, "Too many entries in A matrix file");        // :737
     if (count != need) throw ConpError(CONP_ERR_IO, "Too few entries in A matrix file");     // :746
-    try { idx.renumber_from_tags(tags, at->nlocal, at->tag, at->echeck, &rc); }
+    try { idx.renumber_from_tags(tags, at->nlocal, at->tag, at->echeck, &xch.cb); }
     catch (const std::exception &e) { throw ConpError(CONP_ERR_IO, e.what()); }
     upload_atoms_static(at);                                   // atom2eleall follows the new numbering
     build_b_rows_device(at, at->nlocal);                                   // rows follow the new numbering (the list is on the device)
@@ -1881,8 +1806,8 @@ struct conp_fix : DevCtx {
     const int ne = idx.elenum_all;
     pm.invalidate();                              // positions / charges may have changed: the mesh caches are this update's or nobody's
     ew.invalidate();                              // (so are the Ewald per-atom potentials)
-    const double *ex = decomposed ? d_xg.p : dx, *eq = decomposed ? d_qg.p : dq;
-    const int *eidx = decomposed ? d_iota.p : d_elyte_idx.p;
+    const double *ex = xch.decomposed ? d_xg.p : dx, *eq = xch.decomposed ? d_qg.p : dq;
+    const int *eidx = xch.decomposed ? d_iota.p : d_elyte_idx.p;
     if (!kspace_ready || !tables_current || d_b == nullptr)
       throw ConpError(CONP_ERR_STATE, "b_cal before the k tables / electrode phase tables exist (setup_post_neighbor, a_cal)");
     if (timed) {
@@ -1891,14 +1816,14 @@ struct conp_fix : DevCtx {
     }
     const int slab = (kt.slabflag && env.rank == 0) ? 1 : 0;
     // real-space rows: with replicated atoms this rank's row range; a sub-domain's list holds its own electrode atoms' rows only
-    const int rr0 = !coulyes ? 0 : (decomposed ? 0 : row0), rr1 = !coulyes ? 0 : (decomposed ? ne : row1);
+    const int rr0 = !coulyes ? 0 : (xch.decomposed ? 0 : row0), rr1 = !coulyes ? 0 : (xch.decomposed ? ne : row1);
     bool ride = false, use_fin = false, ride_hc = false;
     BRowArgs fin{}, pairs_keep{};
     if (args.pppm) {
       // `pppm` keyword: the k-space b comes from the mesh (pppm_conp.cpp:269-316); the mesh is not sharded -- rank 0 owns it
       // one rank: the real-space pair sums ride in the spread launch and the stencil gather completes the rows of b (slab term,
       // pair sums): no b_real_combine launch behind the mesh (round 4; CONP_TIME_SPLIT: as before)
-      const bool mesh_fin = env.nranks == 1 && !nccl && !decomposed && !(timed && time_split);
+      const bool mesh_fin = env.nranks == 1 && !xch.has_comm() && !xch.decomposed && !(timed && time_split);
       BRowArgs pairs = make_brow(ne, ne_pad, rr0, rr1, d_b_rowptr.p, d_b_ele.p, d_b_oth.p, dx, dq, d_type.p, real_params(), 0,
                                  nullptr, 0, nullptr, nullptr, 0, 0.0, nullptr, nullptr);
       fin = make_brow(ne, ne_pad, rr0, rr1, d_b_rowptr.p, d_b_ele.p, d_b_oth.p, dx, dq, d_type.p, real_params(), 1, d_bk.p, slab,
@@ -1918,7 +1843,7 @@ struct conp_fix : DevCtx {
       // A workgroup of this launch owns its CU (registers): the pair workgroups run on the CUs sk_gemm leaves free, in at most two
       // rounds of ~5 us -- shorter than the ~13 us the sk_gemm workgroups take
       const int nwg_sk = (int)seg_ptr_h.size() - 1;
-      const bool fuse_phase = ride && env.nranks == 1 && !nccl && !decomposed && nl_pad <= 4096 && max_seg_chunks <= 4 && n_slab_slots > 0 &&
+      const bool fuse_phase = ride && env.nranks == 1 && !xch.has_comm() && !xch.decomposed && nl_pad <= 4096 && max_seg_chunks <= 4 && n_slab_slots > 0 &&
                               nwg_sk < num_cus && (ne + 7) / 8 <= 2 * (num_cus - nwg_sk) && !no_phase_fuse;
       SkFuse fz;
       std::memset(&fz, 0, sizeof fz);           // (padding bytes too: the block is compared bytewise below)
@@ -2073,7 +1998,7 @@ struct conp_fix : DevCtx {
   // several ranks: after the setup only the rows [row0, row1) of S are ever read (fix_conp.cpp:1135-1139 does the same row-local
   // ddot_).  Keep those, release the Ne x Ne buffer: 2.1 GB -> 268 MB per rank at Ne = 16384 on 8 ranks.
   void shard_rows() {
-    if (s_sharded || !setup_sharded() || args.minimizer != CONP_SOLVER_INV || runstage < 3) return;
+    if (s_sharded || !xch.can_exchange() || args.minimizer != CONP_SOLVER_INV || runstage < 3) return;
     const size_t ne = idx.elenum_all, nr = (size_t)(row1 - row0);
     d_Srows.reserve(std::max<size_t>(nr * ne, 1));
     if (nr) HIP_TRY(hipMemcpyAsync(d_Srows.p, d_A.p + (size_t)row0 * ne, nr * ne * sizeof(double), hipMemcpyDeviceToDevice, stream));
@@ -2086,18 +2011,9 @@ struct conp_fix : DevCtx {
     if (!s_sharded) return;
     const size_t ne = idx.elenum_all, nr = (size_t)(row1 - row0);
     d_A.reserve(std::max<size_t>((size_t)rows_per * env.nranks, ne) * ne);
-    if (nccl) {
-      if (nr) HIP_TRY(hipMemcpyAsync(d_A.p + (size_t)env.rank * rows_per * ne, d_Srows.p, nr * ne * sizeof(double), hipMemcpyDeviceToDevice, stream));
-      g_rccl.ok(g_rccl.AllGather(d_A.p + (size_t)env.rank * rows_per * ne, d_A.p, (size_t)rows_per * ne, ncclDouble, nccl, stream), "all-gather(S)");
-    } else {
-      std::vector<double> mine(std::max<size_t>(nr * ne, 1)), all(ne * ne);
-      if (nr) HIP_TRY(hipMemcpyAsync(mine.data(), d_Srows.p, nr * ne * sizeof(double), hipMemcpyDeviceToHost, stream));
-      sync();
-      std::vector<int> rows(env.nranks);
-      for (int r = 0; r < env.nranks; ++r) rows[r] = std::min<int>((int)ne, (r + 1) * rows_per) - std::min<int>((int)ne, r * rows_per);
-      rc.gatherv(mine.data(), rows, (int)ne, all.data());
-      HIP_TRY(hipMemcpyAsync(d_A.p, all.data(), ne * ne * sizeof(double), hipMemcpyHostToDevice, stream));
-    }
+    if (nr) HIP_TRY(hipMemcpyAsync(d_A.p + (size_t)row0 * ne, d_Srows.p, nr * ne * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    std::vector<double> h(xch.callbacks_active() ? (ne + rows_per) * ne : 0);
+    xch.gather_rows(d_A.p, (int)ne, rows_per, (int)ne, h.data(), "all-gather(S)");
     sync();
     d_Srows.release();
     s_sharded = false;
@@ -2108,7 +2024,7 @@ struct conp_fix : DevCtx {
     const int ne = idx.elenum_all;
     if (args.minimizer == CONP_SOLVER_INV) {
       if (runstage < 3) throw ConpError(CONP_ERR_STATE, "solve before the inverse exists");
-      if (!s_sharded && setup_sharded()) shard_rows();          // first update after the setup
+      if (!s_sharded && xch.can_exchange()) shard_rows();          // first update after the setup
       prof.begin("gemv", stream);
       launch_gemv_rows(stream, ne, row0, row1, s_base(), d_b, d_eleallq);
       prof.end(stream);
@@ -2118,47 +2034,26 @@ struct conp_fix : DevCtx {
   }
 
   // ---- the two exchanges of an update: all-reduce(b), all-gather(q) ---------------------------------------------
-  // RCCL on the library's stream when a communicator exists (one rank per GPU), else the host's callbacks through the
-  // page-locked staging buffer (ranks that share a GPU, the LAMMPS glue's default).  MPI_Allgatherv + MPI_Allreduce of the
-  // reference: fix_conp.cpp:643 (b_comm of b and of q), :1356 (newtonbuf).
+  // xch's two primitives on the handle's vectors.  The callbacks stage through the page-locked buffer, whose layout is this
+  // handle's: results in the first ne_pad + 8 doubles, uploads behind them.
   void allreduce_b() {
-    if (env.nranks <= 1 && !nccl) return;
-    const int ne = idx.elenum_all;
+    if (env.nranks <= 1 && !xch.has_comm()) return;
     prof.begin("allreduce_b", stream);
-    if (nccl) g_rccl.ok(g_rccl.AllReduce(d_b, d_b, (size_t)ne, ncclDouble, ncclSum, nccl, stream), "all-reduce(b)");
-    else if (rc.active()) {
-      double *h = pinned((size_t)ne_pad + 8);
-      HIP_TRY(hipMemcpyAsync(h, d_b, ne * sizeof(double), hipMemcpyDeviceToHost, stream));
-      sync();
-      rc.sum(h, ne);
-      HIP_TRY(hipMemcpyAsync(d_b, h, ne * sizeof(double), hipMemcpyHostToDevice, stream));
-    } else throw ConpError(CONP_ERR_STATE, "an update on several ranks needs conp_fix_comm_init_rccl or conp_fix_set_comm (or do the "
-                                           "two collectives yourself between conp_fix_b_cal_device / _solve_device / _scatter_device)");
+    xch.sum(d_b, (size_t)idx.elenum_all, xch.callbacks_active() ? pinned((size_t)ne_pad + 8) : nullptr, "all-reduce(b)");
     prof.end(stream);
   }
   void allgather_q() {
-    if ((env.nranks <= 1 && !nccl) || args.minimizer != CONP_SOLVER_INV) return;    // CG solves all rows on every rank, like the reference
+    if ((env.nranks <= 1 && !xch.has_comm()) || args.minimizer != CONP_SOLVER_INV) return;    // CG solves all rows on every rank, like the reference
     const int ne = idx.elenum_all;
     prof.begin("allgather_q", stream);
-    if (nccl) {
-      double *mine = d_eleallq + (size_t)env.rank * rows_per;
-      g_rccl.ok(g_rccl.AllGather(mine, d_eleallq, (size_t)rows_per, ncclDouble, nccl, stream), "all-gather(q)");
-    } else if (rc.active()) {
-      double *h = pinned((size_t)ne_pad + 8 + (size_t)ne + rows_per) + ne_pad + 8;
-      const int nr = row1 - row0;
-      if (nr) HIP_TRY(hipMemcpyAsync(h + ne, d_eleallq + row0, nr * sizeof(double), hipMemcpyDeviceToHost, stream));
-      sync();
-      std::vector<int> rows(env.nranks);
-      for (int r = 0; r < env.nranks; ++r) rows[r] = std::min(ne, (r + 1) * rows_per) - std::min(ne, r * rows_per);
-      rc.gatherv(h + ne, rows, 1, h);
-      HIP_TRY(hipMemcpyAsync(d_eleallq, h, ne * sizeof(double), hipMemcpyHostToDevice, stream));
-    }
+    double *h = xch.callbacks_active() ? pinned((size_t)ne_pad + 8 + (size_t)ne + rows_per) + ne_pad + 8 : nullptr;
+    xch.gather_rows(d_eleallq, ne, rows_per, 1, h, "all-gather(q)");
     prof.end(stream);
   }
 
   // plain `fix conp` on one rank with the inverse solver: GEMV and charge write in one launch (gemv_finish_kernel)
   bool can_fuse_solve() const {
-    return args.minimizer == CONP_SOLVER_INV && !args.conq && !args.cond && env.nranks == 1 && !nccl && !s_sharded &&
+    return args.minimizer == CONP_SOLVER_INV && !args.conq && !args.cond && env.nranks == 1 && !xch.has_comm() && !s_sharded &&
            runstage >= 3;
   }
   // The projected inverse as a symmetric matrix (conp_kernels.hip "GEMV ... as a SYMMETRIC matrix"): from 2048 electrode atoms up
@@ -2359,7 +2254,7 @@ struct conp_fix : DevCtx {
     // the correction only acts where the Gaussians overlap (eta^2 r^2 < 5.8, r < 1.2 A at eta = 1.979): in a normal MD step no
     // pair is that close, the force array on the device is still all zero and is not brought over
     pf_f_dirty = acc[8] > 0.0;
-    if (decomposed) rc.sum(acc + 7, 1);            // MPI_Allreduce of the electrode sum q^2 (fix_conp.cpp:1176, :1193)
+    if (xch.decomposed) xch.cb.sum(acc + 7, 1);            // MPI_Allreduce of the electrode sum q^2 (fix_conp.cpp:1176, :1193)
     if (pf_f_dirty) {
       double *fh = acc - nf;
       HIP_TRY(hipMemcpyAsync(fh, d_f.p, nf * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -2379,8 +2274,7 @@ struct conp_fix : DevCtx {
   DevBuf<double> d_pfd_part;
   void post_force_device(const double *dx, const double *dq, double *df, double *dout) {
     if (!dx || !dq) throw ConpError(CONP_ERR_ARG, "null argument");
-    if (decomposed) throw ConpError(CONP_ERR_STATE, "device-resident updates take replicated atoms (conp_env.rank / nranks); "
-                                                    "spatially decomposed runs use the host-buffer hooks");
+    xch.need_replicated();
     if (runstage < 2 || !idx.initialised || nlocal_cur <= 0 || nall <= 0) throw ConpError(CONP_ERR_STATE, "post_force before setup");
     drop_graph();
     if (!df && !dout) return;
@@ -2446,7 +2340,7 @@ struct conp_fix : DevCtx {
   void post_neighbor_device_check(const double *dx, const double *dq) const {
     const char *w = "conp_fix_post_neighbor_device: ";
     if (!dx || !dq) throw ConpError(CONP_ERR_ARG, std::string(w) + "null argument");
-    if (decomposed) throw ConpError(CONP_ERR_STATE, std::string(w) + "the handle is spatially decomposed (conp_fix_set_comm): the host hook re-neighbours it");
+    if (xch.decomposed) throw ConpError(CONP_ERR_STATE, std::string(w) + "the handle is spatially decomposed (conp_fix_set_comm): the host hook re-neighbours it");
     if (!idx.initialised || nlocal_cur <= 0 || nall <= 0)
       throw ConpError(CONP_ERR_STATE, std::string(w) + "before conp_fix_setup_post_neighbor (host arrays, once per run)");
     if (runstage < 2) throw ConpError(CONP_ERR_STATE, std::string(w) + "before conp_fix_linalg_setup / conp_fix_setup_pre_force");
@@ -2670,8 +2564,7 @@ struct conp_fix : DevCtx {
   // d_out from the atomic entry's own kernels (the <no force, sums> instantiation and the finish: the same bytes), the forces gathered
   void post_force_ordered_device(const double *dx, const double *dq, double *df, double *dout) {
     if (!dx || !dq) throw ConpError(CONP_ERR_ARG, "null argument");
-    if (decomposed) throw ConpError(CONP_ERR_STATE, "device-resident updates take replicated atoms (conp_env.rank / nranks); "
-                                                    "spatially decomposed runs use the host-buffer hooks");
+    xch.need_replicated();
     if (runstage < 2 || !idx.initialised || nlocal_cur <= 0 || nall <= 0) throw ConpError(CONP_ERR_STATE, "post_force before setup");
     if (!fix_tr.valid || fix_tr.nall != nall)
       throw ConpError(CONP_ERR_STATE, "conp_fix_post_force_ordered_device: no transposed list of the fix's current list "
@@ -2703,11 +2596,11 @@ struct conp_fix : DevCtx {
     if (time_host) { const double t1 = now_s(); th[1] += t1 - t0; t0 = t1; }
     if (elyte_list_stale(at)) { sync(); build_elyte_list(at); }       // km_ewald.cpp:686 is evaluated every step
     if (time_host) { const double t1 = now_s(); th[0] += t1 - t0; t0 = t1; }
-    if (decomposed) gather_elyte(at);
+    if (xch.decomposed) gather_elyte(at);
     b_cal_device(d_x.p, d_q.p, true, true);
     if (time_host) { const double t1 = now_s(); th[2] += t1 - t0; t0 = t1; }
     // (a handle that is rank r of N WITHOUT a communicator leaves this rank's shard in b: the caller sums the shards itself)
-    if (nccl || rc.active()) allreduce_b();
+    if (xch.can_exchange()) allreduce_b();
   }
 
   // ---- one device-resident update as a HIP graph ------------------------------------------------
@@ -2733,15 +2626,14 @@ struct conp_fix : DevCtx {
     g_warm = 0;
   }
   void update_direct(const double *dx, double *dq, double potdiff) {
-    if (decomposed) throw ConpError(CONP_ERR_STATE, "device-resident updates take replicated atoms (conp_env.rank / nranks); "
-                                                    "spatially decomposed runs use the host-buffer hooks");
+    xch.need_replicated();
     b_cal_device(dx, dq, true);
     if (can_fuse_solve()) { solve_scatter_fused(dq, potdiff); return; }
     allreduce_b();
     // CG on one rank: the charge write is enqueued behind every batch of iterations BEFORE the host reads the convergence flag
     // (cg()): the device does not idle through the read-back and a launch from cold; a batch that did not converge just wrote
     // intermediate charges, which the next batch's write replaces
-    const bool spec = args.minimizer == CONP_SOLVER_CG && env.nranks <= 1 && !nccl && !args.conq && !args.cond;
+    const bool spec = args.minimizer == CONP_SOLVER_CG && env.nranks <= 1 && !xch.has_comm() && !args.conq && !args.cond;
     if (spec) { spec_dq = dq; spec_pot = potdiff; spec_done = false; }
     solve_device();
     spec_dq = nullptr;
@@ -2952,10 +2844,7 @@ int conp_fix_post_neighbor(conp_fix *f, const conp_atoms *at) {
   f->drop_graph();
   const bool overflowed = f->zn_take_flag_before_rebuild();
   f->post_neighbor(at);
-  if (overflowed)
-    throw ConpError(CONP_ERR_NUMERIC, "a device-resident update's z-window overflowed before this re-neighbouring (an electrolyte atom drifted "
-                                      "more than 2.5 A in z): the charges of the updates since the previous list build are invalid; the list "
-                                      "is rebuilt at the new positions");
+  conp_fix::zn_raise_after_rebuild(overflowed);
   CONP_GUARD_END
 }
 
@@ -2967,10 +2856,7 @@ int conp_fix_post_neighbor_device(conp_fix *f, const double *d_x, const double *
   f->drop_graph();
   const bool overflowed = f->zn_take_flag_before_rebuild();
   f->post_neighbor_device(d_x, d_q);
-  if (overflowed)
-    throw ConpError(CONP_ERR_NUMERIC, "a device-resident update's z-window overflowed before this re-neighbouring (an electrolyte atom drifted "
-                                      "more than 2.5 A in z): the charges of the updates since the previous list build are invalid; the list "
-                                      "is rebuilt at the new positions");
+  conp_fix::zn_raise_after_rebuild(overflowed);
   CONP_GUARD_END
 }
 
@@ -3097,7 +2983,7 @@ int conp_km_a_cal(conp_fix *f, const conp_atoms *at, double *aaa) {
   f->km_a_read(at);
   f->km_a_cal_device();
   const double MY_PIS = 1.77245385090551602729;
-  if (!f->setup_sharded() || f->env.rank == 0)
+  if (!f->xch.can_exchange() || f->env.rank == 0)
     launch_a_diag_slab(f->stream, ne, f->kt.ug_tot - (2.0 / MY_PIS) * f->kt.g_ewald, 0.0, nullptr, f->kt.slabflag == 1,
                        12.56637061435917295384 / f->kt.volume, f->d_ele_z.p, f->d_A.p);
   f->allreduce_matrix(f->d_A.p, (size_t)ne * ne);
@@ -3114,9 +3000,9 @@ int conp_km_b_cal(conp_fix *f, const conp_atoms *at, double *bbb) {
   if (at->nlocal + at->nghost != f->nall) throw ConpError(CONP_ERR_STATE, "atom count changed without post_neighbor");
   if (f->elyte_list_stale(at)) { f->sync(); f->build_elyte_list(at); }
   f->upload_xq(at);
-  if (f->decomposed) f->gather_elyte(at);
+  if (f->xch.decomposed) f->gather_elyte(at);
   f->b_cal_device(f->d_x.p, f->d_q.p, false);
-  if (f->nccl || f->rc.active()) f->allreduce_b();
+  if (f->xch.can_exchange()) f->allreduce_b();
   HIP_TRY(hipMemcpyAsync(bbb, f->d_b, f->idx.elenum_all * sizeof(double), hipMemcpyDeviceToHost, f->stream));
   f->sync();
   CONP_GUARD_END
@@ -3421,7 +3307,7 @@ static void potential_atom_tail(conp_fix *f, const conp_atoms *at, const conp_po
     CompSum dipole, charge;
     for (int i = 0; i < at->nlocal; ++i) { dipole.add(2 * pi2vol * at->q[i] * at->x[3 * (size_t)i + 2]); charge.add(at->q[i]); }
     double slabcorr = dipole.value(), qsum = charge.value();
-    { double two[2] = {slabcorr, qsum}; f->rc.sum(two, 2); slabcorr = two[0]; qsum = two[1]; }
+    { double two[2] = {slabcorr, qsum}; f->xch.cb.sum(two, 2); slabcorr = two[0]; qsum = two[1]; }
     for (int i : idx) {
       const double z = at->x[3 * (size_t)i + 2];
       pot[i] += z * slabcorr;
@@ -3488,7 +3374,7 @@ int conp_pppm_compute_particle_potential(conp_fix *f, const conp_atoms *at, int 
   need_pppm(f);
   if (!u || i < 0 || i >= at->nlocal) throw ConpError(CONP_ERR_ARG, "atom index out of range");
   if (!f->pm.u_valid) {
-    if (f->decomposed || f->env.nranks > 1)
+    if (f->xch.decomposed || f->env.nranks > 1)
       throw ConpError(CONP_ERR_STATE, "pppm/conp/hip: compute_particle_potential is rank-local -- under several MPI ranks the mesh potential "
                                       "has to be formed by a collective call first (conp_pppm_compute / compute_group_potential)");
     upload_atoms(f, at);
@@ -3538,7 +3424,7 @@ int conp_ewald_compute_particle_potential(conp_fix *f, const conp_atoms *at, int
   if (i < 0 || i >= at->nlocal) throw ConpError(CONP_ERR_ARG, "atom index out of range");
   if (!f->ew.u_valid || (int)f->ew.u_h.size() != at->nlocal) {
     if (!f->ew.g_valid) {
-      if (f->decomposed || f->env.nranks > 1)
+      if (f->xch.decomposed || f->env.nranks > 1)
         throw ConpError(CONP_ERR_STATE, "conp_ewald_compute_particle_potential is rank-local -- under several MPI ranks the structure "
                                         "factor has to be formed by a collective call first (conp_ewald_compute / compute_group_potential)");
       ewald_structure_factor(f, at);
@@ -3594,8 +3480,7 @@ static void kspace_device_check(conp_fix *f, void (*need)(conp_fix *), const dou
   if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
   f->drop_graph();
   need(f);
-  if (f->decomposed) throw ConpError(CONP_ERR_STATE, "device-resident updates take replicated atoms (conp_env.rank / nranks); "
-                                                     "spatially decomposed runs use the host-buffer hooks");
+  f->xch.need_replicated();
   if (!dx || !dq) throw ConpError(CONP_ERR_ARG, "null argument");
 }
 }  // namespace
@@ -4186,8 +4071,7 @@ int conp_potential_atom_device(conp_fix *f, const double *d_x, const double *d_q
   const std::string who = "conp_potential_atom_device: ";
   if (!f || !d_x || !d_q || !pa) throw ConpError(CONP_ERR_ARG, "null argument");
   f->drop_graph();
-  if (f->decomposed) throw ConpError(CONP_ERR_STATE, "device-resident updates take replicated atoms (conp_env.rank / nranks); "
-                                                     "spatially decomposed runs use the host-buffer hooks");
+  f->xch.need_replicated();
   if (!f->idx.initialised || f->nlocal_cur <= 0 || f->nall <= 0) throw ConpError(CONP_ERR_STATE, who + "before a post_neighbor");
   const int nlocal = f->nlocal_cur, ntotal = f->env.newton_pair ? f->nall : nlocal;
   if (ntargets < 0 || ntargets > nlocal) throw ConpError(CONP_ERR_ARG, who + "ntargets outside [0, nlocal]");
@@ -4240,36 +4124,24 @@ int conp_fix_set_comm(conp_fix *f, const conp_comm *comm) {
   CONP_GUARD_BEGIN
   if (!f || !comm) throw ConpError(CONP_ERR_ARG, "null argument");
   if (f->idx.initialised) throw ConpError(CONP_ERR_STATE, "conp_fix_set_comm after setup_post_neighbor");
-  if (comm->nranks < 1 || comm->rank < 0 || comm->rank >= comm->nranks) throw ConpError(CONP_ERR_ARG, "bad rank/nranks");
-  if (comm->nranks > 1 && (!comm->allreduce_sum || !comm->allreduce_max_int || !comm->allgather_int || !comm->allgatherv))
-    throw ConpError(CONP_ERR_ARG, "conp_comm: every callback is needed with more than one rank");
-  f->rc.c = *comm; f->rc.have = true; f->rc.rank_ = comm->rank; f->rc.nranks_ = comm->nranks;
+  f->xch.set_callbacks(comm);
   f->env.rank = comm->rank; f->env.nranks = comm->nranks;
-  f->decomposed = true;
-  f->ew.ranks = f->pm.ranks = &f->rc;
+  f->ew.ranks = f->pm.ranks = &f->xch.cb;
   CONP_GUARD_END
 }
 
 int conp_rccl_unique_id(void *id_out) {
   CONP_GUARD_BEGIN
   if (!id_out) throw ConpError(CONP_ERR_ARG, "null argument");
-  static_assert(sizeof(ncclUniqueId) == CONP_RCCL_ID_BYTES, "ncclUniqueId size");
-  g_rccl.load();
-  ncclUniqueId id;
-  g_rccl.ok(g_rccl.GetUniqueId(&id), "ncclGetUniqueId");
-  std::memcpy(id_out, &id, sizeof(id));
+  RankExchange::unique_id(id_out);
   CONP_GUARD_END
 }
 
 int conp_fix_comm_init_rccl(conp_fix *f, const void *id_in) {
   CONP_GUARD_BEGIN
   if (!f || !id_in) throw ConpError(CONP_ERR_ARG, "null argument");
-  if (f->nccl) throw ConpError(CONP_ERR_STATE, "RCCL communicator already initialised");
   f->drop_graph();
-  g_rccl.load();
-  ncclUniqueId id;
-  std::memcpy(&id, id_in, sizeof(id));
-  g_rccl.ok(g_rccl.CommInitRank(&f->nccl, f->env.nranks, id, f->env.rank), "ncclCommInitRank");
+  f->xch.init_rccl(id_in, f->env.nranks, f->env.rank);
   // results of the in-library collectives land in the library's own vectors
   f->d_b = f->d_b_own.p; f->d_eleallq = f->d_eleallq_own.p;
   f->b_bound = f->q_bound = false;
@@ -4280,8 +4152,7 @@ int conp_fix_comm_init_rccl(conp_fix *f, const void *id_in) {
 // every rank and AGREE on the answer (MPI_Allreduce MIN, torch.distributed ...) BEFORE the collective conp_fix_comm_init_rccl,
 // so that a rank without RCCL cannot leave its partners waiting inside ncclCommInitRank.
 int conp_rccl_available(void) {
-  try { g_rccl.load(); } catch (...) { return CONP_ERR_NO_DEVICE; }
-  return CONP_OK;
+  return RankExchange::available() ? CONP_OK : CONP_ERR_NO_DEVICE;
 }
 
 // Gives the communicator back (all ranks, together: after an initialisation that failed on some rank, the host falls back to
@@ -4290,7 +4161,8 @@ int conp_fix_comm_destroy_rccl(conp_fix *f) {
   CONP_GUARD_BEGIN
   if (!f) throw ConpError(CONP_ERR_ARG, "null argument");
   f->drop_graph();
-  if (f->nccl) { f->sync(); (void)g_rccl.CommDestroy(f->nccl); f->nccl = nullptr; }
+  if (f->xch.has_comm()) f->sync();      // (reports a stream in error; destroy_rccl's own wait does not)
+  f->xch.destroy_rccl();
   CONP_GUARD_END
 }
 
@@ -4307,7 +4179,7 @@ int conp_fix_bind_device_buffers(conp_fix *f, double *d_b, double *d_q) {
   CONP_GUARD_BEGIN
   f->drop_graph();
   f->sync();
-  if (f->nccl && d_q) throw ConpError(CONP_ERR_STATE, "with an RCCL communicator the library gathers q into its own buffer "
+  if (f->xch.has_comm() && d_q) throw ConpError(CONP_ERR_STATE, "with an RCCL communicator the library gathers q into its own buffer "
                                                       "(nranks * ceil(Ne / nranks) entries); read it with conp_fix_get_vectors");
   const size_t nb = f->idx.elenum_all * sizeof(double);
   if (d_b) { if (f->d_b && nb) HIP_TRY(hipMemcpy(d_b, f->d_b, nb, hipMemcpyDeviceToDevice)); f->d_b = d_b; f->b_bound = true; }

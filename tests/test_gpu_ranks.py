@@ -3,7 +3,7 @@ processes share cuda:0 and the callbacks run on torch.distributed gloo) against 
 inside the library -- a one-rank communicator exercises every RCCL call site (all-reduce of b and of the sharded A build,
 in-place all-gather of q, row-sharded S and its re-assembly) on the one GPU this box has; several GPUs are the driver's bench;
 (3) the sharded A build on decks with 28 and 210 tiles, two and three ranks.  Out of scope: the by_range real-space split of a_cal
-(setup_sharded && !decomposed) exists only under a multi-rank RCCL communicator, which one GPU cannot form."""
+(can_exchange() && !decomposed) exists only under a multi-rank RCCL communicator, which one GPU cannot form."""
 import os
 import sys
 
@@ -214,12 +214,12 @@ def _tiled_worker(rank, world, port, name, axis, out):
     ids=["il_onelayer-x2", "il_onelayer-z3_middle_rank_without_electrode_atoms", "il_onelayer_rough-y3", "cond2-x2",
          "il_onelayer_newton-x2"])
 def test_sharded_a_build_with_several_tiles_per_rank(name, axis, world, nzc, tiles, every_rank_owns_electrode):
-    """setup_sharded(): the lower-triangle tiles of A dealt cyclically to 2 / 3 ranks (tile_first = rank, tile_stride = nranks),
+    """RankExchange::can_exchange(): the lower-triangle tiles of A dealt cyclically to 2 / 3 ranks (tile_first = rank, tile_stride = nranks),
     diagonal and slab term on rank 0 only, real-space rows by owner, the partial matrices summed through conp_comm -- on decks with
     28 and 210 tiles, where every rank really gets several.  Every element is written by one rank's tile and at most one rank's
     real-space row, so each rank's A must be the one-rank A (permuted by tag) to rounding of the row sums: 1e-11 of the largest
     entry (TOL_A); then the setup is finished and one update made: charges and scalar to 1e-9 as in the test above.
-    Not covered: the by_range real-space split (setup_sharded && !decomposed) only exists under a multi-rank RCCL communicator,
+    Not covered: the by_range real-space split (can_exchange() && !decomposed) only exists under a multi-rank RCCL communicator,
     which one GPU cannot form."""
     import torch.multiprocessing as mp
     s = _make_tiled(name)
